@@ -1,16 +1,23 @@
 """Benchmark of the VyomAI transformer hot path on MI355X (driver contract: see the task brief).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* = one CLM training step (forward + backward + gradient all-reduce + fused AdamW) of the
 GPT-style decoder of BASELINE.json configs[1]: 12 layers, d=768, 12 heads, RoPE, vocab 50265,
 per-GPU batch 32 x seq 512, bf16 kernels with fp32 master weights, synthetic tokens, recipe
-weights.  `value` = whole-job training tokens/s (weak scaling: per-GPU work fixed).  After the
-timed training region the same run measures KV-cache greedy decode (512-token prompts, 128 new
-tokens, static cache) and reports it as `decode_tokens_per_sec`.
+weights.  `value` = whole-job training tokens/s (weak scaling: per-GPU work fixed); `ms_per_step` =
+wall time of one timed step.  A plain run sets up, warms up, times the K steps and prints the line.
 
-Extra objects on the JSON line:
+--dump-outputs DIR  after the timed steps, writes what the last step handed its caller (see dump_outputs)
+                    as float32 .npy files; inputs are fixed by the recipe and seeds, so two builds compare
+                    output for output.
+--full              adds the side measurements below, after the timed steps (--no-decode, --no-cpu-baseline
+                    and --no-other-configs leave single ones out): KV-cache greedy decode (512-token prompts,
+                    128 new tokens, static cache) reported as `decode_tokens_per_sec`, the roofline probe, the
+                    CPU baseline and the other BASELINE.json configurations (`other_configs`).
+
+Extra objects on the JSON line of a --full run:
   roofline      dominant kernel = the bf16 MFMA GEMM (forward projections/FFN of one step); achieved
                 = algorithmic FLOPs / HIP-event time of those launches, measured live on the launch
                 stream; peak = 2500 TFLOP/s dense bf16 (MI355X_MICROARCH.md).  `block_forward`
@@ -48,6 +55,9 @@ def parse():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--decode-tokens", type=int, default=128)
     ap.add_argument("--attn", default="none", choices=["none", "gqa"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: decode, roofline probe, CPU baseline, other configurations")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[3] / configs[4] side measurements")
@@ -58,7 +68,10 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal on a one-GPU box: a ONE-rank process group whose bucket collectives are really issued "
                          "(RCCL init, async all-reduce, stream waits, barrier); not a benchmark configuration")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def make_cfg(a):
@@ -290,6 +303,34 @@ def time_training(trainer, model, ids, steps, warmup, barrier, dev, dist_on):
     return float(tmax.item()), loss
 
 
+DUMP_SAMPLE = 16384   # values kept per parameter tensor (about 11 MB of .npy in all for the 12-layer model)
+
+
+def dump_outputs(out_dir, loss, model) -> None:
+    """What the last training step hands its caller, as float32 files in out_dir: loss.npy (the step's loss),
+    params.npy (the fp32 master parameters after the AdamW update) and grads.npy (the gradients that update
+    used).  params / grads concatenate model.named_parameters() in order; a tensor of more than DUMP_SAMPLE
+    values contributes a fixed sample of them, at sorted positions drawn from a generator seeded by the
+    parameter's name, so the same positions are compared whatever the build."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params, grads = [], []
+    for name, p in model.named_parameters():
+        w, g = p.detach().reshape(-1), p.grad.reshape(-1)
+        n = w.numel()
+        if n > DUMP_SAMPLE:
+            pick = np.random.default_rng(zlib.crc32(name.encode())).choice(n, DUMP_SAMPLE, replace=False)
+            idx = torch.from_numpy(np.sort(pick)).to(w.device)
+            w, g = w.index_select(0, idx), g.index_select(0, idx)
+        params.append(w.float().cpu().numpy())
+        grads.append(g.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(out_dir, "params.npy"), np.concatenate(params))
+    np.save(os.path.join(out_dir, "grads.npy"), np.concatenate(grads))
+
+
 def time_decode(model, cfg, attn, ids, new_tokens, dev, world, dist_on):
     """KV-cache greedy decode behind the (B, L) prompts, static cache: time per token step from two runs (1 and n new
     tokens), and the HBM roofline of a step -- every layer / head weight once (the embedding table only B rows) + the
@@ -445,19 +486,21 @@ def main():
     dt, loss = time_training(trainer, model, ids, a.steps, a.warmup, barrier, dev, dist_on)
     tokens = world * B * L * a.steps
     final_loss = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
 
     # ---- decode: replicas only (independent sequences per GPU, no collective) -------------------
     dec = None
-    if not a.no_decode:
+    if a.full and not a.no_decode:
         dec = time_decode(model, cfg, a.attn, ids, a.decode_tokens, dev, world, dist_on)
 
     roof = cpu = None
     others = None
-    if rank == 0:
+    if a.full and rank == 0:
         roof = roofline_probe(cfg, B, L, dev)
         if world == 1 and not a.no_cpu_baseline:
             cpu = cpu_baseline(cfg, L)
-    if not a.no_other_configs:
+    if a.full and not a.no_other_configs:
         # the other BASELINE.json configurations, measured beside the headline (never part of `value`):
         # the training model is released first; a failure here leaves a note, not a broken bench line.
         # configs[3] (caption training, "B=64 on 1->8 GPUs") runs on every rank under the same process group;
@@ -512,8 +555,8 @@ def main():
             "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": f"configs[1]: GPT-style Decoder {cfg.num_hidden_layers}L d=768 h=12 RoPE vocab 50265, "
-                                   f"CLM training B={B}/GPU seq={L}, AdamW, bf16 kernels + fp32 masters; "
-                                   f"then KV-cache greedy decode {a.decode_tokens} tok",
+                                   f"CLM training B={B}/GPU seq={L}, AdamW, bf16 kernels + fp32 masters"
+                                   + (f"; then KV-cache greedy decode {a.decode_tokens} tok" if dec else ""),
                        "global_batch": world * B, "seq_len": L, "parallelism": f"dp{world}",
                        "attention": a.attn, "weights": "deterministic recipe (vyomai_amd.recipe)"},
             "final_loss": round(final_loss, 4),

@@ -81,7 +81,7 @@ def test_dgrad(M, N, K, act):
     check(got, want, 4e-2, 1e-2, "dgrad")
 
 
-@pytest.mark.parametrize("M,N", [(1000, 768), (64, 64), (5000, 768)])
+@pytest.mark.parametrize("M,N", [(1000, 768), (64, 64), (5000, 768), (260, 768)])
 def test_layernorm_bwd(M, N):
     ops = _ops()
     x = (rnd(M, N, seed=1) * 2 + 0.3).to(BF)
@@ -97,6 +97,12 @@ def test_layernorm_bwd(M, N):
     check(dx, xd.grad, 3e-2, 1e-2, "dx")
     check(dg, gd.grad, 2e-3 * math.sqrt(M), 1e-3, "dgamma")
     check(dbt, bd.grad, 2e-3 * math.sqrt(M), 1e-3, "dbeta")
+    # the column sums have no atomics: a second call gives the same bits, and accumulate adds onto them
+    dg2, db2 = dg.clone(), dbt.clone()
+    ops.layernorm_bwd(dy.to(DEV), x.to(DEV), g.to(DEV), mean, rstd, dg2, db2, accumulate=False)
+    assert torch.equal(dg2, dg) and torch.equal(db2, dbt)
+    ops.layernorm_bwd(dy.to(DEV), x.to(DEV), g.to(DEV), mean, rstd, dg2, db2, accumulate=True)
+    assert torch.equal(dg2, dg + dg) and torch.equal(db2, dbt + dbt)
 
 
 BWD_CASES = [

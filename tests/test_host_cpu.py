@@ -274,6 +274,35 @@ def test_bench_starts_its_own_ranks_and_never_misreports_n_gpus():
     assert bad.returncode != 0 and not bad.stdout.strip()
 
 
+def test_bench_dump_outputs_are_float32_at_fixed_positions(tmp_path):
+    """`bench.py --dump-outputs`: loss, parameters and gradients as float32 .npy, a tensor larger than DUMP_SAMPLE
+    sampled at positions that depend on its name only, so two runs (or two builds) compare value for value."""
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 100), torch.nn.LayerNorm(100))   # 30000 weights > DUMP_SAMPLE
+    loss = m(torch.randn(4, 300)).square().mean()
+    loss.backward()
+    with torch.no_grad():   # each weight holds its own flat position, its gradient -2 times that
+        m[0].weight.copy_(torch.arange(30000.0).view(100, 300))
+        m[0].weight.grad.copy_(-2 * m[0].weight)
+    bench.dump_outputs(str(tmp_path / "a"), loss, m)
+    bench.dump_outputs(str(tmp_path / "b"), loss, m)
+    k = bench.DUMP_SAMPLE
+    for name in ("loss", "params", "grads"):
+        a, b = (np.load(tmp_path / d / f"{name}.npy") for d in "ab")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == loss.item()
+    for name, t in (("params", lambda p: p.detach()), ("grads", lambda p: p.grad)):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        rest = [t(p).reshape(-1).numpy() for p in list(m.parameters())[1:]]
+        assert got.shape == (k + 300,)
+        assert np.array_equal(got[k:], np.concatenate(rest))
+    # the sampled weights are k distinct positions in increasing order, and the gradients come from the same ones
+    pos, grads = (np.load(tmp_path / "a" / f"{name}.npy")[:k] for name in ("params", "grads"))
+    assert (np.diff(pos) > 0).all() and 0 <= pos[0] and pos[-1] < 30000
+    assert np.array_equal(grads, -2 * pos)
+
+
 def test_wrapped_projection_is_refused_not_ignored():
     """The reference's adapters replace attention.query by a wrapper holding the Linear at `.linear`
     (layers/adapters.py:21-24): the fused QKV path must say that it cannot honour it, not silently drop it."""

@@ -39,7 +39,7 @@ def close(got, want, atol, what=""):
 def test_encoder_config1(golden, pos, at):
     """BASELINE.json configs[0] on the HIP path: EncoderModel default config, B=4, seq=128."""
     import vyomai_amd as V
-    g = golden("models_text")
+    g = golden("encoder")
     cfg = cases.with_kv(cases.test_cfg(), at)
     m = build(V.EncoderModel, cfg, pos, at)
     ids = T(recipe.token_ids("enc.ids", (4, 128), 3, cfg.vocab_size)).to(DEV)

@@ -93,7 +93,7 @@ def test_modules(golden, tag):
 @pytest.mark.parametrize("pos,at", [("absolute", None), ("rope", None), ("sinusoidal", "gqa"), ("rope", "gqa")])
 def test_encoder_config1(golden, pos, at):
     """BASELINE.json configs[0]: EncoderModel(EncoderConfig default) B=4 seq=128 on CPU."""
-    g = golden("models_text")
+    g = golden("encoder")
     cfg = cases.with_kv(cases.test_cfg(), at)
     sd = sd_from(cases.text_model_shapes(cfg, pos, at, head=False))
     ids = T(recipe.token_ids("enc.ids", (4, 128), 3, cfg.vocab_size))

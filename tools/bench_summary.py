@@ -1,4 +1,4 @@
-"""One line of the figures quoted in README.md from a bench.py JSON line:  python tools/bench_summary.py gpurun_out/bench.json"""
+"""One line of the figures quoted in README.md from a `bench.py --full` JSON line:  python tools/bench_summary.py bench.json"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 o = d.get("other_configs") or {}

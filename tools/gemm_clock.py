@@ -26,7 +26,7 @@ for N, K in ((768, 768), (768, 3072), (2304, 768), (3072, 768)):
         mhz, n, us = read()
         print(f"micro N={N} K={K} x{iters}: {t:7.1f} us/launch, workgroup 0 alive {us:6.1f} us, shader clock {mhz:6.0f} MHz ({n} launches)")
 
-sys.argv = ["bench.py", "--no-decode", "--no-cpu-baseline", "--steps", "6", "--warmup", "2"]
+sys.argv = ["bench.py", "--full", "--no-decode", "--no-cpu-baseline", "--steps", "6", "--warmup", "2"]
 read()
 bench.main()
 mhz, n, us = read()

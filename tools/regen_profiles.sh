@@ -28,7 +28,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/vlm -o v -- python3
 echo "configs[3] training traced"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train -o t -- python3 $ROOT/tools/train_only.py 10 > $OUT/train.log 2>&1
 echo "configs[1] training steps traced"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python3 $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs > $OUT/bench.log 2>&1
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- python3 $ROOT/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs > $OUT/bench.log 2>&1
 echo "bench traced"
 # the raw per-launch traces are large and not needed (the stats tables are what profiles/ keeps)
 find $OUT -name "*kernel_trace.csv" -delete

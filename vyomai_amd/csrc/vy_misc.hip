@@ -287,12 +287,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
   }
 }
 
-// column sums of the [W, N] partial slabs, accumulated into out0/out1 (zeroed by the launcher
-// when beta == 0): grid = (column blocks of 64) x (row slices), 4 row groups per block reduced
-// through LDS, one fp32 atomic per column per block
-__global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __restrict__ ws, int W, int N,
+// column sums of the [W, N] partial slabs: grid = (column blocks of 64) x (row slices), 4 row groups
+// per block reduced through LDS.  No atomics, so dgamma / dbeta are the same from run to run: with one
+// slice the block writes out0/out1 itself (added to them when acc); with several, each block leaves its
+// sums in the first slab row of its slice (rows only this block reads) and colsum_finish_kernel adds
+// the slices up in slice order.
+__global__ __launch_bounds__(256) void colsum_partials_kernel(float* __restrict__ ws, int W, int N,
                                                               float* __restrict__ out0, float* __restrict__ out1,
-                                                              int rows_per_slice) {
+                                                              int rows_per_slice, int acc) {
   __shared__ float red[2][4][64];
   const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int n = blockIdx.x * 64 + c;
@@ -317,12 +319,32 @@ __global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __res
   }
   red[0][g][c] = a; red[1][g][c] = b;
   __syncthreads();
-  if (g == 0 && n < N) {
+  if (g == 0 && n < N && w0 < w1) {
     a = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
     b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
-    if (out0) atomicAdd(out0 + n, a);
-    if (out1) atomicAdd(out1 + n, b);
+    if (gridDim.y == 1) {
+      if (out0) out0[n] = (acc ? out0[n] : 0.f) + a;
+      if (out1) out1[n] = (acc ? out1[n] : 0.f) + b;
+    } else {
+      ws[(int64_t)w0 * N + n] = a;
+      ws[(int64_t)(W + w0) * N + n] = b;
+    }
   }
+}
+
+// out0/out1[n] (+)= the slice sums colsum_partials_kernel left in slab rows 0, rps, 2 rps, ... < W, in that order
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ ws, int W, int N,
+                                                            float* __restrict__ out0, float* __restrict__ out1,
+                                                            int rows_per_slice, int acc) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float a = 0.f, b = 0.f;
+  for (int w = 0; w < W; w += rows_per_slice) {
+    a += ws[(int64_t)w * N + n];
+    b += ws[(int64_t)(W + w) * N + n];
+  }
+  if (out0) out0[n] = (acc ? out0[n] : 0.f) + a;
+  if (out1) out1[n] = (acc ? out1[n] : 0.f) + b;
 }
 
 // ---- RoPE (standalone, in place) ------------------------------------------------------------
@@ -739,17 +761,18 @@ int ln_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, co
   else VY_FAIL(VY_ERR_UNSUPPORTED, "vy_layernorm_bwd: N=%ld too wide", (long)N);
 #undef LN_GO
   VY_CHECK_LAUNCH("vy_layernorm_bwd");
-  if (beta == 0.f) {
-    if (dgamma && hipMemsetAsync(dgamma, 0, N * sizeof(float), st) != hipSuccess) VY_FAIL(VY_ERR_LAUNCH, "vy_layernorm_bwd: memset failed");
-    if (dbeta && hipMemsetAsync(dbeta, 0, N * sizeof(float), st) != hipSuccess) VY_FAIL(VY_ERR_LAUNCH, "vy_layernorm_bwd: memset failed");
-  } else if (beta != 1.f) {
-    VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: beta must be 0 or 1");
-  }
+  if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: beta must be 0 or 1");
+  const int acc = beta == 1.f;
   const int slices = WB >= 64 ? 16 : 1;
   const int rps = (int)vy_cdiv(WB, slices);
   hipLaunchKernelGGL(colsum_partials_kernel, dim3((unsigned)vy_cdiv(N, 64), (unsigned)slices), dim3(256), 0, st, ws, WB,
-                     (int)N, dgamma, dbeta, rps);
+                     (int)N, dgamma, dbeta, rps, acc);
   VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum)");
+  if (slices > 1) {
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)vy_cdiv(N, 256)), dim3(256), 0, st, ws, WB, (int)N, dgamma,
+                       dbeta, rps, acc);
+    VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum finish)");
+  }
   return VY_OK;
 }
 
