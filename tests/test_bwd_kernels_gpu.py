@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import vyom_oracle as O
-from tests.test_kernels_gpu import check, rnd, _dense_mask
+from tests.test_kernels_gpu import check, rnd, _dense_mask, ints, thin_ternary, assert_bf16_exact, check_exact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -79,6 +79,79 @@ def test_dgrad(M, N, K, act):
     check(wt, w.t(), 0, 0, "transpose")
     got = ops.linear_dgrad(dy.to(DEV), wt, pre.to(DEV) if act else None, act, add.to(DEV))
     check(got, want, 4e-2, 1e-2, "dgrad")
+
+
+# ---- exact-integer twins (see tests/test_kernels_gpu.py): small-integer operands, fp32 accumulation exact in any order,
+# so the result is compared bit for bit
+@pytest.mark.parametrize("M,N,K", [(300, 768, 3072), (1024, 768, 768), (51, 3072, 768), (2112, 3072, 768),
+                                   (2112, 768, 3072), (264, 2048, 2048), (264, 16384, 2048)])
+def test_dgrad_exact(M, N, K):
+    """Every shape of test_dgrad with act = 0 and `add`; the reduction runs over N, so the weight is thinned by N."""
+    ops = _ops()
+    dy = ints(M, N, seed=1)
+    w = thin_ternary(N, K, N, seed=2)
+    add = ints(M, K, seed=4, lo=-2, hi=2)
+    want = dy @ w + add
+    assert_bf16_exact(want, f"dgrad {M}x{N}x{K}")
+    wt = ops.transpose(w.to(BF).to(DEV))
+    check_exact(wt, w.t(), "transpose")
+    got = ops.linear_dgrad(dy.to(BF).to(DEV), wt, None, 0, add.to(BF).to(DEV))
+    check_exact(got, want, f"dgrad exact {M}x{N}x{K} (m, k)")
+
+
+@pytest.mark.parametrize("dtype,M,N,K", [(BF, 256, 128, 128), (BF, 1000, 768, 768), (BF, 4096, 3072, 768),
+                                         (BF, 777, 768, 3072), (BF, 64, 2304, 768),
+                                         (torch.float32, 256, 128, 128), (torch.float32, 1000, 768, 520),
+                                         (torch.float32, 77, 50265, 64), (torch.float32, 4100, 72, 3072)])
+def test_wgrad_exact(dtype, M, N, K):
+    """The shapes of test_wgrad (bf16) and test_wgrad_fp32.  Dense operands in {-2..2}: |sum| <= 4 M, exact in the fp32
+    output.  dW and db after the first call, after accumulate=True, after alpha = 0.5 (half-integers: still exact), and
+    through the grouped entry point."""
+    ops = _ops()
+    ld = (N + 7) // 8 * 8
+    dy = ints(M, N, seed=1, lo=-2, hi=2)
+    x = ints(M, K, seed=2, lo=-2, hi=2)
+    dy_full = torch.zeros(M, ld)
+    dy_full[:, :N] = dy
+    dyg, xg = dy_full.to(dtype).to(DEV)[:, :N], x.to(dtype).to(DEV)
+    dw = torch.full((N, K), 7.0, dtype=torch.float32, device=DEV)
+    db = torch.full((N,), 7.0, dtype=torch.float32, device=DEV)
+    want, want_b = dy.t() @ x, dy.sum(0)
+    ops.linear_wgrad(dyg, xg, dw, db, accumulate=False)
+    check_exact(dw, want, "dW (n, k)")
+    check_exact(db, want_b, "db")
+    ops.linear_wgrad(dyg, xg, dw, db, accumulate=True)
+    check_exact(dw, 2 * want, "dW accumulate (n, k)")
+    check_exact(db, 2 * want_b, "db accumulate")
+    alpha = torch.tensor([0.5], dtype=torch.float32, device=DEV)
+    ops.linear_wgrad(dyg, xg, dw, db, accumulate=True, alpha=alpha)
+    check_exact(dw, 2.5 * want, "dW accumulate with alpha (n, k)")
+    check_exact(db, 2.5 * want_b, "db accumulate with alpha")
+    ops.linear_wgrad_grouped([(dyg, xg, dw, db)])
+    check_exact(dw, 3.5 * want, "grouped entry point (n, k)")
+    check_exact(db, 3.5 * want_b, "grouped entry point, db")
+
+
+def test_wgrad_grouped_exact():
+    """The strided / ragged group of test_wgrad_grouped on integer data, accumulated onto 3.0."""
+    ops = _ops()
+    shapes = [(4096, 768, 768, True), (4096, 3072, 768, True), (4096, 768, 3072, False), (4100, 2304, 768, True),
+              (1000, 520, 264, True), (300, 56, 8, False)]
+    items, wants = [], []
+    for i, (M, N, K, bias) in enumerate(shapes):
+        dy_full = ints(M, N + 8, seed=10 + i, lo=-2, hi=2)       # row stride N + 8
+        x = ints(M, K, seed=30 + i, lo=-2, hi=2)
+        dw = torch.full((N, K), 3.0, dtype=torch.float32, device=DEV)
+        db = torch.full((N,), 3.0, dtype=torch.float32, device=DEV) if bias else None
+        items.append((dy_full.to(BF).to(DEV)[:, :N], x.to(BF).to(DEV), dw, db))
+        wants.append((dy_full[:, :N].t() @ x, dy_full[:, :N].sum(0)))
+    ops.linear_wgrad_grouped(items)
+    for i, ((dy, x, dw, db), (w_dw, w_db)) in enumerate(zip(items, wants)):
+        check_exact(dw, w_dw + 3.0, f"grouped dW, item {i} (n, k)")
+        if db is not None:
+            check_exact(db, w_db + 3.0, f"grouped db, item {i}")
+    ops.linear_wgrad_grouped(items[:1])      # a group of one
+    check_exact(items[0][2], 2 * wants[0][0] + 3.0, "second accumulation (n, k)")
 
 
 @pytest.mark.parametrize("M,N", [(1000, 768), (64, 64), (5000, 768), (260, 768)])

@@ -105,6 +105,112 @@ def test_linear_bf16_wide_mid_m_and_split_k_equals_unsplit():
             O_._mid_ws = saved
         d = (split.float() - whole.float()).abs().max().item()
         assert d <= 2 ** -6 * max(1.0, whole.float().abs().max().item()), (M, N, K, d)   # a bf16 rounding step at most
+        # the same two launches on integer data: every partial sum is exact, so the split is invisible
+        xi, wi = ints(M, K, seed=3).bfloat16().to(DEV), thin_ternary(N, K, K, seed=4).bfloat16().to(DEV)
+        bi, ri = ints(N, seed=5, lo=-2, hi=2).bfloat16().to(DEV), ints(M, N, seed=6, lo=-2, hi=2).bfloat16().to(DEV)
+        want = xi.float().cpu() @ wi.float().cpu().t() + bi.float().cpu() + ri.float().cpu()
+        assert_bf16_exact(want, f"split-K {M}x{N}x{K}")
+        for act in (0, 1):
+            split = ops.linear(xi, wi, bi, act=act, residual=ri)
+            call("vy_workspace_set", st.cuda_stream, None, 0)
+            ops._WS.pop((st.device_index, st.cuda_stream), None)
+            try:
+                saved, O_._mid_ws = O_._mid_ws, lambda rows: None
+                whole = ops.linear(xi, wi, bi, act=act, residual=ri)
+            finally:
+                O_._mid_ws = saved
+            check_exact(split, whole, f"split-K against one launch, integer data, act {act}, {M}x{N}x{K} (m, n)")
+            if act == 0:
+                check_exact(whole, want, f"one launch, integer data {M}x{N}x{K} (m, n)")
+
+
+# ---- exact-integer GEMMs: small-integer inputs are exact in bf16, every partial sum is an integer far below 2^24, so
+# fp32 accumulation is exact IN ANY ORDER (split-K included) and the bar is zero.  These cover indexing, tails, tiling and
+# the epilogue order; the Gaussian tests above cover GELU and the bars on real-valued data.
+def ints(*shape, seed=0, lo=-1, hi=1):
+    g = torch.Generator().manual_seed(seed + 1000 * len(shape) + sum(shape))
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def thin_ternary(N, K, red, seed=0):
+    """Weight in {-1, 0, 1}, each entry kept with probability min(1, 1024 / red) (red: the reduction length).  The WEIGHT
+    is thinned, not the activation, so that every k of every activation row meets a non-zero weight in some column."""
+    g = torch.Generator().manual_seed(seed + 77 * N + K)
+    keep = torch.rand(N, K, generator=g) < min(1.0, 1024.0 / red)
+    return ints(N, K, seed=seed) * keep
+
+
+def assert_bf16_exact(want, what):
+    """bf16 holds every integer of magnitude <= 256: the expected values must all be there (100 % of the elements)."""
+    big = float(want.abs().max())
+    assert big <= 256, f"{what}: expected magnitude {big} is not exact in bf16; the test data is wrong"
+
+
+def check_exact(got, want, what):
+    got = got.detach().float().cpu()
+    want = want.detach().float().cpu()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    if not torch.equal(got, want):
+        bad = ~(got == want)
+        idx = bad.nonzero()[0].tolist()
+        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} not bit-exact; first at {idx}: "
+                             f"got {got[tuple(idx)]} want {want[tuple(idx)]}")
+
+
+LINEAR_SHAPES = [(128, 128, 64), (256, 384, 768), (51, 1003, 768), (300, 768, 72),
+                 (16, 768, 768), (1, 256, 3072), (1024, 3072, 768), (640, 768, 3072),
+                 (32, 3072, 768), (32, 1003, 768), (7, 768, 3072), (32, 64, 40),
+                 (1, 2048, 16384), (2, 1003, 768), (3, 770, 264), (4, 768, 3072), (1, 5, 8),
+                 (2000, 768, 768), (4096, 1003, 768), (1500, 384, 72), (3072, 3072, 768),
+                 (264, 2048, 2048), (264, 2048, 16384), (256, 4304, 1152), (256, 1152, 4304), (2112, 768, 3072),
+                 (2112, 768, 768)]       # test_linear_bf16's list
+LINEAR_EDGES = [
+    # gemv (<= 4 rows) / skinny
+    (5, 768, 3072), (5, 1003, 768),
+    # skinny (<= 32 rows) / mid
+    (33, 3072, 768), (33, 1003, 768),
+    # the all-rows tiles: 128 x 128 up to 128 rows, 256 x 128 up to 256, 320 x 128 up to 320, then 128 x 128 again
+    (128, 768, 768), (129, 768, 768), (256, 768, 768), (257, 768, 768), (320, 768, 768), (321, 768, 768),
+    (129, 1003, 264), (257, 1003, 264), (321, 1003, 264),
+    # mid / large: 1025 rows leave the mid-size tiles once the 256 x 192 grid has 160 tiles (N >= 5953)
+    (1024, 768, 768), (1025, 768, 768), (1024, 6144, 264), (1025, 6144, 264),
+    # 256 x 192 tiles with the three-deep ring (N < 3072) / 256 x 256 tiles; at 2048 rows the 3071 / 3072 grids have 128
+    # tiles and stay on the mid-size kernel, at 4096 rows they are the two large kernels
+    (2048, 3071, 768), (2048, 3072, 768), (4096, 3071, 768), (4096, 3072, 264),
+    # skinny width limit (N <= 8192), then the 32 x 128 fallback
+    (32, 8192, 768), (32, 8200, 768),
+    # K = 16: not a multiple of 32 (the 32-column skinny kernel); K = 8: the 32 x 128 fallback
+    (32, 768, 16), (32, 768, 8)]
+assert not set(LINEAR_SHAPES) & set(LINEAR_EDGES)
+
+
+@pytest.mark.parametrize("M,N,K", LINEAR_SHAPES + LINEAR_EDGES)
+def test_linear_bf16_exact(M, N, K):
+    ops, _ = _ops()
+    x = ints(M, K, seed=1)
+    w = thin_ternary(N, K, K, seed=2)
+    b = ints(N, seed=3, lo=-2, hi=2)
+    r = ints(M, N, seed=4, lo=-2, hi=2)
+    plain = x @ w.t()                   # fp32 on the CPU: integers below 2^24, exact
+    pre_ref = plain + b
+    want = pre_ref + r
+    for t, what in ((plain, "x w^T"), (pre_ref, "pre"), (want, "y")):
+        assert_bf16_exact(t, f"{M}x{N}x{K} {what}")
+    xd, wd = x.bfloat16().to(DEV), w.bfloat16().to(DEV)
+    ldy = (N + 7) // 8 * 8
+    pre = torch.zeros(M, ldy, dtype=torch.bfloat16, device=DEV)
+    y = ops.linear(xd, wd, b.bfloat16().to(DEV), act=0, residual=r.bfloat16().to(DEV), pre_out=pre[:, :N])
+    torch.cuda.synchronize()
+    check_exact(y, want, f"linear bf16 exact {M}x{N}x{K} (m, n)")
+    check_exact(pre[:, :N], pre_ref, "pre_out (m, n)")
+    if ldy > N:
+        assert float(pre[:, N:].abs().max()) == 0, "pre_out: padding columns written"
+    check_exact(ops.linear(xd, wd), plain, f"linear bf16 exact plain {M}x{N}x{K} (m, n)")
+    if N % 8:
+        # rows that are not 16-byte aligned: the scalar epilogue
+        out = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
+        ops.linear(xd, wd, out=out)
+        check_exact(out, plain, f"linear bf16 exact, unpadded rows {M}x{N}x{K} (m, n)")
 
 
 @pytest.mark.parametrize("M,N,K", [(51, 1003, 768), (130, 64, 16), (64, 64, 4), (257, 192, 260)])
@@ -161,6 +267,33 @@ def test_qkv_rope(dtype, B, L, K, h, hk, dh, rope):
     check(kc[:, :, pos0:pos0 + L], kr, tol, tol, "k (cache slice)")
     check(vc[:, :, pos0:pos0 + L], vr, tol, tol, "v (cache slice)")
     assert float(kc[:, :, :pos0].abs().max()) == 0 and float(kc[:, :, pos0 + L:].abs().max()) == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("B,L,K,h,hk,dh", [(3, 50, 768, 12, 12, 64), (5, 1, 768, 12, 4, 64), (3, 1, 256, 2, 1, 128),
+                                          (4, 1, 768, 12, 4, 64), (2, 2, 1152, 16, 16, 72)])
+def test_qkv_no_rope_exact(dtype, B, L, K, h, hk, dh):
+    """The rows of test_qkv_rope without rotary, on integer data: q and the K / V cache slices bit-exact, the cache rows
+    outside [pos0, pos0 + L) still zero."""
+    ops, _ = _ops()
+    pos0 = 5
+    N = (h + 2 * hk) * dh
+    x = ints(B, L, K, seed=1)
+    w = thin_ternary(N, K, K, seed=2)
+    b = ints(N, seed=3, lo=-2, hi=2)
+    y = x @ w.t() + b
+    assert_bf16_exact(y, "qkv")
+    qr, kr, vr = (O.split_heads(t, dh) for t in y.split([h * dh, hk * dh, hk * dh], dim=-1))
+    q = torch.zeros(B, h, L, dh, dtype=dtype, device=DEV)
+    kc = torch.zeros(B, hk, pos0 + L + 3, dh, dtype=dtype, device=DEV)
+    vc = torch.zeros_like(kc)
+    ops.qkv_rope(x.to(dtype).to(DEV), w.to(dtype).to(DEV), b.to(dtype).to(DEV), h, hk, dh, None, None, pos0, q,
+                 kc[:, :, pos0:pos0 + L], vc[:, :, pos0:pos0 + L])
+    check_exact(q, qr, "q (b, head, l, c)")
+    check_exact(kc[:, :, pos0:pos0 + L], kr, "k (cache slice)")
+    check_exact(vc[:, :, pos0:pos0 + L], vr, "v (cache slice)")
+    for c in (kc, vc):
+        assert float(c[:, :, :pos0].abs().max()) == 0 and float(c[:, :, pos0 + L:].abs().max()) == 0
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])

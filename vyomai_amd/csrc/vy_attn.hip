@@ -903,8 +903,9 @@ int vy_attn_decode_ex(const void* q, int64_t q_sb, int64_t q_sh, const void* k, 
                       int64_t o_sb, int64_t B, int h, int hk, int64_t S, const int* pos_dev, int dh, float scale,
                       int dtype, void* stream) {
   const char* who = "vy_attn_decode";
-  // the resident-context kernel of vy_decode.hip (bf16, head widths 64 / 256, contexts up to 640 / 384 keys); under a
-  // graph the context length is read on the device and the cache capacity is not known here: S bounds it
+  // the resident-context kernel of vy_decode.hip (bf16, head widths 64 / 256, contexts up to 768 / 384 keys: 12
+  // passes of 64 / 32); under a graph the context length is read on the device and the cache capacity is not known
+  // here: S bounds it
   if (dtype == VY_BF16 && q_sh == dh && k_sb == v_sb && k_sh == v_sh && k_sl == v_sl) {
     const int rc = vy_dec_attn(q, q_sb, k, v, k_sb, k_sh, k_sl, out, o_sb, (int)B, h, hk, S, pos_dev ? k_sh / (k_sl ? k_sl : 1) : S,
                                pos_dev, dh, scale, (hipStream_t)stream);

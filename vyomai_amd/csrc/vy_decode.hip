@@ -654,11 +654,19 @@ __global__ __launch_bounds__(64 * NW) void dec_attn_kernel(const DecAttnArgs p) 
   }
 }
 
+// test aid, not part of include/vyom_hip.h: what the last vy_dec_attn call launched, {DH, NP, NT, R}; zeros when it
+// returned VY_ERR_UNSUPPORTED (the caller then runs the row-wise kernel).  Host-side statics only.
+static int g_attn_last[4];
+extern "C" void vy_debug_decode_attn_last(int out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = g_attn_last[i];
+}
+
 template <int DH, int NW, bool NT, int R = 1>
 int dec_attn_go(const DecAttnArgs& a, int B, int Smax, hipStream_t st) {
   constexpr int KPP = NW * (64 / (DH / 8));
   const dim3 grid((unsigned)(R == 1 ? a.h : a.hk), (unsigned)B), block(64 * NW);
   const int np = (Smax + KPP - 1) / KPP;
+  if (np <= 12) { g_attn_last[0] = DH; g_attn_last[1] = np <= 3 ? 3 : np <= 5 ? 5 : np <= 7 ? 7 : np <= 10 ? 10 : 12; g_attn_last[2] = NT; g_attn_last[3] = R; }
   if (np <= 3) hipLaunchKernelGGL((dec_attn_kernel<DH, NW, 3, NT, R>), grid, block, 0, st, a);
   else if (np <= 5) hipLaunchKernelGGL((dec_attn_kernel<DH, NW, 5, NT, R>), grid, block, 0, st, a);
   else if (np <= 7) hipLaunchKernelGGL((dec_attn_kernel<DH, NW, 7, NT, R>), grid, block, 0, st, a);
@@ -940,6 +948,7 @@ int vy_dec_attn(const void* q, int64_t q_sb, const void* k, const void* v, int64
                 int64_t o_sb, int B, int h, int hk, int64_t S, int64_t smax, const int* pos_dev, int dh, float scale,
                 hipStream_t st) {
   static const int on = [] { const char* e = getenv("VY_DEC_ATTN"); return e ? atoi(e) : 1; }();
+  g_attn_last[0] = g_attn_last[1] = g_attn_last[2] = g_attn_last[3] = 0;
   if (!on || (dh != 64 && dh != 256) || hk < 1 || h % hk || S < 1 || c_sl % 8 || c_sh % 8 || c_sb % 8 || q_sb % 8 ||
       ((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)v % 16))
     return VY_ERR_UNSUPPORTED;
