@@ -33,7 +33,17 @@ typedef enum {
   VY_ERR_LAUNCH = -3     /* hipGetLastError() after the launch */
 } vy_status;
 
-typedef enum { VY_ACT_NONE = 0, VY_ACT_GELU_ERF = 1, VY_ACT_GELU_TANH = 2 } vy_act;
+/* Activation fused into a GEMM epilogue: the reference's hidden_act table (VyomAI/layers/ffn.py:7-15) plus the tanh GELU.
+ * silu is x * sigmoid(x) ("swish" is the same function); leaky_relu has nn.LeakyReLU()'s default slope 0.01.  Derivatives
+ * at the kinks follow torch: relu6' = 1 iff 0 < x < 6, leaky_relu' = 1 iff x > 0 (else 0.01).  Codes 0-2 are compiled
+ * into the kernels; the others share one instantiation per kernel family that switches on the code at run time.
+ * Additions to this enum are backward-compatible (old codes keep their values and kernels), so they do not move
+ * vy_abi_version().  An entry point given a code it does not know returns VY_ERR_ARG.
+ * The gated MLP (vy_gated_act_fwd, vy_gemv_gated) takes the GELU codes only. */
+typedef enum {
+  VY_ACT_NONE = 0, VY_ACT_GELU_ERF = 1, VY_ACT_GELU_TANH = 2,
+  VY_ACT_SILU = 3, VY_ACT_TANH = 4, VY_ACT_SIGMOID = 5, VY_ACT_RELU6 = 6, VY_ACT_LEAKY_RELU = 7
+} vy_act;
 /* OR-ed into `act` of vy_linear_fwd / vy_linear_dgrad (training): the tensor saved for backward is act'(x W^T + b)
  * instead of the pre-activation -- the forward epilogue has Phi and the Gaussian of the erf GELU at hand anyway, and
  * the dgrad epilogue (dX = (dY W) * act') becomes one multiply per element instead of an erf + exp evaluation.

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("VY_LIB_PATH") or os.path.join(_HERE, "lib", "libvyom_
 
 VY_F32, VY_BF16 = 0, 1
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH = 0, 1, 2
+# the reference's other hidden_act choices (vy_act in include/vyom_hip.h; leaky_relu: slope 0.01)
+ACT_SILU, ACT_TANH, ACT_SIGMOID, ACT_RELU6, ACT_LEAKY_RELU = 3, 4, 5, 6, 7
 ACT_SAVE_DERIV = 0x100   # saved tensor = act'(pre) instead of pre (include/vyom_hip.h)
 MASK_NONE, MASK_CAUSAL, MASK_KEYPAD, MASK_ADDITIVE = 0, 1, 2, 4
 

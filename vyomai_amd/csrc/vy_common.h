@@ -152,18 +152,66 @@ __device__ __forceinline__ float vy_gelu_erf_grad_fast(float x) {
   return cdf + x * 0.39894228040143267794f * g;
 }
 
+// ---- the reference's other hidden_act choices (VyomAI/layers/ffn.py:7-15) -----------------------
+// sigmoid as 1 / (1 + e^-x) and tanh as 1 - 2 / (1 + e^2x): e^t = inf gives 0 / 1 / -1, never inf - inf or inf / inf.
+// Derivatives at the kinks are torch's: relu6' = 1 iff 0 < x < 6, leaky_relu' = 1 iff x > 0 (slope 0.01 otherwise).
+constexpr float VY_LEAKY_SLOPE = 0.01f;
+__device__ __forceinline__ float vy_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float vy_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float vy_tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+__device__ __forceinline__ float vy_relu6(float x) { return fminf(fmaxf(x, 0.0f), 6.0f); }
+__device__ __forceinline__ float vy_relu6_grad(float x) { return (x > 0.0f && x < 6.0f) ? 1.0f : 0.0f; }
+__device__ __forceinline__ float vy_leaky_relu(float x) { return x > 0.0f ? x : VY_LEAKY_SLOPE * x; }
+__device__ __forceinline__ float vy_leaky_relu_grad(float x) { return x > 0.0f ? 1.0f : VY_LEAKY_SLOPE; }
+
+// ACT value of the one kernel instantiation per family that takes the activation as a run-time code (every vy_act
+// above VY_ACT_GELU_TANH): not a vy_act, never crosses the C ABI
+constexpr int VY_ACT_RUNTIME = 0x40;
+
 template <int ACT>
 __device__ __forceinline__ float vy_act_fwd(float x) {
+  static_assert(ACT != VY_ACT_RUNTIME, "resolve the run-time code with vy_act_dispatch first");
   if constexpr (ACT == VY_ACT_GELU_ERF) return vy_gelu_erf(x);
   else if constexpr (ACT == VY_ACT_GELU_TANH) return vy_gelu_tanh(x);
+  else if constexpr (ACT == VY_ACT_SILU) return x * vy_sigmoid(x);
+  else if constexpr (ACT == VY_ACT_TANH) return tanhf(x);
+  else if constexpr (ACT == VY_ACT_SIGMOID) return vy_sigmoid(x);
+  else if constexpr (ACT == VY_ACT_RELU6) return vy_relu6(x);
+  else if constexpr (ACT == VY_ACT_LEAKY_RELU) return vy_leaky_relu(x);
   else return x;
 }
 template <int ACT>
 __device__ __forceinline__ float vy_act_grad(float x) {
+  static_assert(ACT != VY_ACT_RUNTIME, "resolve the run-time code with vy_act_dispatch first");
   if constexpr (ACT == VY_ACT_GELU_ERF) return vy_gelu_erf_grad(x);
   else if constexpr (ACT == VY_ACT_GELU_TANH) return vy_gelu_tanh_grad(x);
+  else if constexpr (ACT == VY_ACT_SILU) { const float s = vy_sigmoid(x); return s * (1.0f + x * (1.0f - s)); }
+  else if constexpr (ACT == VY_ACT_TANH) { const float t = tanhf(x); return 1.0f - t * t; }
+  else if constexpr (ACT == VY_ACT_SIGMOID) { const float s = vy_sigmoid(x); return s * (1.0f - s); }
+  else if constexpr (ACT == VY_ACT_RELU6) return vy_relu6_grad(x);
+  else if constexpr (ACT == VY_ACT_LEAKY_RELU) return vy_leaky_relu_grad(x);
   else return 1.0f;
 }
+
+// f(integral_constant<int, A>) with A = ACT, or, for ACT == VY_ACT_RUNTIME, A = the activation `code` names: the body
+// is compiled once per run-time code and the switch sits outside the element loops.  `code` is a kernel argument, so
+// the branch is scalar (wave-uniform).  The host admits only known codes; anything else would take the last case.
+template <int ACT, typename F>
+__device__ __forceinline__ void vy_act_dispatch(int code, F&& f) {
+  if constexpr (ACT != VY_ACT_RUNTIME) {
+    f(std::integral_constant<int, ACT>{});
+  } else {
+    switch (code) {
+      case VY_ACT_SILU: f(std::integral_constant<int, VY_ACT_SILU>{}); break;
+      case VY_ACT_TANH: f(std::integral_constant<int, VY_ACT_TANH>{}); break;
+      case VY_ACT_SIGMOID: f(std::integral_constant<int, VY_ACT_SIGMOID>{}); break;
+      case VY_ACT_RELU6: f(std::integral_constant<int, VY_ACT_RELU6>{}); break;
+      default: f(std::integral_constant<int, VY_ACT_LEAKY_RELU>{}); break;
+    }
+  }
+}
+// the codes the run-time instantiation serves (host side)
+static inline bool vy_act_is_runtime(int act) { return act >= VY_ACT_SILU && act <= VY_ACT_LEAKY_RELU; }
 
 __device__ __forceinline__ float vy_wave_sum(float v) {
 #pragma unroll
@@ -180,11 +228,17 @@ __device__ __forceinline__ float vy_wave_max(float v) {
 template <int ACT>
 __device__ __forceinline__ float vy_act_fwd_fast(float x) {
   if constexpr (ACT == VY_ACT_GELU_ERF) return vy_gelu_erf_fast(x);
+  else if constexpr (ACT == VY_ACT_SILU) return x * vy_sigmoid_fast(x);
+  else if constexpr (ACT == VY_ACT_TANH) return vy_tanh_fast(x);
+  else if constexpr (ACT == VY_ACT_SIGMOID) return vy_sigmoid_fast(x);
   else return vy_act_fwd<ACT>(x);
 }
 template <int ACT>
 __device__ __forceinline__ float vy_act_grad_fast(float x) {
   if constexpr (ACT == VY_ACT_GELU_ERF) return vy_gelu_erf_grad_fast(x);
+  else if constexpr (ACT == VY_ACT_SILU) { const float s = vy_sigmoid_fast(x); return s * (1.0f + x * (1.0f - s)); }
+  else if constexpr (ACT == VY_ACT_TANH) { const float t = vy_tanh_fast(x); return 1.0f - t * t; }
+  else if constexpr (ACT == VY_ACT_SIGMOID) { const float s = vy_sigmoid_fast(x); return s * (1.0f - s); }
   else return vy_act_grad<ACT>(x);
 }
 

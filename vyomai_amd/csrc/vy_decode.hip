@@ -59,6 +59,7 @@ struct DecGemmArgs {
   int wt;                              // write-through stores
   const bf16* residual; int ldr;       // DEC_STORE: y = bf16(act(x W^T + b) + residual)
   const bf16* ln_g; const bf16* ln_b; float ln_eps;   // LNP kernels: the rows of X are LayerNorm'ed on the way in
+  int act;                             // the vy_act code, read by the ACT == VY_ACT_RUNTIME instantiations only
 };
 
 // sum over the 64 lanes, result in every lane: four DPP rotations inside each row of 16 lanes, then the two
@@ -262,12 +263,14 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
     if (16 + r16 < p.M) dec_store(dst + 16ll * p.N, acc1, p.wt);
   } else if constexpr (EPI == DEC_STORE) {
     bf16x4 o0, o1;
+    vy_act_dispatch<ACT>(p.act, [&](auto ac) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      // (+ residual in fp32, one rounding: the value dec_finish_ln_kernel normalises)
-      o0[i] = (bf16)(vy_act_fwd_fast<ACT>(acc0[i] + (float)bias4[i]) + (float)res0[i]);
-      o1[i] = (bf16)(vy_act_fwd_fast<ACT>(acc1[i] + (float)bias4[i]) + (float)res1[i]);
-    }
+      for (int i = 0; i < 4; ++i) {
+        // (+ residual in fp32, one rounding: the value dec_finish_ln_kernel normalises)
+        o0[i] = (bf16)(vy_act_fwd_fast<decltype(ac)::value>(acc0[i] + (float)bias4[i]) + (float)res0[i]);
+        o1[i] = (bf16)(vy_act_fwd_fast<decltype(ac)::value>(acc1[i] + (float)bias4[i]) + (float)res1[i]);
+      }
+    });
     bf16* dst = p.y + (long long)r16 * p.ldy + nq0;
     if (r16 < p.M) dec_store(dst, o0, p.wt);
     if (16 + r16 < p.M) dec_store(dst + 16ll * p.ldy, o1, p.wt);
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(256) void dec_finish_ln_kernel(const float* __restr
                                                             const bf16* __restrict__ residual, int ldr,
                                                             const bf16* __restrict__ gamma,
                                                             const bf16* __restrict__ beta, bf16* __restrict__ y,
-                                                            int ldy, float eps, int wt, const DecDbg dbg) {
+                                                            int ldy, float eps, int wt, const DecDbg dbg, int act) {
   __shared__ float red[2][4];
   unsigned long long dbg_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   DEC_STAMP(0)
@@ -406,9 +409,15 @@ __global__ __launch_bounds__(256) void dec_finish_ln_kernel(const float* __restr
       }
     }
 #pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += (float)b4[i][e];
+    if constexpr (ACT != VY_ACT_NONE) {
+      vy_act_dispatch<ACT>(act, [&](auto ac) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] = vy_act_fwd_fast<decltype(ac)::value>(a[e]);
+      });
+    }
+#pragma unroll
     for (int e = 0; e < 4; ++e) {
-      a[e] += (float)b4[i][e];
-      if constexpr (ACT != VY_ACT_NONE) a[e] = vy_act_fwd_fast<ACT>(a[e]);
       a[e] += (float)r4[i][e];
       v[i][e] = ok ? vy_round_bf16(a[e]) : 0.f;
       s += v[i][e];
@@ -823,6 +832,20 @@ int vy_dec_qkv(const void* x, const void* w, const void* bias, const float* cos_
   return VY_OK;
 }
 
+static bool dec_act_known(int act) { return (act >= VY_ACT_NONE && act <= VY_ACT_GELU_TANH) || vy_act_is_runtime(act); }
+
+// the DEC_STORE launch of activation `act`: the GELUs and the identity are compiled in, the other codes share the
+// run-time instantiation.  Returns nonzero for a code no kernel serves (nothing is launched); *rc = dec_gemm_go's result
+static int dec_store_go(DecGemmArgs& a, int K, int act, hipStream_t st, int* rc) {
+  a.act = act;
+  if (act == VY_ACT_GELU_ERF) *rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_ERF>(a, K, 1, st);
+  else if (act == VY_ACT_GELU_TANH) *rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_TANH>(a, K, 1, st);
+  else if (act == VY_ACT_NONE) *rc = dec_gemm_go<DEC_STORE, VY_ACT_NONE>(a, K, 1, st);
+  else if (vy_act_is_runtime(act)) *rc = dec_gemm_go<DEC_STORE, VY_ACT_RUNTIME>(a, K, 1, st);
+  else return 1;
+  return 0;
+}
+
 // y[B][N] = bf16(act(LN(x) W^T + b) + residual), K one chunk.  residual / ln_g / ln_b may be NULL (no residual / x as is)
 int vy_dec_linear_ex(const void* x, int ldx, const void* w, const void* bias, const void* residual, int ldr, const void* ln_g,
                      const void* ln_b, float ln_eps, void* y, int ldy, int B, int N, int K, int act, hipStream_t st) {
@@ -833,9 +856,7 @@ int vy_dec_linear_ex(const void* x, int ldx, const void* w, const void* bias, co
   a.ln_g = (const bf16*)ln_g; a.ln_b = (const bf16*)ln_b; a.ln_eps = ln_eps;
   if (a.ln_g && (K % 8 || ((uintptr_t)ln_g & 15) || ((uintptr_t)ln_b & 15))) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_dec_linear_ex: LayerNorm operands");
   int rc;
-  if (act == VY_ACT_GELU_ERF) rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_ERF>(a, K, 1, st);
-  else if (act == VY_ACT_GELU_TANH) rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_TANH>(a, K, 1, st);
-  else rc = dec_gemm_go<DEC_STORE, VY_ACT_NONE>(a, K, 1, st);
+  if (dec_store_go(a, K, act, st, &rc)) VY_FAIL(VY_ERR_ARG, "vy_dec_linear_ex: unknown activation %d", act);
   if (rc) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_dec_linear_ex: K = %d", K);
   VY_CHECK_LAUNCH("vy_dec_linear_ex");
   return VY_OK;
@@ -848,9 +869,7 @@ int vy_dec_linear(const void* x, int ldx, const void* w, const void* bias, void*
   a.X = (const bf16*)x; a.W = (const bf16*)w; a.bias = (const bf16*)bias;
   a.ldx = ldx; a.ldw = K; a.M = B; a.N = N; a.y = (bf16*)y; a.ldy = ldy;
   int rc;
-  if (act == VY_ACT_GELU_ERF) rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_ERF>(a, K, 1, st);
-  else if (act == VY_ACT_GELU_TANH) rc = dec_gemm_go<DEC_STORE, VY_ACT_GELU_TANH>(a, K, 1, st);
-  else rc = dec_gemm_go<DEC_STORE, VY_ACT_NONE>(a, K, 1, st);
+  if (dec_store_go(a, K, act, st, &rc)) VY_FAIL(VY_ERR_ARG, "vy_dec_linear: unknown activation %d", act);
   if (rc) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_dec_linear: K = %d", K);
   VY_CHECK_LAUNCH("vy_dec_linear");
   return VY_OK;
@@ -861,6 +880,7 @@ int vy_dec_linear_res_ln(const void* x, int ldx, const void* w, const void* bias
                          const void* gamma, const void* beta, float eps, void* y, int ldy, float* part, int B, int N, int K,
                          int act, hipStream_t st) {
   const char* who = "vy_dec_linear_res_ln";
+  if (!dec_act_known(act)) VY_FAIL(VY_ERR_ARG, "%s: unknown activation %d", who, act);
   if (N % 16 || N % 4 || N > 8192) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: N = %d", who, N);
   DecGemmArgs a{};
   a.X = (const bf16*)x; a.W = (const bf16*)w; a.ldx = ldx; a.ldw = K; a.M = B; a.N = N; a.part = part;
@@ -878,10 +898,10 @@ int vy_dec_linear_res_ln(const void* x, int ldx, const void* w, const void* bias
   do {                                                                                                                 \
     if (dbg_on)                                                                                                        \
       hipLaunchKernelGGL((dec_finish_ln_kernel<KS, Q, A, true>), dim3((unsigned)B), dim3(256), 0, st, part, chunks, N, \
-                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg); \
+                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg, act); \
     else                                                                                                               \
       hipLaunchKernelGGL((dec_finish_ln_kernel<KS, Q, A, false>), dim3((unsigned)B), dim3(256), 0, st, part, chunks, N, \
-                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg); \
+                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg, act); \
   } while (0)
 #define FIN_Q(KS, A)                                                                                                   \
   do { if (qpt <= 1) FIN(KS, 1, A); else if (qpt <= 2) FIN(KS, 2, A); else if (qpt <= 4) FIN(KS, 4, A); else FIN(KS, 8, A); } while (0)
@@ -889,7 +909,8 @@ int vy_dec_linear_res_ln(const void* x, int ldx, const void* w, const void* bias
   do { if (chunks <= 1) FIN_Q(1, A); else if (chunks <= 4) FIN_Q(4, A); else if (chunks <= 8) FIN_Q(8, A); else if (chunks <= 16) FIN_Q(16, A); else FIN_Q(24, A); } while (0)
   if (act == VY_ACT_GELU_ERF) FIN_K(VY_ACT_GELU_ERF);
   else if (act == VY_ACT_GELU_TANH) FIN_K(VY_ACT_GELU_TANH);
-  else FIN_K(VY_ACT_NONE);
+  else if (act == VY_ACT_NONE) FIN_K(VY_ACT_NONE);
+  else FIN_K(VY_ACT_RUNTIME);   // checked on entry: one of the run-time codes
 #undef FIN_K
 #undef FIN_Q
 #undef FIN

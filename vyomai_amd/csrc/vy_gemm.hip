@@ -83,11 +83,12 @@ struct EpiPlain {
   VyDrop drop; // dropout on act(x W^T + b) before the residual add (thr == 0: none)
   int wt_store; // large outputs: write-through (sc1) stores from the staged epilogue
   int pre_deriv; // VY_ACT_SAVE_DERIV: `pre` receives act'(x W^T + b) / `gradpre` already holds act' (see include/vyom_hip.h)
+  int act;       // the vy_act code, read by the ACT == VY_ACT_RUNTIME instantiations only (vy_act_dispatch)
 };
 
 template <typename T, int ACT, bool GRAD>
-__device__ __forceinline__ void epi_plain_quad(const EpiPlain<T>& e, float (&v)[4], int64_t m, int n,
-                                               int N) {
+__device__ __forceinline__ void epi_plain_quad_act(const EpiPlain<T>& e, float (&v)[4], int64_t m, int n,
+                                                   int N) {
   if (n >= N) return;
   const bool full = e.vec_ok && (n + 3 < N);
   if (full) {
@@ -142,6 +143,59 @@ __device__ __forceinline__ void epi_plain_quad(const EpiPlain<T>& e, float (&v)[
       if (e.residual2) x += VyT<T>::ld(e.residual2 + m * e.ldr2 + n + i);
       VyT<T>::st(e.y + m * e.ldy + n + i, x);
     }
+  }
+}
+
+// ACT == VY_ACT_RUNTIME: the quad epilogue of the activation e.act names
+template <typename T, int ACT, bool GRAD>
+__device__ __forceinline__ void epi_plain_quad(const EpiPlain<T>& e, float (&v)[4], int64_t m, int n,
+                                               int N) {
+  if constexpr (ACT != VY_ACT_RUNTIME) epi_plain_quad_act<T, ACT, GRAD>(e, v, m, n, N);
+  else vy_act_dispatch<ACT>(e.act, [&](auto a) __attribute__((always_inline)) { epi_plain_quad_act<T, decltype(a)::value, GRAD>(e, v, m, n, N); });
+}
+
+// dgrad: the factor a gradient takes from the saved tensor g -- act' itself (VY_ACT_SAVE_DERIV) or the pre-activation
+template <int ACT>
+__device__ __forceinline__ float gradpre_factor_fast(float g, int pre_deriv, int code) {
+  if constexpr (ACT != VY_ACT_RUNTIME) {
+    return pre_deriv ? g : vy_act_grad_fast<ACT>(g);
+  } else {
+    float r = g;
+    if (!pre_deriv) vy_act_dispatch<ACT>(code, [&](auto a) __attribute__((always_inline)) { r = vy_act_grad_fast<decltype(a)::value>(g); });
+    return r;
+  }
+}
+
+// the activation of one staged 16-byte chunk (gemm_epilogue): v = act(v) in place; dual with VY_ACT_SAVE_DERIV also stores
+// act'(v) to ep.pre
+template <int ACT>
+__device__ __forceinline__ void epi_chunk_act(const EpiPlain<bf16>& ep, float (&v)[8], bool dual, int64_t m, int n, int N) {
+  if (dual && ep.pre_deriv) {
+    // the derivative is saved instead of the pre-activation: for the erf GELU both come out of one
+    // evaluation of Phi and the Gaussian (vy_phi_fast), so the backward epilogue is one multiply per element
+    bf16x8 d8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if constexpr (ACT == VY_ACT_GELU_ERF) {
+        float cdf, gs;
+        vy_phi_fast(v[e], cdf, gs);
+        d8[e] = (bf16)(cdf + v[e] * 0.39894228040143267794f * gs);
+        v[e] = v[e] * cdf;
+      } else {
+        d8[e] = (bf16)vy_act_grad_fast<ACT>(v[e]);
+        v[e] = vy_act_fwd_fast<ACT>(v[e]);
+      }
+    }
+    if (ep.vec_ok && n + 8 <= N) {
+      // read again only by the backward pass, milliseconds later: streamed, so that it does not take the place of
+      // the activation written beside it (FFN2's operand) in the Infinity Cache
+      __builtin_nontemporal_store(d8, reinterpret_cast<bf16x8*>(ep.pre + m * ep.ldy + n));
+    } else {
+      for (int e = 0; e < 8 && n + e < N; ++e) ep.pre[m * ep.ldy + n + e] = d8[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = vy_act_fwd_fast<ACT>(v[e]);
   }
 }
 
@@ -434,33 +488,8 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
           }
         }
         if constexpr (!GRAD && ACT != VY_ACT_NONE) {
-          if (dual && ep.pre_deriv) {
-            // the derivative is saved instead of the pre-activation: for the erf GELU both come out of one
-            // evaluation of Phi and the Gaussian (vy_phi_fast), so the backward epilogue is one multiply per element
-            bf16x8 d8;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              if constexpr (ACT == VY_ACT_GELU_ERF) {
-                float cdf, gs;
-                vy_phi_fast(v[e], cdf, gs);
-                d8[e] = (bf16)(cdf + v[e] * 0.39894228040143267794f * gs);
-                v[e] = v[e] * cdf;
-              } else {
-                d8[e] = (bf16)vy_act_grad_fast<ACT>(v[e]);
-                v[e] = vy_act_fwd_fast<ACT>(v[e]);
-              }
-            }
-            if (ep.vec_ok && n + 8 <= N) {
-              // read again only by the backward pass, milliseconds later: streamed, so that it does not take the place of
-              // the activation written beside it (FFN2's operand) in the Infinity Cache
-              __builtin_nontemporal_store(d8, reinterpret_cast<bf16x8*>(ep.pre + m * ep.ldy + n));
-            } else {
-              for (int e = 0; e < 8 && n + e < N; ++e) ep.pre[m * ep.ldy + n + e] = d8[e];
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = vy_act_fwd_fast<ACT>(v[e]);
-          }
+          if constexpr (ACT != VY_ACT_RUNTIME) epi_chunk_act<ACT>(ep, v, dual, m, n, N);
+          else vy_act_dispatch<ACT>(ep.act, [&](auto a) __attribute__((always_inline)) { epi_chunk_act<decltype(a)::value>(ep, v, dual, m, n, N); });
         }
         if constexpr (!GRAD) {
           if (ep.drop.thr) {   // n is a multiple of 8: one Philox call covers the chunk
@@ -475,7 +504,7 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
             if (ep.gradpre) {
               const bf16x8 g = pf ? p8 : *reinterpret_cast<const bf16x8*>(ep.gradpre + m * ep.ldg + n);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] *= ep.pre_deriv ? (float)g[e] : vy_act_grad_fast<ACT>((float)g[e]);
+              for (int e = 0; e < 8; ++e) v[e] *= gradpre_factor_fast<ACT>((float)g[e], ep.pre_deriv, ep.act);
             }
           }
           if (ep.residual) {
@@ -502,7 +531,7 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
           for (int e = 0; e < 8 && n + e < N; ++e) {
             float x = v[e];
             if constexpr (GRAD) {
-              if (ep.gradpre) { const float gg = (float)ep.gradpre[m * ep.ldg + n + e]; x *= ep.pre_deriv ? gg : vy_act_grad_fast<ACT>(gg); }
+              if (ep.gradpre) { const float gg = (float)ep.gradpre[m * ep.ldg + n + e]; x *= gradpre_factor_fast<ACT>(gg, ep.pre_deriv, ep.act); }
             }
             if (ep.residual) x += (float)ep.residual[m * ep.ldr + n + e];
             if (ep.residual2) x += (float)ep.residual2[m * ep.ldr2 + n + e];
@@ -1765,8 +1794,10 @@ __global__ __launch_bounds__(256) void gemm_skinny16_bf16_kernel(
     for (int r = 0; r < 4; ++r) v[r] = blk == 0 ? acc0[r] : acc1[r];
     if constexpr (EPI == 0) {
       if (fast && !ep.pre && !ep.residual2 && !ep.drop.thr) {   // epi_plain_quad on the prefetched operands
+        vy_act_dispatch<ACT>(ep.act, [&](auto a) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = vy_act_fwd<ACT>(v[i] + (float)bias4[i]);
+          for (int i = 0; i < 4; ++i) v[i] = vy_act_fwd<decltype(a)::value>(v[i] + (float)bias4[i]);
+        });
         if (ep.residual) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] += (float)res4[blk][i];
@@ -2018,8 +2049,10 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16* __restrict__
       ep.y[m * ep.ldy + n] = (bf16)x;
     } else if constexpr (EPI == 0) {
       if (ep.bias) x += (float)ep.bias[n];
-      if (ep.pre) ep.pre[m * ep.ldy + n] = (bf16)(ep.pre_deriv ? vy_act_grad<ACT>(vy_round_bf16(x)) : x);
-      x = vy_act_fwd<ACT>(x);
+      vy_act_dispatch<ACT>(ep.act, [&](auto a) __attribute__((always_inline)) {
+        if (ep.pre) ep.pre[m * ep.ldy + n] = (bf16)(ep.pre_deriv ? vy_act_grad<decltype(a)::value>(vy_round_bf16(x)) : x);
+        x = vy_act_fwd<decltype(a)::value>(x);
+      });
       if (ep.drop.thr) {
         uint32_t lots[4];
         vy_drop_lots(ep.drop, m, n >> 3, lots);
@@ -2149,6 +2182,7 @@ int linear_impl(const void* x, int64_t ldx, const void* w, int64_t ldw, const vo
   EpiPlain<T> ep;
   ep.pre_deriv = (act & VY_ACT_SAVE_DERIV) ? 1 : 0;
   act &= ~VY_ACT_SAVE_DERIV;
+  ep.act = act;
   ep.bias = (const T*)bias; ep.residual = (const T*)residual; ep.ldr = ldr;
   ep.residual2 = (const T*)residual2; ep.ldr2 = ldr2;
   if (residual2 && !residual) VY_FAIL(VY_ERR_ARG, "%s: add_to2 without add_to", who);
@@ -2176,11 +2210,15 @@ int linear_impl(const void* x, int64_t ldx, const void* w, int64_t ldw, const vo
     if (act == VY_ACT_NONE) VY_GO(VY_ACT_NONE, false);
     else if (act == VY_ACT_GELU_ERF) VY_GO(VY_ACT_GELU_ERF, false);
     else if (act == VY_ACT_GELU_TANH) VY_GO(VY_ACT_GELU_TANH, false);
+    else if (vy_act_is_runtime(act)) VY_GO(VY_ACT_RUNTIME, false);   // one instantiation for the other codes: ep.act
     else VY_FAIL(VY_ERR_ARG, "%s: unknown activation %d", who, act);
   } else {
     if (act == VY_ACT_NONE || !gradpre) VY_GO(VY_ACT_NONE, true);
     else if (act == VY_ACT_GELU_ERF) VY_GO(VY_ACT_GELU_ERF, true);
     else if (act == VY_ACT_GELU_TANH) VY_GO(VY_ACT_GELU_TANH, true);
+    // a saved act' is only multiplied in, whatever the activation was: the identity's kernels do that
+    else if (vy_act_is_runtime(act) && ep.pre_deriv) VY_GO(VY_ACT_NONE, true);
+    else if (vy_act_is_runtime(act)) VY_GO(VY_ACT_RUNTIME, true);
     else VY_FAIL(VY_ERR_ARG, "%s: unknown activation %d", who, act);
   }
 #undef VY_GO

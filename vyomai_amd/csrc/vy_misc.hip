@@ -900,6 +900,12 @@ extern "C" int vy_act_bwd(const void* dy, int64_t lddy, const void* pre, int64_t
   else if (dtype == VY_BF16 && act == VY_ACT_GELU_TANH) AB_GO(bf16, VY_ACT_GELU_TANH);
   else if (dtype == VY_F32 && act == VY_ACT_GELU_ERF) AB_GO(float, VY_ACT_GELU_ERF);
   else if (dtype == VY_F32 && act == VY_ACT_GELU_TANH) AB_GO(float, VY_ACT_GELU_TANH);
+  // the reference's other hidden_act choices: an elementwise pass, one small kernel per code
+#define AB_CODE(A)                                          \
+  else if (dtype == VY_BF16 && act == A) AB_GO(bf16, A);    \
+  else if (dtype == VY_F32 && act == A) AB_GO(float, A);
+  AB_CODE(VY_ACT_SILU) AB_CODE(VY_ACT_TANH) AB_CODE(VY_ACT_SIGMOID) AB_CODE(VY_ACT_RELU6) AB_CODE(VY_ACT_LEAKY_RELU)
+#undef AB_CODE
   else VY_FAIL(VY_ERR_ARG, "vy_act_bwd: unsupported act %d / dtype %d", act, dtype);
 #undef AB_GO
   VY_CHECK_LAUNCH("vy_act_bwd");

@@ -2,7 +2,7 @@
 LN(dropout(out(act(intermediate(x)))) + input_tensor), width multiplier*hidden (NOT
 config.intermediate_size, like the reference :19-23).
 
-MI355X: two MFMA GEMM launches -- bias+GELU in the first epilogue, bias+dropout+residual in the
+MI355X: two MFMA GEMM launches -- bias+activation in the first epilogue, bias+dropout+residual in the
 second -- and one LayerNorm launch."""
 from __future__ import annotations
 
@@ -11,12 +11,14 @@ from typing import Union
 import torch
 import torch.nn as nn
 
-from .._lib import ACT_GELU_ERF, ACT_GELU_TANH
+from .._lib import (ACT_GELU_ERF, ACT_GELU_TANH, ACT_LEAKY_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU,
+                    ACT_TANH)
 
-# activations with a fused HIP epilogue; the reference's table (:7-15) also lists leaky_relu,
-# relu6, sigmoid, silu/swish, tanh, which no shipped model or test selects.
-_FUSED_ACT = {"gelu": ACT_GELU_ERF, "gelu_tanh": ACT_GELU_TANH, "gelu_pytorch_tanh": ACT_GELU_TANH}
-_REFERENCE_ACTS = {"gelu", "leaky_relu", "relu6", "sigmoid", "silu", "swish", "tanh"}
+# every name of the reference's table (:7-15) has a fused HIP epilogue ("swish" is silu, leaky_relu has
+# nn.LeakyReLU()'s default slope); gelu_tanh is this package's addition for the PaliGemma-shape model.
+_FUSED_ACT = {"gelu": ACT_GELU_ERF, "gelu_tanh": ACT_GELU_TANH, "gelu_pytorch_tanh": ACT_GELU_TANH,
+              "leaky_relu": ACT_LEAKY_RELU, "relu6": ACT_RELU6, "sigmoid": ACT_SIGMOID,
+              "silu": ACT_SILU, "swish": ACT_SILU, "tanh": ACT_TANH}
 
 
 class FeedForward(nn.Module):
@@ -27,12 +29,8 @@ class FeedForward(nn.Module):
         self.dropout = nn.Dropout(config.hidden_dropout_prob)
         self.layernorm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
         name = getattr(config, "hidden_act", None)
-        if name in _FUSED_ACT:
-            self.act = _FUSED_ACT[name]
-        elif name in _REFERENCE_ACTS:
-            raise NotImplementedError(f"hidden_act={name!r} has no fused MI355X epilogue yet (gelu only)")
-        else:
-            self.act = ACT_GELU_ERF  # unknown names fall back to GELU like the reference (:26-29)
+        # unknown names fall back to GELU like the reference (:26-29)
+        self.act = _FUSED_ACT.get(name, ACT_GELU_ERF)
         self.out = nn.Linear(inner, config.hidden_size)
 
     def forward(self, hidden_state: torch.Tensor, input_tensor: torch.Tensor) -> torch.Tensor:
