@@ -12,7 +12,8 @@
 //     (ds_read_b128) from a [rows][64] bf16 LDS image; the image is XOR-swizzled on the 16-B
 //     chunk index with (row>>1)&7, applied on the *source address* of the
 //     global_load_lds_dwordx4 (the LDS destination of an LDS-DMA is lane-linear) and again on
-//     the read -- conflict-free for the 16-lane groups of ds_read_b128;
+//     the read -- conflict-free for the 16-lane groups of ds_read_b128; that image, its writer and its reader are
+//     GemmTile, which the four LDS-DMA kernels share: each of them adds only its ring schedule;
 //   * the accumulator is kept TRANSPOSED (A operand = W fragment, B operand = X fragment), so a
 //     lane owns one output row m and 4 consecutive columns n per register quad: bias is a
 //     per-register value, residual / RoPE / head-split / stores are 8-byte row-local accesses,
@@ -291,6 +292,10 @@ __device__ __forceinline__ void epi_qkv_quad(const EpiQkv<T>& e, float (&v)[4], 
 // and 100 MHz ticks (s_memrealtime) here; vy_debug_gemm_clock() reads and clears them
 // (tools/gemm_clock.py): cycles / ticks * 100 = the shader clock in MHz the GEMMs really ran at.
 __device__ unsigned long long vy_gemm_clk[6];   // cycles, ticks, launches, prologue / k-loop / epilogue cycles
+// bits of the knob the launchers hand to the tile kernels (the value of VY_GEMM_ROT)
+constexpr int VY_KNOB_ROT = 1;        // per-tile rotated k order (32 x 32 x 16 kernel only)
+constexpr int VY_KNOB_CLK = 16;       // the clock probe above (32 x 32 x 16 kernel only)
+constexpr int VY_KNOB_NO_BAND = 32;   // tile_of: the plain XCD run instead of the band walk
 #define VY_CLK_BEGIN(on)                                                         \
   const bool clk_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0;              \
   unsigned long long clk_c0_ = 0, clk_w0_ = 0, clk_m_ = 0;                       \
@@ -674,6 +679,118 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
   }
 }
 
+// ---- tile core of the bf16 LDS-DMA kernels -------------------------------------------------------
+// One k-stage of an operand in LDS is rows of BK bf16 (ROWB = 128 bytes, 8 chunks of 16 bytes) in 1-KiB pieces
+// of 8 rows, chunk c of row R stored at chunk position c ^ ((R >> 1) & 7).  This struct is that format: its
+// writer (per-lane global_load_lds sources, one piece per wave-instruction, wave w owns pieces w, w + NW, ...)
+// and its reader (the MFMA fragment addresses), plus the wave's accumulators and the MFMA block.  WHEN a stage
+// is requested, which vmcnt is waited for and where the barrier sits is the schedule -- that is the kernels'.
+// MF16: 16 x 16 blocks of mfma_f32_16x16x32_bf16 (fragment rows lane & 15, chunk 4 ks + (lane >> 4), 2 k-steps
+// per stage); else 32 x 32 blocks of mfma_f32_32x32x16_bf16 (rows lane & 31, chunk 2 ks + (lane >> 5), 4 k-steps).
+// The swizzle is conflict-free for both.
+template <int BM, int BN, int WGM, int WGN, bool MF16>
+struct GemmTile {
+  static constexpr int NW = WGM * WGN;
+  static constexpr int FR = MF16 ? 16 : 32;                       // rows of an MFMA block
+  static constexpr int KS = MF16 ? 2 : 4;                         // k-steps per stage
+  static constexpr int TM = BM / (FR * WGM), TN = BN / (FR * WGN);   // the wave's sub-tile: TN x TM blocks
+  static_assert(TM * FR * WGM == BM && TN * FR * WGN == BN, "tile / wave layout mismatch");
+  static constexpr int PX = BM / 8, PW = BN / 8;                  // 1-KiB LDS-DMA pieces (8 rows) per stage
+  static constexpr int GX = (PX + NW - 1) / NW, GW = (PW + NW - 1) / NW;   // LDS-DMA instructions per wave and stage
+  // one row tile (the 32-row decode launches: the vocabulary projection, 77 MB): every weight tile is read by one
+  // workgroup once per step -- streamed (aux 2 = nt) so that it does not push the layer weights out of the
+  // Infinity Cache (see dec_load_stream, vy_decode.hip)
+  static constexpr int W_AUX = BM == 32 ? 2 : 0;
+  typedef bf16x8 XFrag[TM];
+  typedef bf16x8 WFrag[TN];
+
+  int lane, wave, wm, wn, K;
+  const bf16* xsrc[GX]; int xk[GX];
+  const bf16* wsrc[GW]; int wk[GW];
+  const bf16* zero;
+  bool ktail;
+  typename AccTile<BM, BN, WGM, WGN, MF16>::type acc;
+  unsigned xa[KS], wa[KS];   // fragment addresses of k-step ks in an X region at `lds` / a W region at `lds + w_off`
+
+  __device__ __forceinline__ GemmTile(const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw,
+                                      int m0, int n0, int M, int N, int K_, int wave_, const char* lds, int w_off) {
+    lane = threadIdx.x & 63;
+    wave = wave_;
+    wm = wave / WGN, wn = wave % WGN;
+    K = K_;
+    // per-lane LDS-DMA source pointers (row clamped for M/N tails, chunk pre-swizzled)
+    const int lrow = lane >> 3, slot = lane & 7;
+#pragma unroll
+    for (int t = 0; t < GX; ++t) src_of(X, ldx, m0, M, (wave + NW * t) * 8 + lrow, slot, xsrc[t], xk[t]);
+#pragma unroll
+    for (int t = 0; t < GW; ++t) src_of(W, ldw, n0, N, (wave + NW * t) * 8 + lrow, slot, wsrc[t], wk[t]);
+    zero = reinterpret_cast<const bf16*>(vy_zero16);
+    ktail = (K % BK) != 0;
+#pragma unroll
+    for (int i = 0; i < TN; ++i)
+#pragma unroll
+      for (int j = 0; j < TM; ++j)
+#pragma unroll
+        for (int r = 0; r < (MF16 ? 4 : 16); ++r) acc[i][j][r] = 0.f;
+    // One base address per k-step; the block index goes into the read's offset field (read_frags)
+    const int fr = lane & (FR - 1), fh = lane / FR, fsw = (fr >> 1) & 7;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int coff = (((ks * (8 / KS) + fh) ^ fsw) << 4);
+      xa[ks] = vy_lds_addr(lds) + (wm * FR * TM + fr) * ROWB + coff;
+      wa[ks] = vy_lds_addr(lds) + w_off + (wn * FR * TN + fr) * ROWB + coff;
+    }
+  }
+  // the lane's 16 bytes of tile row R of an operand: the row's chunk g that belongs at chunk position `slot`
+  static __device__ __forceinline__ void src_of(const bf16* P, int64_t ld, int r0, int rows, int R, int slot,
+                                                const bf16*& src, int& k) {
+    const int g = slot ^ ((R >> 1) & 7);
+    int gr = r0 + R; gr = gr < rows ? gr : rows - 1;
+    src = P + (int64_t)gr * ld + g * 8;
+    k = g * 8;
+  }
+  // request k-slice kt of the operand into the stage region at `dst`; chunks past K come from vy_zero16
+  template <int G, int P, int AUX>
+  __device__ __forceinline__ void issue(const bf16* const (&src)[G], const int (&kk)[G], int kt, char* dst) const {
+    const int k0 = kt * BK;
+#pragma unroll
+    for (int t = 0; t < G; ++t) {
+      if (P % NW == 0 || wave + NW * t < P) {   // (the 32 x 128 tile has fewer X pieces than waves)
+        const bf16* s = src[t] + k0;
+        if (ktail && k0 + kk[t] >= K) s = zero;
+        __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(dst + (wave + NW * t) * 1024), 16, 0, AUX);
+      }
+    }
+  }
+  __device__ __forceinline__ void issue_x(int kt, char* dst) const { issue<GX, PX, 0>(xsrc, xk, kt, dst); }
+  __device__ __forceinline__ void issue_w(int kt, char* dst) const { issue<GW, PW, W_AUX>(wsrc, wk, kt, dst); }
+  // The fragment reads are the hidden asm form (vy_common.h): hipcc would retire its own ds_reads with lgkmcnt(0),
+  // i.e. wait for the fragments it has JUST requested as well, exposing the LDS latency on every other k-step; the
+  // kernels double-buffer the fragments in registers and a k-step waits with a counted lgkmcnt for exactly its own
+  // TN + TM reads, then ties them (tie_frags) so that the MFMAs that read them stay below the wait.
+  static __device__ __forceinline__ void read_frags(unsigned wbase, unsigned xbase, WFrag& w_, XFrag& x_) {
+    vy_static_for<TN>([&](auto i_c) { constexpr int i = decltype(i_c)::value; w_[i] = vy_lds_read128_off<i * FR * ROWB>(wbase); });
+    vy_static_for<TM>([&](auto j_c) { constexpr int j = decltype(j_c)::value; x_[j] = vy_lds_read128_off<j * FR * ROWB>(xbase); });
+  }
+  static __device__ __forceinline__ void tie_frags(WFrag& w_, XFrag& x_) {
+#pragma unroll
+    for (int i = 0; i < TN; ++i) vy_tie(w_[i]);
+#pragma unroll
+    for (int j = 0; j < TM; ++j) vy_tie(x_[j]);
+  }
+  __device__ __forceinline__ void mma(WFrag& w_, XFrag& x_) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < TN; ++i)
+#pragma unroll
+      for (int j = 0; j < TM; ++j) {
+        if constexpr (MF16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_[i], x_[j], acc[i][j], 0, 0, 0);
+        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_[i], x_[j], acc[i][j], 0, 0, 0);
+      }
+    __builtin_amdgcn_s_setprio(0);
+  }
+};
+
 // tile BM x BN x 64 with WGM x WGN waves, each owning a (BM/WGM) x (BN/WGN) sub-tile as
 // TN x TM blocks of 32x32.  Shapes in use:
 //   256 x 192, 4x2 waves (512 threads, 1 workgroup per CU, 112 KiB LDS): the training shapes.  Loads
@@ -684,158 +801,65 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
 template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
-    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int rot_on) {
-  constexpr int NW = WGM * WGN, NT = 64 * NW;
-  constexpr int TM = BM / (32 * WGM), TN = BN / (32 * WGN);
-  static_assert(TM * 32 * WGM == BM && TN * 32 * WGN == BN, "tile / wave layout mismatch");
-  VY_CLK_BEGIN(rot_on & 16)
-  constexpr int PX = BM / 8, PW = BN / 8;               // 1-KiB LDS-DMA pieces (8 rows) per stage
-  constexpr int GX = (PX + NW - 1) / NW, GW = (PW + NW - 1) / NW;
+    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
+  typedef GemmTile<BM, BN, WGM, WGN, false> Tile;
+  constexpr int TM = Tile::TM, TN = Tile::TN;
+  VY_CLK_BEGIN(knob & VY_KNOB_CLK)
   constexpr int STAGE = (BM + BN) * ROWB;
-  constexpr int EROW = BN * 2 + 16;                     // epilogue tile row (padded)
   constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI, 1));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(rot_on & 32), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  // ---- per-lane LDS-DMA source pointers (row clamped for M/N tails, chunk pre-swizzled) ----
-  const int lrow = lane >> 3, slot = lane & 7;
-  const bf16* xsrc[GX]; int xk[GX];
-  const bf16* wsrc[GW]; int wk[GW];
-#pragma unroll
-  for (int t = 0; t < GX; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gm = m0 + R; gm = gm < M ? gm : M - 1;
-    xsrc[t] = X + (int64_t)gm * ldx + g * 8;
-    xk[t] = g * 8;
-  }
-#pragma unroll
-  for (int t = 0; t < GW; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gn = n0 + R; gn = gn < N ? gn : N - 1;
-    wsrc[t] = W + (int64_t)gn * ldw + g * 8;
-    wk[t] = g * 8;
-  }
-  const bf16* zero = reinterpret_cast<const bf16*>(vy_zero16);
-  const bool ktail = (K % BK) != 0;
+  Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, BM * ROWB);
   const int KT = (K + BK - 1) / BK;
 
   // optional (VY_GEMM_ROT=1) per-tile rotated k order, an experiment: workgroups that share an operand
   // run in lockstep and request the same not-yet-resident lines at once.  tools/probe/ldsdma_probe
   // shows the L2 merges such requests well (72 GB/s per CU for a 4-way shared stream against 28
   // unshared), and the rotation measured 1-5 % slower -- kept off.
-  const int rot = (rot_on & 1) ? (tile_n * 2 + tile_m) % KT : 0;
+  const int rot = (knob & VY_KNOB_ROT) ? (tile_n * 2 + tile_m) % KT : 0;
   auto stage = [&](int kt, int buf) {
-    char* xb = smem + buf * STAGE;
-    char* wb = xb + BM * ROWB;
     int kr = kt + rot;
     kr = kr >= KT ? kr - KT : kr;
-    const int k0 = kr * BK;
-#pragma unroll
-    for (int t = 0; t < GX; ++t) {
-      if (PX % NW == 0 || wave + NW * t < PX) {
-        const bf16* s = xsrc[t] + k0;
-        if (ktail && k0 + xk[t] >= K) s = zero;
-        __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s,
-                                         (VY_LDS void*)(xb + (wave + NW * t) * 1024), 16, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < GW; ++t) {
-      if (PW % NW == 0 || wave + NW * t < PW) {
-        const bf16* s = wsrc[t] + k0;
-        if (ktail && k0 + wk[t] >= K) s = zero;
-        // one row tile (the 32-row decode launches: the vocabulary projection, 77 MB): every weight tile is read by one
-        // workgroup once per step -- streamed (aux 2 = nt) so that it does not push the layer weights out of the
-        // Infinity Cache (see dec_load_stream, vy_decode.hip)
-        constexpr int W_AUX = BM == 32 ? 2 : 0;
-        __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s,
-                                         (VY_LDS void*)(wb + (wave + NW * t) * 1024), 16, 0, W_AUX);
-      }
-    }
+    t.issue_x(kr, smem + buf * STAGE);
+    t.issue_w(kr, smem + buf * STAGE + BM * ROWB);
   };
 
-  f32x16 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // fragment read offsets: row = base32 + (lane&31); chunk = 2*ks + (lane>>5), swizzle (row>>1)&7
-  const int fr = lane & 31, fh = lane >> 5, fsw = (fr >> 1) & 7;
-  const int xrow_off = (wm * 32 * TM + fr) * ROWB;
-  const int wrow_off = (wn * 32 * TN + fr) * ROWB;
-
-  // Fragments are double-buffered in registers: the reads of k-step ks+1 are issued before the MFMAs
-  // of k-step ks.  The reads are the hidden asm form (vy_common.h): hipcc would retire its own
-  // ds_reads with lgkmcnt(0), i.e. wait for the fragments it has JUST requested as well, exposing
-  // the LDS latency on every other k-step; here a k-step waits with a counted lgkmcnt for exactly
-  // its own TN + TM reads.  One base address per (buffer, k-step); the 32-row fragment index goes
-  // into the instruction's offset field.
-  unsigned xa[4], wa[4];  // buffer 0; buffer 1 is + STAGE (an add per stage, not a register-array index)
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const int coff = (((ks * 2 + fh) ^ fsw) << 4);
-    xa[ks] = vy_lds_addr(smem) + xrow_off + coff;
-    wa[ks] = vy_lds_addr(smem) + BM * ROWB + wrow_off + coff;
-  }
-  bf16x8 wf[2][TN], xf[2][TM];
-  auto read_frags = [&](unsigned wbase, unsigned xbase, bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    vy_static_for<TN>([&](auto i_c) { constexpr int i = decltype(i_c)::value; w_[i] = vy_lds_read128_off<i * 32 * ROWB>(wbase); });
-    vy_static_for<TM>([&](auto j_c) { constexpr int j = decltype(j_c)::value; x_[j] = vy_lds_read128_off<j * 32 * ROWB>(xbase); });
-  };
-  auto tie_frags = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-#pragma unroll
-    for (int i = 0; i < TN; ++i) vy_tie(w_[i]);
-#pragma unroll
-    for (int j = 0; j < TM; ++j) vy_tie(x_[j]);
-  };
-
+  typename Tile::WFrag wf[2];   // fragments of k-step ks + 1 are read before the MFMAs of k-step ks
+  typename Tile::XFrag xf[2];
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  read_frags(wa[0], xa[0], wf[0], xf[0]);
+  t.read_frags(t.wa[0], t.xa[0], wf[0], xf[0]);
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < KT) stage(kt + 1, cur ^ 1);
-    const unsigned boff = cur * STAGE;
+    const unsigned boff = cur * STAGE;   // buffer 1 is + STAGE (an add per stage, not a register-array index)
     unsigned xb4[4], wb4[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) { xb4[ks] = xa[ks] + boff; wb4[ks] = wa[ks] + boff; }
+    for (int ks = 0; ks < 4; ++ks) { xb4[ks] = t.xa[ks] + boff; wb4[ks] = t.wa[ks] + boff; }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       if (ks < 3) {
-        read_frags(wb4[ks + 1], xb4[ks + 1], wf[(ks + 1) & 1], xf[(ks + 1) & 1]);
+        t.read_frags(wb4[ks + 1], xb4[ks + 1], wf[(ks + 1) & 1], xf[(ks + 1) & 1]);
         asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
-      tie_frags(wf[ks & 1], xf[ks & 1]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks & 1][i], xf[ks & 1][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
+      t.tie_frags(wf[ks & 1], xf[ks & 1]);
+      t.mma(wf[ks & 1], xf[ks & 1]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (kt + 1 < KT) read_frags(wa[0] + (STAGE - boff), xa[0] + (STAGE - boff), wf[0], xf[0]);
+    if (kt + 1 < KT) t.read_frags(t.wa[0] + (STAGE - boff), t.xa[0] + (STAGE - boff), wf[0], xf[0]);
   }
   // the epilogue reuses the stage buffers: every LDS read above has been retired (last k-step: lgkmcnt(0))
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD>(acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD>(t.acc, smem, m0, n0, M, N, ep, eq);
   VY_CLK_END()
 }
 
@@ -862,101 +886,26 @@ template <int BN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(512) void gemm_nt_bf16_x3m16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
     int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
-  constexpr int BM = 256, WGM = 4, WGN = 2, NW = 8;
-  constexpr int TM = BM / (16 * WGM), TN = BN / (16 * WGN);   // 4, 6
-  constexpr int PX = BM / 8, PW = BN / 8;
-  constexpr int GX = PX / NW, GW = PW / NW;
-  static_assert(GX * NW == PX && GW * NW == PW, "pieces must divide over the waves");
+  constexpr int BM = 256, WGM = 4, WGN = 2;
+  typedef GemmTile<BM, BN, WGM, WGN, true> Tile;
+  constexpr int TM = Tile::TM, TN = Tile::TN, GX = Tile::GX;   // 4, 6 (BN = 192), 4
+  static_assert(Tile::PX % Tile::NW == 0 && Tile::PW % Tile::NW == 0, "pieces must divide over the waves");
   constexpr int XT = BM * ROWB, WT = BN * ROWB;
   constexpr int WOFF = 3 * XT;
   constexpr int LDS_BYTES = vy_cmax(3 * XT + 2 * WT, epi_lds_bytes(BM, BN, EPI, 1));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & 32), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  const int lrow = lane >> 3, slot = lane & 7;
-  const bf16* xsrc[GX]; int xk[GX];
-  const bf16* wsrc[GW]; int wk[GW];
-#pragma unroll
-  for (int t = 0; t < GX; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gm = m0 + R; gm = gm < M ? gm : M - 1;
-    xsrc[t] = X + (int64_t)gm * ldx + g * 8;
-    xk[t] = g * 8;
-  }
-#pragma unroll
-  for (int t = 0; t < GW; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gn = n0 + R; gn = gn < N ? gn : N - 1;
-    wsrc[t] = W + (int64_t)gn * ldw + g * 8;
-    wk[t] = g * 8;
-  }
-  const bf16* zero = reinterpret_cast<const bf16*>(vy_zero16);
-  const bool ktail = (K % BK) != 0;
+  Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, WOFF);
   const int KT = (K + BK - 1) / BK;
-  auto stage_x = [&](int kt) {
-    char* xb = smem + (kt % 3) * XT;
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int t = 0; t < GX; ++t) {
-      const bf16* s = xsrc[t] + k0;
-      if (ktail && k0 + xk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(xb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
-  };
-  auto stage_w = [&](int kt) {
-    char* wb = smem + WOFF + (kt & 1) * WT;
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int t = 0; t < GW; ++t) {
-      const bf16* s = wsrc[t] + k0;
-      if (ktail && k0 + wk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(wb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
-  };
+  auto stage_x = [&](int kt) { t.issue_x(kt, smem + (kt % 3) * XT); };
+  auto stage_w = [&](int kt) { t.issue_w(kt, smem + WOFF + (kt & 1) * WT); };
 
-  f32x4 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int r16 = lane & 15, kq = lane >> 4, fsw = (r16 >> 1) & 7;
-  unsigned xa[2], wa[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int coff = (((ks * 4 + kq) ^ fsw) << 4);
-    xa[ks] = vy_lds_addr(smem) + (wm * 16 * TM + r16) * ROWB + coff;
-    wa[ks] = vy_lds_addr(smem) + WOFF + (wn * 16 * TN + r16) * ROWB + coff;
-  }
-  bf16x8 wf[2][TN], xf[2][TM];
-  auto read_frags = [&](unsigned wbase, unsigned xbase, bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    vy_static_for<TN>([&](auto i_c) { constexpr int i = decltype(i_c)::value; w_[i] = vy_lds_read128_off<i * 16 * ROWB>(wbase); });
-    vy_static_for<TM>([&](auto j_c) { constexpr int j = decltype(j_c)::value; x_[j] = vy_lds_read128_off<j * 16 * ROWB>(xbase); });
-  };
-  auto tie_frags = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-#pragma unroll
-    for (int i = 0; i < TN; ++i) vy_tie(w_[i]);
-#pragma unroll
-    for (int j = 0; j < TM; ++j) vy_tie(x_[j]);
-  };
-  auto mma = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-      for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_[i], x_[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
+  typename Tile::WFrag wf[2];
+  typename Tile::XFrag xf[2];
   stage_x(0);
   stage_w(0);
   if (KT > 1) stage_x(1);
@@ -964,27 +913,27 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_x3m16_kernel(
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  read_frags(wa[0], xa[0], wf[0], xf[0]);
+  t.read_frags(t.wa[0], t.xa[0], wf[0], xf[0]);
   int xbuf = 0;   // kt % 3
   for (int kt = 0; kt < KT; ++kt) {
     if (kt + 1 < KT) stage_w(kt + 1);
     if (kt + 2 < KT) stage_x(kt + 2);
     const unsigned xo = xbuf * XT, wo = (kt & 1) * WT;
-    read_frags(wa[1] + wo, xa[1] + xo, wf[1], xf[1]);
+    t.read_frags(t.wa[1] + wo, t.xa[1] + xo, wf[1], xf[1]);
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");
-    tie_frags(wf[0], xf[0]);
-    mma(wf[0], xf[0]);
+    t.tie_frags(wf[0], xf[0]);
+    t.mma(wf[0], xf[0]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    tie_frags(wf[1], xf[1]);
-    mma(wf[1], xf[1]);
+    t.tie_frags(wf[1], xf[1]);
+    t.mma(wf[1], xf[1]);
     if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GX) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     xbuf = xbuf == 2 ? 0 : xbuf + 1;
-    if (kt + 1 < KT) read_frags(wa[0] + (WT - wo), xa[0] + xbuf * XT, wf[0], xf[0]);
+    if (kt + 1 < KT) t.read_frags(t.wa[0] + (WT - wo), t.xa[0] + xbuf * XT, wf[0], xf[0]);
   }
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(t.acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -997,119 +946,48 @@ template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
     int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
-  constexpr int NW = WGM * WGN;
-  constexpr int TM = BM / (16 * WGM), TN = BN / (16 * WGN);   // 256 x 256, 4 x 2 waves: 4, 8;  128 x 128, 2 x 2 waves: 4, 4
-  constexpr int PX = BM / 8, PW = BN / 8;
-  constexpr int GX = PX / NW, GW = PW / NW;
-  static_assert(GX * NW == PX && GW * NW == PW, "pieces must divide over the waves");
+  typedef GemmTile<BM, BN, WGM, WGN, true> Tile;
+  constexpr int TM = Tile::TM, TN = Tile::TN;   // 256 x 256, 4 x 2 waves: 4, 8;  128 x 128, 2 x 2 waves: 4, 4
+  static_assert(Tile::PX % Tile::NW == 0 && Tile::PW % Tile::NW == 0, "pieces must divide over the waves");
   constexpr int STAGE = (BM + BN) * ROWB;
   constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI, 1));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & 32), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  const int lrow = lane >> 3, slot = lane & 7;
-  const bf16* xsrc[GX]; int xk[GX];
-  const bf16* wsrc[GW]; int wk[GW];
-#pragma unroll
-  for (int t = 0; t < GX; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gm = m0 + R; gm = gm < M ? gm : M - 1;
-    xsrc[t] = X + (int64_t)gm * ldx + g * 8;
-    xk[t] = g * 8;
-  }
-#pragma unroll
-  for (int t = 0; t < GW; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gn = n0 + R; gn = gn < N ? gn : N - 1;
-    wsrc[t] = W + (int64_t)gn * ldw + g * 8;
-    wk[t] = g * 8;
-  }
-  const bf16* zero = reinterpret_cast<const bf16*>(vy_zero16);
-  const bool ktail = (K % BK) != 0;
+  Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, BM * ROWB);
   const int KT = (K + BK - 1) / BK;
   auto stage = [&](int kt, int buf) {
-    char* xb = smem + buf * STAGE;
-    char* wb = xb + BM * ROWB;
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int t = 0; t < GX; ++t) {
-      const bf16* s = xsrc[t] + k0;
-      if (ktail && k0 + xk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(xb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < GW; ++t) {
-      const bf16* s = wsrc[t] + k0;
-      if (ktail && k0 + wk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(wb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
+    t.issue_x(kt, smem + buf * STAGE);
+    t.issue_w(kt, smem + buf * STAGE + BM * ROWB);
   };
 
-  f32x4 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int r16 = lane & 15, kq = lane >> 4, fsw = (r16 >> 1) & 7;
-  unsigned xa[2], wa[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int coff = (((ks * 4 + kq) ^ fsw) << 4);
-    xa[ks] = vy_lds_addr(smem) + (wm * 16 * TM + r16) * ROWB + coff;
-    wa[ks] = vy_lds_addr(smem) + BM * ROWB + (wn * 16 * TN + r16) * ROWB + coff;
-  }
-  bf16x8 wf[2][TN], xf[2][TM];
-  auto read_frags = [&](unsigned wbase, unsigned xbase, bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    vy_static_for<TN>([&](auto i_c) { constexpr int i = decltype(i_c)::value; w_[i] = vy_lds_read128_off<i * 16 * ROWB>(wbase); });
-    vy_static_for<TM>([&](auto j_c) { constexpr int j = decltype(j_c)::value; x_[j] = vy_lds_read128_off<j * 16 * ROWB>(xbase); });
-  };
-  auto tie_frags = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-#pragma unroll
-    for (int i = 0; i < TN; ++i) vy_tie(w_[i]);
-#pragma unroll
-    for (int j = 0; j < TM; ++j) vy_tie(x_[j]);
-  };
-  auto mma = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-      for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_[i], x_[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
+  typename Tile::WFrag wf[2];
+  typename Tile::XFrag xf[2];
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  read_frags(wa[0], xa[0], wf[0], xf[0]);
+  t.read_frags(t.wa[0], t.xa[0], wf[0], xf[0]);
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < KT) stage(kt + 1, cur ^ 1);
     const unsigned boff = cur * STAGE;
-    read_frags(wa[1] + boff, xa[1] + boff, wf[1], xf[1]);
+    t.read_frags(t.wa[1] + boff, t.xa[1] + boff, wf[1], xf[1]);
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");
-    tie_frags(wf[0], xf[0]);
-    mma(wf[0], xf[0]);
+    t.tie_frags(wf[0], xf[0]);
+    t.mma(wf[0], xf[0]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    tie_frags(wf[1], xf[1]);
-    mma(wf[1], xf[1]);
+    t.tie_frags(wf[1], xf[1]);
+    t.mma(wf[1], xf[1]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (kt + 1 < KT) read_frags(wa[0] + (STAGE - boff), xa[0] + (STAGE - boff), wf[0], xf[0]);
+    if (kt + 1 < KT) t.read_frags(t.wa[0] + (STAGE - boff), t.xa[0] + (STAGE - boff), wf[0], xf[0]);
   }
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(t.acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1134,26 +1012,30 @@ __device__ __forceinline__ void splitk_block_of(int b, int tiles, int S, int& ti
   }
 }
 
+// The split-K workspace, [slice][tile][wave][i][j][lane] x f32x4: where block (i, j) of a wave's accumulators lives.  The
+// index is a sum of one term per coordinate, so both kernels form a base from the coordinates they hold fixed and add
+// the index of the others (zeros elsewhere).
+template <int NW, int TN, int TM>
+__device__ __forceinline__ int64_t splitk_ws_index(int slice, int tiles, int tile, int wave, int i, int j, int lane) {
+  return ((((int64_t)slice * tiles + tile) * NW + wave) * (TN * TM) + (i * TM + j)) * 64 + lane;
+}
+
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_splitk_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
     int K, int tiles_n, int tiles, int S, int kt_per, float* __restrict__ ws) {
-  constexpr int NW = WGM * WGN;
-  constexpr int TM = BM / (16 * WGM), TN = BN / (16 * WGN);
-  constexpr int PX = BM / 8, PW = BN / 8;
-  constexpr int GX = PX / NW, GW = PW / NW;
-  static_assert(GX * NW == PX && GW * NW == PW, "pieces must divide over the waves");
+  typedef GemmTile<BM, BN, WGM, WGN, true> Tile;
+  constexpr int TM = Tile::TM, TN = Tile::TN;
+  static_assert(Tile::PX % Tile::NW == 0 && Tile::PW % Tile::NW == 0, "pieces must divide over the waves");
   constexpr int STAGE = (BM + BN) * ROWB;
   // a slice is 2-16 stages, each a full L2 / MALL round trip: where three stages fit in the CU's 160 KiB (the 256-row
   // all-rows tile: 3 x 48 KiB) two of them stay in flight behind the one being multiplied (counted vmcnt), so a short slice
   // is ONE round trip deep instead of one per stage; the other tiles keep two buffers (one stage ahead)
   constexpr int NBUF = (3 * STAGE <= 160 * 1024 && BM * BN > 128 * 128) ? 3 : 2;
-  constexpr int PIECES = GX + GW;   // LDS-DMA instructions per wave and stage
+  constexpr int PIECES = Tile::GX + Tile::GW;   // LDS-DMA instructions per wave and stage
   __shared__ __attribute__((aligned(16))) char smem[NBUF * STAGE];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile, slice;
   splitk_block_of(blockIdx.x, tiles, S, tile, slice);
   const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
@@ -1162,80 +1044,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_splitk_kernel
   const int kt0 = slice * kt_per;
   const int kt1 = kt0 + kt_per < KT_all ? kt0 + kt_per : KT_all;
 
-  const int lrow = lane >> 3, slot = lane & 7;
-  const bf16* xsrc[GX]; int xk[GX];
-  const bf16* wsrc[GW]; int wk[GW];
-#pragma unroll
-  for (int t = 0; t < GX; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gm = m0 + R; gm = gm < M ? gm : M - 1;
-    xsrc[t] = X + (int64_t)gm * ldx + g * 8;
-    xk[t] = g * 8;
-  }
-#pragma unroll
-  for (int t = 0; t < GW; ++t) {
-    const int R = (wave + NW * t) * 8 + lrow;
-    const int g = slot ^ ((R >> 1) & 7);
-    int gn = n0 + R; gn = gn < N ? gn : N - 1;
-    wsrc[t] = W + (int64_t)gn * ldw + g * 8;
-    wk[t] = g * 8;
-  }
-  const bf16* zero = reinterpret_cast<const bf16*>(vy_zero16);
-  const bool ktail = (K % BK) != 0;
+  Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, BM * ROWB);
   auto stage = [&](int kt, int buf) {
-    char* xb = smem + buf * STAGE;
-    char* wb = xb + BM * ROWB;
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int t = 0; t < GX; ++t) {
-      const bf16* s = xsrc[t] + k0;
-      if (ktail && k0 + xk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(xb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < GW; ++t) {
-      const bf16* s = wsrc[t] + k0;
-      if (ktail && k0 + wk[t] >= K) s = zero;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)s, (VY_LDS void*)(wb + (wave + NW * t) * 1024), 16, 0, 0);
-    }
+    t.issue_x(kt, smem + buf * STAGE);
+    t.issue_w(kt, smem + buf * STAGE + BM * ROWB);
   };
 
-  f32x4 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int r16 = lane & 15, kq = lane >> 4, fsw = (r16 >> 1) & 7;
-  unsigned xa[2], wa[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int coff = (((ks * 4 + kq) ^ fsw) << 4);
-    xa[ks] = vy_lds_addr(smem) + (wm * 16 * TM + r16) * ROWB + coff;
-    wa[ks] = vy_lds_addr(smem) + BM * ROWB + (wn * 16 * TN + r16) * ROWB + coff;
-  }
-  bf16x8 wf[2][TN], xf[2][TM];
-  auto read_frags = [&](unsigned wbase, unsigned xbase, bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    vy_static_for<TN>([&](auto i_c) { constexpr int i = decltype(i_c)::value; w_[i] = vy_lds_read128_off<i * 16 * ROWB>(wbase); });
-    vy_static_for<TM>([&](auto j_c) { constexpr int j = decltype(j_c)::value; x_[j] = vy_lds_read128_off<j * 16 * ROWB>(xbase); });
-  };
-  auto tie_frags = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-#pragma unroll
-    for (int i = 0; i < TN; ++i) vy_tie(w_[i]);
-#pragma unroll
-    for (int j = 0; j < TM; ++j) vy_tie(x_[j]);
-  };
-  auto mma = [&](bf16x8 (&w_)[TN], bf16x8 (&x_)[TM]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-      for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_[i], x_[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
+  typename Tile::WFrag wf[2];
+  typename Tile::XFrag xf[2];
   if (kt0 < kt1) {   // (workgroup-uniform; an empty slice stores zeros)
     const int n = kt1 - kt0;
     stage(kt0, 0);
@@ -1250,22 +1066,22 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_splitk_kernel
       asm volatile("" ::: "memory");
       if (i + NBUF - 1 < n) stage(kt0 + i + NBUF - 1, (i + NBUF - 1) % NBUF);
       const unsigned boff = (unsigned)(i % NBUF) * STAGE;
-      read_frags(wa[0] + boff, xa[0] + boff, wf[0], xf[0]);
-      read_frags(wa[1] + boff, xa[1] + boff, wf[1], xf[1]);
+      t.read_frags(t.wa[0] + boff, t.xa[0] + boff, wf[0], xf[0]);
+      t.read_frags(t.wa[1] + boff, t.xa[1] + boff, wf[1], xf[1]);
       asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");
-      tie_frags(wf[0], xf[0]);
-      mma(wf[0], xf[0]);
+      t.tie_frags(wf[0], xf[0]);
+      t.mma(wf[0], xf[0]);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      tie_frags(wf[1], xf[1]);
-      mma(wf[1], xf[1]);
+      t.tie_frags(wf[1], xf[1]);
+      t.mma(wf[1], xf[1]);
     }
   }
-  // the accumulators as they sit in the registers: [slice][tile][wave][i][j][lane] f32x4
-  f32x4* out = reinterpret_cast<f32x4*>(ws) + (((int64_t)slice * tiles + tile) * NW + wave) * (TN * TM * 64) + lane;
+  // the accumulators as they sit in the registers
+  f32x4* out = reinterpret_cast<f32x4*>(ws) + splitk_ws_index<Tile::NW, TN, TM>(slice, tiles, tile, wave, 0, 0, t.lane);
 #pragma unroll
   for (int i = 0; i < TN; ++i)
 #pragma unroll
-    for (int j = 0; j < TM; ++j) out[(i * TM + j) * 64] = acc[i][j];
+    for (int j = 0; j < TM; ++j) out[splitk_ws_index<Tile::NW, TN, TM>(0, tiles, 0, 0, i, j, 0)] = t.acc[i][j];
 }
 
 // One 64-thread workgroup per 16-ROW BLOCK of a wave's sub-tile (16 x SN outputs, 4 accumulator quads per lane): all S x 4
@@ -1288,14 +1104,13 @@ __global__ __launch_bounds__(64) void gemm_splitk_finish_kernel(
   const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
   const int m0 = tile_m * BM + wm * SM + j * 16, n0 = tile_n * BN + wn * SN;
   if (m0 >= M || n0 >= N) return;   // (workgroup-uniform)
-  const f32x4* in = reinterpret_cast<const f32x4*>(ws) + ((int64_t)tile * NW + wave) * (TN * TM * 64) + j * 64 + lane;
-  const int64_t slice_stride = (int64_t)tiles * NW * (TN * TM * 64);
+  const f32x4* in = reinterpret_cast<const f32x4*>(ws) + splitk_ws_index<NW, TN, TM>(0, tiles, tile, wave, 0, j, lane);
   f32x4 part[SMAX][TN];
 #pragma unroll
   for (int sidx = 0; sidx < SMAX; ++sidx)
     if (sidx < S) {
 #pragma unroll
-      for (int i = 0; i < TN; ++i) part[sidx][i] = in[sidx * slice_stride + (int64_t)i * TM * 64];
+      for (int i = 0; i < TN; ++i) part[sidx][i] = in[splitk_ws_index<NW, TN, TM>(sidx, tiles, 0, 0, i, 0, 0)];
     }
   f32x4 acc[TN][1];
 #pragma unroll
@@ -2072,6 +1887,19 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16* __restrict__
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+// the large-M kernel: a forced variant (8 / 9 / 40 / 41) wins, else the MFMA shape by VY_GEMM_M16 and the tile by width
+enum class LargeM { K32_256x256, K32_256x192, M16_256x256, X3M16_256x192 };
+inline LargeM large_m_kernel(int var, bool m16, bool wide) {
+  switch (var) {
+    case 8: return LargeM::K32_256x256;
+    case 9: return LargeM::K32_256x192;
+    case 40: return LargeM::X3M16_256x192;
+    case 41: return LargeM::M16_256x256;
+  }
+  if (m16) return wide ? LargeM::M16_256x256 : LargeM::X3M16_256x192;
+  return wide ? LargeM::K32_256x256 : LargeM::K32_256x192;
+}
+
 template <int EPI, int ACT, bool GRAD>
 int launch_bf16(const bf16* X, int64_t ldx, const bf16* W, int64_t ldw, int64_t M, int64_t N,
                 int64_t K, const EpiPlain<bf16>& ep, const EpiQkv<bf16>& eq, hipStream_t st) {
@@ -2124,22 +1952,24 @@ int launch_bf16(const bf16* X, int64_t ldx, const bf16* W, int64_t ldw, int64_t 
     // two-stage 32 x 32 x 16 kernel, 40 / 41 force the two default kernels whatever N.  The experimental kernels of rounds
     // 1-2 (persistent pipelined epilogue, two 4-wave workgroups per CU, 4- and 5-slot rings of 32-wide slices, the
     // 32 x 32 x 16 X-ring) measured level or behind these on every box and were removed in round 3.
-    const int var = vy_gemm_variant();
-    const bool wide = (N >= 3072);
-    if (var == 8 || (var != 9 && var != 40 && var != 41 && !vy_m16_on() && wide)) {
-      const int tn2 = (int)vy_cdiv(N, 256);
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
-                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
-    } else if (var == 9 || (var != 40 && var != 41 && !vy_m16_on())) {
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 192, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
-                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
-    } else if (var == 41 || (var != 40 && wide)) {
-      const int tn2 = (int)vy_cdiv(N, 256);
-      hipLaunchKernelGGL((gemm_nt_bf16_m16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
-                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
-    } else {
-      hipLaunchKernelGGL((gemm_nt_bf16_x3m16_kernel<192, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
-                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
+    const int tn2 = (int)vy_cdiv(N, 256);
+    switch (large_m_kernel(vy_gemm_variant(), vy_m16_on(), N >= 3072)) {
+      case LargeM::K32_256x256:
+        hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
+                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
+        break;
+      case LargeM::K32_256x192:
+        hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 192, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
+                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
+        break;
+      case LargeM::M16_256x256:
+        hipLaunchKernelGGL((gemm_nt_bf16_m16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
+                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
+        break;
+      case LargeM::X3M16_256x192:
+        hipLaunchKernelGGL((gemm_nt_bf16_x3m16_kernel<192, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
+                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
+        break;
     }
   }
   return 0;
