@@ -39,7 +39,8 @@ typedef enum {
  * into the kernels; the others share one instantiation per kernel family that switches on the code at run time.
  * Additions to this enum are backward-compatible (old codes keep their values and kernels), so they do not move
  * vy_abi_version().  An entry point given a code it does not know returns VY_ERR_ARG.
- * The gated MLP (vy_gated_act_fwd, vy_gemv_gated) takes the GELU codes only. */
+ * The gated MLP's standalone kernels (vy_gated_act_fwd, vy_gated_act_bwd) take every code, the new ones through the
+ * run-time-switched instantiation; the decode driver's fused matrix-vector form (vy_gemv_gated) takes gelu_tanh only. */
 typedef enum {
   VY_ACT_NONE = 0, VY_ACT_GELU_ERF = 1, VY_ACT_GELU_TANH = 2,
   VY_ACT_SILU = 3, VY_ACT_TANH = 4, VY_ACT_SIGMOID = 5, VY_ACT_RELU6 = 6, VY_ACT_LEAKY_RELU = 7
@@ -157,10 +158,31 @@ int vy_rmsnorm_fwd(const void* x, int64_t ldx, const void* w, void* y, int64_t l
                    int64_t N, float eps, float w_offset, int dtype, void* stream);
 
 /* vy_gated_act_fwd: out[m, i] = act(gate_up[m, i]) * gate_up[m, I + i] -- the GeGLU of GemmaMLP
- * (Examples/paligemma.ipynb cell 11: gelu_tanh(gate_proj(x)) * up_proj(x)) after one packed
- * [gate; up] projection. */
+ * (Examples/paligemma.ipynb cell 11: gelu_tanh(gate_proj(x)) * up_proj(x)) and the SwiGLU of the custom
+ * transformer's MLP (VyomAI/models/custom_transformer.py:88) after one packed [gate; up] projection.  Any vy_act
+ * but VY_ACT_NONE. */
 int vy_gated_act_fwd(const void* gate_up, int64_t ldg, void* out, int64_t ldo, int64_t M, int64_t I,
                      int act, int dtype, void* stream);
+
+/* vy_rmsnorm_bwd: backward of y = x * r * (w_offset + w), r = rsqrt(mean(x^2) + eps), from x alone (no saved
+ * statistics: the row is held in registers, sum x^2 and sum x*g*dy come from the same pass, g = w_offset + w):
+ *   dx = r*g*dy - x * r^3/N * sum(x*g*dy) + add_to        dw[n] (+)= sum_rows dy*x*r
+ * replaces: the autograd of RMSNorm.forward (VyomAI/models/custom_transformer.py:236-241) at its three call sites
+ *   (:269, :286, :488) and the `residual + hidden_states` adds of DecoderLayer (:282, :288): add_to (nullable,
+ *   [M,N]) carries the residual branch's gradient into the same store.
+ * dw fp32 [N], overwritten (beta = 0) or accumulated (beta = 1), deterministic: per-block partials in `ws` (fp32,
+ * at least vy_layernorm_bwd_ws_rows(M) * N elements) are added up in a fixed order, no atomics.
+ * N, every ld: multiples of 8 (bf16) / 4 (f32); operands 16-byte aligned; N <= 8192 (bf16) / 4096 (f32) as forward. */
+int vy_rmsnorm_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w,
+                   const void* add_to, int64_t ldadd, void* dx, int64_t lddx, float* dw, float beta,
+                   float* ws, int64_t M, int64_t N, float eps, float w_offset, int dtype, void* stream);
+
+/* vy_gated_act_bwd: backward of vy_gated_act_fwd from the saved gate_up[M,2I]:
+ *   d_gate_up[m, i] = d_act[m, i] * up * act'(gate)      d_gate_up[m, I + i] = d_act[m, i] * act(gate)
+ * replaces: the autograd of `self.act_fn(self.gate_proj(x)) * self.up_proj(x)` (VyomAI/models/custom_transformer.py:88).
+ * act' at the kinks as in vy_act (torch's conventions).  Every ld a multiple of 8 (bf16) / 4 (f32), 16-byte aligned. */
+int vy_gated_act_bwd(const void* d_act, int64_t lddo, const void* gate_up, int64_t ldg, void* d_gate_up,
+                     int64_t lddg, int64_t M, int64_t I, int act, int dtype, void* stream);
 
 /* vy_rope_fwd: in-place rotary embedding on a (B,heads,L,dh) tensor (strides as above);
  * used when the fused epilogue does not apply.  `inverse` != 0 applies the transpose rotation

@@ -680,3 +680,307 @@ def _wt_padded(param, dtype, ld):
     full = torch.as_strided(wt, (wt.shape[0], ld), (wt.stride(0), 1))
     assert wt.stride(0) == ld
     return full
+
+
+# ------------------------------------------------------------------------------------------
+# Pre-norm residual blocks of the RMSNorm + gated-MLP decoder (reference models/custom_transformer.py)
+# ------------------------------------------------------------------------------------------
+
+
+def _rms_bwd(dy, x, w, eps, add_to=None):
+    """-> (dx + add_to, dw to return to autograd or None when accumulated in place): RMSNorm with w_offset = 0."""
+    dt = x.dtype
+    if _direct(w):
+        dx = ops.rmsnorm_bwd(dy, x, _shadow(w, dt), eps, 0.0, w.grad, True, add_to=add_to)
+        _notify(w)
+        return dx, None
+    dw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
+    dx = ops.rmsnorm_bwd(dy, x, _shadow(w, dt), eps, 0.0, dw, False, add_to=add_to)
+    return dx, dw.to(w.dtype)
+
+
+class PreNormAttentionFn(torch.autograd.Function):
+    """y = x + attn(qkv_rope(RMSNorm(x))) Wo^T: the attention half of the reference's DecoderLayer
+    (models/custom_transformer.py:268-282; biased q/k/v, bias-free o_proj).  `mod` packs q/k/v as the
+    _SelfAttentionBase modules do and carries `o_proj`; inputs after `wo` are its q/k/v parameters in _params() order.
+    The residual branch's gradient is added in the RMSNorm backward's store (vy_rmsnorm_bwd add_to)."""
+
+    @staticmethod
+    def forward(ctx, x, mod, attention_mask, freqs, ln_w, eps, wo, *params):
+        _require_bf16(x)
+        B, L, _ = x.shape
+        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+        dt, dev = x.dtype, x.device
+        if attention_mask is not None and not isinstance(attention_mask, AttnMask):
+            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
+                               "backward kernel")
+        cos, sin, pos0 = resolve_freqs(freqs, dev)
+        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
+        q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
+        k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
+        v = torch.empty_like(k)
+        sw, sb = mod._packed_shadow(dt)
+        ops.qkv_rope(n, sw, sb, h, hk, dh, cos, sin, pos0, q, k, v)
+        lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
+        causal, kp, sp = False, None, 0
+        if attention_mask is not None:
+            causal, kp, sp = attention_mask.causal, attention_mask.keypad, attention_mask.start_pos
+            if kp is not None:
+                kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
+        o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
+        y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+        ctx.save_for_backward(x, n, q, k, v, o, lse)
+        ctx.meta = (mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, n, q, k, v, o, lse = ctx.saved_tensors
+        mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, params = ctx.meta
+        B, L, _ = x.shape
+        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+        dt = x.dtype
+        dy = dy.contiguous()
+        do = ops.linear_dgrad(dy, _wt(wo, dt))
+        dwo, _ = _wgrad(dy, o, wo, None)
+        W = (h + 2 * hk) * dh
+        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
+        dq = packed[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
+        dk = packed[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
+        dv = packed[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
+        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
+                          cos=cos, sin=sin, rope_pos0=pos0)
+        w, b = mod._packed()
+        dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt))
+        grads = _packed_wgrad(mod, packed, n, w, b, params)
+        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        return (dx, None, None, None, dlnw, None, dwo, *grads)
+
+
+def _wt_gate_up(mlp, dtype):
+    """W^T of the packed [gate; up] projection of a gated MLP module (gate_proj / up_proj / _packed_gate_up)."""
+    return _wt_cached(mlp, lambda m: (m.gate_proj.weight._version, m.up_proj.weight._version, WEIGHT_EPOCH[0], dtype),
+                      lambda m: m._packed_gate_up(dtype))
+
+
+def _gate_up_wgrad(dgu, n, wg, wu):
+    """Weight gradients of the packed [gate; up] GEMM, to the two parameters (as _packed_wgrad does for q/k/v)."""
+    I, K = wg.shape
+    if _direct(wg) and _direct(wu) and wu.grad.data_ptr() == wg.grad.data_ptr() + I * K * 4 \
+            and wu.grad.untyped_storage().data_ptr() == wg.grad.untyped_storage().data_ptr():
+        # the trainer lays the two gradients out adjacently: one GEMM writes both
+        dw = torch.as_strided(wg.grad, (2 * I, K), (K, 1))
+        d2, n2 = dgu.view(-1, 2 * I), n.view(-1, K)
+        if _GROUP_WGRADS and d2.shape[0] >= _GROUP_MIN_ROWS and 2 * I < 8192 and 2 * I * K >= 512 * 512 and K % 8 == 0:
+            _wgrad_group.add_tensors(d2, n2, dw, None, [wg, wu])
+        else:
+            ops.linear_wgrad(d2, n2, dw, None, accumulate=True)
+            _notify(wg, wu)
+        return None, None
+    dw = torch.empty((2 * I, K), dtype=torch.float32, device=wg.device)
+    ops.linear_wgrad(dgu, n, dw, None, accumulate=False)
+    outs = []
+    for p, part in ((wg, dw[:I]), (wu, dw[I:])):
+        if _direct(p):
+            p.grad.add_(part)
+            _notify(p)
+            outs.append(None)
+        else:
+            outs.append(part.to(p.dtype))
+    return outs[0], outs[1]
+
+
+class PreNormGatedMlpFn(torch.autograd.Function):
+    """y = x + (act(n Wg^T) * n Wu^T) Wd^T with n = RMSNorm(x): the MLP half of the reference's DecoderLayer
+    (models/custom_transformer.py:76-89, 285-288).  One packed [gate; up] GEMM; gate_up and n are saved, the gated
+    product is recomputed in the backward (one streaming pass) instead of being kept."""
+
+    @staticmethod
+    def forward(ctx, x, mlp, ln_w, eps, act, wg, wu, wd):
+        _require_bf16(x)
+        dt = x.dtype
+        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
+        gu = ops.linear(n, mlp._packed_gate_up(dt))
+        a = ops.gated_act(gu, act)
+        y = ops.linear(a, _shadow(wd, dt), None, residual=x)
+        ctx.save_for_backward(x, n, gu)
+        ctx.meta = (mlp, ln_w, eps, act, wg, wu, wd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, n, gu = ctx.saved_tensors
+        mlp, ln_w, eps, act, wg, wu, wd = ctx.meta
+        dt = x.dtype
+        dy = dy.contiguous()
+        da = ops.linear_dgrad(dy, _wt(wd, dt))
+        dwd, _ = _wgrad(dy, ops.gated_act(gu, act), wd, None)
+        dgu = ops.gated_act_bwd(da, gu, act)
+        dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt))
+        dwg, dwu = _gate_up_wgrad(dgu, n, wg, wu)
+        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        return dx, None, dlnw, None, None, dwg, dwu, dwd
+
+
+class RMSNormFn(torch.autograd.Function):
+    """y = x * rsqrt(mean x^2 + eps) * w (reference models/custom_transformer.py:227-241) on its own: the final norm of
+    the trunk when the hidden state itself is asked for."""
+
+    @staticmethod
+    def forward(ctx, x, w, eps):
+        _require_bf16(x)
+        ctx.save_for_backward(x)
+        ctx.meta = (w, eps)
+        return ops.rmsnorm(x, _shadow(w, x.dtype), eps, 0.0)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        w, eps = ctx.meta
+        dx, dw = _rms_bwd(dy.contiguous(), x, w, eps)
+        return dx, dw, None
+
+
+def _tied_head_backward(buf, V, n, table, table_pending, alpha):
+    """Shared backward of the tied vocabulary projection logits = n E^T: buf ([M, ld], pad columns zero) holds
+    d loss / d logits (to be scaled by the device scalar alpha when given) -> (dn, dE to return to autograd or None).
+    The embedding table receives the vocabulary weight gradient here and, when it also embedded the input ids of
+    this graph (`table_pending`), the embedding scatter later in the same backward: both ACCUMULATE into the one arena
+    gradient (zeroed by zero_grad), this one first, and the table is reported ready by the last of them only -- its
+    bucket must not be reduced or stepped between the two."""
+    dt = n.dtype
+    dn = ops.linear_dgrad(buf, _wt_padded(table, dt, buf.shape[1]))
+    if alpha is not None:
+        dn = dn * alpha.to(dt)
+    logits = buf[:, :V]
+    n2 = n.view(buf.shape[0], -1)
+    if _direct(table):
+        ops.linear_wgrad(logits, n2, table.grad, None, accumulate=True, alpha=alpha)
+        if not table_pending:
+            _notify(table)
+        return dn.view(n.shape), None
+    dtab = torch.empty(table.shape, dtype=torch.float32, device=table.device)
+    ops.linear_wgrad(logits, n2, dtab, None, accumulate=False, alpha=alpha)
+    return dn.view(n.shape), dtab.to(table.dtype)
+
+
+class TiedLMHeadFn(torch.autograd.Function):
+    """logits = n E^T with E the embedding table and no bias (reference models/custom_transformer.py:612-613, 662).
+    The logits row stride is padded and the pad columns are zero, as in LMHeadFn."""
+
+    @staticmethod
+    def forward(ctx, n, table, table_pending):
+        _require_bf16(n)
+        dt = n.dtype
+        V = table.shape[0]
+        ld = _row_stride(V)
+        buf = torch.zeros((*n.shape[:-1], ld), dtype=dt, device=n.device)
+        logits = buf[..., :V]
+        ops.linear(n, _shadow(table, dt), None, out=logits)
+        ctx.save_for_backward(n)
+        ctx.meta = (table, table_pending, ld)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        (n,) = ctx.saved_tensors
+        table, table_pending, ld = ctx.meta
+        V = table.shape[0]
+        buf = torch.zeros((dlogits.numel() // V, ld), dtype=n.dtype, device=dlogits.device)
+        buf[:, :V] = dlogits.reshape(-1, V)
+        dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, None)
+        return dn, dtab, None
+
+
+class ShiftedXentFn(torch.autograd.Function):
+    """mean CE(logits[:, :-1], labels[:, 1:]) with ignore_index over MATERIALISED logits (the reference's
+    ModelForCausalLM.forward with labels, models/custom_transformer.py:664-672): vy_xent_fwd for the loss, vy_xent_bwd
+    on a copy for the gradient.  The fused path that never keeps the logits is TiedLMHeadLossFn."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index):
+        _require_bf16(logits)
+        B, L, V = logits.shape
+        dev = logits.device
+        if logits.stride(-1) != 1 or logits.stride(1) % 8 or logits.stride(0) != L * logits.stride(1):
+            logits = _rehome_logits(logits)
+        l2 = torch.as_strided(logits, (B * L, V), (logits.stride(1), 1), logits.storage_offset())
+        shifted = torch.full((B, L), ignore_index, dtype=torch.long, device=dev)
+        shifted[:, :-1] = labels[:, 1:]
+        shifted = shifted.view(-1)
+        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
+        acc = torch.zeros(2, dtype=torch.float32, device=dev)
+        ops.xent_fwd(l2, shifted, ignore_index, lse, acc[0:1], acc[1:2])
+        ctx.save_for_backward(l2, shifted, lse, acc)
+        ctx.meta = (ignore_index, (B, L, V))
+        return acc[0] / acc[1].clamp_min(1.0)
+
+    @staticmethod
+    def backward(ctx, gout):
+        l2, shifted, lse, acc = ctx.saved_tensors
+        ignore_index, shape = ctx.meta
+        ld = l2.stride(0)
+        buf = torch.empty((l2.shape[0], ld), dtype=l2.dtype, device=l2.device)
+        d2 = buf[:, :l2.shape[1]]
+        d2.copy_(l2)
+        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
+        ops.xent_bwd_(d2, shifted, ignore_index, lse, gs, acc[1:2])
+        return torch.as_strided(buf, shape, (shape[1] * ld, ld, 1)), None, None
+
+
+def _rehome_logits(logits):
+    """logits re-homed in a buffer whose rows are 16-byte aligned (row stride padded, pad columns zero)."""
+    B, L, V = logits.shape
+    ld = _row_stride(V)
+    buf = torch.zeros((B, L, ld), dtype=logits.dtype, device=logits.device)
+    buf[..., :V] = logits
+    return buf[..., :V]
+
+
+class TiedLMHeadLossFn(torch.autograd.Function):
+    """loss = shifted CE(RMSNorm(h) E^T) with E the embedding table: no bias, no transform.  LMHeadLossFn's structure:
+    padded row stride, the logits reduced and overwritten in place by their unit gradient (vy_xent_fused: bf16,
+    V <= 65536; the two-pass pair otherwise), ignore_index -100."""
+
+    @staticmethod
+    def forward(ctx, hidden, labels, ignore_index, ln_w, eps, table, table_pending, err_flag=None):
+        _require_bf16(hidden)
+        dt, dev = hidden.dtype, hidden.device
+        B, L, _ = hidden.shape
+        n = ops.rmsnorm(hidden, _shadow(ln_w, dt), eps, 0.0)
+        V = table.shape[0]
+        ld = _row_stride(V)
+        buf = torch.empty((B * L, ld), dtype=dt, device=dev)
+        if ld != V:
+            buf[:, V:].zero_()  # only the pad columns: the GEMM writes the rest
+        logits = buf[:, :V]
+        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
+        shifted = torch.full((B, L), ignore_index, dtype=torch.long, device=dev)
+        shifted[:, :-1] = labels[:, 1:]
+        shifted = shifted.view(-1)
+        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
+        acc = torch.zeros(2, dtype=torch.float32, device=dev)  # [loss_sum, count]
+        fused = V <= 65536 and dt == BF16
+        if fused:
+            acc[1] = ((shifted != ignore_index) & (shifted >= 0) & (shifted < V)).sum()
+            ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
+        else:
+            ops.xent_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], err_flag)
+        ctx.save_for_backward(hidden, n, buf, shifted, lse, acc)
+        ctx.meta = (ln_w, eps, table, table_pending, ignore_index, fused)
+        return acc[0] / acc[1].clamp_min(1.0)
+
+    @staticmethod
+    def backward(ctx, gout):
+        hidden, n, buf, shifted, lse, acc = ctx.saved_tensors
+        ln_w, eps, table, table_pending, ignore_index, fused = ctx.meta
+        V = table.shape[0]
+        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
+        alpha = None
+        if fused:
+            alpha = gs          # logits already hold the unit gradient
+        else:
+            ops.xent_bwd_(buf[:, :V], shifted, ignore_index, lse, gs, acc[1:2])   # logits <- dlogits
+        dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, alpha)
+        dh, dlnw = _rms_bwd(dn, hidden, ln_w, eps)
+        return dh, None, None, dlnw, None, dtab, None, None

@@ -302,3 +302,42 @@ template <> struct VyT<bf16> {
   static __device__ __forceinline__ float ld(const bf16* p) { return (float)*p; }
   static __device__ __forceinline__ void st(bf16* p, float v) { *p = (bf16)v; }
 };
+
+// 16-byte accesses of the row / streaming kernels (vy_misc.hip, vy_prenorm.hip)
+template <typename T> struct Chunk;  // one 16-byte chunk = VEC elements
+template <> struct Chunk<bf16> {
+  static constexpr int VEC = 8;
+  typedef bf16x8 Raw;
+  static __device__ __forceinline__ void unpack(const Raw& t, float* v) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+  }
+  static __device__ __forceinline__ void load(const bf16* p, float* v) {
+    bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+  }
+  static __device__ __forceinline__ void store(bf16* p, const float* v) {
+    bf16x8 t;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t[e] = (bf16)v[e];
+    *reinterpret_cast<bf16x8*>(p) = t;
+  }
+};
+template <> struct Chunk<float> {
+  static constexpr int VEC = 4;
+  typedef f32x4 Raw;
+  static __device__ __forceinline__ void unpack(const Raw& t, float* v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = t[e];
+  }
+  static __device__ __forceinline__ void load(const float* p, float* v) {
+    f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = t[e];
+  }
+  static __device__ __forceinline__ void store(float* p, const float* v) {
+    f32x4 t = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(p) = t;
+  }
+};

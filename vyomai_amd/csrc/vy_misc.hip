@@ -17,44 +17,6 @@ extern "C" int vy_abi_version(void) { return 5; }
 
 namespace {
 
-template <typename T> struct Chunk;  // one 16-byte chunk = VEC elements
-template <> struct Chunk<bf16> {
-  static constexpr int VEC = 8;
-  typedef bf16x8 Raw;
-  static __device__ __forceinline__ void unpack(const Raw& t, float* v) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-  }
-  static __device__ __forceinline__ void load(const bf16* p, float* v) {
-    bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-  }
-  static __device__ __forceinline__ void store(bf16* p, const float* v) {
-    bf16x8 t;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = (bf16)v[e];
-    *reinterpret_cast<bf16x8*>(p) = t;
-  }
-};
-template <> struct Chunk<float> {
-  static constexpr int VEC = 4;
-  typedef f32x4 Raw;
-  static __device__ __forceinline__ void unpack(const Raw& t, float* v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = t[e];
-  }
-  static __device__ __forceinline__ void load(const float* p, float* v) {
-    f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = t[e];
-  }
-  static __device__ __forceinline__ void store(float* p, const float* v) {
-    f32x4 t = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p) = t;
-  }
-};
-
 // ---- LayerNorm forward: one wave per row, CH chunks per lane -------------------------------
 // mean, then variance about the mean (two reductions on registers): the same two-pass
 // formulation as aten's CPU LayerNorm closely enough for 1e-6 agreement.
@@ -155,22 +117,30 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ 
 }
 
 // ---- gated activation: out[m, i] = act(gu[m, i]) * gu[m, I + i]  (GeGLU / SwiGLU-style MLPs) ----
+// ACT: a GELU code compiled in, or VY_ACT_RUNTIME with the activation named by `code` (the switch sits outside the
+// element loop; bf16 takes the reduced-cost forms, as the GEMM epilogues do for these codes)
 template <typename T, int ACT>
 __global__ void gated_act_kernel(const T* __restrict__ gu, int64_t ldg, T* __restrict__ out, int64_t ldo,
-                                 int64_t M, int I) {
+                                 int64_t M, int I, int code) {
   constexpr int VEC = Chunk<T>::VEC;
   const int nch = I / VEC;
   const int64_t total = M * nch;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t m = i / nch;
-    const int c = (int)(i - m * nch) * VEC;
-    float a[VEC], b[VEC], o[VEC];
-    Chunk<T>::load(gu + m * ldg + c, a);
-    Chunk<T>::load(gu + m * ldg + I + c, b);
+  vy_act_dispatch<ACT>(code, [&](auto a_) {
+    constexpr int A = decltype(a_)::value;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t m = i / nch;
+      const int c = (int)(i - m * nch) * VEC;
+      float a[VEC], b[VEC], o[VEC];
+      Chunk<T>::load(gu + m * ldg + c, a);
+      Chunk<T>::load(gu + m * ldg + I + c, b);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) o[e] = vy_act_fwd<ACT>(a[e]) * b[e];
-    Chunk<T>::store(out + m * ldo + c, o);
-  }
+      for (int e = 0; e < VEC; ++e) {
+        if constexpr (ACT == VY_ACT_RUNTIME && sizeof(T) == 2) o[e] = vy_act_fwd_fast<A>(a[e]) * b[e];
+        else o[e] = vy_act_fwd<A>(a[e]) * b[e];
+      }
+      Chunk<T>::store(out + m * ldo + c, o);
+    }
+  });
 }
 
 // ---- LayerNorm backward -------------------------------------------------------------------
@@ -818,17 +788,22 @@ extern "C" int vy_rmsnorm_fwd(const void* x, int64_t ldx, const void* w, void* y
 extern "C" int vy_gated_act_fwd(const void* gate_up, int64_t ldg, void* out, int64_t ldo, int64_t M, int64_t I, int act,
                                 int dtype, void* stream) {
   if (!gate_up || !out || M <= 0 || I <= 0) VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: bad arguments");
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: bad dtype %d", dtype);
+  if (act != VY_ACT_GELU_ERF && act != VY_ACT_GELU_TANH && !vy_act_is_runtime(act))
+    VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: unsupported act %d", act);
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == VY_BF16 ? 8 : 4;
   if (I % vec || ldg % vec || ldo % vec) VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: I/ld must be multiples of %d", vec);
   const int64_t want = vy_cdiv(M * (I / vec), 256);
   const dim3 grid((unsigned)(want < 8192 ? want : 8192)), block(256);
-#define GA_GO(T, A) hipLaunchKernelGGL((gated_act_kernel<T, A>), grid, block, 0, st, (const T*)gate_up, ldg, (T*)out, ldo, M, (int)I)
+#define GA_GO(T, A) hipLaunchKernelGGL((gated_act_kernel<T, A>), grid, block, 0, st, (const T*)gate_up, ldg, (T*)out, ldo, M, (int)I, act)
   if (dtype == VY_BF16 && act == VY_ACT_GELU_TANH) GA_GO(bf16, VY_ACT_GELU_TANH);
   else if (dtype == VY_BF16 && act == VY_ACT_GELU_ERF) GA_GO(bf16, VY_ACT_GELU_ERF);
   else if (dtype == VY_F32 && act == VY_ACT_GELU_TANH) GA_GO(float, VY_ACT_GELU_TANH);
   else if (dtype == VY_F32 && act == VY_ACT_GELU_ERF) GA_GO(float, VY_ACT_GELU_ERF);
-  else VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: unsupported act %d / dtype %d", act, dtype);
+  // every other vy_act: one instantiation per storage type that switches on the code
+  else if (dtype == VY_BF16) GA_GO(bf16, VY_ACT_RUNTIME);
+  else GA_GO(float, VY_ACT_RUNTIME);
 #undef GA_GO
   VY_CHECK_LAUNCH("vy_gated_act_fwd");
   return VY_OK;

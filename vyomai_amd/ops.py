@@ -630,3 +630,33 @@ def gated_act(gate_up: Tensor, act: int) -> Tensor:
     call("vy_gated_act_fwd", g2.data_ptr(), g2.stride(0), out.data_ptr(), out.stride(0), M, I, act,
          dtype_code(gate_up.dtype), _stream())
     return out.view(*gate_up.shape[:-1], I)
+
+
+def rmsnorm_bwd(dy: Tensor, x: Tensor, w: Tensor, eps: float, w_offset: float, dw: Tensor, accumulate: bool,
+                add_to: Optional[Tensor] = None) -> Tensor:
+    """dx = d/dx [x * rsqrt(mean x^2 + eps) * (w_offset + w)] . dy + add_to; dw (fp32 [N]) (+)= the weight gradient
+    (vy_rmsnorm_bwd: no saved statistics, deterministic dw)."""
+    _need_gpu(dy, x, w, dw, add_to)
+    d2, x2 = _rows(dy), _rows(x)
+    a2 = _rows(add_to) if add_to is not None else None
+    M, N = x2.shape
+    assert dw.dtype == torch.float32 and dw.numel() == N and dw.is_contiguous()
+    dx = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    ws = torch.empty((_lib.load().vy_layernorm_bwd_ws_rows(M) * N,), dtype=torch.float32, device=x.device)
+    call("vy_rmsnorm_bwd", d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0), w.data_ptr(), _ptr(a2),
+         a2.stride(0) if a2 is not None else 0, dx.data_ptr(), dx.stride(0), dw.data_ptr(), 1.0 if accumulate else 0.0,
+         ws.data_ptr(), M, N, float(eps), float(w_offset), dtype_code(x.dtype), _stream())
+    return dx.view(x.shape)
+
+
+def gated_act_bwd(d_act: Tensor, gate_up: Tensor, act: int) -> Tensor:
+    """[d_act * up * act'(gate) | d_act * act(gate)] in gate_up's layout  (vy_gated_act_bwd)."""
+    _need_gpu(d_act, gate_up)
+    d2, g2 = _rows(d_act), _rows(gate_up)
+    M, two_i = g2.shape
+    I = two_i // 2
+    assert d2.shape == (M, I)
+    out = torch.empty((M, two_i), dtype=gate_up.dtype, device=gate_up.device)
+    call("vy_gated_act_bwd", d2.data_ptr(), d2.stride(0), g2.data_ptr(), g2.stride(0), out.data_ptr(), out.stride(0),
+         M, I, act, dtype_code(gate_up.dtype), _stream())
+    return out.view(gate_up.shape)
