@@ -345,6 +345,25 @@ int vy_xent_fused(void* logits, int64_t ld, const int64_t* labels, int64_t ignor
  * never dereferenced: the row counts as ignored (zero loss, zero gradient) and *err_flag (nullable,
  * device int32) is set to 1 for the host to report. */
 
+/* Per-row log-probability of the label, for per-SEQUENCE scores (direct preference optimisation:
+ * Examples/vyom-ai-llm-sft-dpo-training.ipynb, the cells defining compute_logprobs -- log_softmax, gather and
+ * the mask -- and, through it, compute_dpo_loss_batch).  weight[m] (fp32) is the row's share of its sequence's
+ * masked average; rows with weight == 0 are skipped.  Nothing is reduced across rows: the caller sums
+ * weight * logp over each sequence in a fixed order, so two runs agree bit for bit.
+ * fwd:   read-only; lse[m] = logsumexp(logits[m,:V]), logp[m] = logits[m,label] - lse[m]; skipped rows get
+ *        lse = logp = 0.
+ * bwd:   logits[m,:] <- weight[m] * (onehot(label) - softmax(logits[m,:])), in place, from the saved lse (the
+ *        sign of a log-probability, not of a loss); pad columns and skipped rows become 0.
+ * fused: both in ONE pass (bf16, V <= 65536): the logits cross HBM once in each direction.
+ * A label outside [0, V) on a row with weight != 0 is never dereferenced: the row counts as skipped and
+ * *err_flag (nullable, device int32) is set to 1. */
+int vy_logprob_fwd(const void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
+                   float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream);
+int vy_logprob_bwd(void* logits, int64_t ld, const int64_t* labels, const float* weight, const float* lse,
+                   int64_t M, int64_t V, int dtype, void* stream);
+int vy_logprob_fused(void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
+                     float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream);
+
 /* Token embedding (nn.Embedding: VyomAI/models/decoder.py:287, encoder.py:41, multimodel.py):
  * fwd: out[m,:] = table[ids[m],:] (bf16 or fp32).  Ids outside [0,V) give a zero row and set the
  *      optional device flag *err_flag to 1 (the host cannot check ids without a sync).

@@ -841,9 +841,11 @@ class RMSNormFn(torch.autograd.Function):
         return dx, dw, None
 
 
-def _tied_head_backward(buf, V, n, table, table_pending, alpha):
+def _tied_head_backward(buf, V, n, table, table_pending, alpha, row_scale=None):
     """Shared backward of the tied vocabulary projection logits = n E^T: buf ([M, ld], pad columns zero) holds
-    d loss / d logits (to be scaled by the device scalar alpha when given) -> (dn, dE to return to autograd or None).
+    d loss / d logits (to be scaled by the device scalar alpha when given, and row m by row_scale[m] -- fp32 [M] --
+    when given) -> (dn, dE to return to autograd or None).  The row scale never touches buf: dn = s (.) (buf E)
+    scales [M, d] rows afterwards, dE = buf^T (s (.) n) scales the rows of n beforehand.
     The embedding table receives the vocabulary weight gradient here and, when it also embedded the input ids of
     this graph (`table_pending`), the embedding scatter later in the same backward: both ACCUMULATE into the one arena
     gradient (zeroed by zero_grad), this one first, and the table is reported ready by the last of them only -- its
@@ -854,6 +856,10 @@ def _tied_head_backward(buf, V, n, table, table_pending, alpha):
         dn = dn * alpha.to(dt)
     logits = buf[:, :V]
     n2 = n.view(buf.shape[0], -1)
+    if row_scale is not None:
+        rs = row_scale.view(-1, 1)
+        dn = (dn * rs).to(dt)      # (the products are taken in fp32 and rounded once)
+        n2 = (n2 * rs).to(dt)
     if _direct(table):
         ops.linear_wgrad(logits, n2, table.grad, None, accumulate=True, alpha=alpha)
         if not table_pending:
@@ -982,5 +988,73 @@ class TiedLMHeadLossFn(torch.autograd.Function):
         else:
             ops.xent_bwd_(buf[:, :V], shifted, ignore_index, lse, gs, acc[1:2])   # logits <- dlogits
         dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, alpha)
+        dh, dlnw = _rms_bwd(dn, hidden, ln_w, eps)
+        return dh, None, None, dlnw, None, dtab, None, None
+
+
+def logprob_rows(input_ids, selection_mask):
+    """Row operands of the per-sequence average log-probability (the notebook's compute_logprobs: labels and mask are
+    both shifted by one) -> (labels [B*L] int64, w [B, L] fp32): position t is scored against input_ids[t + 1] with
+    weight mask[t + 1] / sum(mask[1:]); the last position has weight 0, and so has every position of a sequence whose
+    mask is empty (its score is 0, not 0 / 0)."""
+    B, L = input_ids.shape
+    labels = torch.zeros((B, L), dtype=torch.long, device=input_ids.device)
+    labels[:, :-1] = input_ids[:, 1:]
+    m = selection_mask.to(device=input_ids.device, dtype=torch.float32)
+    w = torch.zeros((B, L), dtype=torch.float32, device=input_ids.device)
+    w[:, :-1] = m[:, 1:]
+    total = w.sum(-1, keepdim=True)
+    w = torch.where(total > 0, w / total.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(w))
+    return labels.view(-1), w
+
+
+def _sequence_sums(logp, w):
+    """sum_t w[b, t] * logp[b, t]: one fixed-order reduction per sequence (no atomics, the same bits every run)."""
+    return (logp.view(w.shape) * w).sum(-1)
+
+
+class TiedLMHeadLogprobFn(torch.autograd.Function):
+    """seq_logp[b] = sum_t w[b, t] log softmax(RMSNorm(h) E^T)[b, t, label[b, t]] with E the embedding table: the
+    per-sequence average log-probability of direct preference optimisation
+    (Examples/vyom-ai-llm-sft-dpo-training.ipynb: compute_logprobs over model(input_ids).logits).  TiedLMHeadLossFn's
+    structure: padded row stride, the logits reduced and overwritten in place by u = w (.) (onehot - softmax) in one
+    pass (vy_logprob_fused: bf16, V <= 65536; vy_logprob_fwd + vy_logprob_bwd otherwise).  The upstream gradient is
+    one number per SEQUENCE and is known only after every sequence has been scored, so it cannot be baked into u:
+    the backward applies it as a per-row scale around the two GEMMs and never passes over the logits again."""
+
+    @staticmethod
+    def forward(ctx, hidden, labels, w, ln_w, eps, table, table_pending, err_flag=None):
+        _require_bf16(hidden)
+        dt, dev = hidden.dtype, hidden.device
+        B, L, _ = hidden.shape
+        n = ops.rmsnorm(hidden, _shadow(ln_w, dt), eps, 0.0)
+        V = table.shape[0]
+        ld = _row_stride(V)
+        buf = torch.empty((B * L, ld), dtype=dt, device=dev)
+        if ld != V:
+            buf[:, V:].zero_()  # only the pad columns: the GEMM writes the rest
+        logits = buf[:, :V]
+        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
+        wrow = w.reshape(-1)
+        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
+        logp = torch.empty(B * L, dtype=torch.float32, device=dev)
+        fused = V <= 65536 and dt == BF16
+        if fused:
+            ops.logprob_fused_(logits, labels, wrow, lse, logp, err_flag)
+        else:
+            ops.logprob_fwd(logits, labels, wrow, lse, logp, err_flag)
+        ctx.save_for_backward(hidden, n, buf, labels, wrow, lse)
+        ctx.meta = (ln_w, eps, table, table_pending, fused, (B, L))
+        return _sequence_sums(logp, w)
+
+    @staticmethod
+    def backward(ctx, gseq):
+        hidden, n, buf, labels, wrow, lse = ctx.saved_tensors
+        ln_w, eps, table, table_pending, fused, (B, L) = ctx.meta
+        V = table.shape[0]
+        if not fused:
+            ops.logprob_bwd_(buf[:, :V], labels, wrow, lse)   # logits <- u
+        g_row = gseq.detach().to(torch.float32).reshape(B, 1).expand(B, L).reshape(-1)
+        dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, None, row_scale=g_row)
         dh, dlnw = _rms_bwd(dn, hidden, ln_w, eps)
         return dh, None, None, dlnw, None, dtab, None, None

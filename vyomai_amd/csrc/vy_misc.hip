@@ -691,6 +691,154 @@ __global__ __launch_bounds__(1024) void xent_fused_kernel(bf16* __restrict__ log
   }
 }
 
+// ---- per-row log-probability of the label (DPO scoring): the xent kernels without the scalar reduction --------------
+// logp[m] = logits[m, label] - lse[m] for rows with weight != 0; the per-sequence sums are taken afterwards in a
+// fixed order over [B, L] (no float atomics here: two runs agree bit for bit).  A row with weight == 0 is skipped
+// (lse = logp = 0), a label outside [0, V) on a weighted row is never dereferenced: the row counts as skipped and
+// the device error flag is raised, as in xent_fwd_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void logprob_fwd_kernel(const T* __restrict__ logits, int64_t ld,
+                                                          const int64_t* __restrict__ labels,
+                                                          const float* __restrict__ weight, float* __restrict__ lse,
+                                                          float* __restrict__ logp, int V, int* __restrict__ err) {
+  constexpr int VEC = Chunk<T>::VEC;
+  __shared__ float red[4];
+  const int64_t m = blockIdx.x;
+  const int64_t label = labels[m];
+  const bool live = weight[m] != 0.f;
+  const bool oob = live && (label < 0 || label >= V);
+  if (oob && err && threadIdx.x == 0) *err = 1;
+  if (!live || oob) { if (threadIdx.x == 0) { lse[m] = 0.f; logp[m] = 0.f; } return; }
+  const T* row = logits + m * ld;
+  const int nch = (V + VEC - 1) / VEC;
+  float mx = -INFINITY, sm = 0.f;
+  for (int c = threadIdx.x; c < nch; c += blockDim.x) {
+    float v[VEC];
+    Chunk<T>::load(row + (int64_t)c * VEC, v);  // the padded tail of the row is readable
+    float cm = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) if (c * VEC + e < V) cm = fmaxf(cm, v[e]);
+    const float nm = fmaxf(mx, cm);
+    float acc = 0.f;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) if (c * VEC + e < V) acc += __expf(v[e] - nm);
+    sm = sm * __expf(mx - nm) + acc;
+    mx = nm;
+  }
+  const float gmx = block_reduce(mx, red, true);
+  const float gsm = block_reduce(sm * __expf(mx - gmx), red, false);
+  if (threadIdx.x == 0) {
+    const float l = gmx + __logf(gsm);
+    lse[m] = l;
+    logp[m] = VyT<T>::ld(row + label) - l;
+  }
+}
+
+// logits[m,:] <- weight[m] * (onehot(label) - softmax(logits[m,:])) in place, from the saved lse: the gradient of
+// weight[m] * logp[m] (the sign of a log-probability, not of a loss).  Pad columns and skipped rows become zero.
+template <typename T>
+__global__ __launch_bounds__(256) void logprob_bwd_kernel(T* __restrict__ logits, int64_t ld,
+                                                          const int64_t* __restrict__ labels,
+                                                          const float* __restrict__ weight,
+                                                          const float* __restrict__ lse, int V) {
+  constexpr int VEC = Chunk<T>::VEC;
+  const int64_t m = blockIdx.x;
+  const int64_t label = labels[m];
+  T* row = logits + m * ld;
+  const int nch = (V + VEC - 1) / VEC;
+  const float w = weight[m];
+  const bool dead = w == 0.f || label < 0 || label >= V;   // out-of-range labels: skipped rows (vy_logprob_fwd flags them)
+  const float l = lse[m];
+  for (int c = threadIdx.x; c < nch; c += blockDim.x) {
+    float v[VEC], o[VEC];
+    Chunk<T>::load(row + (int64_t)c * VEC, v);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const int col = c * VEC + e;
+      float g = 0.f;
+      if (!dead && col < V) g = ((col == label ? 1.f : 0.f) - __expf(v[e] - l)) * w;
+      o[e] = g;  // pad columns stay zero
+    }
+    Chunk<T>::store(row + (int64_t)c * VEC, o);
+  }
+}
+
+// Both in one pass, the row register-resident as in xent_fused_kernel (1024 threads x 8 chunks of 8 bf16): one read
+// and one write of the logits.
+__global__ __launch_bounds__(1024) void logprob_fused_kernel(bf16* __restrict__ logits, int64_t ld,
+                                                             const int64_t* __restrict__ labels,
+                                                             const float* __restrict__ weight,
+                                                             float* __restrict__ lse, float* __restrict__ logp, int V,
+                                                             int* __restrict__ err) {
+  constexpr int CPT = 8;  // 16-byte chunks per thread
+  __shared__ float red[16];
+  const int tid = threadIdx.x;
+  const int64_t m = blockIdx.x;
+  const int64_t label = labels[m];
+  const float w = weight[m];
+  bf16* row = logits + m * ld;
+  const int nch = (V + 7) / 8;
+  bf16x8 zero8;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) zero8[e] = (bf16)0.f;
+  const bool oob = w != 0.f && (label < 0 || label >= V);   // see logprob_fwd_kernel
+  if (oob && err && tid == 0) *err = 1;
+  if (w == 0.f || oob) {
+    for (int c = tid; c < nch; c += 1024) *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = zero8;
+    if (tid == 0) { lse[m] = 0.f; logp[m] = 0.f; }
+    return;
+  }
+  const float x_label = (float)row[label];  // read before any thread overwrites the row (barriers below)
+  bf16x8 v[CPT];
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    const int c = tid + i * 1024;
+    if (c < nch) v[i] = *reinterpret_cast<const bf16x8*>(row + (int64_t)c * 8);
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    const int c = tid + i * 1024;
+    if (c < nch) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (c * 8 + e < V) mx = fmaxf(mx, (float)v[i][e]);
+    }
+  }
+  const float gmx = block_reduce(mx, red, true);
+  float sm = 0.f;
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    const int c = tid + i * 1024;
+    if (c < nch) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (c * 8 + e < V) sm += __expf((float)v[i][e] - gmx);
+    }
+  }
+  const float gsm = block_reduce(sm, red, false);
+  const float l = gmx + __logf(gsm);
+  if (tid == 0) {
+    lse[m] = l;
+    logp[m] = x_label - l;
+  }
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    const int c = tid + i * 1024;
+    if (c < nch) {
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int col = c * 8 + e;
+        float g = 0.f;  // pad columns stay zero
+        if (col < V) g = ((col == label ? 1.f : 0.f) - __expf((float)v[i][e] - l)) * w;
+        o[e] = (bf16)g;
+      }
+      *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = o;
+    }
+  }
+}
+
 template <typename T>
 int ln_fwd_dispatch(const void* x, int64_t ldx, const void* gamma, const void* beta, void* y, int64_t ldy,
                     float* mean, float* rstd, int64_t M, int64_t N, float eps, hipStream_t st) {
@@ -924,6 +1072,44 @@ extern "C" int vy_xent_fused(void* logits, int64_t ld, const int64_t* labels, in
   hipLaunchKernelGGL(xent_fused_kernel, dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels,
                      ignore_index, lse, loss_sum, count, gscale, (int)V, err_flag);
   VY_CHECK_LAUNCH("vy_xent_fused");
+  return VY_OK;
+}
+
+extern "C" int vy_logprob_fwd(const void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
+                              float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream) {
+  if (!logits || !labels || !weight || !lse || !logp || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: bad arguments");
+  const int vec = dtype == VY_BF16 ? 8 : 4;
+  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: row stride must be a multiple of %d and cover the padded row", vec);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == VY_BF16) hipLaunchKernelGGL(logprob_fwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (const bf16*)logits, ld, labels, weight, lse, logp, (int)V, err_flag);
+  else if (dtype == VY_F32) hipLaunchKernelGGL(logprob_fwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (const float*)logits, ld, labels, weight, lse, logp, (int)V, err_flag);
+  else VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: bad dtype %d", dtype);
+  VY_CHECK_LAUNCH("vy_logprob_fwd");
+  return VY_OK;
+}
+
+extern "C" int vy_logprob_bwd(void* logits, int64_t ld, const int64_t* labels, const float* weight, const float* lse,
+                              int64_t M, int64_t V, int dtype, void* stream) {
+  if (!logits || !labels || !weight || !lse || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: bad arguments");
+  const int vec = dtype == VY_BF16 ? 8 : 4;
+  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: row stride must be a multiple of %d and cover the padded row", vec);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == VY_BF16) hipLaunchKernelGGL(logprob_bwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (bf16*)logits, ld, labels, weight, lse, (int)V);
+  else if (dtype == VY_F32) hipLaunchKernelGGL(logprob_bwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (float*)logits, ld, labels, weight, lse, (int)V);
+  else VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: bad dtype %d", dtype);
+  VY_CHECK_LAUNCH("vy_logprob_bwd");
+  return VY_OK;
+}
+
+extern "C" int vy_logprob_fused(void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
+                                float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream) {
+  if (!logits || !labels || !weight || !lse || !logp || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_fused: bad arguments");
+  if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_logprob_fused: bf16 only (use vy_logprob_fwd + vy_logprob_bwd)");
+  if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_logprob_fused: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use vy_logprob_fwd + vy_logprob_bwd)", (long)V);
+  if (ld % 8 || ld < vy_cdiv(V, 8) * 8 || (uintptr_t)logits % 16) VY_FAIL(VY_ERR_ARG, "vy_logprob_fused: rows must be 16-byte aligned and cover the padded width");
+  hipLaunchKernelGGL(logprob_fused_kernel, dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels,
+                     weight, lse, logp, (int)V, err_flag);
+  VY_CHECK_LAUNCH("vy_logprob_fused");
   return VY_OK;
 }
 

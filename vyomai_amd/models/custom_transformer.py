@@ -394,12 +394,80 @@ class ModelForCausalLM(nn.Module):
         logits are reduced and overwritten by their gradient in place, never copied or up-cast."""
         from ..autograd_train import TiedLMHeadLossFn
         hidden, _ = self.model.forward_hidden(input_ids, attention_mask)
-        flag = getattr(self, "label_error", None)
-        if flag is None or flag.device != hidden.device:
-            flag = self.label_error = torch.zeros(1, dtype=torch.int32, device=hidden.device)
         norm = self.model.norm
         return TiedLMHeadLossFn.apply(hidden, labels, ignore_index, norm.weight, norm.variance_epsilon,
-                                      self.lm_head.weight, self._table_pending(input_ids), flag)
+                                      self.lm_head.weight, self._table_pending(input_ids), self._label_flag(hidden.device))
+
+    def _label_flag(self, dev) -> torch.Tensor:
+        flag = getattr(self, "label_error", None)
+        if flag is None or flag.device != dev:
+            flag = self.label_error = torch.zeros(1, dtype=torch.int32, device=dev)
+        return flag
+
+    def sequence_logprobs(self, input_ids: torch.Tensor, selection_mask: torch.Tensor,
+                          attention_mask: Optional[torch.Tensor] = None,
+                          inputs_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Masked average log-probability of each sequence -> fp32 (B,): the notebook's
+        compute_logprobs(model(input_ids).logits, input_ids, selection_mask)
+        (Examples/vyom-ai-llm-sft-dpo-training.ipynb), with the final RMSNorm, the tied vocabulary GEMM and the
+        log-softmax fused.  With grad the logits are overwritten in place by their unit gradient (TiedLMHeadLogprobFn);
+        under torch.no_grad() they are only read (vy_logprob_fwd) and freed on return.  A sequence whose mask selects
+        nothing scores 0.  `inputs_embeds` replaces the embedding lookup (input_ids still supply the labels)."""
+        from ..autograd_train import TiedLMHeadLogprobFn, _row_stride, _sequence_sums, logprob_rows
+        if selection_mask.shape != input_ids.shape:
+            raise ValueError(f"selection_mask {tuple(selection_mask.shape)} must match input_ids {tuple(input_ids.shape)}")
+        _need_gpu(input_ids, "sequence_logprobs()")
+        if inputs_embeds is None:
+            hidden, _ = self.model.forward_hidden(input_ids, attention_mask)
+        else:
+            hidden, _ = self.model.forward_hidden(None, attention_mask, inputs_embeds=inputs_embeds)
+        labels, w = logprob_rows(input_ids, selection_mask)
+        norm, table = self.model.norm, self.lm_head.weight
+        flag = self._label_flag(hidden.device)
+        if _wants_grad(hidden, norm.weight, table):
+            return TiedLMHeadLogprobFn.apply(hidden, labels, w, norm.weight, norm.variance_epsilon, table,
+                                             self._table_pending(None if inputs_embeds is not None else input_ids), flag)
+        dt = hidden.dtype
+        B, L, _ = hidden.shape
+        V = table.shape[0]
+        n = ops.rmsnorm(hidden, _shadow(norm.weight, dt), norm.variance_epsilon, 0.0)
+        ld = _row_stride(V)
+        buf = torch.empty((B * L, ld), dtype=dt, device=hidden.device)
+        logits = buf[:, :V]   # (the pad columns are never read: the kernel stops at V)
+        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
+        lse = torch.empty(B * L, dtype=torch.float32, device=hidden.device)
+        logp = torch.empty_like(lse)
+        ops.logprob_fwd(logits, labels, w.view(-1), lse, logp, flag)
+        return _sequence_sums(logp, w)
+
+    def dpo_loss(self, batch, ref_model: Optional["ModelForCausalLM"] = None, beta: float = 0.1, ref_logprobs=None):
+        """Direct preference optimisation on one collated batch -> (loss, chosen_rewards, rejected_rewards): the
+        notebook's compute_dpo_loss_batch (Examples/vyom-ai-llm-sft-dpo-training.ipynb).  `batch` is its dict: chosen,
+        rejected (ids) and chosen_mask, rejected_mask, all (B, L) -- dpo_collate pads both sides to one length, so the
+        two are scored as ONE 2B-row batch and this module runs once per graph.  The frozen model is `ref_model`,
+        scored the same way under torch.no_grad(), or its precomputed scores `ref_logprobs = (chosen, rejected)`.
+        loss = mean -logsigmoid(beta * ((pi_c - pi_r) - (ref_c - ref_r))); the rewards are detached means."""
+        chosen, rejected = batch["chosen"], batch["rejected"]
+        cmask, rmask = batch["chosen_mask"], batch["rejected_mask"]
+        if chosen.shape != rejected.shape or cmask.shape != chosen.shape or rmask.shape != rejected.shape:
+            raise ValueError(f"dpo_loss needs chosen {tuple(chosen.shape)}, rejected {tuple(rejected.shape)} and their "
+                             f"masks {tuple(cmask.shape)}, {tuple(rmask.shape)} padded to one common length, as the "
+                             "notebook's dpo_collate does")
+        if (ref_model is None) == (ref_logprobs is None):
+            raise ValueError("dpo_loss needs exactly one of ref_model and ref_logprobs=(chosen, rejected)")
+        B = chosen.shape[0]
+        ids = torch.cat([chosen, rejected], dim=0)
+        mask = torch.cat([cmask, rmask], dim=0)
+        if ref_logprobs is None:
+            with torch.no_grad():   # scored first: its logits are gone before the policy's are allocated
+                ref = ref_model.sequence_logprobs(ids, mask)
+            ref_c, ref_r = ref[:B], ref[B:]
+        else:
+            ref_c, ref_r = (t.detach().to(device=ids.device, dtype=torch.float32) for t in ref_logprobs)
+        pi = self.sequence_logprobs(ids, mask)
+        pi_c, pi_r = pi[:B], pi[B:]
+        losses = -torch.nn.functional.logsigmoid(beta * ((pi_c - pi_r) - (ref_c - ref_r)))
+        return losses.mean(), (pi_c - ref_c).detach().mean(), (pi_r - ref_r).detach().mean()
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,

@@ -609,6 +609,44 @@ def xent_fused_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor
          _stream())
 
 
+def _logprob_args(logits2d: Tensor, labels: Tensor, weight: Tensor, *outs: Tensor):
+    M = logits2d.shape[0]
+    assert labels.dtype == torch.long and labels.numel() == M and labels.is_contiguous()
+    assert weight.dtype == torch.float32 and weight.numel() == M and weight.is_contiguous()
+    for t in outs:
+        assert t.dtype == torch.float32 and t.numel() == M and t.is_contiguous()
+
+
+def logprob_fwd(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor, logp: Tensor,
+                err_flag: Optional[Tensor] = None) -> None:
+    """lse[m] = logsumexp(row m), logp[m] = logits[m, label] - lse[m] for rows with weight != 0 (vy_logprob_fwd);
+    logits2d: (M, V) view with 16-byte aligned, padded rows, read only; labels int64 (M,), weight / lse / logp fp32 (M,)."""
+    _need_gpu(logits2d, labels, weight, lse, logp, err_flag)
+    _logprob_args(logits2d, labels, weight, lse, logp)
+    M, V = logits2d.shape
+    call("vy_logprob_fwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(), lse.data_ptr(),
+         logp.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
+
+
+def logprob_bwd_(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor) -> None:
+    """logits <- weight * (onehot(label) - softmax) in place from the saved lse (vy_logprob_bwd)."""
+    _need_gpu(logits2d, labels, weight, lse)
+    _logprob_args(logits2d, labels, weight, lse)
+    M, V = logits2d.shape
+    call("vy_logprob_bwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(), lse.data_ptr(),
+         M, V, dtype_code(logits2d.dtype), _stream())
+
+
+def logprob_fused_(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor, logp: Tensor,
+                   err_flag: Optional[Tensor] = None) -> None:
+    """One pass: lse / logp as logprob_fwd, then the row overwritten as by logprob_bwd_ (vy_logprob_fused)."""
+    _need_gpu(logits2d, labels, weight, lse, logp, err_flag)
+    _logprob_args(logits2d, labels, weight, lse, logp)
+    M, V = logits2d.shape
+    call("vy_logprob_fused", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(),
+         lse.data_ptr(), logp.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
+
+
 def rmsnorm(x: Tensor, w: Tensor, eps: float, w_offset: float = 1.0) -> Tensor:
     """x * rsqrt(mean x^2 + eps) * (w_offset + w)  (vy_rmsnorm_fwd; Gemma: w_offset = 1)."""
     _need_gpu(x, w)
