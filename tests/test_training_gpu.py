@@ -6,6 +6,8 @@ import torch
 
 from oracle import vyom_oracle as O
 from tests.golden import cases
+from tests.test_causal_lm_gpu import elementwise_bars
+from tests.test_kernels_gpu import check, rnd
 from vyomai_amd import recipe
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +140,93 @@ def test_xent_fused_kernel():
     ref_lse = torch.logsumexp(lg.double(), dim=1)
     keep = labels != -100
     assert (lse.cpu().double()[keep] - ref_lse[keep]).abs().max() < 1e-3
+
+
+def _xent_case(V, dtype, seed):
+    """test_dpo_gpu._kernel_case for the cross-entropy rows: 24 rows of random logits in a padded buffer whose pad
+    columns inside the last 16-byte chunk hold a value that would wreck the row if it were read as a logit; ignored
+    rows (-100: an out-of-range value that is ignore_index must NOT raise the flag); a label of 0 and of V - 1."""
+    from vyomai_amd.autograd_train import _row_stride
+    M = 24
+    x = (2.0 * rnd(M, V, seed=seed)).to(dtype)
+    buf = torch.zeros((M, _row_stride(V)), dtype=dtype)
+    buf[:, :V] = x
+    vec = 16 // x.element_size()
+    buf[:, V:(V + vec - 1) // vec * vec] = 60.0
+    labels = torch.randint(0, V, (M,), generator=torch.Generator().manual_seed(seed))
+    labels[0], labels[1] = 0, V - 1
+    labels[torch.tensor([2, 5, 6, 11, 23])] = -100
+    return x, buf, labels
+
+
+def _xent_run(kind, V, buf, labels, live, gscale):
+    """-> (lse, buffer after the call, loss_sum, count, flag); kind = pair | fused (which is GIVEN the count)."""
+    from vyomai_amd import ops
+    b = buf.to(DEV).clone()
+    lab = labels.to(DEV)
+    lse = torch.full((b.shape[0],), 9.0, device=DEV)
+    acc = torch.zeros(2, device=DEV)
+    gs = torch.full((1,), gscale, device=DEV)
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+    if kind == "fused":
+        acc[1] = float(live.sum())
+        ops.xent_fused_(b[:, :V], lab, -100, lse, acc[0:1], acc[1:2], gs, flag)
+    else:
+        ops.xent_fwd(b[:, :V], lab, -100, lse, acc[0:1], acc[1:2], flag)
+        assert torch.equal(b, buf.to(DEV)), "vy_xent_fwd is read-only"
+        ops.xent_bwd_(b[:, :V], lab, -100, lse, gs, acc[1:2])
+    torch.cuda.synchronize()
+    return lse, b, acc[0].item(), acc[1].item(), int(flag.item())
+
+
+@pytest.mark.parametrize("V", [512, 1000, 1003, 32000, 50265, 65536, 70000])
+@pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["fp32", "bf16"])
+def test_xent_kernels_vs_fp64(V, dtype):
+    """vy_xent_fwd + vy_xent_bwd, and vy_xent_fused where it applies, against fp64 torch cross_entropy on the grid of
+    test_dpo_gpu.test_logprob_kernels_vs_fp64 (the two families are one kernel core): widths on a chunk boundary and
+    ending inside a 16-byte chunk; 70000 and fp32 go through the pair only (vy_xent_fused refuses them).  A label
+    outside [0, V) that is not ignore_index raises the flag, its row comes out zero and does not count in the mean.
+    Bars: elementwise_bars for lse and the gradient, the 1e-3 of test_xent_kernel for the mean loss."""
+    from vyomai_amd import ops
+    from vyomai_amd._lib import VyomHipError
+    atol, rtol = elementwise_bars(dtype)
+    gscale = 0.5
+    x, buf, labels = _xent_case(V, dtype, seed=V % 97)
+    M = x.shape[0]
+    fused_ok = dtype == BF and V <= 65536
+    if not fused_ok:
+        with pytest.raises(VyomHipError, match="vy_xent_fused"):
+            ops.xent_fused_(buf.to(DEV)[:, :V], labels.to(DEV), -100, torch.empty(M, device=DEV),
+                            torch.zeros(1, device=DEV), torch.ones(1, device=DEV), torch.ones(1, device=DEV))
+    kinds = ("pair", "fused") if fused_ok else ("pair",)
+    for oob_row in (None, 7):
+        lab = labels.clone()
+        ref_lab = labels.clone()
+        if oob_row is not None:
+            lab[oob_row] = -1 if V % 2 else V      # just outside either end
+            ref_lab[oob_row] = -100
+        live = ref_lab != -100
+        xd = x.double().requires_grad_(True)
+        ref = torch.nn.functional.cross_entropy(xd, ref_lab, ignore_index=-100)
+        (gscale * ref).backward()
+        lse64 = torch.where(live, torch.logsumexp(x.double(), dim=-1), torch.zeros((), dtype=torch.float64))
+        got = {}
+        for kind in kinds:
+            lse, b, loss_sum, count, flag = got[kind] = _xent_run(kind, V, buf, lab, live, gscale)
+            what = f"V={V} {kind} oob={oob_row}"
+            assert flag == (0 if oob_row is None else 1), what
+            assert count == float(live.sum()), "rows in the mean: " + what
+            print(f"{what}: mean loss {loss_sum / count:.6f} fp64 {ref.item():.6f}")
+            assert abs(loss_sum / count - ref.item()) < 1e-3, what
+            check(lse, lse64, atol, rtol, "lse " + what)
+            check(b[:, :V], xd.grad, atol, rtol, "gscale * (softmax - onehot) / count " + what)
+            assert not b[:, V:].any(), "pad columns come out zero: " + what
+            assert not b[(~live).to(DEV)].any() and not lse[(~live).to(DEV)].any(), "skipped rows are zero: " + what
+            again = _xent_run(kind, V, buf, lab, live, gscale)
+            assert torch.equal(lse, again[0]) and torch.equal(b, again[1]), "two runs differ: " + what
+        if fused_ok:
+            check(got["fused"][0], got["pair"][0], atol, rtol, f"fused vs pair lse V={V} oob={oob_row}")
+            check(got["fused"][1], got["pair"][1], atol, rtol, f"fused vs pair buffer V={V} oob={oob_row}")
 
 
 def test_lm_head_loss_upstream_gradient_scale():

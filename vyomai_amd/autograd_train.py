@@ -542,6 +542,98 @@ def _offsets(ps):
     return offs
 
 
+# ------------------------------------------------------------------------------------------
+# Vocabulary heads: the pieces the six Functions below (and the no-grad scoring path) share
+# ------------------------------------------------------------------------------------------
+
+
+def _head_transform(hidden, wd, bd, ln_w, ln_b, eps):
+    """n = LN(gelu(h Wd^T + bd)) -> (pre, g, n, mean, rstd), all kept for _head_transform_backward."""
+    dt = hidden.dtype
+    pre = torch.empty_like(hidden)
+    g = torch.empty_like(hidden)
+    ops.linear(hidden, _shadow(wd, dt), _shadow(bd, dt), act=ACT_GELU_ERF, pre_out=pre, out=g)
+    n, mean, rstd = ops.layernorm(g, _shadow(ln_w, dt), _shadow(ln_b, dt), eps, save_stats=True)
+    return pre, g, n, mean, rstd
+
+
+def _head_transform_backward(dn, hidden, pre, g, mean, rstd, wd, bd, ln_w, ln_b):
+    """-> (dh, dwd, dbd, dgamma, dbeta) from dn = d loss / d n."""
+    dg, dgam, dbet = _ln_bwd(dn, g, ln_w, ln_b, mean, rstd)
+    dpre = ops.act_bwd(dg, pre, ACT_GELU_ERF)
+    dh = ops.linear_dgrad(dpre, _wt(wd, hidden.dtype))
+    dwd, dbd = _wgrad(dpre, hidden, wd, bd)
+    return dh, dwd, dbd, dgam, dbet
+
+
+def _vocab_logits(n, w, bias, zero_pad=True):
+    """logits = n W^T (+ bias) over all B * L rows into a fresh buffer with a padded row stride -> (buf [M, ld],
+    logits = buf[:, :V]).  zero_pad: the pad columns are zeroed (only they: the GEMM writes the rest), as the backward
+    GEMMs need that contract over the padded width; a reader that stops at V does not."""
+    dt = n.dtype
+    V = w.shape[0]
+    ld = _row_stride(V)
+    buf = torch.empty((n.numel() // n.shape[-1], ld), dtype=dt, device=n.device)
+    if zero_pad and ld != V:
+        buf[:, V:].zero_()
+    logits = buf[:, :V]
+    ops.linear(n.view(buf.shape[0], -1), _shadow(w, dt), None if bias is None else _shadow(bias, dt), out=logits)
+    return buf, logits
+
+
+def _rehome(x, ld, dtype, reuse=False):
+    """x [..., V] in a buffer [..., ld] of `dtype` whose pad columns are zero (ld: a padded row stride, so the rows are
+    16-byte aligned and GEMMs can contract over the padded width).  reuse: an x that already sits in such a buffer is
+    taken as it is, and only its pad columns are zeroed; otherwise it is copied."""
+    V = x.shape[-1]
+    if reuse and x.stride(-1) == 1 and x.stride(-2) == ld and x.dtype == dtype:
+        buf = torch.as_strided(x, (*x.shape[:-1], ld), x.stride())
+        if ld != V:
+            buf[..., V:].zero_()
+        return buf
+    buf = torch.zeros((*x.shape[:-1], ld), dtype=dtype, device=x.device)
+    buf[..., :V] = x
+    return buf
+
+
+def _shifted_labels(labels, ignore_index, dev):
+    """Position t is scored against token t + 1, the last one against nothing: labels[:, 1:] and one ignore_index per
+    sequence, flat [B * L] on dev."""
+    shifted = torch.full(labels.shape, ignore_index, dtype=torch.long, device=dev)
+    shifted[:, :-1] = labels[:, 1:]
+    return shifted.view(-1)
+
+
+def _xent_forward(logits, shifted, ignore_index, err_flag=None, in_place=True):
+    """Mean cross-entropy of the live rows -> (loss, lse, acc = [loss_sum, count], fused).  in_place: the logits may
+    be overwritten, and where one kernel can do it (vy_xent_fused: bf16, V <= 65536) they then hold the UNIT gradient
+    (d loss / d logits for an upstream gradient of 1; backward scales by the actual one, by linearity); otherwise
+    vy_xent_fwd only reads them."""
+    V = logits.shape[1]
+    dev = logits.device
+    lse = torch.empty(logits.shape[0], dtype=torch.float32, device=dev)
+    acc = torch.zeros(2, dtype=torch.float32, device=dev)
+    fused = in_place and V <= 65536 and logits.dtype == BF16
+    if fused:
+        # rows with an out-of-range label contribute neither loss nor gradient -- the kernel raises err_flag for
+        # them -- so they must not count in the mean either, exactly as on the two-pass path
+        acc[1] = ((shifted != ignore_index) & (shifted >= 0) & (shifted < V)).sum()
+        ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
+    else:
+        ops.xent_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], err_flag)
+    return acc[0] / acc[1].clamp_min(1.0), lse, acc, fused
+
+
+def _xent_backward(logits, shifted, ignore_index, lse, acc, fused, gout):
+    """logits <- d loss / d logits, up to the factor returned: the upstream gradient as a device scalar where the
+    logits already hold the unit gradient (fused), None after vy_xent_bwd has written the scaled one."""
+    gs = gout.detach().to(torch.float32).reshape(1).contiguous()
+    if fused:
+        return gs
+    ops.xent_bwd_(logits, shifted, ignore_index, lse, gs, acc[1:2])
+    return None
+
+
 class LMHeadFn(torch.autograd.Function):
     """logits = LN(gelu(h Wd^T + bd)) Wv^T + bias (reference models/decoder.py:267-275).  The logits
     row stride is padded to 8 and the pad columns are zero, so the backward GEMMs can contract
@@ -551,10 +643,7 @@ class LMHeadFn(torch.autograd.Function):
     def forward(ctx, hidden, wd, bd, ln_w, ln_b, wv, bias, eps):
         _require_bf16(hidden)
         dt = hidden.dtype
-        pre = torch.empty_like(hidden)
-        g = torch.empty_like(hidden)
-        ops.linear(hidden, _shadow(wd, dt), _shadow(bd, dt), act=ACT_GELU_ERF, pre_out=pre, out=g)
-        n, mean, rstd = ops.layernorm(g, _shadow(ln_w, dt), _shadow(ln_b, dt), eps, save_stats=True)
+        pre, g, n, mean, rstd = _head_transform(hidden, wd, bd, ln_w, ln_b, eps)
         V = wv.shape[0]
         ld = _row_stride(V)
         buf = torch.zeros((*hidden.shape[:-1], ld), dtype=dt, device=hidden.device)
@@ -570,28 +659,12 @@ class LMHeadFn(torch.autograd.Function):
         hidden, pre, g, n, mean, rstd = ctx.saved_tensors
         wd, bd, ln_w, ln_b, wv, bias = ctx.params
         dt = hidden.dtype
-        V, ld = wv.shape[0], ctx.ld
-        # the contraction of the dgrad GEMM runs over the PADDED vocabulary width (multiple of 8, pad
-        # columns of both operands zero): re-home the gradient unless it already sits in such a buffer
-        if dlogits.stride(-1) != 1 or dlogits.stride(-2) != ld or dlogits.dtype != dt:
-            buf = torch.zeros((*dlogits.shape[:-1], ld), dtype=dt, device=dlogits.device)
-            buf[..., :V] = dlogits
-        else:
-            buf = torch.as_strided(dlogits, (*dlogits.shape[:-1], ld), dlogits.stride())
-            if ld != V:
-                buf[..., V:].zero_()
-        dlogits = buf[..., :V]
-        dn = ops.linear_dgrad(buf, _wt_padded(wv, dt, ld))
-        dwv, dbias = _wgrad(dlogits, n, wv, bias)
-        dg, dgam, dbet = _ln_bwd(dn, g, ln_w, ln_b, mean, rstd)
-        dpre = _gelu_bwd(dg, pre)
-        dh = ops.linear_dgrad(dpre, _wt(wd, dt))
-        dwd, dbd = _wgrad(dpre, hidden, wd, bd)
-        return dh, dwd, dbd, dgam, dbet, dwv, dbias, None
-
-
-def _gelu_bwd(dy, pre):
-    return ops.act_bwd(dy, pre, ACT_GELU_ERF)
+        # the contraction of the dgrad GEMM runs over the PADDED vocabulary width: a gradient that autograd hands
+        # back in the padded logits buffer is used where it is
+        buf = _rehome(dlogits, ctx.ld, dt, reuse=True)
+        dn = ops.linear_dgrad(buf, _wt_padded(wv, dt, ctx.ld))
+        dwv, dbias = _wgrad(buf[..., :wv.shape[0]], n, wv, bias)
+        return (*_head_transform_backward(dn, hidden, pre, g, mean, rstd, wd, bd, ln_w, ln_b), dwv, dbias, None)
 
 
 class LMHeadLossFn(torch.autograd.Function):
@@ -605,62 +678,29 @@ class LMHeadLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, labels, ignore_index, wd, bd, ln_w, ln_b, wv, bias, eps, err_flag=None):
         _require_bf16(hidden)
-        dt, dev = hidden.dtype, hidden.device
-        B, L, _ = hidden.shape
-        pre = torch.empty_like(hidden)
-        g = torch.empty_like(hidden)
-        ops.linear(hidden, _shadow(wd, dt), _shadow(bd, dt), act=ACT_GELU_ERF, pre_out=pre, out=g)
-        n, mean, rstd = ops.layernorm(g, _shadow(ln_w, dt), _shadow(ln_b, dt), eps, save_stats=True)
-        V = wv.shape[0]
-        ld = _row_stride(V)
-        buf = torch.empty((B * L, ld), dtype=dt, device=dev)
-        if ld != V:
-            buf[:, V:].zero_()  # only the pad columns: the GEMM writes the rest
-        logits = buf[:, :V]
-        ops.linear(n.view(B * L, -1), _shadow(wv, dt), _shadow(bias, dt), out=logits)
-        shifted = torch.full((B, L), ignore_index, dtype=torch.long, device=dev)
-        shifted[:, :-1] = labels[:, 1:]
-        shifted = shifted.view(-1)
-        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
-        acc = torch.zeros(2, dtype=torch.float32, device=dev)  # [loss_sum, count]
-        fused = V <= 65536 and dt == BF16   # (vy_xent_fused is a bf16 kernel; fp32 takes the two-pass pair)
-        if fused:
-            # one pass: loss AND the unit gradient (d loss / d logits for an upstream gradient of 1),
-            # written over the logits; backward scales by the actual upstream gradient (linearity)
-            # (rows with an out-of-range label contribute neither loss nor gradient -- the kernel raises err_flag for
-            # them -- so they must not count in the mean either, exactly as on the two-pass path)
-            acc[1] = ((shifted != ignore_index) & (shifted >= 0) & (shifted < V)).sum()
-            ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
-        else:
-            ops.xent_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], err_flag)
+        pre, g, n, mean, rstd = _head_transform(hidden, wd, bd, ln_w, ln_b, eps)
+        buf, logits = _vocab_logits(n, wv, bias)
+        shifted = _shifted_labels(labels, ignore_index, hidden.device)
+        loss, lse, acc, fused = _xent_forward(logits, shifted, ignore_index, err_flag)
         ctx.save_for_backward(hidden, pre, g, n, mean, rstd, buf, shifted, lse, acc)
         ctx.params = (wd, bd, ln_w, ln_b, wv, bias)
         ctx.ignore = ignore_index
         ctx.fused = fused
-        return acc[0] / acc[1].clamp_min(1.0)
+        return loss
 
     @staticmethod
     def backward(ctx, gout):
         hidden, pre, g, n, mean, rstd, buf, shifted, lse, acc = ctx.saved_tensors
         wd, bd, ln_w, ln_b, wv, bias = ctx.params
         dt = hidden.dtype
-        V = wv.shape[0]
-        logits = buf[:, :V]
-        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
-        alpha = None
-        if ctx.fused:
-            alpha = gs          # logits already hold the unit gradient
-        else:
-            ops.xent_bwd_(logits, shifted, ctx.ignore, lse, gs, acc[1:2])   # logits <- dlogits
+        logits = buf[:, :wv.shape[0]]
+        alpha = _xent_backward(logits, shifted, ctx.ignore, lse, acc, ctx.fused, gout)
         # contract over the padded vocabulary width (pad columns of both operands are zero)
         dn = ops.linear_dgrad(buf, _wt_padded(wv, dt, buf.shape[1]))
         if alpha is not None:
             dn = dn * alpha.to(dt)
         dwv, dbias = _wgrad(logits, n.view(buf.shape[0], -1), wv, bias, alpha=alpha)
-        dg, dgam, dbet = _ln_bwd(dn.view(g.shape), g, ln_w, ln_b, mean, rstd)
-        dpre = _gelu_bwd(dg, pre)
-        dh = ops.linear_dgrad(dpre, _wt(wd, dt))
-        dwd, dbd = _wgrad(dpre, hidden, wd, bd)
+        dh, dwd, dbd, dgam, dbet = _head_transform_backward(dn.view(g.shape), hidden, pre, g, mean, rstd, wd, bd, ln_w, ln_b)
         return dh, None, None, dwd, dbd, dgam, dbet, dwv, dbias, None, None
 
 
@@ -892,8 +932,7 @@ class TiedLMHeadFn(torch.autograd.Function):
         (n,) = ctx.saved_tensors
         table, table_pending, ld = ctx.meta
         V = table.shape[0]
-        buf = torch.zeros((dlogits.numel() // V, ld), dtype=n.dtype, device=dlogits.device)
-        buf[:, :V] = dlogits.reshape(-1, V)
+        buf = _rehome(dlogits.reshape(-1, V), ld, n.dtype)
         dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, None)
         return dn, dtab, None
 
@@ -907,19 +946,14 @@ class ShiftedXentFn(torch.autograd.Function):
     def forward(ctx, logits, labels, ignore_index):
         _require_bf16(logits)
         B, L, V = logits.shape
-        dev = logits.device
         if logits.stride(-1) != 1 or logits.stride(1) % 8 or logits.stride(0) != L * logits.stride(1):
-            logits = _rehome_logits(logits)
+            logits = _rehome(logits, _row_stride(V), logits.dtype)[..., :V]   # rows 16-byte aligned
         l2 = torch.as_strided(logits, (B * L, V), (logits.stride(1), 1), logits.storage_offset())
-        shifted = torch.full((B, L), ignore_index, dtype=torch.long, device=dev)
-        shifted[:, :-1] = labels[:, 1:]
-        shifted = shifted.view(-1)
-        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
-        acc = torch.zeros(2, dtype=torch.float32, device=dev)
-        ops.xent_fwd(l2, shifted, ignore_index, lse, acc[0:1], acc[1:2])
+        shifted = _shifted_labels(labels, ignore_index, logits.device)
+        loss, lse, acc, _ = _xent_forward(l2, shifted, ignore_index, in_place=False)
         ctx.save_for_backward(l2, shifted, lse, acc)
         ctx.meta = (ignore_index, (B, L, V))
-        return acc[0] / acc[1].clamp_min(1.0)
+        return loss
 
     @staticmethod
     def backward(ctx, gout):
@@ -929,18 +963,8 @@ class ShiftedXentFn(torch.autograd.Function):
         buf = torch.empty((l2.shape[0], ld), dtype=l2.dtype, device=l2.device)
         d2 = buf[:, :l2.shape[1]]
         d2.copy_(l2)
-        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
-        ops.xent_bwd_(d2, shifted, ignore_index, lse, gs, acc[1:2])
+        _xent_backward(d2, shifted, ignore_index, lse, acc, False, gout)
         return torch.as_strided(buf, shape, (shape[1] * ld, ld, 1)), None, None
-
-
-def _rehome_logits(logits):
-    """logits re-homed in a buffer whose rows are 16-byte aligned (row stride padded, pad columns zero)."""
-    B, L, V = logits.shape
-    ld = _row_stride(V)
-    buf = torch.zeros((B, L, ld), dtype=logits.dtype, device=logits.device)
-    buf[..., :V] = logits
-    return buf[..., :V]
 
 
 class TiedLMHeadLossFn(torch.autograd.Function):
@@ -951,42 +975,20 @@ class TiedLMHeadLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, labels, ignore_index, ln_w, eps, table, table_pending, err_flag=None):
         _require_bf16(hidden)
-        dt, dev = hidden.dtype, hidden.device
-        B, L, _ = hidden.shape
-        n = ops.rmsnorm(hidden, _shadow(ln_w, dt), eps, 0.0)
-        V = table.shape[0]
-        ld = _row_stride(V)
-        buf = torch.empty((B * L, ld), dtype=dt, device=dev)
-        if ld != V:
-            buf[:, V:].zero_()  # only the pad columns: the GEMM writes the rest
-        logits = buf[:, :V]
-        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
-        shifted = torch.full((B, L), ignore_index, dtype=torch.long, device=dev)
-        shifted[:, :-1] = labels[:, 1:]
-        shifted = shifted.view(-1)
-        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
-        acc = torch.zeros(2, dtype=torch.float32, device=dev)  # [loss_sum, count]
-        fused = V <= 65536 and dt == BF16
-        if fused:
-            acc[1] = ((shifted != ignore_index) & (shifted >= 0) & (shifted < V)).sum()
-            ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
-        else:
-            ops.xent_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], err_flag)
+        n = ops.rmsnorm(hidden, _shadow(ln_w, hidden.dtype), eps, 0.0)
+        buf, logits = _vocab_logits(n, table, None)
+        shifted = _shifted_labels(labels, ignore_index, hidden.device)
+        loss, lse, acc, fused = _xent_forward(logits, shifted, ignore_index, err_flag)
         ctx.save_for_backward(hidden, n, buf, shifted, lse, acc)
         ctx.meta = (ln_w, eps, table, table_pending, ignore_index, fused)
-        return acc[0] / acc[1].clamp_min(1.0)
+        return loss
 
     @staticmethod
     def backward(ctx, gout):
         hidden, n, buf, shifted, lse, acc = ctx.saved_tensors
         ln_w, eps, table, table_pending, ignore_index, fused = ctx.meta
         V = table.shape[0]
-        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
-        alpha = None
-        if fused:
-            alpha = gs          # logits already hold the unit gradient
-        else:
-            ops.xent_bwd_(buf[:, :V], shifted, ignore_index, lse, gs, acc[1:2])   # logits <- dlogits
+        alpha = _xent_backward(buf[:, :V], shifted, ignore_index, lse, acc, fused, gout)
         dn, dtab = _tied_head_backward(buf, V, n, table, table_pending, alpha)
         dh, dlnw = _rms_bwd(dn, hidden, ln_w, eps)
         return dh, None, None, dlnw, None, dtab, None, None
@@ -1008,44 +1010,41 @@ def logprob_rows(input_ids, selection_mask):
     return labels.view(-1), w
 
 
-def _sequence_sums(logp, w):
-    """sum_t w[b, t] * logp[b, t]: one fixed-order reduction per sequence (no atomics, the same bits every run)."""
-    return (logp.view(w.shape) * w).sum(-1)
+def tied_head_logprobs(hidden, labels, w, ln_w, eps, table, err_flag=None, in_place=False):
+    """seq_logp[b] = sum_t w[b, t] log softmax(RMSNorm(h) E^T)[b, t, label[b, t]] -> (seq_logp fp32 [B], what
+    TiedLMHeadLogprobFn saves).  in_place=False scores only (no-grad): the logits are read by vy_logprob_fwd and freed
+    on return, and their pad columns, which that kernel never reads, are not zeroed.  in_place=True leaves in the
+    logits u = w (.) (onehot - softmax) for the backward GEMMs: in one pass where vy_logprob_fused applies (bf16,
+    V <= 65536), by vy_logprob_bwd in the backward otherwise."""
+    dev = hidden.device
+    n = ops.rmsnorm(hidden, _shadow(ln_w, hidden.dtype), eps, 0.0)
+    buf, logits = _vocab_logits(n, table, None, zero_pad=in_place)
+    wrow = w.reshape(-1)
+    lse = torch.empty(buf.shape[0], dtype=torch.float32, device=dev)
+    logp = torch.empty(buf.shape[0], dtype=torch.float32, device=dev)
+    fused = in_place and table.shape[0] <= 65536 and hidden.dtype == BF16
+    if fused:
+        ops.logprob_fused_(logits, labels, wrow, lse, logp, err_flag)
+    else:
+        ops.logprob_fwd(logits, labels, wrow, lse, logp, err_flag)
+    # one fixed-order reduction per sequence (no atomics, the same bits every run)
+    return (logp.view(w.shape) * w).sum(-1), (n, buf, wrow, lse, fused)
 
 
 class TiedLMHeadLogprobFn(torch.autograd.Function):
-    """seq_logp[b] = sum_t w[b, t] log softmax(RMSNorm(h) E^T)[b, t, label[b, t]] with E the embedding table: the
-    per-sequence average log-probability of direct preference optimisation
+    """tied_head_logprobs with a backward: the per-sequence average log-probability of direct preference optimisation
     (Examples/vyom-ai-llm-sft-dpo-training.ipynb: compute_logprobs over model(input_ids).logits).  TiedLMHeadLossFn's
-    structure: padded row stride, the logits reduced and overwritten in place by u = w (.) (onehot - softmax) in one
-    pass (vy_logprob_fused: bf16, V <= 65536; vy_logprob_fwd + vy_logprob_bwd otherwise).  The upstream gradient is
+    structure: padded row stride, the logits reduced and overwritten in place by u.  The upstream gradient is
     one number per SEQUENCE and is known only after every sequence has been scored, so it cannot be baked into u:
     the backward applies it as a per-row scale around the two GEMMs and never passes over the logits again."""
 
     @staticmethod
     def forward(ctx, hidden, labels, w, ln_w, eps, table, table_pending, err_flag=None):
         _require_bf16(hidden)
-        dt, dev = hidden.dtype, hidden.device
-        B, L, _ = hidden.shape
-        n = ops.rmsnorm(hidden, _shadow(ln_w, dt), eps, 0.0)
-        V = table.shape[0]
-        ld = _row_stride(V)
-        buf = torch.empty((B * L, ld), dtype=dt, device=dev)
-        if ld != V:
-            buf[:, V:].zero_()  # only the pad columns: the GEMM writes the rest
-        logits = buf[:, :V]
-        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
-        wrow = w.reshape(-1)
-        lse = torch.empty(B * L, dtype=torch.float32, device=dev)
-        logp = torch.empty(B * L, dtype=torch.float32, device=dev)
-        fused = V <= 65536 and dt == BF16
-        if fused:
-            ops.logprob_fused_(logits, labels, wrow, lse, logp, err_flag)
-        else:
-            ops.logprob_fwd(logits, labels, wrow, lse, logp, err_flag)
+        seq, (n, buf, wrow, lse, fused) = tied_head_logprobs(hidden, labels, w, ln_w, eps, table, err_flag, in_place=True)
         ctx.save_for_backward(hidden, n, buf, labels, wrow, lse)
-        ctx.meta = (ln_w, eps, table, table_pending, fused, (B, L))
-        return _sequence_sums(logp, w)
+        ctx.meta = (ln_w, eps, table, table_pending, fused, w.shape)
+        return seq
 
     @staticmethod
     def backward(ctx, gseq):

@@ -3,6 +3,7 @@
 // accesses per lane; LayerNorm keeps the whole row in registers (one wave per row).
 #include "vy_common.h"
 #include <stdarg.h>
+#include <string.h>
 
 // ---- error string ------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -534,7 +535,7 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy, int64_t lddy, const T* 
   }
 }
 
-// ---- softmax cross-entropy: one workgroup (4 waves) per row ------------------------------------
+// ---- vocabulary-row softmax (cross-entropy, per-row log-probability): one workgroup per row ----------
 __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
   v = is_max ? vy_wave_max(v) : vy_wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -546,169 +547,71 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
   return r;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ logits, int64_t ld,
-                                                       const int64_t* __restrict__ labels, int64_t ignore,
-                                                       float* __restrict__ lse, float* __restrict__ loss_sum,
-                                                       float* __restrict__ count, int V, int* __restrict__ err) {
+// The three kernels below stream or hold a row, reduce it to lse = max + log(sum exp) and / or overwrite it with a
+// gradient.  A row policy carries what differs between the two users and nothing else:
+//   load(m, grad)      the per-row operands, read ONCE into a State (re-read at the scale point they are loaded again
+//                      after the barriers of the fused kernel, and after its atomic no longer as scalar loads);
+//                      `grad`: the gradient scale is wanted (a constant at every call site)
+//   live(s, label)     the row takes part; the others are skipped: lse = 0, the row zeroed by the gradient kernels
+//   skip(m)            what a skipped row writes besides lse
+//   emit(m, l, x)      what thread 0 writes besides lse = l, from the label's logit x
+//   grad(s, e, onehot) d / d logit of a live row from e = softmax
+// A label outside [0, V) on a live row (e.g. -100 padding under another ignore_index) would be an out-of-bounds read:
+// the row counts as skipped and the device error flag is raised instead.
+
+// Cross-entropy: live = label != ignore, loss_sum += lse - x (a float atomic over rows), the gradient of the MEAN
+// loss times the upstream gscale.  COUNT: the forward also counts the live rows (vy_xent_fwd; vy_xent_fused is given
+// the count, it needs it before the last row is done).
+template <bool COUNT>
+struct XentRow {
+  int64_t ignore;
+  const float *gscale, *count;   // (next to ignore: one kernel-argument load fetches the three)
+  float *loss_sum, *count_out;
+  struct State { float sc; };
+  __device__ __forceinline__ State load(int64_t, bool grad) const { return State{grad ? *gscale / fmaxf(*count, 1.0f) : 0.f}; }
+  __device__ __forceinline__ bool live(const State&, int64_t label) const { return label != ignore; }
+  __device__ __forceinline__ void skip(int64_t) const {}
+  __device__ __forceinline__ void emit(int64_t, float l, float x) const {
+    atomicAdd(loss_sum, l - x);
+    if constexpr (COUNT) atomicAdd(count_out, 1.0f);
+  }
+  __device__ __forceinline__ float grad(const State& s, float e, float onehot) const {
+    return (e - onehot) * s.sc;
+  }
+};
+
+// Log-probability of the label (DPO scoring): live = weight[m] != 0, logp[m] = x - lse[m]; the per-sequence sums are
+// taken afterwards in a fixed order over [B, L] (no float atomics here: two runs agree bit for bit).  The gradient is
+// that of weight[m] * logp[m] (the sign of a log-probability, not of a loss), and is not written (e - onehot) * -w:
+// where e underflows to 0 that stores -0 for +0.
+struct LogprobRow {
+  const float* weight;
+  float* logp;
+  struct State { float w; };
+  __device__ __forceinline__ State load(int64_t m, bool) const { return State{weight[m]}; }
+  __device__ __forceinline__ bool live(const State& s, int64_t) const { return s.w != 0.f; }
+  __device__ __forceinline__ void skip(int64_t m) const { logp[m] = 0.f; }
+  __device__ __forceinline__ void emit(int64_t m, float l, float x) const { logp[m] = x - l; }
+  __device__ __forceinline__ float grad(const State& s, float e, float onehot) const { return (onehot - e) * s.w; }
+};
+
+// Forward: lse[m] and the policy's output, the logits only read (online max / sum over 16-byte chunks).
+template <typename T, typename P>
+__global__ __launch_bounds__(256) void row_lse_kernel(const T* __restrict__ logits, int64_t ld,
+                                                      const int64_t* __restrict__ labels, const P p,
+                                                      float* __restrict__ lse, int V, int* __restrict__ err) {
   constexpr int VEC = Chunk<T>::VEC;
   __shared__ float red[4];
   const int64_t m = blockIdx.x;
   const int64_t label = labels[m];
-  // a label outside [0, V) that is not ignore_index (e.g. -100 padding under another ignore_index) would be
-  // an out-of-bounds read: the row is treated as ignored and the device error flag raised instead
-  const bool oob = label != ignore && (label < 0 || label >= V);
-  if (oob && err && threadIdx.x == 0) *err = 1;
-  if (label == ignore || oob) { if (threadIdx.x == 0) lse[m] = 0.f; return; }
-  const T* row = logits + m * ld;
-  const int nch = (V + VEC - 1) / VEC;
-  float mx = -INFINITY, sm = 0.f;
-  for (int c = threadIdx.x; c < nch; c += blockDim.x) {
-    float v[VEC];
-    Chunk<T>::load(row + (int64_t)c * VEC, v);  // the padded tail of the row is readable
-    float cm = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) if (c * VEC + e < V) cm = fmaxf(cm, v[e]);
-    const float nm = fmaxf(mx, cm);
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) if (c * VEC + e < V) acc += __expf(v[e] - nm);
-    sm = sm * __expf(mx - nm) + acc;
-    mx = nm;
-  }
-  const float gmx = block_reduce(mx, red, true);
-  const float gsm = block_reduce(sm * __expf(mx - gmx), red, false);
-  if (threadIdx.x == 0) {
-    const float l = gmx + __logf(gsm);
-    lse[m] = l;
-    atomicAdd(loss_sum, l - VyT<T>::ld(row + label));
-    atomicAdd(count, 1.0f);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void xent_bwd_kernel(T* __restrict__ logits, int64_t ld,
-                                                       const int64_t* __restrict__ labels, int64_t ignore,
-                                                       const float* __restrict__ lse, const float* __restrict__ gscale,
-                                                       const float* __restrict__ count, int V) {
-  constexpr int VEC = Chunk<T>::VEC;
-  const int64_t m = blockIdx.x;
-  const int64_t label = labels[m];
-  T* row = logits + m * ld;
-  const int nch = (V + VEC - 1) / VEC;
-  const bool dead = label == ignore || label < 0 || label >= V;   // out-of-range labels: ignored rows (vy_xent_fwd flags them)
-  const float sc = dead ? 0.f : (*gscale) / fmaxf(*count, 1.0f);
-  const float l = lse[m];
-  for (int c = threadIdx.x; c < nch; c += blockDim.x) {
-    float v[VEC], o[VEC];
-    Chunk<T>::load(row + (int64_t)c * VEC, v);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const int col = c * VEC + e;
-      float g = 0.f;
-      if (!dead && col < V) g = (__expf(v[e] - l) - (col == label ? 1.f : 0.f)) * sc;
-      o[e] = g;  // pad columns stay zero
-    }
-    Chunk<T>::store(row + (int64_t)c * VEC, o);
-  }
-}
-
-// Fused forward + backward: the row (<= 65536 bf16 logits) lives in the registers of a 1024-thread
-// workgroup between the two reductions and the gradient store, so the logits cross HBM exactly
-// twice (one read, one write) instead of three reads and one write for vy_xent_fwd + vy_xent_bwd.
-__global__ __launch_bounds__(1024) void xent_fused_kernel(bf16* __restrict__ logits, int64_t ld,
-                                                          const int64_t* __restrict__ labels, int64_t ignore,
-                                                          float* __restrict__ lse, float* __restrict__ loss_sum,
-                                                          const float* __restrict__ count,
-                                                          const float* __restrict__ gscale, int V,
-                                                          int* __restrict__ err) {
-  constexpr int CPT = 8;  // 16-byte chunks per thread
-  __shared__ float red[16];
-  const int tid = threadIdx.x;
-  const int64_t m = blockIdx.x;
-  const int64_t label = labels[m];
-  bf16* row = logits + m * ld;
-  const int nch = (V + 7) / 8;
-  bf16x8 zero8;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) zero8[e] = (bf16)0.f;
-  const bool oob = label != ignore && (label < 0 || label >= V);   // see xent_fwd_kernel
-  if (oob && err && tid == 0) *err = 1;
-  if (label == ignore || oob) {
-    for (int c = tid; c < nch; c += 1024) *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = zero8;
-    if (tid == 0) lse[m] = 0.f;
-    return;
-  }
-  const float x_label = (float)row[label];  // read before any thread overwrites the row (barriers below)
-  bf16x8 v[CPT];
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int c = tid + i * 1024;
-    if (c < nch) v[i] = *reinterpret_cast<const bf16x8*>(row + (int64_t)c * 8);
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int c = tid + i * 1024;
-    if (c < nch) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (c * 8 + e < V) mx = fmaxf(mx, (float)v[i][e]);
-    }
-  }
-  const float gmx = block_reduce(mx, red, true);
-  float sm = 0.f;
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int c = tid + i * 1024;
-    if (c < nch) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (c * 8 + e < V) sm += __expf((float)v[i][e] - gmx);
-    }
-  }
-  const float gsm = block_reduce(sm, red, false);
-  const float l = gmx + __logf(gsm);
-  if (tid == 0) {
-    lse[m] = l;
-    atomicAdd(loss_sum, l - x_label);
-  }
-  const float sc = (*gscale) / fmaxf(*count, 1.0f);
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int c = tid + i * 1024;
-    if (c < nch) {
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int col = c * 8 + e;
-        float g = 0.f;  // pad columns stay zero
-        if (col < V) g = (__expf((float)v[i][e] - l) - (col == label ? 1.f : 0.f)) * sc;
-        o[e] = (bf16)g;
-      }
-      *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = o;
-    }
-  }
-}
-
-// ---- per-row log-probability of the label (DPO scoring): the xent kernels without the scalar reduction --------------
-// logp[m] = logits[m, label] - lse[m] for rows with weight != 0; the per-sequence sums are taken afterwards in a
-// fixed order over [B, L] (no float atomics here: two runs agree bit for bit).  A row with weight == 0 is skipped
-// (lse = logp = 0), a label outside [0, V) on a weighted row is never dereferenced: the row counts as skipped and
-// the device error flag is raised, as in xent_fwd_kernel.
-template <typename T>
-__global__ __launch_bounds__(256) void logprob_fwd_kernel(const T* __restrict__ logits, int64_t ld,
-                                                          const int64_t* __restrict__ labels,
-                                                          const float* __restrict__ weight, float* __restrict__ lse,
-                                                          float* __restrict__ logp, int V, int* __restrict__ err) {
-  constexpr int VEC = Chunk<T>::VEC;
-  __shared__ float red[4];
-  const int64_t m = blockIdx.x;
-  const int64_t label = labels[m];
-  const bool live = weight[m] != 0.f;
+  const auto s = p.load(m, false);
+  const bool live = p.live(s, label);
   const bool oob = live && (label < 0 || label >= V);
   if (oob && err && threadIdx.x == 0) *err = 1;
-  if (!live || oob) { if (threadIdx.x == 0) { lse[m] = 0.f; logp[m] = 0.f; } return; }
+  if (!live || oob) {
+    if (threadIdx.x == 0) { lse[m] = 0.f; p.skip(m); }
+    return;
+  }
   const T* row = logits + m * ld;
   const int nch = (V + VEC - 1) / VEC;
   float mx = -INFINITY, sm = 0.f;
@@ -730,24 +633,23 @@ __global__ __launch_bounds__(256) void logprob_fwd_kernel(const T* __restrict__ 
   if (threadIdx.x == 0) {
     const float l = gmx + __logf(gsm);
     lse[m] = l;
-    logp[m] = VyT<T>::ld(row + label) - l;
+    p.emit(m, l, VyT<T>::ld(row + label));
   }
 }
 
-// logits[m,:] <- weight[m] * (onehot(label) - softmax(logits[m,:])) in place, from the saved lse: the gradient of
-// weight[m] * logp[m] (the sign of a log-probability, not of a loss).  Pad columns and skipped rows become zero.
-template <typename T>
-__global__ __launch_bounds__(256) void logprob_bwd_kernel(T* __restrict__ logits, int64_t ld,
-                                                          const int64_t* __restrict__ labels,
-                                                          const float* __restrict__ weight,
-                                                          const float* __restrict__ lse, int V) {
+// Backward: logits[m, :] <- the policy's gradient in place, from the saved lse.  Pad columns and skipped rows
+// (out-of-range labels among them: the forward flags those) become zero.
+template <typename T, typename P>
+__global__ __launch_bounds__(256) void row_grad_kernel(T* __restrict__ logits, int64_t ld,
+                                                       const int64_t* __restrict__ labels, const P p,
+                                                       const float* __restrict__ lse, int V) {
   constexpr int VEC = Chunk<T>::VEC;
   const int64_t m = blockIdx.x;
   const int64_t label = labels[m];
   T* row = logits + m * ld;
   const int nch = (V + VEC - 1) / VEC;
-  const float w = weight[m];
-  const bool dead = w == 0.f || label < 0 || label >= V;   // out-of-range labels: skipped rows (vy_logprob_fwd flags them)
+  const auto s = p.load(m, true);
+  const bool dead = !p.live(s, label) || label < 0 || label >= V;
   const float l = lse[m];
   for (int c = threadIdx.x; c < nch; c += blockDim.x) {
     float v[VEC], o[VEC];
@@ -756,36 +658,37 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(T* __restrict__ logits
     for (int e = 0; e < VEC; ++e) {
       const int col = c * VEC + e;
       float g = 0.f;
-      if (!dead && col < V) g = ((col == label ? 1.f : 0.f) - __expf(v[e] - l)) * w;
+      if (!dead && col < V) g = p.grad(s, __expf(v[e] - l), col == label ? 1.f : 0.f);
       o[e] = g;  // pad columns stay zero
     }
     Chunk<T>::store(row + (int64_t)c * VEC, o);
   }
 }
 
-// Both in one pass, the row register-resident as in xent_fused_kernel (1024 threads x 8 chunks of 8 bf16): one read
-// and one write of the logits.
-__global__ __launch_bounds__(1024) void logprob_fused_kernel(bf16* __restrict__ logits, int64_t ld,
-                                                             const int64_t* __restrict__ labels,
-                                                             const float* __restrict__ weight,
-                                                             float* __restrict__ lse, float* __restrict__ logp, int V,
-                                                             int* __restrict__ err) {
+// Fused forward + backward: the row (<= 65536 bf16 logits) lives in the registers of a 1024-thread workgroup
+// (8 chunks of 8 bf16 per thread) between the two reductions and the gradient store, so the logits cross HBM exactly
+// twice (one read, one write) instead of three reads and one write for the pair above.
+template <typename P>
+__global__ __launch_bounds__(1024) void row_fused_kernel(bf16* __restrict__ logits, int64_t ld,
+                                                         const int64_t* __restrict__ labels, const P p,
+                                                         float* __restrict__ lse, int V, int* __restrict__ err) {
   constexpr int CPT = 8;  // 16-byte chunks per thread
   __shared__ float red[16];
   const int tid = threadIdx.x;
   const int64_t m = blockIdx.x;
   const int64_t label = labels[m];
-  const float w = weight[m];
+  const auto s = p.load(m, true);
   bf16* row = logits + m * ld;
   const int nch = (V + 7) / 8;
   bf16x8 zero8;
 #pragma unroll
   for (int e = 0; e < 8; ++e) zero8[e] = (bf16)0.f;
-  const bool oob = w != 0.f && (label < 0 || label >= V);   // see logprob_fwd_kernel
+  const bool live = p.live(s, label);
+  const bool oob = live && (label < 0 || label >= V);
   if (oob && err && tid == 0) *err = 1;
-  if (w == 0.f || oob) {
+  if (!live || oob) {
     for (int c = tid; c < nch; c += 1024) *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = zero8;
-    if (tid == 0) { lse[m] = 0.f; logp[m] = 0.f; }
+    if (tid == 0) { lse[m] = 0.f; p.skip(m); }
     return;
   }
   const float x_label = (float)row[label];  // read before any thread overwrites the row (barriers below)
@@ -820,7 +723,7 @@ __global__ __launch_bounds__(1024) void logprob_fused_kernel(bf16* __restrict__ 
   const float l = gmx + __logf(gsm);
   if (tid == 0) {
     lse[m] = l;
-    logp[m] = x_label - l;
+    p.emit(m, l, x_label);
   }
 #pragma unroll
   for (int i = 0; i < CPT; ++i) {
@@ -831,12 +734,60 @@ __global__ __launch_bounds__(1024) void logprob_fused_kernel(bf16* __restrict__ 
       for (int e = 0; e < 8; ++e) {
         const int col = c * 8 + e;
         float g = 0.f;  // pad columns stay zero
-        if (col < V) g = ((col == label ? 1.f : 0.f) - __expf((float)v[i][e] - l)) * w;
+        if (col < V) g = p.grad(s, __expf((float)v[i][e] - l), col == label ? 1.f : 0.f);
         o[e] = (bf16)g;
       }
       *reinterpret_cast<bf16x8*>(row + (int64_t)c * 8) = o;
     }
   }
+}
+
+// Host side of the six entry points: one set of checks (fn: the entry point's name, for the error strings; ptrs: every
+// pointer operand is there) and one launch per kernel.
+int row_check(const char* fn, bool ptrs, const void* logits, int64_t ld, int64_t M, int64_t V, int dtype, bool fused) {
+  if (!ptrs || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "%s: bad arguments", fn);
+  if (fused) {
+    const int b = (int)strlen(fn) - 6;  // "vy_xent" of "vy_xent_fused": names the two-pass pair
+    if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: bf16 only (use %.*s_fwd + %.*s_bwd)", fn, b, fn, b, fn);
+    if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use %.*s_fwd + %.*s_bwd)", fn, (long)V, b, fn, b, fn);
+    if (ld % 8 || ld < vy_cdiv(V, 8) * 8 || (uintptr_t)logits % 16) VY_FAIL(VY_ERR_ARG, "%s: rows must be 16-byte aligned and cover the padded width", fn);
+    return VY_OK;
+  }
+  const int vec = dtype == VY_BF16 ? 8 : 4;
+  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "%s: row stride must be a multiple of %d and cover the padded row", fn, vec);
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "%s: bad dtype %d", fn, dtype);
+  return VY_OK;
+}
+
+template <typename P>
+int row_lse(const char* fn, bool ptrs, const void* logits, int64_t ld, const int64_t* labels, const P& p, float* lse,
+            int64_t M, int64_t V, int32_t* err, int dtype, void* stream) {
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, false)) return rc;
+  const dim3 grid((unsigned)M), block(256);
+  if (dtype == VY_BF16) hipLaunchKernelGGL((row_lse_kernel<bf16, P>), grid, block, 0, (hipStream_t)stream, (const bf16*)logits, ld, labels, p, lse, (int)V, err);
+  else hipLaunchKernelGGL((row_lse_kernel<float, P>), grid, block, 0, (hipStream_t)stream, (const float*)logits, ld, labels, p, lse, (int)V, err);
+  VY_CHECK_LAUNCH(fn);
+  return VY_OK;
+}
+
+template <typename P>
+int row_grad(const char* fn, bool ptrs, void* logits, int64_t ld, const int64_t* labels, const P& p, const float* lse,
+             int64_t M, int64_t V, int dtype, void* stream) {
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, false)) return rc;
+  const dim3 grid((unsigned)M), block(256);
+  if (dtype == VY_BF16) hipLaunchKernelGGL((row_grad_kernel<bf16, P>), grid, block, 0, (hipStream_t)stream, (bf16*)logits, ld, labels, p, lse, (int)V);
+  else hipLaunchKernelGGL((row_grad_kernel<float, P>), grid, block, 0, (hipStream_t)stream, (float*)logits, ld, labels, p, lse, (int)V);
+  VY_CHECK_LAUNCH(fn);
+  return VY_OK;
+}
+
+template <typename P>
+int row_fused(const char* fn, bool ptrs, void* logits, int64_t ld, const int64_t* labels, const P& p, float* lse,
+              int64_t M, int64_t V, int32_t* err, int dtype, void* stream) {
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, true)) return rc;
+  hipLaunchKernelGGL((row_fused_kernel<P>), dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels, p, lse, (int)V, err);
+  VY_CHECK_LAUNCH(fn);
+  return VY_OK;
 }
 
 template <typename T>
@@ -1038,79 +989,39 @@ extern "C" int vy_act_bwd(const void* dy, int64_t lddy, const void* pre, int64_t
 extern "C" int vy_xent_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
                            float* loss_sum, float* count, int64_t M, int64_t V, int32_t* err_flag, int dtype,
                            void* stream) {
-  if (!logits || !labels || !lse || !loss_sum || !count || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_xent_fwd: bad arguments");
-  const int vec = dtype == VY_BF16 ? 8 : 4;
-  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_xent_fwd: row stride must be a multiple of %d and cover the padded row", vec);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VY_BF16) hipLaunchKernelGGL(xent_fwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (const bf16*)logits, ld, labels, ignore_index, lse, loss_sum, count, (int)V, err_flag);
-  else if (dtype == VY_F32) hipLaunchKernelGGL(xent_fwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (const float*)logits, ld, labels, ignore_index, lse, loss_sum, count, (int)V, err_flag);
-  else VY_FAIL(VY_ERR_ARG, "vy_xent_fwd: bad dtype %d", dtype);
-  VY_CHECK_LAUNCH("vy_xent_fwd");
-  return VY_OK;
+  return row_lse("vy_xent_fwd", loss_sum && count, logits, ld, labels,
+                 XentRow<true>{ignore_index, nullptr, nullptr, loss_sum, count}, lse, M, V, err_flag, dtype, stream);
 }
 
 extern "C" int vy_xent_bwd(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, const float* lse,
                            const float* gscale, const float* count, int64_t M, int64_t V, int dtype, void* stream) {
-  if (!logits || !labels || !lse || !gscale || !count || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_xent_bwd: bad arguments");
-  const int vec = dtype == VY_BF16 ? 8 : 4;
-  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_xent_bwd: row stride must be a multiple of %d and cover the padded row", vec);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VY_BF16) hipLaunchKernelGGL(xent_bwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (bf16*)logits, ld, labels, ignore_index, lse, gscale, count, (int)V);
-  else if (dtype == VY_F32) hipLaunchKernelGGL(xent_bwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (float*)logits, ld, labels, ignore_index, lse, gscale, count, (int)V);
-  else VY_FAIL(VY_ERR_ARG, "vy_xent_bwd: bad dtype %d", dtype);
-  VY_CHECK_LAUNCH("vy_xent_bwd");
-  return VY_OK;
+  return row_grad("vy_xent_bwd", gscale && count, logits, ld, labels,
+                  XentRow<false>{ignore_index, gscale, count, nullptr, nullptr}, lse, M, V, dtype, stream);
 }
 
 extern "C" int vy_xent_fused(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
                              float* loss_sum, const float* count, const float* gscale, int64_t M, int64_t V,
                              int32_t* err_flag, int dtype, void* stream) {
-  if (!logits || !labels || !lse || !loss_sum || !count || !gscale || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_xent_fused: bad arguments");
-  if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_xent_fused: bf16 only (use vy_xent_fwd + vy_xent_bwd)");
-  if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_xent_fused: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use vy_xent_fwd + vy_xent_bwd)", (long)V);
-  if (ld % 8 || ld < vy_cdiv(V, 8) * 8 || (uintptr_t)logits % 16) VY_FAIL(VY_ERR_ARG, "vy_xent_fused: rows must be 16-byte aligned and cover the padded width");
-  hipLaunchKernelGGL(xent_fused_kernel, dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels,
-                     ignore_index, lse, loss_sum, count, gscale, (int)V, err_flag);
-  VY_CHECK_LAUNCH("vy_xent_fused");
-  return VY_OK;
+  return row_fused("vy_xent_fused", loss_sum && count && gscale, logits, ld, labels,
+                   XentRow<false>{ignore_index, gscale, count, loss_sum, nullptr}, lse, M, V, err_flag, dtype, stream);
 }
 
 extern "C" int vy_logprob_fwd(const void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
                               float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream) {
-  if (!logits || !labels || !weight || !lse || !logp || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: bad arguments");
-  const int vec = dtype == VY_BF16 ? 8 : 4;
-  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: row stride must be a multiple of %d and cover the padded row", vec);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VY_BF16) hipLaunchKernelGGL(logprob_fwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (const bf16*)logits, ld, labels, weight, lse, logp, (int)V, err_flag);
-  else if (dtype == VY_F32) hipLaunchKernelGGL(logprob_fwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (const float*)logits, ld, labels, weight, lse, logp, (int)V, err_flag);
-  else VY_FAIL(VY_ERR_ARG, "vy_logprob_fwd: bad dtype %d", dtype);
-  VY_CHECK_LAUNCH("vy_logprob_fwd");
-  return VY_OK;
+  return row_lse("vy_logprob_fwd", weight && logp, logits, ld, labels, LogprobRow{weight, logp}, lse, M, V, err_flag,
+                 dtype, stream);
 }
 
 extern "C" int vy_logprob_bwd(void* logits, int64_t ld, const int64_t* labels, const float* weight, const float* lse,
                               int64_t M, int64_t V, int dtype, void* stream) {
-  if (!logits || !labels || !weight || !lse || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: bad arguments");
-  const int vec = dtype == VY_BF16 ? 8 : 4;
-  if (ld % vec || ld < vy_cdiv(V, vec) * vec) VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: row stride must be a multiple of %d and cover the padded row", vec);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VY_BF16) hipLaunchKernelGGL(logprob_bwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, st, (bf16*)logits, ld, labels, weight, lse, (int)V);
-  else if (dtype == VY_F32) hipLaunchKernelGGL(logprob_bwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, st, (float*)logits, ld, labels, weight, lse, (int)V);
-  else VY_FAIL(VY_ERR_ARG, "vy_logprob_bwd: bad dtype %d", dtype);
-  VY_CHECK_LAUNCH("vy_logprob_bwd");
-  return VY_OK;
+  return row_grad("vy_logprob_bwd", weight != nullptr, logits, ld, labels, LogprobRow{weight, nullptr}, lse, M, V, dtype,
+                  stream);
 }
 
 extern "C" int vy_logprob_fused(void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,
                                 float* logp, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream) {
-  if (!logits || !labels || !weight || !lse || !logp || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "vy_logprob_fused: bad arguments");
-  if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_logprob_fused: bf16 only (use vy_logprob_fwd + vy_logprob_bwd)");
-  if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_logprob_fused: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use vy_logprob_fwd + vy_logprob_bwd)", (long)V);
-  if (ld % 8 || ld < vy_cdiv(V, 8) * 8 || (uintptr_t)logits % 16) VY_FAIL(VY_ERR_ARG, "vy_logprob_fused: rows must be 16-byte aligned and cover the padded width");
-  hipLaunchKernelGGL(logprob_fused_kernel, dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels,
-                     weight, lse, logp, (int)V, err_flag);
-  VY_CHECK_LAUNCH("vy_logprob_fused");
-  return VY_OK;
+  return row_fused("vy_logprob_fused", weight && logp, logits, ld, labels, LogprobRow{weight, logp}, lse, M, V,
+                   err_flag, dtype, stream);
 }
 
 extern "C" int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream) {

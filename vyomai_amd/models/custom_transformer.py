@@ -413,7 +413,7 @@ class ModelForCausalLM(nn.Module):
         log-softmax fused.  With grad the logits are overwritten in place by their unit gradient (TiedLMHeadLogprobFn);
         under torch.no_grad() they are only read (vy_logprob_fwd) and freed on return.  A sequence whose mask selects
         nothing scores 0.  `inputs_embeds` replaces the embedding lookup (input_ids still supply the labels)."""
-        from ..autograd_train import TiedLMHeadLogprobFn, _row_stride, _sequence_sums, logprob_rows
+        from ..autograd_train import TiedLMHeadLogprobFn, logprob_rows, tied_head_logprobs
         if selection_mask.shape != input_ids.shape:
             raise ValueError(f"selection_mask {tuple(selection_mask.shape)} must match input_ids {tuple(input_ids.shape)}")
         _need_gpu(input_ids, "sequence_logprobs()")
@@ -427,18 +427,7 @@ class ModelForCausalLM(nn.Module):
         if _wants_grad(hidden, norm.weight, table):
             return TiedLMHeadLogprobFn.apply(hidden, labels, w, norm.weight, norm.variance_epsilon, table,
                                              self._table_pending(None if inputs_embeds is not None else input_ids), flag)
-        dt = hidden.dtype
-        B, L, _ = hidden.shape
-        V = table.shape[0]
-        n = ops.rmsnorm(hidden, _shadow(norm.weight, dt), norm.variance_epsilon, 0.0)
-        ld = _row_stride(V)
-        buf = torch.empty((B * L, ld), dtype=dt, device=hidden.device)
-        logits = buf[:, :V]   # (the pad columns are never read: the kernel stops at V)
-        ops.linear(n.view(B * L, -1), _shadow(table, dt), None, out=logits)
-        lse = torch.empty(B * L, dtype=torch.float32, device=hidden.device)
-        logp = torch.empty_like(lse)
-        ops.logprob_fwd(logits, labels, w.view(-1), lse, logp, flag)
-        return _sequence_sums(logp, w)
+        return tied_head_logprobs(hidden, labels, w, norm.weight, norm.variance_epsilon, table, flag)[0]
 
     def dpo_loss(self, batch, ref_model: Optional["ModelForCausalLM"] = None, beta: float = 0.1, ref_logprobs=None):
         """Direct preference optimisation on one collated batch -> (loss, chosen_rewards, rejected_rewards): the

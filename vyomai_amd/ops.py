@@ -522,11 +522,23 @@ def act_bwd(dy: Tensor, pre: Tensor, act: int) -> Tensor:
     return out.view(pre.shape)
 
 
+def _row_args(logits2d: Tensor, labels: Tensor, *rows: Tensor, scalars=()) -> None:
+    """Operand check of the six xent / logprob calls, whose kernels index by row: labels int64 (M,), every other
+    per-row operand fp32 (M,), all contiguous; the device scalars fp32 with one element."""
+    M = logits2d.shape[0]
+    assert labels.dtype == torch.long and labels.numel() == M and labels.is_contiguous()
+    for t in rows:
+        assert t.dtype == torch.float32 and t.numel() == M and t.is_contiguous()
+    for t in scalars:
+        assert t.dtype == torch.float32 and t.numel() == 1
+
+
 def xent_fwd(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, loss_sum: Tensor, count: Tensor,
              err_flag: Optional[Tensor] = None) -> None:
     """logits2d: (M, V) view with 16-byte aligned, padded rows; labels int64 (M,).  err_flag: device int32,
     set to 1 when a label is neither ignore_index nor in [0, V) (such rows count as ignored)."""
     _need_gpu(logits2d, labels, lse, loss_sum, count, err_flag)
+    _row_args(logits2d, labels, lse, scalars=(loss_sum, count))
     M, V = logits2d.shape
     call("vy_xent_fwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index, lse.data_ptr(),
          loss_sum.data_ptr(), count.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
@@ -535,9 +547,22 @@ def xent_fwd(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, l
 def xent_bwd_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, gscale: Tensor, count: Tensor) -> None:
     """Overwrite logits with d loss / d logits (in place)."""
     _need_gpu(logits2d, labels, lse, gscale, count)
+    _row_args(logits2d, labels, lse, scalars=(gscale, count))
     M, V = logits2d.shape
     call("vy_xent_bwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index, lse.data_ptr(),
          gscale.data_ptr(), count.data_ptr(), M, V, dtype_code(logits2d.dtype), _stream())
+
+
+def xent_fused_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, loss_sum: Tensor,
+                count: Tensor, gscale: Tensor, err_flag: Optional[Tensor] = None) -> None:
+    """One pass: lse / loss_sum as xent_fwd, then logits <- d loss / d logits in place (vy_xent_fused).
+    count (#rows with label != ignore) is an input here."""
+    _need_gpu(logits2d, labels, lse, loss_sum, count, gscale, err_flag)
+    _row_args(logits2d, labels, lse, scalars=(loss_sum, count, gscale))
+    M, V = logits2d.shape
+    call("vy_xent_fused", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index, lse.data_ptr(),
+         loss_sum.data_ptr(), count.data_ptr(), gscale.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype),
+         _stream())
 
 
 def embedding(table: Tensor, ids: Tensor, err_flag: Optional[Tensor] = None) -> Tensor:
@@ -598,31 +623,12 @@ def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[
          dtype_code(dout.dtype), _stream())
 
 
-def xent_fused_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, loss_sum: Tensor,
-                count: Tensor, gscale: Tensor, err_flag: Optional[Tensor] = None) -> None:
-    """One pass: lse / loss_sum as xent_fwd, then logits <- d loss / d logits in place (vy_xent_fused).
-    count (#rows with label != ignore) is an input here."""
-    _need_gpu(logits2d, labels, lse, loss_sum, count, gscale, err_flag)
-    M, V = logits2d.shape
-    call("vy_xent_fused", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index, lse.data_ptr(),
-         loss_sum.data_ptr(), count.data_ptr(), gscale.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype),
-         _stream())
-
-
-def _logprob_args(logits2d: Tensor, labels: Tensor, weight: Tensor, *outs: Tensor):
-    M = logits2d.shape[0]
-    assert labels.dtype == torch.long and labels.numel() == M and labels.is_contiguous()
-    assert weight.dtype == torch.float32 and weight.numel() == M and weight.is_contiguous()
-    for t in outs:
-        assert t.dtype == torch.float32 and t.numel() == M and t.is_contiguous()
-
-
 def logprob_fwd(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor, logp: Tensor,
                 err_flag: Optional[Tensor] = None) -> None:
     """lse[m] = logsumexp(row m), logp[m] = logits[m, label] - lse[m] for rows with weight != 0 (vy_logprob_fwd);
     logits2d: (M, V) view with 16-byte aligned, padded rows, read only; labels int64 (M,), weight / lse / logp fp32 (M,)."""
     _need_gpu(logits2d, labels, weight, lse, logp, err_flag)
-    _logprob_args(logits2d, labels, weight, lse, logp)
+    _row_args(logits2d, labels, weight, lse, logp)
     M, V = logits2d.shape
     call("vy_logprob_fwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(), lse.data_ptr(),
          logp.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
@@ -631,7 +637,7 @@ def logprob_fwd(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor, l
 def logprob_bwd_(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor) -> None:
     """logits <- weight * (onehot(label) - softmax) in place from the saved lse (vy_logprob_bwd)."""
     _need_gpu(logits2d, labels, weight, lse)
-    _logprob_args(logits2d, labels, weight, lse)
+    _row_args(logits2d, labels, weight, lse)
     M, V = logits2d.shape
     call("vy_logprob_bwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(), lse.data_ptr(),
          M, V, dtype_code(logits2d.dtype), _stream())
@@ -641,7 +647,7 @@ def logprob_fused_(logits2d: Tensor, labels: Tensor, weight: Tensor, lse: Tensor
                    err_flag: Optional[Tensor] = None) -> None:
     """One pass: lse / logp as logprob_fwd, then the row overwritten as by logprob_bwd_ (vy_logprob_fused)."""
     _need_gpu(logits2d, labels, weight, lse, logp, err_flag)
-    _logprob_args(logits2d, labels, weight, lse, logp)
+    _row_args(logits2d, labels, weight, lse, logp)
     M, V = logits2d.shape
     call("vy_logprob_fused", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), weight.data_ptr(),
          lse.data_ptr(), logp.data_ptr(), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
