@@ -17,7 +17,10 @@ def _ops():
     return ops
 
 
-@pytest.mark.parametrize("M,N,K", [(256, 128, 128), (1000, 768, 768), (4096, 3072, 768), (777, 768, 3072), (64, 2304, 768)])
+# (4100, 8200, 264): the single-launch 256 x 256 path (N >= 8192 and M >= 4096) -- three M-splits of 1408 rows, the last
+# chunk 1284 rows with 4 rows in its last 32-row stage, a ragged N tile (32 * 256 + 8) and a ragged K tile (256 + 8)
+@pytest.mark.parametrize("M,N,K", [(256, 128, 128), (1000, 768, 768), (4096, 3072, 768), (777, 768, 3072), (64, 2304, 768),
+                                   (4100, 8200, 264)])
 def test_wgrad(M, N, K):
     ops = _ops()
     dy, x = rnd(M, N, seed=1).to(BF), rnd(M, K, seed=2).to(BF)
@@ -102,7 +105,9 @@ def test_dgrad_exact(M, N, K):
 @pytest.mark.parametrize("dtype,M,N,K", [(BF, 256, 128, 128), (BF, 1000, 768, 768), (BF, 4096, 3072, 768),
                                          (BF, 777, 768, 3072), (BF, 64, 2304, 768),
                                          (torch.float32, 256, 128, 128), (torch.float32, 1000, 768, 520),
-                                         (torch.float32, 77, 50265, 64), (torch.float32, 4100, 72, 3072)])
+                                         (torch.float32, 77, 50265, 64), (torch.float32, 4100, 72, 3072),
+                                         # bf16, last so that the ids of the cases above (dtypeN-...) keep their index
+                                         (BF, 4100, 8200, 264)])
 def test_wgrad_exact(dtype, M, N, K):
     """The shapes of test_wgrad (bf16) and test_wgrad_fp32.  Dense operands in {-2..2}: |sum| <= 4 M, exact in the fp32
     output.  dW and db after the first call, after accumulate=True, after alpha = 0.5 (half-integers: still exact), and

@@ -40,308 +40,142 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* base, int row_bytes) {
 
 // ------------------------------------------------------------------------------------------
 // wgrad: dW[n,k] += sum_m dY[m,n] X[m,k]
-// tile 128(n) x 128(k), 64 rows of m per stage, 4 waves 2x2 of 64x64, split over M
+// tile BT(n) x BT(k), MS rows of m per stage; (BT/64) x 2 waves, each 64(n) x BT/2(k); split over M.
+// Two shapes are built: 128 x 128 with 64-row stages in a 2-deep ring (64 KiB of LDS, two workgroups per CU) and
+// 256 x 256 with 32-row stages in a 4-deep ring (128 KiB, one workgroup per CU).
+// The kernel is three parts: WgradTile (the LDS image of a stage and its writer), one ring in wgrad_tn_bf16_body
+// (when a stage is requested, which vmcnt is waited for, where the barrier sits) and a fragment policy per MFMA
+// shape, WgradMma32 / WgradMma16 (accumulators, the k-step schedule of one stage, bias gradient, atomic epilogue).
 // ------------------------------------------------------------------------------------------
-// tile BN(n) x BKW(k), MS rows of m per stage; (BN/64) x 2 waves, each 64(n) x BKW/2(k)
-// NS stages of LDS: the loads of the next NS-1 stages are in flight while a stage is multiplied; a
-// stage is waited for with a COUNTED vmcnt (its PA+PB LDS-DMA instructions are the wave's oldest)
-// and one raw s_barrier.
-// NS == 0 selects the asymmetric ring: the dY tile three deep, the X tile two deep (3*ATILE + 2*BTILE =
-// 80 KiB at 128 x 128 x 64: still two workgroups per CU) -- the dY loads of stage s+2 stay in flight
-// across the barrier that ends stage s, as X does in gemm_nt_bf16_x3m16_kernel (vy_gemm.hip).
-// MF16: mfma_f32_16x16x32_bf16 instead of 32x32x16 (as in the forward / dgrad GEMMs: fewer cycles per stage and a higher
-// clock, vy_gemm.hip): 4 x WKT/16 blocks of 16 x 16 per wave, 32 rows of m per MFMA.  The transposing reads of a 16-lane
-// group take the 4 rows 4 (lane >> 4) + q (and + 16), so the two groups of a 32-lane half read DIFFERENT rows of the same
-// columns: the source-side swizzle gets a second bit ((row >> 2) & 1) << 5 that puts them in the two 32-byte halves of a
-// 64-byte slot (conflict-free).  The atomic epilogue exchanges lane halves of two neighbouring k blocks
-// (v_permlane32_swap) so that a wave instruction is again two 128-byte row segments.
-template <int BN, int BKW, int MS, int NS, bool MF16 = false>
-__device__ __forceinline__ void wgrad_tn_bf16_body(
-    const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
-    float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
-    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int diag, int wg) {
-  constexpr int NW = BN / 32;                 // waves: (BN/64) x 2
-  constexpr int WKT = BKW / 2, TJ = WKT / 32; // k extent of a wave, 32-wide fragments along k
-  constexpr int AROW = BN * 2, BROW = BKW * 2;  // LDS row bytes of the dY and X tiles
-  constexpr int ATILE = MS * AROW, BTILE = MS * BROW;
-  constexpr int STAGE = ATILE + BTILE;
-  constexpr int PA = ATILE / 1024 / NW, PB = BTILE / 1024 / NW;  // LDS-DMA pieces per wave
-  constexpr int KS = MS / 16;
-  static_assert(PA * 1024 * NW == ATILE && PB * 1024 * NW == BTILE && (KS == 2 || KS == 4), "tile / wave layout mismatch");
-  constexpr bool A3 = NS == 0;
-  __shared__ __attribute__((aligned(16))) char smem[A3 ? 3 * ATILE + 2 * BTILE : NS * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wn = wave >> 1, wk = wave & 1;
-  const int split = wg / tiles_nk, t2 = wg - split * tiles_nk;
-  const int tile_n = t2 / tiles_k, tile_k = t2 - tile_n * tiles_k;
-  const int n0 = tile_n * BN, k0 = tile_k * BKW;
-  const int m_begin = split * m_chunk;
-  const int m_end = min(M, m_begin + m_chunk);
-  if (m_begin >= m_end) return;
-  const int nst = (m_end - m_begin + MS - 1) / MS;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
-  // LDS-DMA geometry: 1-KiB pieces; 64-byte swizzle (row & 3) << 6 on the source side
-  int a_row[PA], a_off[PA], b_row[PB], b_off[PB];
-#pragma unroll
-  for (int t = 0; t < PA; ++t) {
-    const int P = (wave * PA + t) * 1024 + lane * 16;
-    const int row = P / AROW, off = P % AROW;
-    a_row[t] = row;
-    a_off[t] = (off ^ (((row & 3) << 6) | (MF16 ? ((row >> 2) & 1) << 5 : 0))) >> 1;
-  }
-#pragma unroll
-  for (int t = 0; t < PB; ++t) {
-    const int P = (wave * PB + t) * 1024 + lane * 16;
-    const int row = P / BROW, off = P % BROW;
-    b_row[t] = row;
-    b_off[t] = (off ^ (((row & 3) << 6) | (MF16 ? ((row >> 2) & 1) << 5 : 0))) >> 1;
-  }
-  const bf16* zero = reinterpret_cast<const bf16*>(vy_zero16);
+// One stage of an operand in LDS: MS rows of BT bf16, row-major, staged by LDS-DMA in 1-KiB pieces (wave w owns
+// pieces w PP .. w PP + PP - 1), with the 64-byte swizzle (row & 3) << 6 on the source side.  MF16: the
+// transposing reads of a 16-lane group take the 4 rows 4 (lane >> 4) + q (and + 16), so the two groups of a 32-lane
+// half read DIFFERENT rows of the same columns: a second swizzle bit ((row >> 2) & 1) << 5 puts them in the two
+// 32-byte halves of a 64-byte slot (conflict-free).  The dY and the X tile have the same shape, so a lane's row and
+// column within a piece are the same for both.
+template <int BT, int MS_, bool MF16>
+struct WgradTile {
+  static constexpr int MS = MS_;                     // rows of m per stage
+  static constexpr int NW = BT / 32;                 // waves: (BT/64) x 2
+  static constexpr int WKT = BT / 2;                 // k extent of a wave
+  static constexpr int ROWB = BT * 2;                // LDS row bytes of either tile
+  static constexpr int TILE = MS * ROWB, STAGE = 2 * TILE;   // a stage: the dY tile, then the X tile
+  static constexpr int PP = TILE / 1024 / NW;        // LDS-DMA pieces per wave and operand
+  static_assert(PP * 1024 * NW == TILE, "tile / wave layout mismatch");
+
+  int wave, nst, m_begin, m_end;
+  bool ragged;                                       // the last stage holds fewer than MS rows
+  int row[PP];
+  const bf16* a_ptr[PP]; const bf16* b_ptr[PP];
+  int64_t a_step[PP], b_step[PP];
+  const bf16* zero;
+
   // Per-piece source pointers are advanced by MS rows per stage (one 64-bit add each) instead of being
   // rebuilt from row * ld every stage (the 64-bit multiplies and selects were ~120 instructions per
   // stage and wave, next to 16 MFMAs).  A lane whose columns lie beyond N / K reads the zero page all
   // along; only the LAST stage of a chunk can have rows beyond m_end and takes the checked path.
-  const bf16* a_ptr[PA]; const bf16* b_ptr[PB];
-  int64_t a_step[PA], b_step[PB];
-#pragma unroll
-  for (int t = 0; t < PA; ++t) {
-    const bool ok = n0 + a_off[t] < N;
-    a_ptr[t] = ok ? dY + (int64_t)(m_begin + a_row[t]) * lddy + n0 + a_off[t] : zero;
-    a_step[t] = ok ? (int64_t)MS * lddy : 0;
+  __device__ __forceinline__ WgradTile(const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
+                                       int n0, int k0, int N, int K, int m_begin_, int m_end_, int wave_, int lane) {
+    wave = wave_, m_begin = m_begin_, m_end = m_end_;
+    nst = (m_end - m_begin + MS - 1) / MS;
+    ragged = ((m_end - m_begin) % MS) != 0;
+    zero = reinterpret_cast<const bf16*>(vy_zero16);
+    sources(dY, lddy, n0, N, lane, a_ptr, a_step);
+    sources(X, ldx, k0, K, lane, b_ptr, b_step);
   }
+  // the lane's 16 bytes of each of the wave's pieces of stage 0, and the step to the next stage
+  __device__ __forceinline__ void sources(const bf16* __restrict__ src, int64_t ld, int c0, int C, int lane,
+                                          const bf16* (&ptr)[PP], int64_t (&step)[PP]) {
 #pragma unroll
-  for (int t = 0; t < PB; ++t) {
-    const bool ok = k0 + b_off[t] < K;
-    b_ptr[t] = ok ? X + (int64_t)(m_begin + b_row[t]) * ldx + k0 + b_off[t] : zero;
-    b_step[t] = ok ? (int64_t)MS * ldx : 0;
+    for (int t = 0; t < PP; ++t) {
+      const int P = (wave * PP + t) * 1024 + lane * 16;
+      const int r = P / ROWB, off = P % ROWB;
+      const int col = (off ^ (((r & 3) << 6) | (MF16 ? ((r >> 2) & 1) << 5 : 0))) >> 1;
+      const bool ok = c0 + col < C;
+      row[t] = r;
+      ptr[t] = ok ? src + (int64_t)(m_begin + r) * ld + c0 + col : zero;
+      step[t] = ok ? (int64_t)MS * ld : 0;
+    }
   }
-  const bool ragged = ((m_end - m_begin) % MS) != 0;   // the last stage holds fewer than MS rows
-  auto stage_a = [&](int s, char* dst) {
+  __device__ __forceinline__ void issue(const bf16* (&ptr)[PP], const int64_t (&step)[PP], int s, char* dst) {
     const bool tail = ragged && s == nst - 1;
     const int rows = m_end - (m_begin + s * MS);
 #pragma unroll
-    for (int t = 0; t < PA; ++t) {
-      const bf16* a = (tail && a_row[t] >= rows) ? zero : a_ptr[t];
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)a, (VY_LDS void*)(dst + (wave * PA + t) * 1024), 16, 0, 0);
-      a_ptr[t] += a_step[t];
+    for (int t = 0; t < PP; ++t) {
+      const bf16* p = (tail && row[t] >= rows) ? zero : ptr[t];
+      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)p, (VY_LDS void*)(dst + (wave * PP + t) * 1024), 16, 0, 0);
+      ptr[t] += step[t];
     }
-  };
-  auto stage_b = [&](int s, char* dst) {
-    const bool tail = ragged && s == nst - 1;
-    const int rows = m_end - (m_begin + s * MS);
-#pragma unroll
-    for (int t = 0; t < PB; ++t) {
-      const bf16* b = (tail && b_row[t] >= rows) ? zero : b_ptr[t];
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)b, (VY_LDS void*)(dst + (wave * PB + t) * 1024), 16, 0, 0);
-      b_ptr[t] += b_step[t];
-    }
-  };
-  auto stage = [&](int s, int buf) {
-    stage_a(s, smem + buf * STAGE);
-    stage_b(s, smem + buf * STAGE + ATILE);
-  };
+  }
+  // request stage s (stages are requested in order) into the stage region at `dst`
+  __device__ __forceinline__ void stage(int s, char* dst) {
+    issue(a_ptr, a_step, s, dst);
+    issue(b_ptr, b_step, s, dst + TILE);
+  }
+};
 
-  if constexpr (MF16) {
-    static_assert(MS % 32 == 0 && !(NS == 0), "16x16x32: stages of 32-row k-steps, symmetric ring");
-    constexpr int TI = 4, TJ16 = WKT / 16, KS16 = MS / 32, JH = TJ16 / 2;
-    f32x4 acc[TI][TJ16];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool do_db = db != nullptr && tile_k == 0 && wk == 0;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-    const bf16x2_t ones2 = {(__bf16)1.0f, (__bf16)1.0f};
-    float sdb[TI] = {0.f, 0.f, 0.f, 0.f};
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int q_ = r16 >> 2, p_ = r16 & 3;
-    const int sw16 = (q_ << 6) | ((kq & 1) << 5);
-    unsigned a_lds[TI], b_lds[TJ16];   // stage 0, k-step 0, first read (rows 4 kq + q_)
-#pragma unroll
-    for (int i = 0; i < TI; ++i) a_lds[i] = vy_lds_addr(smem) + (4 * kq + q_) * AROW + ((2 * (wn * 64 + 16 * i + 4 * p_)) ^ sw16);
-#pragma unroll
-    for (int j = 0; j < TJ16; ++j) b_lds[j] = vy_lds_addr(smem) + (4 * kq + q_) * BROW + ((2 * (wk * WKT + 16 * j + 4 * p_)) ^ sw16);
-#pragma unroll
-    for (int s_ = 0; s_ < NS - 1; ++s_)
-      if (s_ < nst) stage(s_, s_);
-    for (int s = 0; s < nst; ++s) {
-      const int cur = s % NS;
-      const int younger = min(NS - 2, nst - 1 - s);
-      if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PA + PB)) : "memory");
-      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (s + NS - 1 < nst) stage(s + NS - 1, (s + NS - 1) % NS);
-      unsigned a_base[TI], b_base[TJ16];
-#pragma unroll
-      for (int i = 0; i < TI; ++i) a_base[i] = a_lds[i] + cur * STAGE;
-#pragma unroll
-      for (int j = 0; j < TJ16; ++j) b_base[j] = b_lds[j] + cur * STAGE;
-      // per k-step: the dY fragments and the first half of the X fragments, the second half requested before the
-      // first half's MFMAs (counted lgkmcnt: two reads per fragment)
-      vy_static_for<KS16>([&](auto ks_c) {
-        constexpr int ks = decltype(ks_c)::value;
-        bf16x8 af[TI], bfr[TJ16];
-        vy_static_for<TI>([&](auto i_c) {
-          constexpr int i = decltype(i_c)::value;
-          af[i] = vy_lds_tr16_pair_off<32 * ks * AROW, (32 * ks + 16) * AROW>(a_base[i]);
-        });
-        vy_static_for<JH>([&](auto j_c) {
-          constexpr int j = decltype(j_c)::value;
-          bfr[j] = vy_lds_tr16_pair_off<ATILE + 32 * ks * BROW, ATILE + (32 * ks + 16) * BROW>(b_base[j]);
-        });
-        vy_static_for<JH>([&](auto j_c) {
-          constexpr int j = JH + decltype(j_c)::value;
-          bfr[j] = vy_lds_tr16_pair_off<ATILE + 32 * ks * BROW, ATILE + (32 * ks + 16) * BROW>(b_base[j]);
-        });
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * JH) : "memory");
-#pragma unroll
-        for (int i = 0; i < TI; ++i) vy_tie(af[i]);
-#pragma unroll
-        for (int j = 0; j < JH; ++j) vy_tie(bfr[j]);
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = 0; j < JH; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int j = JH; j < TJ16; ++j) vy_tie(bfr[j]);
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = JH; j < TJ16; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        if (do_db) {
-#pragma unroll
-          for (int i = 0; i < TI; ++i) {
-            union { bf16x8 v; bf16x2_t h[4]; } u_;
-            u_.v = af[i];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sdb[i] = __builtin_amdgcn_fdot2_f32_bf16(u_.h[e], ones2, sdb[i], false);
-          }
-        }
-      });
-    }
-    if (diag == 1) {  // timing-only: no atomic epilogue (results wrong)
-      if (acc[0][0][0] == 12345.678f) dW[0] = 1.f;
-      return;
-    }
-    const float alpha = alpha_dev ? *alpha_dev : 1.0f;
-    if (do_db) {
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        float t_ = sdb[i];
-        t_ += __shfl_xor(t_, 16, 64);
-        t_ += __shfl_xor(t_, 32, 64);
-        const int n = n0 + wn * 64 + 16 * i + r16;
-        if (kq == 0 && n < N) atomicAdd(db + n, t_ * alpha);
-      }
-    }
-    // D[n][k] of block (i, j): lane = k index (lane & 15), register r = n row 4 kq + r.  Blocks j and j + 1 trade lane
-    // halves so that one wave instruction adds rows {r, 4 + r} (then {8 + r, 12 + r}) x 32 consecutive k
-    const bool hi = lane >= 32;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int jp = 0; jp < JH; ++jp) {
-        const int k = k0 + wk * WKT + 16 * (2 * jp + (hi ? 1 : 0)) + r16;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const unsigned x = __builtin_bit_cast(unsigned, acc[i][2 * jp][r] * alpha);
-          const unsigned y = __builtin_bit_cast(unsigned, acc[i][2 * jp + 1][r] * alpha);
-          auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-          const int nlo = n0 + wn * 64 + 16 * i + 4 * (kq & 1) + r;
-          if (k < K) {
-            if (nlo < N) atomicAdd(dW + (int64_t)nlo * lddw + k, __builtin_bit_cast(float, (unsigned)sw[0]));
-            if (nlo + 8 < N) atomicAdd(dW + (int64_t)(nlo + 8) * lddw + k, __builtin_bit_cast(float, (unsigned)sw[1]));
-          }
-        }
-      }
-  } else {
-  f32x16 acc[2][TJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // bias gradient db[n] = sum_m dY[m,n] in the k-tile-0 workgroups: the dY fragments are already
-  // in registers (row n = lane & 31, 8 m values per lane), so it is 4 v_dot2_f32_bf16 against ones
-  // per fragment on the otherwise idle VALU, plus one cross-half add at the end
-  const bool do_db = db != nullptr && tile_k == 0 && wk == 0;
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+// db[n] partial of one dY fragment (8 m values of one column n per lane): 4 v_dot2_f32_bf16 against ones on the
+// otherwise idle VALU
+__device__ __forceinline__ float wgrad_db_dot(const bf16x8& a, float s) {
   const bf16x2_t ones2 = {(__bf16)1.0f, (__bf16)1.0f};
-  float sdb[2] = {0.f, 0.f};
+  union { bf16x8 v; bf16x2_t h[4]; } u_;
+  u_.v = a;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_fdot2_f32_bf16(u_.h[e], ones2, s, false);
+  return s;
+}
 
-  const int li = lane & 15, g16 = (lane >> 4) & 1, fh = lane >> 5;
-  const int tr_row = 4 * fh + (li >> 2);                  // + 16*s (second read +8)
-  const int tr_sw = ((li >> 2) & 3) << 6;                 // (row & 3) << 6
-  const int a_rd = (2 * (wn * 64 + 16 * g16 + 4 * (li & 3)));  // + 64*i, then ^ tr_sw
-  const int b_rd = (2 * (wk * WKT + 16 * g16 + 4 * (li & 3)));
-  unsigned a_lds[2], b_lds[TJ];   // LDS byte address of fragment column i / j, row tr_row, stage 0
-#pragma unroll
-  for (int i = 0; i < 2; ++i) a_lds[i] = vy_lds_addr(smem) + tr_row * AROW + ((a_rd + 64 * i) ^ tr_sw);
-#pragma unroll
-  for (int j = 0; j < TJ; ++j) b_lds[j] = vy_lds_addr(smem) + tr_row * BROW + ((b_rd + 64 * j) ^ tr_sw);
+// mfma_f32_32x32x16_bf16: 2 x TJ blocks of 32 x 32 per wave, 16 rows of m per k-step.
+template <class T>
+struct WgradMma32 {
+  static constexpr int TJ = T::WKT / 32, KS = T::MS / 16, ROWB = T::ROWB;
+  f32x16 acc[2][TJ];
+  float sdb[2];
+  int fr, fh;
+  unsigned a_lds[2], b_lds[TJ];   // LDS byte address of fragment column i / j, row tr_row, stage 0 (X: + TILE)
 
-  if constexpr (A3) {
-    stage_a(0, smem);
-    stage_b(0, smem + 3 * ATILE);
-    if (nst > 1) stage_a(1, smem + ATILE);
-  } else {
+  __device__ __forceinline__ WgradMma32(const char* smem, int lane, int wn, int wk) {
 #pragma unroll
-    for (int s_ = 0; s_ < NS - 1; ++s_)
-      if (s_ < nst) stage(s_, s_);
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    sdb[0] = sdb[1] = 0.f;
+    fr = lane & 31, fh = lane >> 5;
+    const int li = lane & 15, g16 = (lane >> 4) & 1;
+    const int tr_row = 4 * fh + (li >> 2);                  // + 16*s (second read +8)
+    const int tr_sw = ((li >> 2) & 3) << 6;                 // (row & 3) << 6
+    const int a_rd = (2 * (wn * 64 + 16 * g16 + 4 * (li & 3)));  // + 64*i, then ^ tr_sw
+    const int b_rd = (2 * (wk * T::WKT + 16 * g16 + 4 * (li & 3)));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) a_lds[i] = vy_lds_addr(smem) + tr_row * ROWB + ((a_rd + 64 * i) ^ tr_sw);
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) b_lds[j] = vy_lds_addr(smem) + tr_row * ROWB + ((b_rd + 64 * j) ^ tr_sw);
   }
-  int abuf = 0;   // s % 3 (A3)
-  for (int s = 0; s < nst; ++s) {
+  // The stage at byte offset `off`: fragments of k-step ks+1 are requested before the MFMAs of k-step ks (asm reads +
+  // counted lgkmcnt: see vy_common.h -- the builtin form would drain the LDS-DMA prefetch first).  One
+  // base address per fragment column; the k-step and the +8 row go into the offset field.
+  __device__ __forceinline__ void mma_stage(unsigned off, bool do_db) {
     unsigned a_base[2], b_base[TJ];
-    if constexpr (A3) {
-      // the wave's queue, oldest first: A(s), B(s), A(s+1) -- the youngest PA instructions may stay
-      if (s + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (s + 1 < nst) stage_b(s + 1, smem + 3 * ATILE + ((s + 1) & 1) * BTILE);
-      if (s + 2 < nst) stage_a(s + 2, smem + (abuf == 0 ? 2 : abuf - 1) * ATILE);   // (s + 2) % 3
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a_base[i] = a_lds[i] + abuf * ATILE;
+    for (int i = 0; i < 2; ++i) a_base[i] = a_lds[i] + off;
 #pragma unroll
-      for (int j = 0; j < TJ; ++j) b_base[j] = b_lds[j] + 2 * ATILE + (s & 1) * BTILE;
-      abuf = abuf == 2 ? 0 : abuf + 1;
-    } else {
-      const int cur = s % (NS > 0 ? NS : 1);
-      const int younger = min(NS - 2, nst - 1 - s);  // stages issued after stage s
-      if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PA + PB)) : "memory");
-      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (s + NS - 1 < nst) stage(s + NS - 1, (s + NS - 1) % (NS > 0 ? NS : 1));  // the buffer stage s-1 was read from
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a_base[i] = a_lds[i] + cur * STAGE;
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) b_base[j] = b_lds[j] + cur * STAGE;
-    }
-    // fragments of k-step ks+1 are requested before the MFMAs of k-step ks (asm reads + counted
-    // lgkmcnt: see vy_common.h -- the builtin form would drain the LDS-DMA prefetch first).  One
-    // base address per fragment column; the k-step and the +8 row go into the offset field.
+    for (int j = 0; j < TJ; ++j) b_base[j] = b_lds[j] + off;
     bf16x8 af[2][2], bfr[2][TJ];
     auto frags = [&](auto ks_c, bf16x8* a_, bf16x8* b_) {
       constexpr int ks = decltype(ks_c)::value;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        a_[i] = vy_lds_tr16_pair_off<16 * ks * AROW, (16 * ks + 8) * AROW>(a_base[i]);
+        a_[i] = vy_lds_tr16_pair_off<16 * ks * ROWB, (16 * ks + 8) * ROWB>(a_base[i]);
 #pragma unroll
       for (int j = 0; j < TJ; ++j)
-        b_[j] = vy_lds_tr16_pair_off<ATILE + 16 * ks * BROW, ATILE + (16 * ks + 8) * BROW>(b_base[j]);
+        b_[j] = vy_lds_tr16_pair_off<T::TILE + 16 * ks * ROWB, T::TILE + (16 * ks + 8) * ROWB>(b_base[j]);
     };
     frags(std::integral_constant<int, 0>{}, af[0], bfr[0]);
-    auto kstep = [&](auto ks_c) {
+    vy_static_for<KS>([&](auto ks_c) {
       constexpr int ks = decltype(ks_c)::value;
       constexpr int c_ = ks & 1;
       if constexpr (ks < KS - 1) {
@@ -359,54 +193,201 @@ __device__ __forceinline__ void wgrad_tn_bf16_body(
 #pragma unroll
         for (int j = 0; j < TJ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[c_][i], bfr[c_][j], acc[i][j], 0, 0, 0);
+      // the dY fragments are already in registers: row n = lane & 31, 8 m values per lane
       if (do_db) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          union { bf16x8 v; bf16x2_t h[4]; } u_;
-          u_.v = af[c_][i];
+        for (int i = 0; i < 2; ++i) sdb[i] = wgrad_db_dot(af[c_][i], sdb[i]);
+      }
+    });
+  }
+  // nw / kw: first dW row / column of the wave's sub-tile
+  __device__ __forceinline__ void epilogue(float* __restrict__ dW, int64_t lddw, float* __restrict__ db, bool do_db,
+                                           float alpha, int nw, int kw, int N, int K) {
+    if (do_db) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) sdb[i] = __builtin_amdgcn_fdot2_f32_bf16(u_.h[e], ones2, sdb[i], false);
+      for (int i = 0; i < 2; ++i) {
+        const float t_ = (sdb[i] + __shfl_xor(sdb[i], 32, 64)) * alpha;   // the one cross-half add
+        const int n = nw + 32 * i + fr;
+        if (fh == 0 && n < N) atomicAdd(db + n, t_);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int k = kw + 32 * j + fr;
+        if (k >= K) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int n = nw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
+          if (n < N) atomicAdd(dW + (int64_t)n * lddw + k, acc[i][j][r] * alpha);
         }
       }
-    };
-    vy_static_for<KS>(kstep);
   }
-  const int fr = lane & 31;
+};
+
+// mfma_f32_16x16x32_bf16 (as in the forward / dgrad GEMMs: fewer cycles per stage and a higher clock, vy_gemm.hip):
+// 4 x TJ blocks of 16 x 16 per wave, 32 rows of m per k-step.
+template <class T>
+struct WgradMma16 {
+  static constexpr int TI = 4, TJ = T::WKT / 16, KS = T::MS / 32, JH = TJ / 2, ROWB = T::ROWB;
+  f32x4 acc[TI][TJ];
+  float sdb[TI];
+  int r16, kq;
+  unsigned a_lds[TI], b_lds[TJ];   // stage 0, k-step 0, first read (rows 4 kq + q_)
+
+  __device__ __forceinline__ WgradMma16(const char* smem, int lane, int wn, int wk) {
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TI; ++i) sdb[i] = 0.f;
+    r16 = lane & 15, kq = lane >> 4;
+    const int q_ = r16 >> 2, p_ = r16 & 3;
+    const int sw16 = (q_ << 6) | ((kq & 1) << 5);
+#pragma unroll
+    for (int i = 0; i < TI; ++i) a_lds[i] = vy_lds_addr(smem) + (4 * kq + q_) * ROWB + ((2 * (wn * 64 + 16 * i + 4 * p_)) ^ sw16);
+#pragma unroll
+    for (int j = 0; j < TJ; ++j)
+      b_lds[j] = vy_lds_addr(smem) + (4 * kq + q_) * ROWB + ((2 * (wk * T::WKT + 16 * j + 4 * p_)) ^ sw16);
+  }
+  // The stage at byte offset `off`, per k-step: the dY fragments and the first half of the X fragments, the second half
+  // requested before the first half's MFMAs (counted lgkmcnt: two reads per fragment)
+  __device__ __forceinline__ void mma_stage(unsigned off, bool do_db) {
+    unsigned a_base[TI], b_base[TJ];
+#pragma unroll
+    for (int i = 0; i < TI; ++i) a_base[i] = a_lds[i] + off;
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) b_base[j] = b_lds[j] + off;
+    vy_static_for<KS>([&](auto ks_c) {
+      constexpr int ks = decltype(ks_c)::value;
+      bf16x8 af[TI], bfr[TJ];
+      vy_static_for<TI>([&](auto i_c) {
+        constexpr int i = decltype(i_c)::value;
+        af[i] = vy_lds_tr16_pair_off<32 * ks * ROWB, (32 * ks + 16) * ROWB>(a_base[i]);
+      });
+      vy_static_for<TJ>([&](auto j_c) {
+        constexpr int j = decltype(j_c)::value;
+        bfr[j] = vy_lds_tr16_pair_off<T::TILE + 32 * ks * ROWB, T::TILE + (32 * ks + 16) * ROWB>(b_base[j]);
+      });
+      asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * JH) : "memory");
+#pragma unroll
+      for (int i = 0; i < TI; ++i) vy_tie(af[i]);
+#pragma unroll
+      for (int j = 0; j < JH; ++j) vy_tie(bfr[j]);
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < JH; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int j = JH; j < TJ; ++j) vy_tie(bfr[j]);
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = JH; j < TJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      // the dY fragments are already in registers: row n = lane & 15, 8 m values per lane
+      if (do_db) {
+#pragma unroll
+        for (int i = 0; i < TI; ++i) sdb[i] = wgrad_db_dot(af[i], sdb[i]);
+      }
+    });
+  }
+  // nw / kw: first dW row / column of the wave's sub-tile
+  __device__ __forceinline__ void epilogue(float* __restrict__ dW, int64_t lddw, float* __restrict__ db, bool do_db,
+                                           float alpha, int nw, int kw, int N, int K) {
+    if (do_db) {
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        float t_ = sdb[i];
+        t_ += __shfl_xor(t_, 16, 64);
+        t_ += __shfl_xor(t_, 32, 64);
+        const int n = nw + 16 * i + r16;
+        if (kq == 0 && n < N) atomicAdd(db + n, t_ * alpha);
+      }
+    }
+    // D[n][k] of block (i, j): lane = k index (lane & 15), register r = n row 4 kq + r.  Blocks j and j + 1 trade lane
+    // halves (v_permlane32_swap) so that one wave instruction adds rows {r, 4 + r} (then {8 + r, 12 + r}) x 32
+    // consecutive k: again two 128-byte row segments
+    const bool hi = kq >= 2;
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int jp = 0; jp < JH; ++jp) {
+        const int k = kw + 16 * (2 * jp + (hi ? 1 : 0)) + r16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned x = __builtin_bit_cast(unsigned, acc[i][2 * jp][r] * alpha);
+          const unsigned y = __builtin_bit_cast(unsigned, acc[i][2 * jp + 1][r] * alpha);
+          auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+          const int nlo = nw + 16 * i + 4 * (kq & 1) + r;
+          if (k < K) {
+            if (nlo < N) atomicAdd(dW + (int64_t)nlo * lddw + k, __builtin_bit_cast(float, (unsigned)sw[0]));
+            if (nlo + 8 < N) atomicAdd(dW + (int64_t)(nlo + 8) * lddw + k, __builtin_bit_cast(float, (unsigned)sw[1]));
+          }
+        }
+      }
+  }
+};
+
+// The ring: NS stages of LDS, the loads of the next NS-1 stages in flight while a stage is multiplied; a stage is
+// waited for with a COUNTED vmcnt (its 2 PP LDS-DMA instructions are the wave's oldest) and one raw s_barrier.
+template <int BN, int BKW, int MS, int NS, bool MF16>
+__device__ __forceinline__ void wgrad_tn_bf16_body(
+    const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
+    float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
+    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int diag, int wg) {
+  static_assert(BN == BKW && ((BN == 128 && MS == 64 && NS == 2) || (BN == 256 && MS == 32 && NS == 4)),
+                "built shapes: 128 x 128 x 64 in 2 stages, 256 x 256 x 32 in 4");
+  typedef WgradTile<BN, MS, MF16> Tile;
+  typedef std::conditional_t<MF16, WgradMma16<Tile>, WgradMma32<Tile>> Mma;
+  constexpr int STAGE = Tile::STAGE, PS = 2 * Tile::PP;   // LDS-DMA instructions per wave and stage
+  __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wn = wave >> 1, wk = wave & 1;
+  const int split = wg / tiles_nk, t2 = wg - split * tiles_nk;
+  const int tile_n = t2 / tiles_k, tile_k = t2 - tile_n * tiles_k;
+  const int n0 = tile_n * BN, k0 = tile_k * BKW;
+  const int m_begin = split * m_chunk;
+  const int m_end = min(M, m_begin + m_chunk);
+  if (m_begin >= m_end) return;
+
+  Tile t(dY, lddy, X, ldx, n0, k0, N, K, m_begin, m_end, wave, lane);
+  const bool do_db = db != nullptr && tile_k == 0 && wk == 0;   // bias gradient db[n] = sum_m dY[m,n]: the k-tile-0 workgroups
+  Mma mma(smem, lane, wn, wk);
+  const int nst = t.nst;
+#pragma unroll
+  for (int s_ = 0; s_ < NS - 1; ++s_)
+    if (s_ < nst) t.stage(s_, smem + s_ * STAGE);
+  for (int s = 0; s < nst; ++s) {
+    const int younger = min(NS - 2, nst - 1 - s);  // stages issued after stage s
+    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PS) : "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (s + NS - 1 < nst) t.stage(s + NS - 1, smem + (s + NS - 1) % NS * STAGE);  // the buffer stage s-1 was read from
+    mma.mma_stage(s % NS * STAGE, do_db);
+  }
   if (diag == 1) {  // timing-only: no atomic epilogue (results wrong)
-    if (acc[0][0][0] == 12345.678f) dW[0] = 1.f;
+    if (mma.acc[0][0][0] == 12345.678f) dW[0] = 1.f;
     return;
   }
   const float alpha = alpha_dev ? *alpha_dev : 1.0f;
-  if (do_db) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float t_ = (sdb[i] + __shfl_xor(sdb[i], 32, 64)) * alpha;
-      const int n = n0 + wn * 64 + 32 * i + fr;
-      if (fh == 0 && n < N) atomicAdd(db + n, t_);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) {
-      const int k = k0 + wk * WKT + 32 * j + fr;
-      if (k >= K) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
-        if (n < N) atomicAdd(dW + (int64_t)n * lddw + k, acc[i][j][r] * alpha);
-      }
-    }
-  }
+  mma.epilogue(dW, lddw, db, do_db, alpha, n0 + wn * 64, k0 + wk * Tile::WKT, N, K);
 }
 
-template <int BN, int BKW, int MS, int NS, bool MF16 = false>
+template <int BN, int BKW, int MS, int NS, bool MF16>
 __global__ __launch_bounds__(BN * 2, BN == 128 ? 2 : 1) void wgrad_tn_bf16_kernel(
     const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
     float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
     int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int diag) {
   wgrad_tn_bf16_body<BN, BKW, MS, NS, MF16>(dY, lddy, X, ldx, dW, lddw, db, alpha_dev, M, N, K, tiles_k, tiles_nk, m_chunk,
-                                      diag, xcd_remap(blockIdx.x, gridDim.x));
+                                            diag, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Several weight gradients in ONE launch (vy_linear_wgrad_grouped): the four GEMMs of a transformer layer
@@ -419,7 +400,7 @@ struct WgradItem {
 };
 struct WgradGroup { WgradItem g[8]; int n; };
 
-template <int BN, int BKW, int MS, int NS, bool MF16 = false>
+template <int BN, int BKW, int MS, int NS, bool MF16>
 __global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, int diag) {
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   int d = 0;
@@ -432,7 +413,7 @@ __global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradG
   for (int i = 1; i < 8; ++i)
     if (d == i) it = grp.g[i];
   wgrad_tn_bf16_body<BN, BKW, MS, NS, MF16>(it.dY, it.lddy, it.X, it.ldx, it.dW, it.lddw, it.db, nullptr, it.M, it.N, it.K,
-                                      it.tiles_k, it.tiles_nk, it.m_chunk, diag, id - it.item0);
+                                            it.tiles_k, it.tiles_nk, it.m_chunk, diag, id - it.item0);
 }
 
 // db[n] += sum_m dY[m,n]: block = 64 lanes x 8 columns, 256 rows per block
@@ -1019,6 +1000,29 @@ int wgrad_f32(const char* who, const void* dy, int64_t lddy, const void* x, int6
   return VY_OK;
 }
 
+// bf16 operands: N may be odd (vocabulary) as long as every dY row is readable up to the next multiple of 8
+bool wgrad_bf16_operands_ok(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t N, int64_t K) {
+  return !(K % 8 || lddy % 8 || ldx % 8 || lddy < vy_cdiv(N, 8) * 8 || (uintptr_t)dy % 16 || (uintptr_t)x % 16);
+}
+
+// M rows in `want` chunks of whole 64-row blocks, none shorter than 256 rows (>= 4 stages of 64 rows) unless M is
+struct WgradSplit { int64_t splits, m_chunk; };
+WgradSplit wgrad_split(int64_t M, int64_t want) {
+  const int64_t max_splits = vy_cdiv(M, 256);
+  if (want > max_splits) want = max_splits;
+  if (want < 1) want = 1;
+  const int64_t m_chunk = vy_cdiv(vy_cdiv(M, want), 64) * 64;
+  return {vy_cdiv(M, m_chunk), m_chunk};
+}
+
+int wgrad_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// VY_WGRAD_M16, 16 x 16 x 32 MFMAs: 3 % faster on the 256 x 256 tiles (vocabulary projection 1.62 -> 1.57 ms, +0.25 % on
+// the training step), 2-8 % SLOWER on the 128 x 128 tiles (these kernels are bound by the transposing LDS reads and the
+// atomic epilogue, not by the matrix pipe): 1 = the wide tiles only (default), 2 = everywhere, 0 = off
+int wgrad_m16() { static const int v = wgrad_env("VY_WGRAD_M16", 1); return v; }
+int wgrad_diag() { static const int v = wgrad_env("VY_WGRAD_DIAG", 0); return v; }
+
 }  // namespace
 
 extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
@@ -1031,10 +1035,14 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
     if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "%s: beta must be 0 or 1", who);
     return wgrad_f32(who, dy, lddy, x, ldx, dw, lddw, db, beta, alpha_dev, M, N, K, (hipStream_t)stream);
   }
-  // N may be odd (vocabulary) as long as every dY row is readable up to the next multiple of 8
-  if (K % 8 || lddy % 8 || ldx % 8 || lddy < vy_cdiv(N, 8) * 8 || (uintptr_t)dy % 16 || (uintptr_t)x % 16)
+  if (!wgrad_bf16_operands_ok(dy, lddy, x, ldx, N, K))
     VY_FAIL(VY_ERR_ARG, "%s: K and leading dimensions must be multiples of 8 (lddy >= roundup8(N)), operands 16-byte aligned", who);
   if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "%s: beta must be 0 or 1", who);
+  // VY_WGRAD_VARIANT: 0 = the 128 x 128 tile, 8 = the 256 x 256 tile, unset = by shape (below)
+  static const int wv = wgrad_env("VY_WGRAD_VARIANT", -1);
+  static const int tgt = wgrad_env("VY_WGRAD_TARGET", 0);
+  if (wv != -1 && wv != 0 && wv != 8)
+    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: VY_WGRAD_VARIANT=%d was removed (the values left are 0 and 8; unset selects by shape)", who, wv);
   hipStream_t st = (hipStream_t)stream;
   if (beta == 0.f) {
     if (hipMemset2DAsync(dw, lddw * sizeof(float), 0, K * sizeof(float), N, st) != hipSuccess)
@@ -1042,54 +1050,24 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
     if (db && hipMemsetAsync(db, 0, N * sizeof(float), st) != hipSuccess)
       VY_FAIL(VY_ERR_LAUNCH, "%s: memset failed", who);
   }
-  // tile 128(n) x 128(k), 4 waves, 2 stages = 64 KiB of LDS: TWO workgroups per CU, which hides the
+  // default: tile 128(n) x 128(k), 4 waves, 2 stages = 64 KiB of LDS: TWO workgroups per CU, which hides the
   // load latency better than one 256 x 128 workgroup (8 waves, 96 KiB) or a deeper ring with one
   // workgroup per CU -- measured inside the training step: 256-wide 142/165 us vs 96/125 us (QKV /
-  // FFN1), 3- and 4-stage rings +45 %.  VY_WGRAD_VARIANT=1 / VY_WGRAD_STAGES keep them selectable.
-  static const int wv = [] { const char* e = getenv("VY_WGRAD_VARIANT"); return e ? atoi(e) : -1; }();
-  static const int diag = [] { const char* e = getenv("VY_WGRAD_DIAG"); return e ? atoi(e) : 0; }();
-  static const int tgt = [] { const char* e = getenv("VY_WGRAD_TARGET"); return e ? atoi(e) : 0; }();
-  // wv: 0 = 128 x 128 (64-row stages), 1 = 256 x 128, 2 = 128(n) x 256(k) with 32-row stages
-  // (11.7 instead of 15.6 LDS-DMA bytes per kFLOP, still two workgroups per CU), 4 = the same, 3-deep ring
-  // default 0.  5 = 32-row stages (32 KiB of LDS, three workgroups per CU, 720 work items on 768 slots
-  // instead of 432 on 512): 6 % faster on the FFN shapes alone, no difference inside the training step
-  // default: 128 x 128; the vocabulary projection (N = 50265: every tile reduces all M rows, so the 256 KiB
-  // atomic epilogue of a 256 x 256 tile is paid once per 512 stages) takes the 256 x 256 ring: +9 %
-  const int var = wv < 0 ? (N >= 8192 && M >= 4096 ? 8 : 0) : wv;
-  const bool big = var == 7 || var == 8;   // 256 x 256, 32-row stages, 3- / 4-deep ring, one workgroup per CU
-  const int BNt = (var == 1 || big) ? 256 : 128, BKt = (var == 2 || var == 4 || big) ? 256 : 128;
-  const int tiles_n = (int)vy_cdiv(N, BNt), tiles_k = (int)vy_cdiv(K, BKt);
-  const int tiles = tiles_n * tiles_k;
-  int64_t splits = vy_cdiv(tgt > 0 ? tgt : (var == 1 ? 256 : (var == 5 ? 704 : 384)), tiles);  // ~1.5 workgroups per CU
-  if (big && tgt <= 0) splits = 256 / tiles;                 // at most one round of 256 workgroups
-  const int64_t max_splits = vy_cdiv(M, 256);                // >= 4 stages of 64 rows each
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int64_t m_chunk = vy_cdiv(vy_cdiv(M, splits), 64) * 64;
-  splits = vy_cdiv(M, m_chunk);
-  static const int ns = [] { const char* e = getenv("VY_WGRAD_STAGES"); return e ? atoi(e) : 2; }();
-#define WG_GO(BN_, BK_, MS_, NS_)                                                                          \
-  hipLaunchKernelGGL((wgrad_tn_bf16_kernel<BN_, BK_, MS_, NS_>), dim3((unsigned)(tiles * splits)), dim3(BN_ * 2), 0, \
-                     st, (const bf16*)dy, lddy, (const bf16*)x, ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, \
-                     (int)K, tiles_k, tiles, (int)m_chunk, diag)
-#define WG_GO16(BN_, BK_, MS_, NS_)                                                                        \
-  hipLaunchKernelGGL((wgrad_tn_bf16_kernel<BN_, BK_, MS_, NS_, true>), dim3((unsigned)(tiles * splits)), dim3(BN_ * 2), 0, \
-                     st, (const bf16*)dy, lddy, (const bf16*)x, ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, \
-                     (int)K, tiles_k, tiles, (int)m_chunk, diag)
-  // 16 x 16 x 32 MFMAs: 3 % faster on the 256 x 256 tiles (vocabulary projection 1.62 -> 1.57 ms, +0.25 % on the training
-  // step), 2-8 % SLOWER on the 128 x 128 tiles (these kernels are bound by the transposing LDS reads and the atomic
-  // epilogue, not by the matrix pipe): 1 = the wide tiles only (default), 2 = everywhere, 0 = off
-  static const int w16 = [] { const char* e = getenv("VY_WGRAD_M16"); return e ? atoi(e) : 1; }();
-  if (var == 1) { if (ns == 3) WG_GO(256, 128, 64, 3); else WG_GO(256, 128, 64, 2); }
-  else if (var == 2) WG_GO(128, 256, 32, 2);
-  else if (var == 4) WG_GO(128, 256, 32, 3);
-  else if (var == 5) WG_GO(128, 128, 32, 2);   // 32 KiB of LDS: three workgroups per CU
-  else if (var == 6) WG_GO(128, 128, 64, 0);   // dY three deep, X two deep: 80 KiB, two workgroups per CU
-  else if (var == 7) WG_GO(256, 256, 32, 3);   // 7.8 LDS-DMA bytes per kFLOP, 96 KiB
-  else if (var == 8) { if (w16) WG_GO16(256, 256, 32, 4); else WG_GO(256, 256, 32, 4); }   // ... 128 KiB
-  else { if (ns == 3) WG_GO(128, 128, 64, 3); else if (w16 >= 2) WG_GO16(128, 128, 64, 2); else WG_GO(128, 128, 64, 2); }
-#undef WG_GO
-#undef WG_GO16
+  // FFN1), 3- and 4-stage rings +45 %; 32-row stages (three workgroups per CU) 6 % faster on the FFN shapes alone, no
+  // difference inside the training step (that code is in the history).
+  // The vocabulary projection (N = 50265: every tile reduces all M rows, so the 256 KiB atomic epilogue of a
+  // 256 x 256 tile is paid once per 512 stages) takes the 256 x 256 tile, 32-row stages, 4-deep ring, one workgroup
+  // per CU (7.8 instead of 15.6 LDS-DMA bytes per kFLOP): +9 %
+  const bool big = wv < 0 ? (N >= 8192 && M >= 4096) : wv == 8;
+  const int BT = big ? 256 : 128;
+  const int tiles_k = (int)vy_cdiv(K, BT), tiles = (int)vy_cdiv(N, BT) * tiles_k;
+  // 128 x 128: ~1.5 workgroups per CU; 256 x 256: at most one round of 256 workgroups
+  const WgradSplit sp = wgrad_split(M, tgt > 0 ? vy_cdiv(tgt, tiles) : big ? 256 / tiles : vy_cdiv(384, tiles));
+  const int w16 = wgrad_m16();
+  auto kernel = big ? (w16 ? wgrad_tn_bf16_kernel<256, 256, 32, 4, true> : wgrad_tn_bf16_kernel<256, 256, 32, 4, false>)
+                    : (w16 >= 2 ? wgrad_tn_bf16_kernel<128, 128, 64, 2, true> : wgrad_tn_bf16_kernel<128, 128, 64, 2, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * sp.splits)), dim3(BT * 2), 0, st, (const bf16*)dy, lddy, (const bf16*)x,
+                     ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, (int)K, tiles_k, tiles, (int)sp.m_chunk, wgrad_diag());
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }
@@ -1110,41 +1088,28 @@ extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, in
   for (int i = 0; i < n; ++i) {
     const vy_wgrad_desc& d = descs[i];
     if (!d.dy || !d.x || !d.dw || d.M <= 0 || d.N <= 0 || d.K <= 0) VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: bad arguments", who, i);
-    if (d.K % 8 || d.lddy % 8 || d.ldx % 8 || d.lddy < vy_cdiv(d.N, 8) * 8 || (uintptr_t)d.dy % 16 || (uintptr_t)d.x % 16)
+    if (!wgrad_bf16_operands_ok(d.dy, d.lddy, d.x, d.ldx, d.N, d.K))
       VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: K and leading dimensions must be multiples of 8, operands 16-byte aligned", who, i);
     tiles_total += vy_cdiv(d.N, 256) * vy_cdiv(d.K, 256);
   }
-  static const int tgt = [] { const char* e = getenv("VY_WGRAD_GROUP_TARGET"); return e ? atoi(e) : 256; }();
-  static const int diag = [] { const char* e = getenv("VY_WGRAD_DIAG"); return e ? atoi(e) : 0; }();
-  const int64_t want = tgt / tiles_total > 0 ? tgt / tiles_total : 1;   // M-splits: at most one round of workgroups
+  static const int tgt = wgrad_env("VY_WGRAD_GROUP_TARGET", 256);
   WgradGroup grp;
   grp.n = n;
   int64_t items = 0;
   for (int i = 0; i < n; ++i) {
     const vy_wgrad_desc& d = descs[i];
     const int64_t tiles_k = vy_cdiv(d.K, 256), tiles = vy_cdiv(d.N, 256) * tiles_k;
-    int64_t splits = want, max_splits = vy_cdiv(d.M, 256);
-    if (splits > max_splits) splits = max_splits;
-    const int64_t m_chunk = vy_cdiv(vy_cdiv(d.M, splits), 64) * 64;
-    splits = vy_cdiv(d.M, m_chunk);
+    const WgradSplit sp = wgrad_split(d.M, tgt / tiles_total);   // at most one round of workgroups
     WgradItem& it = grp.g[i];
     it.dY = (const bf16*)d.dy; it.X = (const bf16*)d.x; it.dW = d.dw; it.db = d.db;
     it.lddy = d.lddy; it.ldx = d.ldx; it.lddw = d.lddw;
     it.M = (int)d.M; it.N = (int)d.N; it.K = (int)d.K;
-    it.tiles_k = (int)tiles_k; it.tiles_nk = (int)tiles; it.m_chunk = (int)m_chunk; it.item0 = (int)items;
-    items += tiles * splits;
+    it.tiles_k = (int)tiles_k; it.tiles_nk = (int)tiles; it.m_chunk = (int)sp.m_chunk; it.item0 = (int)items;
+    items += tiles * sp.splits;
   }
   for (int i = n; i < 8; ++i) grp.g[i] = grp.g[0];
-  // 16 x 16 x 32 MFMAs: 3 % faster on the 256 x 256 tiles (vocabulary projection 1.62 -> 1.57 ms, +0.25 % on the training
-  // step), 2-8 % SLOWER on the 128 x 128 tiles (these kernels are bound by the transposing LDS reads and the atomic
-  // epilogue, not by the matrix pipe): 1 = the wide tiles only (default), 2 = everywhere, 0 = off
-  static const int w16 = [] { const char* e = getenv("VY_WGRAD_M16"); return e ? atoi(e) : 1; }();
-  if (w16)
-    hipLaunchKernelGGL((wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, true>), dim3((unsigned)items), dim3(512), 0,
-                       (hipStream_t)stream, grp, diag);
-  else
-    hipLaunchKernelGGL((wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4>), dim3((unsigned)items), dim3(512), 0, (hipStream_t)stream,
-                       grp, diag);
+  auto kernel = wgrad_m16() ? wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, true> : wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)items), dim3(512), 0, (hipStream_t)stream, grp, wgrad_diag());
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }
