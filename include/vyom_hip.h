@@ -341,6 +341,54 @@ int vy_xent_bwd(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_
 int vy_xent_fused(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
                   float* loss_sum, const float* count, const float* gscale, int64_t M, int64_t V,
                   int32_t* err_flag, int dtype, void* stream);
+/* vy_xent_fwd / vy_xent_fused that also sample one replacement token per live row: ELECTRA's generator step,
+ * replaces sample(logits[masked_indices], temperature) = argmax(t / temperature + noise(t)) with
+ * noise(t) = -log(-log(uniform + 1e-9) + 1e-9) (VyomAI/pretraining/collators.py:65-78,88-91): a zeros_like, a
+ * uniform_, two logs, an add and an argmax over the gathered rows, i.e. a second pass over the generator logits.
+ * sampled[m] = argmax_v fp32(logits[m,v] * inv_temperature + noise(m,v)), the lowest index among equal maxima;
+ * skipped rows (ignore_index, or an out-of-range label, which still raises err_flag) get -1, as does a row whose scores are all NaN.  noise(m,v) is a pure
+ * function of (seed, offset, m, v): Philox4x32-7 on the counter {v / 4, m, offset}, word v & 3, u = its top 24
+ * bits * 2^-24.  lse, each row's term of loss_sum and (fused) the in-place unit gradient are those of vy_xent_fwd /
+ * vy_xent_fused bit for bit (loss_sum itself is, there as here, a float atomic over rows in arrival order); the limits
+ * are theirs (fused: bf16, V <= 65536); backward of the unfused form is vy_xent_bwd. */
+int vy_xent_sample_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
+                       float* loss_sum, float* count, int64_t* sampled, float inv_temperature, uint64_t seed,
+                       uint64_t offset, int64_t M, int64_t V, int32_t* err_flag, int dtype, void* stream);
+int vy_xent_sample_fused(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
+                         float* loss_sum, const float* count, const float* gscale, int64_t* sampled,
+                         float inv_temperature, uint64_t seed, uint64_t offset, int64_t M, int64_t V,
+                         int32_t* err_flag, int dtype, void* stream);
+/* out[m, v] (fp32, row stride ld) = noise(m, v) of the two calls above, for tests (as vy_dropout exports the mask). */
+int vy_gumbel_noise(float* out, int64_t ld, int64_t M, int64_t V, uint64_t seed, uint64_t offset, void* stream);
+
+/* ELECTRA's discriminator head and loss: replaces nn.Linear(hidden_size, 1) (Examples/electra-pretraining.ipynb
+ * cell 21, Discriminator.discriminator_head) and binary_cross_entropy_with_logits over the non-pad tokens (cell 27,
+ * ElectraLoss.__call__).  An N = 1 GEMM wastes an MFMA tile; these read h once per pass, one wave per row.
+ * fwd: z[m] (fp32) = h[m,:] . w + b (w [d], b [1] in h's dtype, b nullable; fp32 accumulation).  With target (fp32
+ *      0 / 1) and live (uint8) given, loss_sum += sum over live rows of max(z,0) - z y + log1p(exp(-|z|)) (fp32 device
+ *      scalar, atomic: zero it first); target == NULL only writes z (Discriminator.forward).
+ * bwd: dz[m] = (sigmoid(z[m]) - y[m]) * (*gscale) / max(*count, 1) on live rows, 0 elsewhere; dh[m,:] = dz[m] w in h's
+ *      dtype (dead rows are written as zeros); dw[d] / db[1] (fp32) = sum_m dz[m] h[m,:] / sum_m dz[m], added to what
+ *      is there when accumulate != 0 (the convention of vy_linear_wgrad's beta), by fp32 atomics.  gscale / count:
+ *      device scalars, no host sync.  d % 8 == 0, rows 16-byte aligned.  bwd keeps a wave's share of w and of the dw
+ *      partials in registers: d <= 4096 in bf16, d <= 2048 in fp32 (VY_ERR_UNSUPPORTED beyond); fwd takes any d. */
+int vy_bce_head_fwd(const void* h, int64_t ldh, const void* w, const void* b, float* z, const float* target,
+                    const uint8_t* live, float* loss_sum, int64_t M, int64_t d, int dtype, void* stream);
+int vy_bce_head_bwd(const void* h, int64_t ldh, const void* w, const float* z, const float* target,
+                    const uint8_t* live, const float* gscale, const float* count, void* dh, int64_t lddh, float* dw,
+                    float* db, int accumulate, int64_t M, int64_t d, int dtype, void* stream);
+
+/* Masked-LM corruption of n token ids in one launch: replaces masked_language_modeling
+ * (VyomAI/pretraining/collators.py:9-62) -- the per-row tolist() round trip through
+ * tokenizer.get_special_tokens_mask, three bernoulli draws and a randint -- with the same distribution (not the same
+ * random stream, as with dropout).  One Philox4x32-7 call per token on the counter {i, offset}: token i is selected
+ * iff its id is not in special_ids[n_special] (device, may be empty) and r0 < fraction * 2^32; a selected token
+ * becomes mask_id if r1 < 0.8 * 2^32, else umulhi(r3, vocab) if r2 < 0.5 * 2^32, else stays.  labels = ids on
+ * selected tokens and ignore_index elsewhere; masked (uint8) marks the selection. */
+int vy_mlm_mask(const int64_t* ids, int64_t n, const int64_t* special_ids, int32_t n_special, float fraction,
+                int64_t mask_id, int64_t vocab, int64_t ignore_index, uint64_t seed, uint64_t offset,
+                int64_t* masked_ids, int64_t* labels, uint8_t* masked, void* stream);
+
 /* A label that is neither ignore_index nor inside [0, V) (torch.cross_entropy device-asserts on it) is
  * never dereferenced: the row counts as ignored (zero loss, zero gradient) and *err_flag (nullable,
  * device int32) is set to 1 for the host to report. */

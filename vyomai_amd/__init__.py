@@ -7,6 +7,8 @@ from .utils import EncoderConfig  # noqa: F401
 from .layers.kv_cache import DynamicCache, StaticCache, StaticCacheOne, DynamicCacheOne  # noqa: F401
 from .models.encoder import EncoderModel, EncoderForMaskedLM  # noqa: F401
 from .models.decoder import DecoderModel  # noqa: F401
+from .models.electra import Discriminator, ElectraModel, ElectraLoss  # noqa: F401
+from . import pretraining  # noqa: F401
 from .models.vision_encoder import Vit  # noqa: F401
 from .models.multimodel import VisionLanguageModel  # noqa: F401
 from .models.encoder_decoder import EncoderDecoderModel  # noqa: F401

@@ -56,6 +56,12 @@ PROTOTYPES = {
     "vy_xent_fwd": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _p, _i, _p],
     "vy_xent_bwd": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i, _p],
     "vy_xent_fused": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _i, _p],
+    "vy_xent_sample_fwd": [_p, _i64, _p, _i64, _p, _p, _p, _p, _f, _u64, _u64, _i64, _i64, _p, _i, _p],
+    "vy_xent_sample_fused": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _f, _u64, _u64, _i64, _i64, _p, _i, _p],
+    "vy_gumbel_noise": [_p, _i64, _i64, _i64, _u64, _u64, _p],
+    "vy_bce_head_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p],
+    "vy_bce_head_bwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i, _i64, _i64, _i, _p],
+    "vy_mlm_mask": [_p, _i64, _p, _i, _f, _i64, _i64, _i64, _u64, _u64, _p, _p, _p, _p],
     "vy_logprob_fwd": [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _i, _p],
     "vy_logprob_bwd": [_p, _i64, _p, _p, _p, _i64, _i64, _i, _p],
     "vy_logprob_fused": [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _i, _p],

@@ -242,6 +242,29 @@ def _require_bf16(x: torch.Tensor) -> None:
         raise VyomHipError("training kernels take bf16 or fp32 activations (fp32 master weights), not %s" % x.dtype)
 
 
+# id(table) -> [forwards recorded, backwards run]: a table that several embeddings share (ELECTRA's generator and
+# discriminator, Examples/electra-pretraining.ipynb cell 32) receives one scatter per use, in an order autograd does
+# not fix, and is final -- reported to the reducer -- only after the last of them.  The count only decides how EARLY
+# the table reports: a table that has been scattered into and is still waiting when the backward pass ends (a forward
+# whose graph was dropped, a backward through one of the two uses) is reported then, by an autograd-engine callback.
+_EMB_USES = {}
+_EMB_WAITING = {}   # id(table) -> table: scattered into during this backward pass, not reported yet
+
+
+def reset_embedding_uses() -> None:
+    """Forget forwards whose backward never ran (FlatTrainer.zero_grad)."""
+    _EMB_USES.clear()
+    _EMB_WAITING.clear()
+
+
+def _embedding_end_of_backward() -> None:
+    waiting = list(_EMB_WAITING.values())
+    _EMB_WAITING.clear()
+    for w in waiting:
+        _EMB_USES.pop(id(w), None)
+        _notify(w)
+
+
 class EmbeddingFn(torch.autograd.Function):
     """hidden = table[ids] read from the compute-dtype shadow of the fp32 table; the gradient rows are
     accumulated straight into the flat fp32 gradient arena (nn.Embedding: models/decoder.py:287)."""
@@ -250,6 +273,8 @@ class EmbeddingFn(torch.autograd.Function):
     def forward(ctx, ids, weight, padding_idx, dtype):
         ctx.save_for_backward(ids)
         ctx.weight, ctx.padding_idx = weight, padding_idx
+        if _direct(weight):
+            _EMB_USES.setdefault(id(weight), [0, 0])[0] += 1
         return ops.embedding(_shadow(weight, dtype), ids)
 
     @staticmethod
@@ -258,6 +283,15 @@ class EmbeddingFn(torch.autograd.Function):
         w = ctx.weight
         if _direct(w):
             ops.embedding_bwd_(dout.contiguous(), ids, w.grad, ctx.padding_idx)
+            uses = _EMB_USES.get(id(w))
+            if uses is not None:
+                uses[1] += 1
+                if uses[1] < uses[0]:   # another scatter into this table may still come
+                    _EMB_WAITING[id(w)] = w
+                    torch.autograd.Variable._execution_engine.queue_callback(_embedding_end_of_backward)
+                    return None, None, None, None
+                del _EMB_USES[id(w)]
+                _EMB_WAITING.pop(id(w), None)
             _notify(w)
             return None, None, None, None
         dw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
@@ -604,11 +638,12 @@ def _shifted_labels(labels, ignore_index, dev):
     return shifted.view(-1)
 
 
-def _xent_forward(logits, shifted, ignore_index, err_flag=None, in_place=True):
+def _xent_forward(logits, shifted, ignore_index, err_flag=None, in_place=True, sample=None):
     """Mean cross-entropy of the live rows -> (loss, lse, acc = [loss_sum, count], fused).  in_place: the logits may
     be overwritten, and where one kernel can do it (vy_xent_fused: bf16, V <= 65536) they then hold the UNIT gradient
     (d loss / d logits for an upstream gradient of 1; backward scales by the actual one, by linearity); otherwise
-    vy_xent_fwd only reads them."""
+    vy_xent_fwd only reads them.  sample = (sampled int64 [M], inv_temperature, seed, offset): the same kernels also
+    draw a replacement token per live row (vy_xent_sample_*)."""
     V = logits.shape[1]
     dev = logits.device
     lse = torch.empty(logits.shape[0], dtype=torch.float32, device=dev)
@@ -618,9 +653,14 @@ def _xent_forward(logits, shifted, ignore_index, err_flag=None, in_place=True):
         # rows with an out-of-range label contribute neither loss nor gradient -- the kernel raises err_flag for
         # them -- so they must not count in the mean either, exactly as on the two-pass path
         acc[1] = ((shifted != ignore_index) & (shifted >= 0) & (shifted < V)).sum()
-        ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
-    else:
+        if sample is None:
+            ops.xent_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), err_flag)
+        else:
+            ops.xent_sample_fused_(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], _one(dev), *sample, err_flag)
+    elif sample is None:
         ops.xent_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], err_flag)
+    else:
+        ops.xent_sample_fwd(logits, shifted, ignore_index, lse, acc[0:1], acc[1:2], *sample, err_flag)
     return acc[0] / acc[1].clamp_min(1.0), lse, acc, fused
 
 
@@ -676,20 +716,32 @@ class LMHeadLossFn(torch.autograd.Function):
     item 1).  Backward multiplies by the upstream gradient through the GEMMs (a device scalar)."""
 
     @staticmethod
-    def forward(ctx, hidden, labels, ignore_index, wd, bd, ln_w, ln_b, wv, bias, eps, err_flag=None):
+    def forward(ctx, hidden, labels, ignore_index, wd, bd, ln_w, ln_b, wv, bias, eps, err_flag=None, shift=True,
+                sample=None):
+        """shift=False: position t is scored against label t (the masked-LM loss).  sample = (inv_temperature, seed,
+        offset): also returns one sampled token per position, -1 where the label is ignored (not differentiable)."""
         _require_bf16(hidden)
         pre, g, n, mean, rstd = _head_transform(hidden, wd, bd, ln_w, ln_b, eps)
         buf, logits = _vocab_logits(n, wv, bias)
-        shifted = _shifted_labels(labels, ignore_index, hidden.device)
-        loss, lse, acc, fused = _xent_forward(logits, shifted, ignore_index, err_flag)
+        dev = hidden.device
+        shifted = _shifted_labels(labels, ignore_index, dev) if shift else labels.to(dev).reshape(-1).contiguous()
+        sampled = None
+        if sample is not None:
+            sampled = torch.empty(shifted.shape, dtype=torch.long, device=dev)
+            sample = (sampled, *sample)
+        loss, lse, acc, fused = _xent_forward(logits, shifted, ignore_index, err_flag, sample=sample)
         ctx.save_for_backward(hidden, pre, g, n, mean, rstd, buf, shifted, lse, acc)
         ctx.params = (wd, bd, ln_w, ln_b, wv, bias)
         ctx.ignore = ignore_index
         ctx.fused = fused
-        return loss
+        if sampled is None:
+            return loss
+        sampled = sampled.view(labels.shape)
+        ctx.mark_non_differentiable(sampled)
+        return loss, sampled
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, *_):
         hidden, pre, g, n, mean, rstd, buf, shifted, lse, acc = ctx.saved_tensors
         wd, bd, ln_w, ln_b, wv, bias = ctx.params
         dt = hidden.dtype
@@ -701,7 +753,75 @@ class LMHeadLossFn(torch.autograd.Function):
             dn = dn * alpha.to(dt)
         dwv, dbias = _wgrad(logits, n.view(buf.shape[0], -1), wv, bias, alpha=alpha)
         dh, dwd, dbd, dgam, dbet = _head_transform_backward(dn.view(g.shape), hidden, pre, g, mean, rstd, wd, bd, ln_w, ln_b)
-        return dh, None, None, dwd, dbd, dgam, dbet, dwv, dbias, None, None
+        return dh, None, None, dwd, dbd, dgam, dbet, dwv, dbias, None, None, None, None
+
+
+class BceHeadLossFn(torch.autograd.Function):
+    """ELECTRA's discriminator head and loss: mean over the live (non-pad) tokens of
+    binary_cross_entropy_with_logits(h . w + b, target) (Examples/electra-pretraining.ipynb cells 21, 27) without an
+    N = 1 GEMM: vy_bce_head_fwd / vy_bce_head_bwd read h once each.  -> (loss, z fp32)."""
+
+    @staticmethod
+    def forward(ctx, hidden, w, b, target, live):
+        _require_bf16(hidden)
+        dt = hidden.dtype
+        dev = hidden.device
+        live8 = live.reshape(-1).to(torch.uint8).contiguous()
+        tgt = target.reshape(-1).to(torch.float32).contiguous()
+        acc = torch.zeros(2, dtype=torch.float32, device=dev)
+        acc[1] = live8.sum()
+        ws = _shadow(w, dt).reshape(-1)
+        z = ops.bce_head_fwd(hidden, ws, _shadow(b, dt), tgt, live8, acc[0:1])
+        ctx.save_for_backward(hidden, z, tgt, live8, acc)
+        ctx.params = (w, b)
+        ctx.mark_non_differentiable(z)
+        return acc[0] / acc[1].clamp_min(1.0), z
+
+    @staticmethod
+    def backward(ctx, gout, _gz):
+        hidden, z, tgt, live8, acc = ctx.saved_tensors
+        w, b = ctx.params
+        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
+        ws = _shadow(w, hidden.dtype).reshape(-1)
+        if _direct(w) and _direct(b):
+            dh = ops.bce_head_bwd(hidden, ws, z.view(-1), tgt, live8, gs, acc[1:2], w.grad.view(-1), b.grad, True)
+            _notify(w, b)
+            return dh, None, None, None, None
+        dw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        db = torch.empty(b.shape, dtype=torch.float32, device=w.device)
+        dh = ops.bce_head_bwd(hidden, ws, z.view(-1), tgt, live8, gs, acc[1:2], dw.view(-1), db, False)
+        return dh, dw.to(w.dtype), db.to(b.dtype), None, None
+
+
+class BceHeadLogitsFn(torch.autograd.Function):
+    """z = h . w + b alone (Discriminator.forward, the notebook's own loop: logits, then ElectraLoss, then backward).
+    The backward is vy_bce_head_bwd fed the upstream gradient: its dz is (sigmoid(z) - y) * gscale / count, which
+    with z = -inf (sigmoid exactly 0), y = -gz and gscale = count = 1 is gz bit for bit.  -> z fp32 [M]."""
+
+    @staticmethod
+    def forward(ctx, hidden, w, b):
+        _require_bf16(hidden)
+        ctx.save_for_backward(hidden)
+        ctx.params = (w, b)
+        return ops.bce_head_fwd(hidden, _shadow(w, hidden.dtype).reshape(-1), _shadow(b, hidden.dtype))
+
+    @staticmethod
+    def backward(ctx, gz):
+        (hidden,) = ctx.saved_tensors
+        w, b = ctx.params
+        dev = hidden.device
+        y = (-gz).to(torch.float32).reshape(-1).contiguous()
+        z = torch.full_like(y, float("-inf"))
+        live8 = torch.ones(y.shape, dtype=torch.uint8, device=dev)
+        ws = _shadow(w, hidden.dtype).reshape(-1)
+        if _direct(w) and _direct(b):
+            dh = ops.bce_head_bwd(hidden, ws, z, y, live8, _one(dev), _one(dev), w.grad.view(-1), b.grad, True)
+            _notify(w, b)
+            return dh, None, None
+        dw = torch.empty(w.shape, dtype=torch.float32, device=dev)
+        db = torch.empty(b.shape, dtype=torch.float32, device=dev)
+        dh = ops.bce_head_bwd(hidden, ws, z, y, live8, _one(dev), _one(dev), dw.view(-1), db, False)
+        return dh, dw.to(w.dtype), db.to(b.dtype)
 
 
 _ONES = {}

@@ -292,6 +292,28 @@ __device__ __forceinline__ bool vy_drop_keep(const VyDrop& d, const uint32_t (&r
   return ((r[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= d.thr;
 }
 
+// ---- Gumbel noise: counter-based, for sampling replaced tokens (ELECTRA) -------------------------
+// noise(t) = -log(-log(u + 1e-9) + 1e-9), u uniform on [0, 1) (reference pretraining/collators.py:65-73, epsilons
+// included: they keep g inside [-3.04, 20.73] for every u).  A pure function of (seed, offset, row, column):
+// Philox4x32-7 on the counter {column / 4, row, offset}, one 32-bit word per column, its top 24 bits the uniform.
+// The row kernels (vy_xent_sample_*) and the export (vy_gumbel_noise) both call this one function.
+struct VyNoise {
+  uint32_t seed_lo, seed_hi, off_lo, off_hi;
+};
+__host__ inline VyNoise vy_make_noise(uint64_t seed, uint64_t offset) {
+  return VyNoise{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+}
+// the four words of columns 4 * quad .. 4 * quad + 3 of row m
+__device__ __forceinline__ void vy_noise_words(const VyNoise& n, int64_t m, int quad, uint32_t (&r)[4]) {
+  vy_philox7((uint32_t)quad, (uint32_t)m, n.off_lo, n.off_hi ^ (uint32_t)((uint64_t)m >> 32), n.seed_lo, n.seed_hi, r);
+}
+__device__ __forceinline__ float vy_gumbel(uint32_t word) {
+  const float t = (float)(word >> 8) * 5.9604644775390625e-8f + 1e-9f;   // u = word's top 24 bits * 2^-24 (exact)
+  // -log(t): near t = 1 the result is small against t, so from 1/2 up it is taken as log1p of t - 1 (exact there)
+  const float inner = t < 0.5f ? -logf(t) : -log1pf(t - 1.0f);
+  return -logf(inner + 1e-9f);
+}
+
 // load/store helpers templated on the storage type
 template <typename T> struct VyT;
 template <> struct VyT<float> {

@@ -547,6 +547,26 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
   return r;
 }
 
+// argmax of (score, column) pairs over a workgroup, the lowest column among equal scores
+struct RowBest {
+  float s;
+  int col;
+  __device__ __forceinline__ void take(float s2, int col2) {
+    if (s2 > s || (s2 == s && col2 < col)) { s = s2; col = col2; }
+  }
+};
+__device__ __forceinline__ RowBest block_argmax(RowBest b, RowBest* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) b.take(__shfl_xor(b.s, o, 64), __shfl_xor(b.col, o, 64));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = b;
+  __syncthreads();
+  RowBest r = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r.take(red[w].s, red[w].col);
+  return r;
+}
+
 // The three kernels below stream or hold a row, reduce it to lse = max + log(sum exp) and / or overwrite it with a
 // gradient.  A row policy carries what differs between the two users and nothing else:
 //   load(m, grad)      the per-row operands, read ONCE into a State (re-read at the scale point they are loaded again
@@ -556,6 +576,9 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 //   skip(m)            what a skipped row writes besides lse
 //   emit(m, l, x)      what thread 0 writes besides lse = l, from the label's logit x
 //   grad(s, e, onehot) d / d logit of a live row from e = softmax
+//   kPair              the two-pass route the fused kernel's refusals name
+//   kSample            the forward kernels also draw a column per live row: scan(m, c, v, V, best) folds the VEC logits
+//                      of chunk c into the running argmax, sampled(m, col) stores the winner
 // A label outside [0, V) on a live row (e.g. -100 padding under another ignore_index) would be an out-of-bounds read:
 // the row counts as skipped and the device error flag is raised instead.
 
@@ -567,6 +590,8 @@ struct XentRow {
   int64_t ignore;
   const float *gscale, *count;   // (next to ignore: one kernel-argument load fetches the three)
   float *loss_sum, *count_out;
+  static constexpr bool kSample = false;
+  static constexpr const char* kPair = "vy_xent_fwd + vy_xent_bwd";
   struct State { float sc; };
   __device__ __forceinline__ State load(int64_t, bool grad) const { return State{grad ? *gscale / fmaxf(*count, 1.0f) : 0.f}; }
   __device__ __forceinline__ bool live(const State&, int64_t label) const { return label != ignore; }
@@ -587,12 +612,44 @@ struct XentRow {
 struct LogprobRow {
   const float* weight;
   float* logp;
+  static constexpr bool kSample = false;
+  static constexpr const char* kPair = "vy_logprob_fwd + vy_logprob_bwd";
   struct State { float w; };
   __device__ __forceinline__ State load(int64_t m, bool) const { return State{weight[m]}; }
   __device__ __forceinline__ bool live(const State& s, int64_t) const { return s.w != 0.f; }
   __device__ __forceinline__ void skip(int64_t m) const { logp[m] = 0.f; }
   __device__ __forceinline__ void emit(int64_t m, float l, float x) const { logp[m] = x - l; }
   __device__ __forceinline__ float grad(const State& s, float e, float onehot) const { return (onehot - e) * s.w; }
+};
+
+// Cross-entropy that also samples a replacement token per live row (ELECTRA's generator step: reference
+// pretraining/collators.py:76-78,88-91): sampled[m] = argmax_v fp32(logit[m, v] * inv_t + noise(m, v)), the lowest
+// column among equal maxima, -1 on skipped rows.  Everything else is XentRow, so lse, each row's loss term and the
+// gradient are those of vy_xent_fwd / vy_xent_fused bit for bit.
+template <bool COUNT>
+struct XentSampleRow : XentRow<COUNT> {
+  int64_t* out;
+  float inv_t;
+  VyNoise nz;
+  static constexpr bool kSample = true;
+  static constexpr const char* kPair = "vy_xent_sample_fwd + vy_xent_bwd";
+  __device__ __forceinline__ void skip(int64_t m) const { out[m] = -1; }
+  template <int VEC>
+  __device__ __forceinline__ void scan(int64_t m, int c, const float* v, int V, RowBest& b) const {
+#pragma unroll
+    for (int q = 0; q < VEC / 4; ++q) {
+      const int col0 = c * VEC + q * 4;
+      if (col0 < V) {
+        uint32_t r[4];
+        vy_noise_words(nz, m, col0 >> 2, r);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (col0 + e < V) b.take(fmaf(v[q * 4 + e], inv_t, vy_gumbel(r[e])), col0 + e);
+      }
+    }
+  }
+  // (a row of NaN scores never wins a comparison: it keeps its token, as a skipped row does)
+  __device__ __forceinline__ void sampled(int64_t m, int col) const { out[m] = col == INT32_MAX ? -1 : col; }
 };
 
 // Forward: lse[m] and the policy's output, the logits only read (online max / sum over 16-byte chunks).
@@ -615,9 +672,11 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const T* __restrict__ logi
   const T* row = logits + m * ld;
   const int nch = (V + VEC - 1) / VEC;
   float mx = -INFINITY, sm = 0.f;
+  [[maybe_unused]] RowBest best{-INFINITY, INT32_MAX};
   for (int c = threadIdx.x; c < nch; c += blockDim.x) {
     float v[VEC];
     Chunk<T>::load(row + (int64_t)c * VEC, v);  // the padded tail of the row is readable
+    if constexpr (P::kSample) p.template scan<VEC>(m, c, v, V, best);
     float cm = -INFINITY;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) if (c * VEC + e < V) cm = fmaxf(cm, v[e]);
@@ -634,6 +693,11 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const T* __restrict__ logi
     const float l = gmx + __logf(gsm);
     lse[m] = l;
     p.emit(m, l, VyT<T>::ld(row + label));
+  }
+  if constexpr (P::kSample) {
+    __shared__ RowBest redb[4];
+    const RowBest g = block_argmax(best, redb);
+    if (threadIdx.x == 0) p.sampled(m, g.col);
   }
 }
 
@@ -708,6 +772,21 @@ __global__ __launch_bounds__(1024) void row_fused_kernel(bf16* __restrict__ logi
         if (c * 8 + e < V) mx = fmaxf(mx, (float)v[i][e]);
     }
   }
+  if constexpr (P::kSample) {   // the row is in registers: draw from it before it is overwritten
+    __shared__ RowBest redb[16];
+    RowBest best{-INFINITY, INT32_MAX};
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int c = tid + i * 1024;
+      if (c < nch) {
+        float f[8];
+        Chunk<bf16>::unpack(v[i], f);
+        p.template scan<8>(m, c, f, V, best);
+      }
+    }
+    const RowBest g = block_argmax(best, redb);
+    if (tid == 0) p.sampled(m, g.col);
+  }
   const float gmx = block_reduce(mx, red, true);
   float sm = 0.f;
 #pragma unroll
@@ -744,12 +823,11 @@ __global__ __launch_bounds__(1024) void row_fused_kernel(bf16* __restrict__ logi
 
 // Host side of the six entry points: one set of checks (fn: the entry point's name, for the error strings; ptrs: every
 // pointer operand is there) and one launch per kernel.
-int row_check(const char* fn, bool ptrs, const void* logits, int64_t ld, int64_t M, int64_t V, int dtype, bool fused) {
+int row_check(const char* fn, bool ptrs, const void* logits, int64_t ld, int64_t M, int64_t V, int dtype, const char* pair) {
   if (!ptrs || M <= 0 || V <= 0) VY_FAIL(VY_ERR_ARG, "%s: bad arguments", fn);
-  if (fused) {
-    const int b = (int)strlen(fn) - 6;  // "vy_xent" of "vy_xent_fused": names the two-pass pair
-    if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: bf16 only (use %.*s_fwd + %.*s_bwd)", fn, b, fn, b, fn);
-    if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use %.*s_fwd + %.*s_bwd)", fn, (long)V, b, fn, b, fn);
+  if (pair) {   // the fused kernel; pair: the policy's two-pass route, for the error strings
+    if (dtype != VY_BF16) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: bf16 only (use %s)", fn, pair);
+    if (V > 65536) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: V=%ld exceeds the 65536 columns a workgroup keeps in registers (use %s)", fn, (long)V, pair);
     if (ld % 8 || ld < vy_cdiv(V, 8) * 8 || (uintptr_t)logits % 16) VY_FAIL(VY_ERR_ARG, "%s: rows must be 16-byte aligned and cover the padded width", fn);
     return VY_OK;
   }
@@ -762,7 +840,7 @@ int row_check(const char* fn, bool ptrs, const void* logits, int64_t ld, int64_t
 template <typename P>
 int row_lse(const char* fn, bool ptrs, const void* logits, int64_t ld, const int64_t* labels, const P& p, float* lse,
             int64_t M, int64_t V, int32_t* err, int dtype, void* stream) {
-  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, false)) return rc;
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, nullptr)) return rc;
   const dim3 grid((unsigned)M), block(256);
   if (dtype == VY_BF16) hipLaunchKernelGGL((row_lse_kernel<bf16, P>), grid, block, 0, (hipStream_t)stream, (const bf16*)logits, ld, labels, p, lse, (int)V, err);
   else hipLaunchKernelGGL((row_lse_kernel<float, P>), grid, block, 0, (hipStream_t)stream, (const float*)logits, ld, labels, p, lse, (int)V, err);
@@ -773,7 +851,7 @@ int row_lse(const char* fn, bool ptrs, const void* logits, int64_t ld, const int
 template <typename P>
 int row_grad(const char* fn, bool ptrs, void* logits, int64_t ld, const int64_t* labels, const P& p, const float* lse,
              int64_t M, int64_t V, int dtype, void* stream) {
-  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, false)) return rc;
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, nullptr)) return rc;
   const dim3 grid((unsigned)M), block(256);
   if (dtype == VY_BF16) hipLaunchKernelGGL((row_grad_kernel<bf16, P>), grid, block, 0, (hipStream_t)stream, (bf16*)logits, ld, labels, p, lse, (int)V);
   else hipLaunchKernelGGL((row_grad_kernel<float, P>), grid, block, 0, (hipStream_t)stream, (float*)logits, ld, labels, p, lse, (int)V);
@@ -784,7 +862,7 @@ int row_grad(const char* fn, bool ptrs, void* logits, int64_t ld, const int64_t*
 template <typename P>
 int row_fused(const char* fn, bool ptrs, void* logits, int64_t ld, const int64_t* labels, const P& p, float* lse,
               int64_t M, int64_t V, int32_t* err, int dtype, void* stream) {
-  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, true)) return rc;
+  if (const int rc = row_check(fn, ptrs && logits && labels && lse, logits, ld, M, V, dtype, P::kPair)) return rc;
   hipLaunchKernelGGL((row_fused_kernel<P>), dim3((unsigned)M), dim3(1024), 0, (hipStream_t)stream, (bf16*)logits, ld, labels, p, lse, (int)V, err);
   VY_CHECK_LAUNCH(fn);
   return VY_OK;
@@ -1004,6 +1082,22 @@ extern "C" int vy_xent_fused(void* logits, int64_t ld, const int64_t* labels, in
                              int32_t* err_flag, int dtype, void* stream) {
   return row_fused("vy_xent_fused", loss_sum && count && gscale, logits, ld, labels,
                    XentRow<false>{ignore_index, gscale, count, loss_sum, nullptr}, lse, M, V, err_flag, dtype, stream);
+}
+
+extern "C" int vy_xent_sample_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index,
+                                  float* lse, float* loss_sum, float* count, int64_t* sampled, float inv_temperature,
+                                  uint64_t seed, uint64_t offset, int64_t M, int64_t V, int32_t* err_flag, int dtype,
+                                  void* stream) {
+  XentSampleRow<true> p{{ignore_index, nullptr, nullptr, loss_sum, count}, sampled, inv_temperature, vy_make_noise(seed, offset)};
+  return row_lse("vy_xent_sample_fwd", loss_sum && count && sampled, logits, ld, labels, p, lse, M, V, err_flag, dtype, stream);
+}
+
+extern "C" int vy_xent_sample_fused(void* logits, int64_t ld, const int64_t* labels, int64_t ignore_index, float* lse,
+                                    float* loss_sum, const float* count, const float* gscale, int64_t* sampled,
+                                    float inv_temperature, uint64_t seed, uint64_t offset, int64_t M, int64_t V,
+                                    int32_t* err_flag, int dtype, void* stream) {
+  XentSampleRow<false> p{{ignore_index, gscale, count, loss_sum, nullptr}, sampled, inv_temperature, vy_make_noise(seed, offset)};
+  return row_fused("vy_xent_sample_fused", loss_sum && count && gscale && sampled, logits, ld, labels, p, lse, M, V, err_flag, dtype, stream);
 }
 
 extern "C" int vy_logprob_fwd(const void* logits, int64_t ld, const int64_t* labels, const float* weight, float* lse,

@@ -43,22 +43,35 @@ class LMHead(nn.Module):
 
 
     def loss(self, hidden_state: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100,
-             check_labels: bool = False) -> torch.Tensor:
-        """Shifted CLM cross-entropy fused with the head (no fp32 logits copy): the training-side
+             check_labels: bool = False, shift: bool = True) -> torch.Tensor:
+        """Shifted CLM cross-entropy (shift=False: position t against label t, the masked-LM loss of
+        Examples/masked_language_modeling.ipynb) fused with the head (no fp32 logits copy): the training-side
         entry point; see autograd_train.LMHeadLossFn.  A label that is neither `ignore_index` nor a
         vocabulary id (torch.cross_entropy device-asserts on it) is never dereferenced: its row counts as
         ignored and the device flag `self.label_error` is raised -- `check_labels=True` (or
         `raise_on_label_error()` whenever convenient: it synchronises) turns that into a ValueError."""
+        out = self._loss(hidden_state, labels, ignore_index, shift, None)
+        if check_labels:
+            self.raise_on_label_error()
+        return out
+
+    def _loss(self, hidden_state, labels, ignore_index, shift, sample):
         from ..autograd_train import LMHeadLossFn
         flag = getattr(self, "label_error", None)
         if flag is None or flag.device != hidden_state.device:
             flag = self.label_error = torch.zeros(1, dtype=torch.int32, device=hidden_state.device)
-        out = LMHeadLossFn.apply(hidden_state, labels, ignore_index, self.dense.weight, self.dense.bias,
-                                 self.layer_norm.weight, self.layer_norm.bias, self.decoder.weight, self.bias,
-                                 self.layer_norm.eps, flag)
-        if check_labels:
-            self.raise_on_label_error()
-        return out
+        return LMHeadLossFn.apply(hidden_state, labels, ignore_index, self.dense.weight, self.dense.bias,
+                                  self.layer_norm.weight, self.layer_norm.bias, self.decoder.weight, self.bias,
+                                  self.layer_norm.eps, flag, shift, sample)
+
+    def mlm_loss_and_sample(self, hidden_state: torch.Tensor, labels: torch.Tensor, temperature: float,
+                            ignore_index: int = -100):
+        """-> (masked-LM loss, sampled): the unshifted loss of `loss`, and in the same pass over the logits one
+        token per labelled position drawn as argmax(logits / temperature + Gumbel noise) -- ELECTRA's replaced
+        tokens (reference pretraining/collators.py:76-91) -- with -1 wherever the label is ignore_index.  `sampled`
+        (labels' shape, int64) carries no gradient.  The logits are never read again."""
+        from .. import rng
+        return self._loss(hidden_state, labels, ignore_index, False, (1.0 / float(temperature), *rng.next_offset()))
 
     def raise_on_label_error(self) -> None:
         flag = getattr(self, "label_error", None)

@@ -84,6 +84,13 @@ class EncoderForMaskedLM(nn.Module):
         out = self.encoder(input_ids=input_ids, attention_mask=attention_mask)
         return MLMOutput(hidden_state=out.logits, logits=self.lm_head(out.logits))
 
+    def mlm_loss(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
+                 ignore_index: int = -100) -> torch.Tensor:
+        """Mean cross-entropy of position t against labels[t] over labels != ignore_index, the loss of
+        Examples/masked_language_modeling.ipynb (nn.CrossEntropyLoss on logits.view(-1, V)), fused with the head."""
+        out = self.encoder(input_ids=input_ids, attention_mask=attention_mask)
+        return self.lm_head.loss(out.logits, labels, ignore_index=ignore_index, shift=False)
+
     @classmethod
     def from_config(cls, config, pos_embedding_type: Optional[str] = "absolute", attention_type: str = None):
         return cls(config, pos_embedding_type, attention_type)

@@ -565,6 +565,101 @@ def xent_fused_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor
          _stream())
 
 
+def xent_sample_fwd(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, loss_sum: Tensor, count: Tensor,
+                    sampled: Tensor, inv_temperature: float, seed: int, offset: int,
+                    err_flag: Optional[Tensor] = None) -> None:
+    """xent_fwd that also draws sampled[m] = argmax_v(logits[m, v] * inv_temperature + gumbel(m, v)) on every live row
+    (-1 on skipped rows); sampled int64 (M,) (vy_xent_sample_fwd)."""
+    _need_gpu(logits2d, labels, lse, loss_sum, count, sampled, err_flag)
+    _row_args(logits2d, labels, lse, scalars=(loss_sum, count))
+    M, V = logits2d.shape
+    assert sampled.dtype == torch.long and sampled.numel() == M and sampled.is_contiguous()
+    call("vy_xent_sample_fwd", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index, lse.data_ptr(),
+         loss_sum.data_ptr(), count.data_ptr(), sampled.data_ptr(), float(inv_temperature), int(seed), int(offset), M, V,
+         _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
+
+
+def xent_sample_fused_(logits2d: Tensor, labels: Tensor, ignore_index: int, lse: Tensor, loss_sum: Tensor, count: Tensor,
+                       gscale: Tensor, sampled: Tensor, inv_temperature: float, seed: int, offset: int,
+                       err_flag: Optional[Tensor] = None) -> None:
+    """xent_fused_ that also draws `sampled` as xent_sample_fwd does, from the row it holds in registers
+    (vy_xent_sample_fused)."""
+    _need_gpu(logits2d, labels, lse, loss_sum, count, gscale, sampled, err_flag)
+    _row_args(logits2d, labels, lse, scalars=(loss_sum, count, gscale))
+    M, V = logits2d.shape
+    assert sampled.dtype == torch.long and sampled.numel() == M and sampled.is_contiguous()
+    call("vy_xent_sample_fused", logits2d.data_ptr(), logits2d.stride(0), labels.data_ptr(), ignore_index,
+         lse.data_ptr(), loss_sum.data_ptr(), count.data_ptr(), gscale.data_ptr(), sampled.data_ptr(),
+         float(inv_temperature), int(seed), int(offset), M, V, _ptr(err_flag), dtype_code(logits2d.dtype), _stream())
+
+
+def gumbel_noise(M: int, V: int, seed: int, offset: int, device) -> Tensor:
+    """The (M, V) fp32 noise the two calls above add for the same (seed, offset) (vy_gumbel_noise; for tests)."""
+    out = torch.empty((M, V), dtype=torch.float32, device=device)
+    _need_gpu(out)
+    call("vy_gumbel_noise", out.data_ptr(), out.stride(0), M, V, int(seed), int(offset), _stream())
+    return out
+
+
+def _bce_args(h2: Tensor, w: Tensor, M: int, *rows: Tensor, scalars=()) -> None:
+    assert w.dtype == h2.dtype and w.numel() == h2.shape[1] and w.is_contiguous()
+    for t in rows:
+        assert t.numel() == M and t.is_contiguous()
+    for t in scalars:
+        assert t.dtype == torch.float32 and t.numel() == 1
+
+
+def bce_head_fwd(h: Tensor, w: Tensor, b: Optional[Tensor], target: Optional[Tensor] = None,
+                 live: Optional[Tensor] = None, loss_sum: Optional[Tensor] = None) -> Tensor:
+    """z = h . w + b per row, fp32, shape h.shape[:-1]; with target (fp32 0 / 1) and live (uint8) the BCE-with-logits
+    of the live rows is added to the device scalar loss_sum (vy_bce_head_fwd)."""
+    _need_gpu(h, w, b, target, live, loss_sum)
+    h2 = _rows(h)
+    M, d = h2.shape
+    z = torch.empty(h.shape[:-1], dtype=torch.float32, device=h.device)
+    _bce_args(h2, w, M)
+    if target is not None:
+        _bce_args(h2, w, M, target, live, scalars=(loss_sum,))
+        assert target.dtype == torch.float32 and live.dtype == torch.uint8
+    assert b is None or (b.dtype == h.dtype and b.numel() == 1)
+    call("vy_bce_head_fwd", h2.data_ptr(), h2.stride(0), w.data_ptr(), _ptr(b), z.data_ptr(), _ptr(target), _ptr(live),
+         _ptr(loss_sum), M, d, dtype_code(h.dtype), _stream())
+    return z
+
+
+def bce_head_bwd(h: Tensor, w: Tensor, z: Tensor, target: Tensor, live: Tensor, gscale: Tensor, count: Tensor,
+                 dw: Tensor, db: Tensor, accumulate: bool) -> Tensor:
+    """-> dh (h's shape and dtype); dw [d] / db [1] fp32 written or (accumulate) added to (vy_bce_head_bwd)."""
+    _need_gpu(h, w, z, target, live, gscale, count, dw, db)
+    h2 = _rows(h)
+    M, d = h2.shape
+    _bce_args(h2, w, M, z, target, live, scalars=(gscale, count, db))
+    assert z.dtype == torch.float32 and target.dtype == torch.float32 and live.dtype == torch.uint8
+    assert dw.dtype == torch.float32 and dw.numel() == d and dw.is_contiguous()
+    dh = torch.empty((M, d), dtype=h.dtype, device=h.device)
+    call("vy_bce_head_bwd", h2.data_ptr(), h2.stride(0), w.data_ptr(), z.data_ptr(), target.data_ptr(), live.data_ptr(),
+         gscale.data_ptr(), count.data_ptr(), dh.data_ptr(), dh.stride(0), dw.data_ptr(), db.data_ptr(),
+         1 if accumulate else 0, M, d, dtype_code(h.dtype), _stream())
+    return dh.view(h.shape)
+
+
+def mlm_mask(ids: Tensor, special_ids: Tensor, fraction: float, mask_id: int, vocab: int, ignore_index: int,
+             seed: int, offset: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (masked_ids, labels, masked bool) of ids' shape (vy_mlm_mask).  special_ids: int64 device list, may be
+    empty."""
+    _need_gpu(ids, special_ids)
+    assert ids.dtype == torch.long and special_ids.dtype == torch.long and special_ids.is_contiguous()
+    idc = ids.contiguous()
+    out = torch.empty_like(idc)
+    labels = torch.empty_like(idc)
+    masked = torch.empty(idc.shape, dtype=torch.uint8, device=ids.device)
+    ns = special_ids.numel()
+    call("vy_mlm_mask", idc.data_ptr(), idc.numel(), special_ids.data_ptr() if ns else None, ns, float(fraction),
+         int(mask_id), int(vocab), int(ignore_index), int(seed), int(offset), out.data_ptr(), labels.data_ptr(),
+         masked.data_ptr(), _stream())
+    return out, labels, masked.view(torch.bool)
+
+
 def embedding(table: Tensor, ids: Tensor, err_flag: Optional[Tensor] = None) -> Tensor:
     """out[..., :] = table[ids[...], :]  (vy_embedding_fwd).  table: (V, d) bf16/fp32; ids int64."""
     _need_gpu(table, ids, err_flag)

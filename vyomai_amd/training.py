@@ -470,8 +470,9 @@ class FlatTrainer:
         if 0 < self._micro < self.accumulate_steps:   # in the middle of an accumulation window: keep adding
             return
         self._micro = 0            # (a finished window that was never stepped is dropped here: its gradients are cleared)
-        from .autograd_train import _wgrad_group
+        from .autograd_train import _wgrad_group, reset_embedding_uses
         _wgrad_group.discard()   # (only an aborted backward can have left deferred weight gradients behind)
+        reset_embedding_uses()   # (likewise embedding forwards whose backward never ran)
         self.arena.zero_grad()
         self.reducer.reset()
         self._stepped = set()
