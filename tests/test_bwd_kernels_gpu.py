@@ -6,6 +6,7 @@ import torch
 
 from oracle import vyom_oracle as O
 from tests.test_kernels_gpu import check, rnd, _dense_mask, ints, thin_ternary, assert_bf16_exact, check_exact
+from tests.test_kernels_gpu import attn_tile_case, attn_tile_fwd, same_bytes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -251,6 +252,45 @@ def test_attention_bwd(case):
     check(dq, qd.grad, 4e-2, 3e-2, "dq")
     check(dk, kd.grad, 4e-2, 3e-2, "dk")
     check(dv, vd.grad, 4e-2, 3e-2, "dv")
+
+
+# ---- the tuned kernels' stage writer and mask words, byte for byte (dh = 64; see tests.test_kernels_gpu) ---------------
+# 4 query tiles x 2 heads = 8 ring stages in the dK/dV kernel
+def attn_tile_bwd(ops, q, k, v, S, causal, keypad):
+    out, lse = attn_tile_fwd(ops, q, k, v, S, causal, keypad)
+    do = rnd(1, 200, 2 * 64, seed=24).to(BF).to(DEV)
+    dq = torch.zeros(1, 2, 200, 64, dtype=BF, device=DEV)
+    dk = torch.zeros(1, 1, 256, 64, dtype=BF, device=DEV)
+    dv = torch.zeros_like(dk)
+    delta = torch.zeros(1, 2, 200, dtype=torch.float32, device=DEV)
+    ops.attention_bwd(q, k[:, :, :S], v[:, :, :S], out, do, lse, dq, dk[:, :, :S], dv[:, :, :S], causal=causal,
+                      keypad=keypad, delta=delta)
+    return {"out": out, "lse": lse, "dq": dq, "dk": dk, "dv": dv, "delta_ws": delta}
+
+
+@pytest.mark.parametrize("causal", [True, False])
+def test_attention_bwd_keypad_of_ones_equals_no_keypad(causal):
+    ops = _ops()
+    q, k, v, _hide = attn_tile_case(64)
+    a = attn_tile_bwd(ops, q, k, v, 200, causal, None)
+    b = attn_tile_bwd(ops, q, k, v, 200, causal, torch.ones(1, 200, dtype=torch.uint8, device=DEV))
+    for name in ("out", "lse", "dq", "dk", "dv", "delta_ws"):
+        same_bytes(a[name], b[name], name)
+
+
+@pytest.mark.parametrize("causal", [True, False])
+def test_attention_bwd_short_s_equals_padded_s(causal):
+    """S = 200 without a mask == S = 256 with keys 200..255 hidden by a key-padding mask; the hidden keys get exact
+    zeros (masked scores are replaced by select, hidden keys multiply finite rows by an exact 0)."""
+    ops = _ops()
+    q, k, v, hide = attn_tile_case(64)
+    a = attn_tile_bwd(ops, q, k, v, 200, causal, None)
+    b = attn_tile_bwd(ops, q, k, v, 256, causal, hide)
+    for name in ("out", "lse", "dq", "delta_ws"):
+        same_bytes(a[name], b[name], name)
+    for name in ("dk", "dv"):
+        same_bytes(a[name][:, :, :200], b[name][:, :, :200], name + "[:, :, :200]")
+        assert (b[name][:, :, 200:] == 0).all(), name + " of the hidden keys"
 
 
 def test_adamw_matches_torch():

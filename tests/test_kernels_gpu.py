@@ -382,6 +382,57 @@ def test_attention_fwd(dtype, case):
           2e-2 if dtype == torch.bfloat16 else 1e-4, 1e-4, "lse")
 
 
+# ---- the tuned kernels' stage writer and mask words, byte for byte ----------------------------------------------------
+# B = 1, h = 2, hk = 1, L = 200, K / V with 256 random rows.  200 keys are four key tiles for the three-deep ring (a slot
+# is reused) and end in a ragged tile of 8 keys.
+def attn_tile_case(dh, seed=20):
+    q = rnd(1, 2, 200, dh, seed=seed).to(torch.bfloat16).to(DEV)
+    k = rnd(1, 1, 256, dh, seed=seed + 1).to(torch.bfloat16).to(DEV)
+    v = rnd(1, 1, 256, dh, seed=seed + 2).to(torch.bfloat16).to(DEV)
+    hide = torch.ones(1, 256, dtype=torch.uint8, device=DEV)
+    hide[:, 200:] = 0
+    return q, k, v, hide
+
+
+def attn_tile_fwd(ops, q, k, v, S, causal, keypad):
+    lse = torch.zeros(1, 2, 200, dtype=torch.float32, device=DEV)
+    out = ops.attention(q, k[:, :, :S], v[:, :, :S], causal=causal, keypad=keypad, lse=lse)
+    return out, lse
+
+
+def same_bytes(a, b, what):
+    assert a.dtype == b.dtype and a.shape == b.shape, what
+    a, b = a.contiguous().cpu(), b.contiguous().cpu()
+    n = a.element_size()
+    diff = (a.view(torch.uint8).view(-1, n) != b.view(torch.uint8).view(-1, n)).any(-1)
+    assert not diff.any(), f"{what}: {int(diff.sum())}/{diff.numel()} elements differ, first at flat index {int(diff.nonzero()[0])}"
+
+
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("dh", [64, 128])
+def test_attention_fwd_keypad_of_ones_equals_no_keypad(dh, causal):
+    ops, _ = _ops()
+    q, k, v, _hide = attn_tile_case(dh)
+    ones = torch.ones(1, 200, dtype=torch.uint8, device=DEV)
+    a = attn_tile_fwd(ops, q, k, v, 200, causal, None)
+    b = attn_tile_fwd(ops, q, k, v, 200, causal, ones)
+    same_bytes(a[0], b[0], "out")
+    same_bytes(a[1], b[1], "lse")
+
+
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("dh", [64, 128])
+def test_attention_fwd_short_s_equals_padded_s(dh, causal):
+    """S = 200 without a mask (the last tile takes the clamped-row writer path) == S = 256 with keys 200..255 hidden by a
+    key-padding mask (the same tile takes the whole-tile path, the mask word hides the keys)."""
+    ops, _ = _ops()
+    q, k, v, hide = attn_tile_case(dh)
+    a = attn_tile_fwd(ops, q, k, v, 200, causal, None)
+    b = attn_tile_fwd(ops, q, k, v, 256, causal, hide)
+    same_bytes(a[0], b[0], "out")
+    same_bytes(a[1], b[1], "lse")
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("B,h,hk,S,dh", [(3, 12, 12, 37, 64), (32, 12, 4, 640, 64), (2, 8, 1, 300, 256), (1, 4, 2, 1, 16)])
 def test_attention_decode(dtype, B, h, hk, S, dh):

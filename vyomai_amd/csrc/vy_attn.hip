@@ -20,12 +20,11 @@
 //
 // Reference: F.scaled_dot_product_attention call sites, VyomAI/layers/attention.py:128,209,283,
 // 373,619 and VyomAI/models/decoder.py:107,195.
-#include "vy_common.h"
+#include "vy_attn_tile.h"
 #include <float.h>
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
 struct AttnParams {
@@ -49,35 +48,21 @@ struct AttnParams {
 template <int DH>
 __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(AttnParams p) {
   constexpr int RB = DH * 2;            // bytes per K/V row
-  constexpr int TILE = 64 * RB;         // bytes per 64-key tile
-  constexpr int NP = TILE / 1024 / 4;   // 1-KiB LDS-DMA pieces per wave per tile
   constexpr int KS = DH / 16;           // k-steps of the QK^T contraction
   constexpr int ND = DH / 32;           // 32-wide d blocks of O^T
   constexpr int NS = 3;                 // K/V tiles in the LDS ring: NS - 1 tiles of loads in flight (4: no gain)
   constexpr int KPW = 256;              // key-padding visibility words (64 keys each): S <= 16384
+  typedef AttnStage<RB, NS, true> Stage;
+  constexpr int TILE = Stage::TILE;     // bytes per 64-key tile
   // ONE shared object (a second one makes hipcc wait vmcnt(0) before every ds_read while LDS-DMA
   // is in flight): K ring, V ring, then 4 flag words for the block-wide OR below
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE + 64 + KPW * 8];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = (p.L + 127) / 128;
-  // grid = (h*B, query blocks): the dispatcher walks x first, so ALL the heaviest query blocks
-  // (most keys under a causal mask) of every (batch, head) start before any lighter one --
-  // longest-processing-time order; with (query block, head, batch) order the last (batch, head)
-  // groups still start full-length workgroups at the very end and causal ran as long as full
-  const int qb = nqb - 1 - (int)blockIdx.y;
-  const int head = (int)blockIdx.x % p.h, b = (int)blockIdx.x / p.h;
-  const int kvh = head / (p.h / p.hk);
-  const int q0 = qb * 128;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int qi = q0 + wave * 32 + fr;  // this lane's query row
-  const int qrow = qi < p.L ? qi : p.L - 1;
-
-  const bf16* Q = (const bf16*)p.q + (int64_t)b * p.q_sb + (int64_t)head * p.q_sh + (int64_t)qrow * p.q_sl;
-  const bf16* Kb = (const bf16*)p.k + (int64_t)b * p.k_sb + (int64_t)kvh * p.k_sh;
-  const bf16* Vb = (const bf16*)p.v + (int64_t)b * p.v_sb + (int64_t)kvh * p.v_sh;
-
+  const AttnLane ln;
+  const AttnQBlock blk(p, ln);
+  const int lane = ln.lane, wave = ln.wave, fr = ln.fr, fh = ln.fh, li = ln.li, g16 = ln.g16, tid = threadIdx.x;
+  const int head = blk.head, b = blk.b, q0 = blk.q0, qi = blk.qi, qrow = blk.qrow;
+  const bf16 *Q = blk.Q, *Kb = blk.Kb, *Vb = blk.Vb;
   bf16x8 qf[KS];  // loaded after the first K/V tiles are in flight (below)
   const bool causal = p.mask_kind & VY_MASK_CAUSAL;
   const bool haskp = p.mask_kind & VY_MASK_KEYPAD;
@@ -85,56 +70,21 @@ __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(At
   const uint8_t* kp = haskp ? p.keypad + (int64_t)b * p.kp_sb : nullptr;
   const float* am = hasadd ? p.addmask + (int64_t)b * p.am_sb + (int64_t)qrow * p.am_sl : nullptr;
 
-  // LDS-DMA source geometry: piece pc covers LDS bytes [pc*1024, +1024); lane byte P
-  int ld_row[NP], ld_koff[NP], ld_voff[NP];
-  // per-lane source pointers of tile 0 (rows clamped to the last key): a full tile adds a wave-uniform offset to them --
-  // two 64-bit adds per piece instead of the clamp + 64-bit multiplies by the row strides (12 quarter-rate multiplies per
-  // tile and wave in a loop that is bound by vector issue)
-  const bf16* ksrc0[NP];
-  const bf16* vsrc0[NP];
-#pragma unroll
-  for (int t = 0; t < NP; ++t) {
-    const int P = (wave * NP + t) * 1024 + lane * 16;
-    const int row = P / RB, off = P % RB;
-    const int ksw = (RB == 128) ? ((row >> 1) & 7) : (row & 15);
-    const int vsw = (RB == 128) ? (((row >> 1) & 1) << 6) : ((row & 3) << 6);
-    ld_row[t] = row;
-    ld_koff[t] = ((((off >> 4) ^ ksw) << 4)) >> 1;  // element offset inside the row
-    ld_voff[t] = (off ^ vsw) >> 1;
-    const int r0 = row < p.S ? row : p.S - 1;
-    ksrc0[t] = Kb + (int64_t)r0 * p.k_sl + ld_koff[t];
-    vsrc0[t] = Vb + (int64_t)r0 * p.v_sl + ld_voff[t];
-  }
+  // K is read by rows, V transposed; whole tiles take the pre-computed pointers, the ragged last one the clamp
+  Stage st_w(ln, SwRows<RB>{}, SwTr64<RB>{});
+  st_w.whole_tiles(Kb, p.k_sl, Vb, p.v_sl, p.S);
   const int64_t k_tile = 64 * p.k_sl, v_tile = 64 * p.v_sl;   // elements per 64-key tile
   auto stage = [&](int tile, int buf) {
     const int k0 = tile * 64;
     if (k0 + 64 <= p.S) {   // wave-uniform: every row of the tile exists
-      const int64_t ko = (int64_t)tile * k_tile, vo = (int64_t)tile * v_tile;
-#pragma unroll
-      for (int t = 0; t < NP; ++t) {
-        __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)(ksrc0[t] + ko),
-                                         (VY_LDS void*)(smem + buf * TILE + (wave * NP + t) * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)(vsrc0[t] + vo),
-                                         (VY_LDS void*)(smem + (NS + buf) * TILE + (wave * NP + t) * 1024), 16, 0, 0);
-      }
+      st_w.issue_whole(smem, wave, buf, tile, k_tile, v_tile);
       return;
     }
-#pragma unroll
-    for (int t = 0; t < NP; ++t) {
-      int kr = k0 + ld_row[t];
-      kr = kr < p.S ? kr : p.S - 1;
-      const bf16* ks = Kb + (int64_t)kr * p.k_sl + ld_koff[t];
-      const bf16* vs = Vb + (int64_t)kr * p.v_sl + ld_voff[t];
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)ks,
-                                       (VY_LDS void*)(smem + buf * TILE + (wave * NP + t) * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)vs,
-                                       (VY_LDS void*)(smem + (NS + buf) * TILE + (wave * NP + t) * 1024), 16, 0, 0);
-    }
+    st_w.issue(smem, wave, buf, k0, p.S, Kb, p.k_sl, Vb, p.v_sl);
   };
 
   // read-side lane constants
-  const int k_sw = (RB == 128) ? ((fr >> 1) & 7) : (fr & 15);
-  const int li = lane & 15, g16 = (lane >> 4) & 1;
+  const int k_sw = SwRows<RB>::key(fr);
   const int v_sw = (RB == 128) ? (((li >> 3) & 1) << 6) : (((li >> 2) & 3) << 6);
   const int v_lane_row = 4 * fh + (li >> 2);            // + 32kb + 16s + 8u
   const int v_lane_off = 32 * g16 + 8 * (li & 3);       // + 64n, then ^ v_sw
@@ -157,28 +107,10 @@ __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(At
   float m_run = -FLT_MAX, l_run = 0.f;
   const float c = p.scale * LOG2E;
 
-  // pure causal: keys beyond the diagonal of the block's last row are never visible -> skipped
-  const int nt_all = (p.S + 63) / 64;
-  int nt = nt_all;
-  if (causal) {
-    const int kv_end = min(p.S, p.start_pos + q0 + 128);
-    nt = (kv_end + 63) / 64;
-    if (nt < 1) nt = 1;
-  }
+  const int nt = blk.key_tiles(p, causal);
   const int wave_first = q0 + wave * 32, wave_last = wave_first + 31;
-
-  // key-padding mask -> one 64-bit visibility word per key tile, built once (an ordinary load inside
-  // the tile loop would make the compiler drain the LDS-DMA ring with vmcnt(0) every tile)
   unsigned long long* kpbits = reinterpret_cast<unsigned long long*>(smem + 2 * NS * TILE + 64);
-  if (haskp) {
-    for (int t = wave; t < nt; t += 4) {
-      const int kj = t * 64 + lane;
-      const bool vis = kj < p.S && kp[kj < p.S ? kj : 0] != 0;
-      const unsigned long long bits = __ballot(vis);
-      if (lane == 0) kpbits[t] = bits;
-    }
-    __syncthreads();
-  }
+  if (haskp) attn_keypad_words(kpbits, kp, nt, p.S, ln);
 
   auto compute = [&](int tile, int buf) {
     const int k0 = tile * 64;
@@ -235,16 +167,13 @@ __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(At
       // key index of register r is k0 + 4fh + kofs, kofs = 32kb + (r&3) + 8(r>>2).  Visibility of
       // the lane's 32 keys as one bit word: padding bits shifted by 4fh, AND kofs <= klim (causal
       // diagonal and end of sequence)
-      int klim = p.S - 1 - k0 - 4 * fh;
-      if (causal) klim = min(klim, qi + p.start_pos - k0 - 4 * fh);
-      unsigned long long lm = klim >= 63 ? ~0ull : (klim < 0 ? 0ull : ((2ull << klim) - 1ull));
-      lm &= vis >> (4 * fh);
+      const unsigned long long lm = attn_key_bits(k0, fh, p.S, causal, qi + p.start_pos, vis);
       const unsigned lmw[2] = {(unsigned)lm, (unsigned)(lm >> 32)};
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int bit = (r & 3) + 8 * (r >> 2);
+          const int bit = attn_reg_bit(r);
           float t = st[kb][r];
           if (hasadd) {
             // in-range guard only: invisible keys are overwritten below
@@ -304,31 +233,19 @@ __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(At
       o[f >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[f], pf[(f >> 1) & 1][f & 1], o[f >> 2], 0, 0, 0);
   };
 
-  // Loads run NS-1 tiles ahead of the MFMAs: a tile is waited for with a COUNTED vmcnt (its own
-  // 2*NP LDS-DMA instructions are the oldest outstanding ones of the wave) and one raw s_barrier per
-  // tile; nothing in the loop drains the memory pipe, so the L2/HBM latency of a tile is covered
-  // by the softmax + MFMA work of the previous tiles instead of being paid once per tile.
-  auto wait_tile = [&](int younger) {   // `younger` tiles (2*NP LDS-DMA instructions each) may stay in flight
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * NP) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-  // The Q fragments came through ordinary loads: make the compiler retire them HERE (an asm that
-  // reads them), before any LDS-DMA is in flight -- otherwise its wait for them sits at the first
-  // MFMA inside the loop as vmcnt(0) and drains the ring every tile.
+  typedef AttnRing<NS, Stage::DMA> Ring;
 #pragma unroll
-  for (int s_ = 0; s_ < NS - 1; ++s_)
+  for (int s_ = 0; s_ < Ring::AHEAD; ++s_)
     if (s_ < nt) stage(s_, s_);
-  // Q after the first K/V tiles are requested: one memory latency for both, not two in a row
+  // Q after the first K/V tiles are requested (one memory latency for both, not two in a row), and retired -- an asm
+  // that reads it -- before the loop
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(Q + ks * 16 + fh * 8);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(qf[ks]));
   for (int t = 0; t < (p.diag == 2 ? 0 : nt); ++t) {
-    wait_tile(min(NS - 2, nt - 1 - t));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (t + NS - 1 < nt) stage(t + NS - 1, (t + NS - 1) % NS);  // the buffer tile t-1 was read from
+    Ring::arrive(t, nt);
+    if (t + Ring::AHEAD < nt) stage(t + Ring::AHEAD, (t + Ring::AHEAD) % NS);
     compute(t, t % NS);
   }
 

@@ -16,13 +16,12 @@
 // The backward formulas are the ones autograd derives for the reference modules; the attention
 // one is spelled out by the reference author in Examples/vyom-ai-decoder-fused.ipynb cell 7
 // (dS = P o (dP - rowsum(dO o O))).
-#include "vy_common.h"
+#include "vy_attn_tile.h"
 #include <float.h>
 #include <stdlib.h>
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
@@ -452,77 +451,20 @@ struct BwdParams {
   const float* cos_tab; const float* sin_tab; int rope_pos0;  // NULL: no RoPE backward fused
 };
 
-// delta_ws[b,h,q] = -sum_d dO[b,q,h*dh+d] * O[b,q,h*dh+d]; one wave per (b,q) row, dh = 64
-__global__ __launch_bounds__(256) void attn_delta_kernel(BwdParams p) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (int64_t)p.B * p.L) return;
-  const int b = (int)(row / p.L), qi = (int)(row - (int64_t)b * p.L);
-  const bf16* o = p.o + (int64_t)b * p.o_sb + (int64_t)qi * p.o_sl;
-  const bf16* g = p.dout + (int64_t)b * p.o_sb + (int64_t)qi * p.o_sl;
-  const int nch = p.h * 8;  // 16-byte chunks per row (dh = 64 -> 8 per head)
-  for (int c = lane; c < ((nch + 63) / 64) * 64; c += 64) {
-    float s = 0.f;
-    if (c < nch) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8*>(o + c * 8);
-      const bf16x8 d = *reinterpret_cast<const bf16x8*>(g + c * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += (float)a[e] * (float)d[e];
-    }
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-    if (c < nch && (c & 7) == 0) p.delta[((int64_t)b * p.h + (c >> 3)) * p.L + qi] = -s;  // NEGATED: it is the dP accumulator's initial value
-  }
-}
-
-// RoPE is an orthogonal map, so its backward is the transposed rotation of the gradient pair
-// (d, d+32): lo' = lo*c + hi*s, hi' = hi*c - lo*s, with the same storage-rounded cos/sin the forward
-// used.  pos = token position, d0 = first of the 4 consecutive d (< 32) of this quad.
-__device__ __forceinline__ void rope_bwd_quad(const BwdParams& p, int64_t pos, int d0, float (&lo)[4], float (&hi)[4]) {
-  const f32x4 c4 = *reinterpret_cast<const f32x4*>(p.cos_tab + pos * 32 + d0);
-  const f32x4 s4 = *reinterpret_cast<const f32x4*>(p.sin_tab + pos * 32 + d0);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float c = vy_round_bf16(c4[e]), s = vy_round_bf16(s4[e]);
-    const float a = lo[e], b = hi[e];
-    lo[e] = a * c + b * s;
-    hi[e] = b * c - a * s;
-  }
-}
-
-// chunk swizzle of a 128-B-row LDS image that is read BOTH by rows (ds_read_b128) and transposed
-// (ds_read_b64_tr_b16): conflict-free for both ("dual-use image")
-__device__ __forceinline__ int dual_sw(int row) {
-  const int v = (row >> 1) & 7;
-  return ((v & 1) << 2) | (v >> 1);
-}
-
-// visibility bits [lo, hi) of a 32- or 64-wide index range (lo/hi may lie outside it)
-__device__ __forceinline__ unsigned long long range_bits64(int lo, int hi) {
-  const unsigned long long up = hi >= 64 ? ~0ull : (hi <= 0 ? 0ull : ((1ull << hi) - 1ull));
-  const unsigned long long dn = lo >= 64 ? 0ull : (lo <= 0 ? ~0ull : (~0ull << lo));
-  return up & dn;
-}
-
 // ---- dq kernel: forward structure, no online softmax --------------------------------------
 // K/V tiles of 64 keys run through a 3-deep LDS-DMA ring with counted vmcnt waits (as in the
 // forward kernel); masks are per-lane bit words, P is recomputed as exp2(fma(s, c, -lse*log2e)).
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
-  constexpr int DH = 64, RB = 128, TILE = 64 * RB, NS = 3, KPW = 256;
+  constexpr int DH = 64, RB = 128, NS = 3, KPW = 256;
+  typedef AttnStage<RB, NS> Stage;
+  constexpr int TILE = Stage::TILE;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE + KPW * 8];  // K ring, V ring, key-padding words
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = (p.L + 127) / 128;
-  const int qb = nqb - 1 - (int)blockIdx.y;  // grid (h*B, query blocks): heaviest blocks of ALL heads first
-  const int head = (int)blockIdx.x % p.h, b = (int)blockIdx.x / p.h;
-  const int kvh = head / (p.h / p.hk);
-  const int q0 = qb * 128;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int qi = q0 + wave * 32 + fr;
-  const int qrow = qi < p.L ? qi : p.L - 1;
-  const bf16* Q = p.q + (int64_t)b * p.q_sb + (int64_t)head * p.q_sh + (int64_t)qrow * p.q_sl;
+  const AttnLane ln;
+  const AttnQBlock blk(p, ln);
+  const int wave = ln.wave, fr = ln.fr, fh = ln.fh;
+  const int head = blk.head, b = blk.b, q0 = blk.q0, qi = blk.qi, qrow = blk.qrow;
+  const bf16 *Q = blk.Q, *Kb = blk.Kb, *Vb = blk.Vb;
   const bf16* dO = p.dout + (int64_t)b * p.o_sb + (int64_t)qrow * p.o_sl + head * DH;
-  const bf16* Kb = p.k + (int64_t)b * p.k_sb + (int64_t)kvh * p.k_sh;
-  const bf16* Vb = p.v + (int64_t)b * p.v_sb + (int64_t)kvh * p.v_sh;
   bf16x8 qf[4], gf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
@@ -553,60 +495,21 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
   const bool haskp = p.mask_kind & VY_MASK_KEYPAD;
   const uint8_t* kp = haskp ? p.keypad + (int64_t)b * p.kp_sb : nullptr;
 
-  int ld_row[2], ld_koff[2], ld_voff[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int P = (wave * 2 + t) * 1024 + lane * 16;
-    const int row = P / RB, off = P % RB;
-    ld_row[t] = row;
-    ld_koff[t] = (((off >> 4) ^ dual_sw(row)) << 4) >> 1;   // K: dual-use image
-    ld_voff[t] = (((off >> 4) ^ ((row >> 1) & 7)) << 4) >> 1;  // V: row reads only
-  }
-  auto stage = [&](int tile, int buf) {
-    const int k0 = tile * 64;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      int kr = k0 + ld_row[t];
-      kr = kr < p.S ? kr : p.S - 1;
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)(Kb + (int64_t)kr * p.k_sl + ld_koff[t]),
-                                       (VY_LDS void*)(smem + buf * TILE + (wave * 2 + t) * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)(Vb + (int64_t)kr * p.v_sl + ld_voff[t]),
-                                       (VY_LDS void*)(smem + (NS + buf) * TILE + (wave * 2 + t) * 1024), 16, 0, 0);
-    }
-  };
-  const int k_sw = dual_sw(fr), v_sw = (fr >> 1) & 7;
-  const int li = lane & 15, g16 = (lane >> 4) & 1;
-  const int t_row = 4 * fh + (li >> 2);
-  const int t_chunk = 2 * g16 + ((li & 3) >> 1), t_byte = 8 * (li & 1);
+  const Stage st_w(ln, SwDual{}, SwRows<RB>{});   // K: dual-use image; V: row reads only
+  auto stage = [&](int tile, int buf) { st_w.issue(smem, wave, buf, tile * 64, p.S, Kb, p.k_sl, Vb, p.v_sl); };
+  const int k_sw = dual_sw(fr), v_sw = SwRows<RB>::key(fr);
   unsigned k_lds[2][2];  // K^T fragment of d block n, rows t_row (+8), K ring buffer 0
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int row = t_row + 8 * u;
-      k_lds[n][u] = vy_lds_addr(smem) + row * RB + (((4 * n + t_chunk) ^ dual_sw(row)) << 4) + t_byte;
-    }
-
+  attn_tr_bases(k_lds, smem, ln);
   f32x16 dq[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq[n][r] = 0.f;
 
-  int nt = (p.S + 63) / 64;
-  if (causal) nt = max(1, min(nt, (min(p.S, p.start_pos + q0 + 128) + 63) / 64));
+  const int nt = blk.key_tiles(p, causal);
   const int wave_first = q0 + wave * 32, wave_last = wave_first + 31;
-
   unsigned long long* kpbits = reinterpret_cast<unsigned long long*>(smem + 2 * NS * TILE);
-  if (haskp) {
-    for (int t = wave; t < nt; t += 4) {
-      const int kj = t * 64 + lane;
-      const bool vis = kj < p.S && kp[kj < p.S ? kj : 0] != 0;
-      const unsigned long long bits = __ballot(vis);
-      if (lane == 0) kpbits[t] = bits;
-    }
-    __syncthreads();
-  }
+  if (haskp) attn_keypad_words(kpbits, kp, nt, p.S, ln);
 
   auto compute = [&](int tile, int buf) {
     const int k0 = tile * 64;
@@ -616,10 +519,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
     unsigned long long vis = ~0ull;
     if (haskp) vis = kpbits[tile];
     const bool need_mask = (k0 + 64 > p.S) || (causal && k0 + 63 > p.start_pos + wave_first) || vis != ~0ull;
-    // key of register r: k0 + 4fh + kofs, kofs = 32kb + (r&3) + 8(r>>2); visible iff kofs <= klim
-    int klim = p.S - 1 - k0 - 4 * fh;
-    if (causal) klim = min(klim, qi + p.start_pos - k0 - 4 * fh);
-    const unsigned long long lm = need_mask ? (range_bits64(0, klim + 1) & (vis >> (4 * fh))) : ~0ull;
+    const unsigned long long lm = need_mask ? attn_key_bits(k0, fh, p.S, causal, qi + p.start_pos, vis) : ~0ull;
     const unsigned lmw[2] = {(unsigned)lm, (unsigned)(lm >> 32)};
     // one 32-key block at a time: scores and dP of a block are turned into dS (8 registers) before the next block's
     // accumulators exist -- both blocks' st / dp tiles live at once cost 32 more registers, the difference between two
@@ -638,11 +538,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, gf[ks], dp, 0, 0, 0);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pr = __builtin_amdgcn_exp2f(fmaf(st[r], c, neg_lse));
-        pr = ((lmw[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u) ? pr : 0.f;
-        ds[kb][r >> 3][r & 7] = (bf16)(pr * dp[r]);
-      }
+      for (int r = 0; r < 16; ++r) ds[kb][r >> 3][r & 7] = (bf16)(attn_p<true>(st[r], c, neg_lse, lmw[kb], r) * dp[r]);
     }
     // dQ^T[d][q] += K^T[d][key] . dS^T[key][q]; K^T fragments by asm transposing reads, one ahead.
     // Base addresses per (d block, row / row+8); key block and k-step go into the offset field.
@@ -653,11 +549,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
       for (int u = 0; u < 2; ++u) kbase[n][u] = k_lds[n][u] + buf * TILE;
     auto kfrag = [&](auto f_c) {
       constexpr int f = decltype(f_c)::value;
-      constexpr int n = f >> 2, ro = (32 * ((f >> 1) & 1) + 16 * (f & 1)) * RB;
-      union { struct { s16x4 a, b; } s_; bf16x8 v; } u;
-      u.s_.a = vy_lds_tr16_off<ro>(kbase[n][0]);
-      u.s_.b = vy_lds_tr16_off<ro>(kbase[n][1]);
-      return u.v;
+      return attn_tr_frag<(32 * ((f >> 1) & 1) + 16 * (f & 1)) * RB>(kbase[f >> 2]);
     };
     bf16x8 kfr[2];
     kfr[0] = kfrag(std::integral_constant<int, 0>{});
@@ -674,36 +566,21 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
     vy_static_for<8>(step);
   };
 
-  // every ordinary load is retired before the first LDS-DMA (else the compiler's wait for it
-  // becomes a vmcnt(0) inside the loop and drains the ring every tile)
+  typedef AttnRing<NS, Stage::DMA> Ring;
 #pragma unroll
-  for (int s_ = 0; s_ < NS - 1; ++s_)
+  for (int s_ = 0; s_ < Ring::AHEAD; ++s_)
     if (s_ < nt) stage(s_, s_);
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) { vy_tie(qf[ks]); vy_tie(gf[ks]); }
+  for (int ks = 0; ks < 4; ++ks) { vy_tie(qf[ks]); vy_tie(gf[ks]); }   // retire the ordinary loads
   vy_tie(neg_lse); vy_tie(neg_delta);
   for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (t + NS - 1 < nt) stage(t + NS - 1, (t + NS - 1) % NS);
+    Ring::arrive(t, nt);
+    if (t + Ring::AHEAD < nt) stage(t + Ring::AHEAD, (t + Ring::AHEAD) % NS);
     compute(t, t % NS);
   }
   if (qi < p.L) {
     bf16* D = p.dq + (int64_t)b * p.dq_sb + (int64_t)head * p.dq_sh + (int64_t)qi * p.dq_sl;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      float lo[4], hi[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { lo[e] = dq[0][4 * rg + e] * p.scale; hi[e] = dq[1][4 * rg + e] * p.scale; }
-      if (p.cos_tab) rope_bwd_quad(p, (int64_t)p.rope_pos0 + qi, 8 * rg + 4 * fh, lo, hi);
-      bf16x4 wl, wh;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { wl[e] = (bf16)lo[e]; wh[e] = (bf16)hi[e]; }
-      *reinterpret_cast<bf16x4*>(D + 8 * rg + 4 * fh) = wl;
-      *reinterpret_cast<bf16x4*>(D + 32 + 8 * rg + 4 * fh) = wh;
-    }
+    attn_store_scaled_rope(D, dq, p.scale, p.cos_tab, p.sin_tab, (int64_t)p.rope_pos0 + qi, fh);
   }
 }
 
@@ -714,15 +591,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdParams p) {
 // through a 3-deep ring; the tile's row statistics (lse, -delta) ride along as one 4-byte-per-lane
 // LDS-DMA per wave, so the loop holds no ordinary load and is paced by counted vmcnt waits only.
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
-  constexpr int DH = 64, RB = 128, QR = 64, QT = QR * RB, NS = 3;  // one 64-row tile = 8 KiB
+  constexpr int DH = 64, RB = 128, QR = 64, NS = 3;
+  typedef AttnStage<RB, NS> Stage;
+  constexpr int QT = Stage::TILE;                                  // one 64-row tile = 8 KiB
   constexpr int ST_OFF = 2 * NS * QT;                              // NS x [lse 64 floats][-delta 64 floats]
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * QT + NS * 512];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const AttnLane ln;
+  const int lane = ln.lane, wave = ln.wave, fr = ln.fr, fh = ln.fh;
   // grid (hk*B, key blocks): key block 0 sees every query row under a causal mask -> all of them first
   const int kblk = blockIdx.y, kvh = (int)blockIdx.x % p.hk, b = (int)blockIdx.x / p.hk;
   const int n_rep = p.h / p.hk;
-  const int fr = lane & 31, fh = lane >> 5;
   const int key0 = kblk * 128 + wave * 32;
   const int kj = key0 + fr;                       // this lane's key (column of S)
   const int krow = kj < p.S ? kj : p.S - 1;
@@ -756,28 +634,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
   const int per_head = nqt > qt_first ? nqt - qt_first : 0;
   const int total = per_head * n_rep;
 
-  // LDS-DMA: tile = 8 pieces of 1 KiB; wave w loads pieces 2w, 2w+1 of the Q tile and of the dO tile
-  int ld_row[2], ld_eoff[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int P = (wave * 2 + t) * 1024 + lane * 16;
-    const int row = P / RB, off = P % RB;
-    ld_row[t] = row;
-    ld_eoff[t] = (((off >> 4) ^ dual_sw(row)) << 4) >> 1;
-  }
+  const Stage st_w(ln, SwDual{}, SwDual{});   // Q and dO: dual-use images
   const float* stat_src = (wave & 1) ? p.delta : p.lse;
   auto stage = [&](int it, int buf) {
     const int hh = it / per_head, qt = qt_first + (it - hh * per_head);
     const int head = kvh * n_rep + hh;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      int qr = qt * QR + ld_row[t];
-      qr = qr < p.L ? qr : p.L - 1;
-      const bf16* qs = p.q + (int64_t)b * p.q_sb + (int64_t)head * p.q_sh + (int64_t)qr * p.q_sl + ld_eoff[t];
-      const bf16* gs = p.dout + (int64_t)b * p.o_sb + (int64_t)qr * p.o_sl + head * DH + ld_eoff[t];
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)qs, (VY_LDS void*)(smem + buf * QT + (wave * 2 + t) * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const VY_GLOBAL void*)gs, (VY_LDS void*)(smem + (NS + buf) * QT + (wave * 2 + t) * 1024), 16, 0, 0);
-    }
+    st_w.issue(smem, wave, buf, qt * QR, p.L, p.q + (int64_t)b * p.q_sb + (int64_t)head * p.q_sh, p.q_sl,
+               p.dout + (int64_t)b * p.o_sb + head * DH, p.o_sl);
     // row statistics: even waves bring lse, odd waves -delta (both pairs write the same bytes)
     int sr = qt * QR + lane;
     sr = sr < p.L ? sr : p.L - 1;
@@ -785,18 +648,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
                                      (VY_LDS void*)(smem + ST_OFF + buf * 512 + (wave & 1) * 256), 4, 0, 0);
   };
   const int r_sw = dual_sw(fr);
-  const int li = lane & 15, g16 = (lane >> 4) & 1;
-  const int t_row = 4 * fh + (li >> 2);
-  const int t_chunk = 2 * g16 + ((li & 3) >> 1), t_byte = 8 * (li & 1);
   unsigned t_lds[2][2];  // transposed fragment of d block n, rows t_row (+8), ring buffer 0
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int row = t_row + 8 * u;
-      t_lds[n][u] = vy_lds_addr(smem) + row * RB + (((4 * n + t_chunk) ^ dual_sw(row)) << 4) + t_byte;
-    }
-
+  attn_tr_bases(t_lds, smem, ln);
   auto compute = [&](int it, int buf) {
     const int hh = it / per_head, qt = qt_first + (it - hh * per_head);
     const char* qb_ = smem + buf * QT;
@@ -843,15 +696,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
         rm = key_dead ? 0u : rm >> (4 * fh);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float pr = __builtin_amdgcn_exp2f(fmaf(st[r], c, nl[r]));
-          pr = ((rm >> ((r & 3) + 8 * (r >> 2))) & 1u) ? pr : 0.f;
+          const float pr = attn_p<true>(st[r], c, nl[r], rm, r);
           pf[r >> 3][r & 7] = (bf16)pr;
           dsf[r >> 3][r & 7] = (bf16)(pr * dp[r]);
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float pr = __builtin_amdgcn_exp2f(fmaf(st[r], c, nl[r]));
+          const float pr = attn_p<false>(st[r], c, nl[r], 0u, r);
           pf[r >> 3][r & 7] = (bf16)pr;
           dsf[r >> 3][r & 7] = (bf16)(pr * dp[r]);
         }
@@ -859,11 +711,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
       // dV^T[d][key] += dO^T[d][q] . P[q][key];   dK^T[d][key] += Q^T[d][q] . dS[q][key]
       auto frag = [&](auto f_c, const unsigned (&base)[2][2]) {
         constexpr int f = decltype(f_c)::value;
-        constexpr int n = f >> 1, ro = 16 * (f & 1) * RB;
-        union { struct { s16x4 a, b; } s_; bf16x8 v; } u;
-        u.s_.a = vy_lds_tr16_off<ro>(base[n][0] + 32 * blk * RB);
-        u.s_.b = vy_lds_tr16_off<ro>(base[n][1] + 32 * blk * RB);
-        return u.v;
+        return attn_tr_frag<16 * (f & 1) * RB>(base[f >> 1], 32 * blk * RB);
       };
       bf16x8 gfr[2], qfr[2];
       gfr[0] = frag(std::integral_constant<int, 0>{}, gbase);
@@ -884,36 +732,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(BwdParams p) {
     }
   };
 
+  typedef AttnRing<NS, Stage::DMA + 1> Ring;   // + the statistics rider
 #pragma unroll
-  for (int s_ = 0; s_ < NS - 1; ++s_)
+  for (int s_ = 0; s_ < Ring::AHEAD; ++s_)
     if (s_ < total) stage(s_, s_);
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) { vy_tie(kf[ks]); vy_tie(vf[ks]); }
+  for (int ks = 0; ks < 4; ++ks) { vy_tie(kf[ks]); vy_tie(vf[ks]); }   // retire the ordinary loads
   for (int it = 0; it < total; ++it) {
-    if (it + 1 < total) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (it + NS - 1 < total) stage(it + NS - 1, (it + NS - 1) % NS);
+    Ring::arrive(it, total);
+    if (it + Ring::AHEAD < total) stage(it + Ring::AHEAD, (it + Ring::AHEAD) % NS);
     compute(it, it % NS);
   }
   if (kj < p.S) {
     bf16* DK = p.dk + (int64_t)b * p.dk_sb + (int64_t)kvh * p.dk_sh + (int64_t)kj * p.dk_sl;
     bf16* DV = p.dv + (int64_t)b * p.dv_sb + (int64_t)kvh * p.dv_sh + (int64_t)kj * p.dv_sl;
+    attn_store_scaled_rope(DK, dk, p.scale, p.cos_tab, p.sin_tab, (int64_t)p.rope_pos0 + kj, fh);
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
-      float lo[4], hi[4];
+      bf16x4 vl, vh;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { lo[e] = dk[0][4 * rg + e] * p.scale; hi[e] = dk[1][4 * rg + e] * p.scale; }
-      if (p.cos_tab) rope_bwd_quad(p, (int64_t)p.rope_pos0 + kj, 8 * rg + 4 * fh, lo, hi);
-      bf16x4 wl, wh, vl, vh;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        wl[e] = (bf16)lo[e]; wh[e] = (bf16)hi[e];
-        vl[e] = (bf16)dv[0][4 * rg + e]; vh[e] = (bf16)dv[1][4 * rg + e];
-      }
-      *reinterpret_cast<bf16x4*>(DK + 8 * rg + 4 * fh) = wl;
-      *reinterpret_cast<bf16x4*>(DK + 32 + 8 * rg + 4 * fh) = wh;
+      for (int e = 0; e < 4; ++e) { vl[e] = (bf16)dv[0][4 * rg + e]; vh[e] = (bf16)dv[1][4 * rg + e]; }
       *reinterpret_cast<bf16x4*>(DV + 8 * rg + 4 * fh) = vl;
       *reinterpret_cast<bf16x4*>(DV + 32 + 8 * rg + 4 * fh) = vh;
     }
@@ -1128,6 +966,8 @@ extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, in
 //               dV^T += dO^T P, dK^T += Q^T dS
 // Rows without a visible key contribute nothing (as in the dh = 64 kernels).
 // ------------------------------------------------------------------------------------------
+namespace {
+
 template <int DHP>
 struct GenBwd {
   static constexpr int PITCH = (DHP + 8) * 2, KS = DHP / 32, NDB = DHP / 16, CPRW = DHP / 8, CPT = 64 * CPRW / 256;
@@ -1605,6 +1445,8 @@ __global__ __launch_bounds__(256) void attn_bwd_f32_dkdv_kernel(BwdParams p, int
   }
 }
 
+}  // namespace
+
 extern "C" int vy_attn_bwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sl, const void* k,
                            int64_t k_sb, int64_t k_sh, int64_t k_sl, const void* v, int64_t v_sb,
                            int64_t v_sh, int64_t v_sl, const void* out, const void* dout, int64_t o_sb,
@@ -1640,40 +1482,33 @@ extern "C" int vy_attn_bwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
   if ((cos_tab == nullptr) != (sin_tab == nullptr)) VY_FAIL(VY_ERR_ARG, "%s: cos/sin must both be given", who);
   p.cos_tab = cos_tab; p.sin_tab = sin_tab; p.rope_pos0 = (int)rope_pos0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == VY_F32) {
-    // the parity path: plain fp32 kernels (the BwdParams pointers are fp32 here), rotary inverse afterwards
-    const dim3 gq((unsigned)(h * B), (unsigned)((L + 15) / 16), 1), gk((unsigned)(hk * B), (unsigned)((S + 15) / 16), 1), block(256);
-    hipLaunchKernelGGL(attn_bwd_f32_dq_kernel, gq, block, 0, st, p, dh);
-    VY_CHECK_LAUNCH("vy_attn_bwd(dq)");
-    hipLaunchKernelGGL(attn_bwd_f32_dkdv_kernel, gk, block, 0, st, p, dh);
-    VY_CHECK_LAUNCH("vy_attn_bwd(dkdv)");
-    if (cos_tab) {
-      const int rc = vy_rope_fwd(dq, dq_sb, dq_sh, dq_sl, cos_tab, sin_tab, rope_pos0, B, h, L, dh, 1, dtype, stream);
-      if (rc != VY_OK) return rc;
-      return vy_rope_fwd(dk, dk_sb, dk_sh, dk_sl, cos_tab, sin_tab, rope_pos0, B, hk, S, dh, 1, dtype, stream);
+  if (dtype == VY_F32 || dh != 64) {
+    if (dtype == VY_F32) {
+      // the parity path: plain fp32 kernels (the BwdParams pointers are fp32 here)
+      const dim3 gq((unsigned)(h * B), (unsigned)((L + 15) / 16), 1), gk((unsigned)(hk * B), (unsigned)((S + 15) / 16), 1), block(256);
+      hipLaunchKernelGGL(attn_bwd_f32_dq_kernel, gq, block, 0, st, p, dh);
+      VY_CHECK_LAUNCH("vy_attn_bwd(dq)");
+      hipLaunchKernelGGL(attn_bwd_f32_dkdv_kernel, gk, block, 0, st, p, dh);
+      VY_CHECK_LAUNCH("vy_attn_bwd(dkdv)");
+    } else {
+      // other head widths: the general kernels
+      const dim3 gq((unsigned)(h * B), (unsigned)((L + 63) / 64), 1), gk((unsigned)(hk * B), (unsigned)((S + 63) / 64), 1), block(256);
+      if (dh <= 96) hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<96>, gq, block, 0, st, p, dh);
+      else if (dh <= 128) hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<128>, gq, block, 0, st, p, dh);
+      else hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<256>, gq, block, 0, st, p, dh);
+      VY_CHECK_LAUNCH("vy_attn_bwd(dq)");
+      if (dh <= 96) hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<96>, gk, block, 0, st, p, dh);
+      else if (dh <= 128) hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<128>, gk, block, 0, st, p, dh);
+      else hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<256>, gk, block, 0, st, p, dh);
+      VY_CHECK_LAUNCH("vy_attn_bwd(dkdv)");
     }
-    return VY_OK;
+    // neither family fuses the rotary inverse: dq, then dk, are rotated back afterwards
+    if (!cos_tab) return VY_OK;
+    const int rc = vy_rope_fwd(dq, dq_sb, dq_sh, dq_sl, cos_tab, sin_tab, rope_pos0, B, h, L, dh, 1, dtype, stream);
+    if (rc != VY_OK) return rc;
+    return vy_rope_fwd(dk, dk_sb, dk_sh, dk_sl, cos_tab, sin_tab, rope_pos0, B, hk, S, dh, 1, dtype, stream);
   }
-  if (dh != 64) {
-    // other head widths: the general kernels (no fused rotary inverse: dq / dk are rotated back afterwards)
-    const dim3 gq((unsigned)(h * B), (unsigned)((L + 63) / 64), 1), gk((unsigned)(hk * B), (unsigned)((S + 63) / 64), 1), block(256);
-    if (dh <= 96) hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<96>, gq, block, 0, st, p, dh);
-    else if (dh <= 128) hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<128>, gq, block, 0, st, p, dh);
-    else hipLaunchKernelGGL(attn_bwd_gen_dq_kernel<256>, gq, block, 0, st, p, dh);
-    VY_CHECK_LAUNCH("vy_attn_bwd(dq)");
-    if (dh <= 96) hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<96>, gk, block, 0, st, p, dh);
-    else if (dh <= 128) hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<128>, gk, block, 0, st, p, dh);
-    else hipLaunchKernelGGL(attn_bwd_gen_dkdv_kernel<256>, gk, block, 0, st, p, dh);
-    VY_CHECK_LAUNCH("vy_attn_bwd(dkdv)");
-    if (cos_tab) {
-      const int rc = vy_rope_fwd(dq, dq_sb, dq_sh, dq_sl, cos_tab, sin_tab, rope_pos0, B, h, L, dh, 1, dtype, stream);
-      if (rc != VY_OK) return rc;
-      return vy_rope_fwd(dk, dk_sb, dk_sh, dk_sl, cos_tab, sin_tab, rope_pos0, B, hk, S, dh, 1, dtype, stream);
-    }
-    return VY_OK;
-  }
-  // (delta = rowsum(dO * O) is computed by the dQ kernel for its own rows and left in delta_ws for the
-  // dK/dV kernel; attn_delta_kernel remains for reference)
+  // (delta = rowsum(dO * O) is computed by the dQ kernel for its own rows and left in delta_ws for the dK/dV kernel)
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((unsigned)(h * B), (unsigned)((L + 127) / 128), 1), dim3(256), 0, st, p);
   VY_CHECK_LAUNCH("vy_attn_bwd(dq)");
   hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3((unsigned)(hk * B), (unsigned)((S + 127) / 128), 1), dim3(256), 0, st, p);

@@ -402,8 +402,10 @@ def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tens
 
 def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, causal: bool, start_pos: int = 0,
                   keypad: Optional[Tensor] = None, scale: Optional[float] = None,
-                  cos: Optional[Tensor] = None, sin: Optional[Tensor] = None, rope_pos0: int = 0) -> None:
-    """Flash attention backward; dq/dk/dv are (B, heads, L|S, dh) views written in place."""
+                  cos: Optional[Tensor] = None, sin: Optional[Tensor] = None, rope_pos0: int = 0,
+                  delta: Optional[Tensor] = None) -> None:
+    """Flash attention backward; dq/dk/dv are (B, heads, L|S, dh) views written in place.  delta: optional (B, h, L)
+    fp32 workspace the dQ kernel leaves rowsum(dO * O) in (negated on the bf16 path) -- allocated here when None."""
     _need_gpu(q, k, v, out, dout, lse, dq, dk, dv, keypad)
     B, h, L, dh = q.shape
     hk, S = k.shape[1], k.shape[2]
@@ -411,7 +413,9 @@ def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, causal: bool, start_po
     if scale is None:
         scale = 1.0 / math.sqrt(dh)
     assert out.stride() == dout.stride() and out.stride(2) == 1
-    delta = torch.empty((B, h, L), dtype=torch.float32, device=q.device)
+    if delta is None:
+        delta = torch.empty((B, h, L), dtype=torch.float32, device=q.device)
+    assert delta.dtype == torch.float32 and delta.is_contiguous() and delta.shape == (B, h, L)
     call("vy_attn_bwd", q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
          k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
          v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
