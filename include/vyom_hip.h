@@ -143,6 +143,50 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
                    float scale, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Paged KV cache (Examples/simple_vllm.ipynb cell 2).  Per layer k_cache / v_cache are (max_blocks, block_size, hk, dh),
+ * contiguous; slot = block * block_size + offset.  block_size: a power of two from 8 to 256; dh: a multiple of 8 up to
+ * 256; bf16 and fp32.  Anything else is VY_ERR_ARG before a launch.  None of the three allocates.
+ *
+ * vy_paged_rope_write: after the packed QKV projection of a step's T tokens (qkv[T][ld], rows [q heads; k heads; v
+ *   heads] of dh columns): token t's q and k heads are rotated IN PLACE with row positions[t] (int32, device) of the
+ *   fp32 cos / sin tables [table_rows][dh/2] (rotate_half pairing d, d + dh/2, evaluated in fp32, one rounding), then its
+ *   rotated k heads and its v heads are stored into slot slot_mapping[t] (int64, device) of the pages.  A negative slot
+ *   (or one past the pages) writes nothing; a position outside the table is clamped into it.
+ *   replaces: apply_rope on q and k with the gathered metadata['cos'] / ['sin'] rows and the
+ *   `k_cache[b_idx, o_idx] = k`, `v_cache[b_idx, o_idx] = v` scatters of GroupedQueryAttention.forward.
+ *
+ * vy_attn_paged_decode: one query token per sequence against its pages.  q row of sequence b: q + row * q_ld with
+ *   row = q_rows ? q_rows[b] : b (int32, device), heads of dh columns side by side; out (row stride o_ld >= h * dh) is
+ *   written at the same rows.  block_table int32 [B][bt_stride] and seqlens int32 [B] live on the device; keys
+ *   [0, seqlens[b]) are attended, entries of the table at or past ceil(seqlen / block_size) are never read, seqlen 0
+ *   writes zeros.  max_seqlen (host, >= every seqlen) only sizes the launch.  n_split workgroups share a context
+ *   (0 = chosen from B, hk and max_seqlen); with more than one, fp32 partials go through ws (at least
+ *   vy_attn_paged_decode_ws_bytes of the same arguments; an automatic split without it runs unsplit).
+ *   Memory safety only, not a service to the caller: a seqlen above bt_stride * block_size is cut to it, a negative one
+ *   counts as 0, a block-table entry outside [0, max_blocks) is clamped into it -- all silently, the result is then
+ *   not meaningful.
+ *   replaces: flash_attn_with_kvcache(q.unsqueeze(1), k_cache, v_cache, cache_seqlens=..., block_table=...,
+ *   causal=True) in the same forward.
+ *
+ * vy_paged_gather: keys [0, S) of ONE sequence (block_table: its n_blocks entries, device) copied from the pages into
+ *   contiguous (hk, S, dh) buffers, K and V in one launch -- the keys of a prefill that starts from cached prefix blocks.
+ *   The rows of a block-table entry outside [0, max_blocks) are written as zeros (memory safety only, silently).
+ * ------------------------------------------------------------------------------------------ */
+int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
+                        const float* cos_tab, const float* sin_tab, int64_t table_rows, void* k_cache,
+                        void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh,
+                        int dtype, void* stream);
+int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* q_rows, const void* k_cache,
+                         const void* v_cache, int64_t max_blocks, int block_size,
+                         const int32_t* block_table, int64_t bt_stride, const int32_t* seqlens,
+                         int64_t max_seqlen, void* out, int64_t o_ld, int64_t B, int h, int hk, int dh,
+                         float scale, int n_split, void* ws, int64_t ws_bytes, int dtype, void* stream);
+int64_t vy_attn_paged_decode_ws_bytes(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split, int dtype);
+int vy_paged_gather(const void* k_cache, const void* v_cache, int64_t max_blocks, int block_size,
+                    const int32_t* block_table, int64_t n_blocks, int64_t S, void* k_out, void* v_out,
+                    int hk, int dh, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * vy_layernorm_fwd: y = (x - mean) * rstd * gamma + beta over the last dim (biased variance).
  * replaces: nn.LayerNorm in AttentionSelfOutput / FeedForward / LMHead
  *   (VyomAI/layers/attention.py:71, VyomAI/layers/ffn.py:39, VyomAI/models/decoder.py:270).

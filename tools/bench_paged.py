@@ -1,0 +1,175 @@
+"""Paged decode attention against the resident-context kernel on the same keys, and the continuous-batching engine against
+generate() on the same prompts.   python tools/bench_paged.py [--iters 1000] [--splits 1 2 4] [--skip-engine]
+
+Kernels: vy_attn_paged_decode (bf16, block_size 256, pages in shuffled physical order) and vy_attn_decode on the same keys
+in a contiguous (B, hk, S, dh) cache, each timed as a link of a captured chain of 50 calls, the chains replayed in turn;
+bytes = the K and V rows each has to read.
+dh = 128 at S = 4096 has no resident-context counterpart and is reported against the 1 GiB copy ceiling measured in the
+same run (vy_debug_copy, the probe behind bench.py --full).  Engine: 6 requests of mixed lengths, generated tokens per
+second, against generate() on the prompts left-padded into one batch that runs until its longest request is done.
+Prints one JSON line per measurement."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vyomai_amd as V  # noqa: E402
+from vyomai_amd import _lib, ops  # noqa: E402
+
+DEV, BF = "cuda", torch.bfloat16
+SHAPES = [  # B, h, hk, dh, S, has a contiguous counterpart
+    (32, 12, 12, 64, 640, True), (32, 12, 4, 64, 640, True), (8, 16, 8, 128, 512, True), (8, 16, 8, 128, 4096, False)]
+
+
+def timed(fns, warmup, iters):
+    """us per call of each fn with the host's launch cost in it (long kernels only)."""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    out = []
+    for f in fns:
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            f()
+        e.record()
+        torch.cuda.synchronize()
+        out.append(s.elapsed_time(e) * 1e3 / iters)
+    return out
+
+
+def timed_graph(fns, warmup, iters, reps=50):
+    """us per call of each fn as a link of a captured chain of `reps` calls (a Python call costs more host time than
+    these kernels take on the device); the chains of the fns are replayed in turn, iters / reps times each."""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    graphs = []
+    for f in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(reps):
+                f()
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    rounds = max(1, iters // reps)
+    total = [0.0] * len(fns)
+    for _ in range(rounds):
+        for i, g in enumerate(graphs):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            g.replay()
+            e.record()
+            torch.cuda.synchronize()
+            total[i] += s.elapsed_time(e)
+    return [t * 1e3 / (rounds * reps) for t in total]
+
+
+def copy_ceiling_gbs():
+    lib = _lib.load()
+    lib.vy_debug_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    n = 1 << 30
+    a = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    b = torch.empty_like(a)
+    st = torch.cuda.current_stream().cuda_stream
+    t, = timed([lambda: lib.vy_debug_copy(a.data_ptr(), b.data_ptr(), n, st)], 3, 10)
+    return 2.0 * n / t * 1e-3
+
+
+def bench_kernels(iters, splits=()):
+    ceiling = copy_ceiling_gbs()
+    print(json.dumps({"what": "copy ceiling", "GBs": round(ceiling, 1)}))
+    bs = 256
+    for B, h, hk, dh, S, dense in SHAPES:
+        g = torch.Generator().manual_seed(S + dh)
+        k = torch.randn(B, hk, S, dh, generator=g).to(BF).to(DEV)
+        v = torch.randn(B, hk, S, dh, generator=g).to(BF).to(DEV)
+        q = torch.randn(B, h * dh, generator=g).to(BF).to(DEV)
+        pages = (S + bs - 1) // bs
+        nblk = B * pages
+        table = torch.randperm(nblk, generator=g).to(torch.int32).view(B, pages)
+        kc = torch.zeros(nblk, bs, hk, dh, dtype=BF, device=DEV)
+        vc = torch.zeros_like(kc)
+        j = torch.arange(S)
+        slot = (table[:, j // bs].long() * bs + j % bs).to(DEV)                  # (B, S)
+        kc.view(-1, hk, dh)[slot] = k.permute(0, 2, 1, 3)
+        vc.view(-1, hk, dh)[slot] = v.permute(0, 2, 1, 3)
+        table, seqlens = table.to(DEV), torch.full((B,), S, dtype=torch.int32, device=DEV)
+        out = torch.empty(B, h * dh, dtype=BF, device=DEV)
+        q4 = q.view(B, h, 1, dh)
+        fns = [lambda: ops.attention_paged_decode(q, kc, vc, table, seqlens, S, h, out=out)]
+        for n in splits:
+            fns.append(lambda n=n: ops.attention_paged_decode(q, kc, vc, table, seqlens, S, h, out=out, n_split=n))
+        if dense:
+            fns.append(lambda: ops.attention_decode(q4, k, v, S))
+        t = timed_graph(fns, 20, iters)
+        nbytes = 2 * B * hk * S * dh * 2
+        ns = (_lib.load().vy_attn_paged_decode_ws_bytes(B, h, hk, dh, S, 0, 1) // (B * h * (dh + 2) * 4)) or 1
+        rec = {"what": "decode attention", "B": B, "h": h, "hk": hk, "dh": dh, "S": S, "n_split": ns,
+               "paged_us": round(t[0], 2), "paged_GBs": round(nbytes / t[0] * 1e-3, 1),
+               "paged_share_of_copy_ceiling": round(nbytes / t[0] * 1e-3 / ceiling, 3)}
+        for n, us in zip(splits, t[1:]):
+            rec[f"paged_n_split_{n}_us"] = round(us, 2)
+        if dense:
+            diff = (out.float() - ops.attention_decode(q4, k, v, S).view(B, -1).float()).abs().max().item()
+            rec.update(contiguous_us=round(t[-1], 2), ratio=round(t[0] / t[-1], 3), max_abs_diff=diff)
+        print(json.dumps(rec))
+
+
+def bench_engine():
+    cfg = V.Config(vocab_size=32000, hidden_size=896, intermediate_size=4864, num_hidden_layers=4,
+                   num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=1024, pad_token_id=0)
+    torch.manual_seed(0)
+    m = V.ModelForCausalLM(cfg).to(BF).to(DEV).eval()
+    g = torch.Generator().manual_seed(1)
+    plen, glen = [12, 40, 96, 24, 160, 64], [64, 32, 128, 16, 96, 48]
+    prompts = [torch.randint(3, cfg.vocab_size, (n,), generator=g).tolist() for n in plen]
+
+    def run_engine():
+        mgr = V.PagedKVManager(cfg, 64, 16, DEV, BF)
+        eng = V.ContinuousBatchEngine(m, mgr, max_batch_size=8, eos_token_ids=[])
+        for p, n in zip(prompts, glen):
+            eng.add_sequence(p, max_gen_len=n)
+        return eng.run()
+
+    def run_generate():
+        L = max(plen)
+        ids = torch.zeros((len(prompts), L), dtype=torch.long)
+        mask = torch.zeros_like(ids)
+        for r, p in enumerate(prompts):
+            ids[r, L - len(p):] = torch.tensor(p)
+            mask[r, L - len(p):] = 1
+        return m.generate(ids.to(DEV), attention_mask=mask.to(DEV), max_new_tokens=max(glen))
+
+    for name, fn in (("engine", run_engine), ("generate", run_generate)):
+        fn()                                   # warm-up: every shape of the run
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reps = 3
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        print(json.dumps({"what": name, "requests": len(prompts), "requested_tokens": sum(glen),
+                          "seconds": round(dt, 4), "requested_tokens_per_s": round(sum(glen) / dt, 1)}))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--skip-engine", action="store_true")
+    ap.add_argument("--splits", type=int, nargs="*", default=[], help="also time these pinned n_split values")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_paged.py needs the MI355X: there is nothing to time without it")
+    bench_kernels(a.iters, a.splits)
+    if not a.skip_engine:
+        bench_engine()

@@ -1,0 +1,445 @@
+// Paged KV cache (reference Examples/simple_vllm.ipynb cell 2): the per-token RoPE + scatter of a packed step's K/V rows
+// into pages, single-query attention through a block table, and the gather of one sequence's pages for a prefill that
+// starts from cached prefix blocks.  Cache layout per layer: k_cache / v_cache (max_blocks, block_size, hk, dh), contiguous;
+// slot s = block * block_size + offset names row s of the (max_blocks * block_size, hk, dh) view.
+//
+// vy_attn_paged_decode follows dec_attn_kernel's R > 1 case (vy_decode.hip): a workgroup serves the query heads of one KV
+// head from ONE read of its K/V rows, K/V go straight to registers, reductions stay on the DPP / permlane path
+// (vy_wave.h).  What differs: the context is not bounded, so a lane group walks its keys with an fp32 online softmax (a
+// running maximum per lane group, rescaled once per U keys, no cross-lane traffic inside the loop but the dot product's
+// group sum), and a long context is split over workgroups whose fp32 (m, l, o) partials a second small launch combines.
+#include "vy_common.h"
+#include "vy_wave.h"
+#include <float.h>
+
+namespace {
+
+constexpr int PD_NW = 4;          // waves per workgroup
+constexpr int PD_U = 4;           // keys per lane group and loop trip: 2 * U 16-byte loads in flight per lane
+constexpr int PD_MAX_SPLIT = 32;
+constexpr int PD_TARGET_WGS = 512;   // two workgroups per CU
+
+struct PagedDecArgs {
+  const void* q; long long q_ld; const int* q_rows;
+  const void* kc; const void* vc;
+  const int* bt; long long bt_stride; const int* seqlens;
+  void* out; long long o_ld;
+  float* ws_ml; float* ws_o;           // n_split > 1: [B][h][n_split]{m, l} and [B][h][n_split][dh]
+  int h, hk, dh, R, lbs, max_blocks, n_split;
+  float scale;
+};
+
+// lane = (key group g, 16-byte chunk ch of the head): LPK lanes per key (the chunks of the head, rounded up to a power of
+// two: lanes past the head's last chunk idle), KPW = 64 / LPK keys per wave instruction.  A wave takes CK = U * KPW
+// CONSECUTIVE keys per trip, aligned to CK: KPW divides every block_size (>= 8), so the keys of one wave instruction sit
+// in one page and the block-table entry is wave-uniform (a scalar load); where the whole trip sits in one page
+// (block_size >= CK) it is loaded once for the trip.  RT query heads per workgroup (R rounded up to 1, 2, 4 or 8; the
+// heads past R compute on head 0's query and store nothing).
+template <typename T, int LPK, int RT>
+__global__ __launch_bounds__(64 * PD_NW) void paged_dec_kernel(const PagedDecArgs p) {
+  using CH = Chunk<T>;
+  using Raw = typename CH::Raw;
+  constexpr int VEC = CH::VEC, NW = PD_NW, U = PD_U, KPW = 64 / LPK, CK = U * KPW, DHP = LPK * VEC;
+  __shared__ float red_m[RT][NW], red_l[RT][NW];
+  __shared__ float red_o[RT][NW][DHP];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z, split = blockIdx.y;
+  const int ngrp = (p.R + RT - 1) / RT;
+  const int kvh = (int)blockIdx.x / ngrp, r0 = ((int)blockIdx.x - kvh * ngrp) * RT;
+  const int nr = p.R - r0 < RT ? p.R - r0 : RT;
+  const int head0 = kvh * p.R + r0;
+  const int g = lane / LPK, ch = lane % LPK;
+  const int nch = p.dh / VEC;
+  const bool lane_on = ch < nch;
+  const int chc = lane_on ? ch : nch - 1;
+  const int bs = 1 << p.lbs;
+  int S = p.seqlens[b];
+  const long long cap = p.bt_stride << p.lbs;       // keys the row of the block table can name
+  if (S > cap) S = (int)cap;
+  const long long qr = p.q_rows ? p.q_rows[b] : b;
+  // this workgroup's keys [k0, k1): equal shares of the sequence, rounded up to whole trips
+  const int per = ((S + p.n_split - 1) / p.n_split + NW * CK - 1) / (NW * CK) * (NW * CK);
+  const int k0 = split * per;
+  const int k1 = k0 + per < S ? k0 + per : S;
+
+  const T* qb = (const T*)p.q + qr * p.q_ld + chc * VEC;
+  Raw q8[RT];
+#pragma unroll
+  for (int r = 0; r < RT; ++r) q8[r] = *reinterpret_cast<const Raw*>(qb + (long long)(head0 + (r < nr ? r : 0)) * p.dh);
+  const int* bt = p.bt + (long long)b * p.bt_stride;
+  const T* kc = (const T*)p.kc + (long long)kvh * p.dh + chc * VEC;
+  const T* vc = (const T*)p.vc + (long long)kvh * p.dh + chc * VEC;
+  const long long row_stride = (long long)p.hk * p.dh;
+
+  float m[RT], l[RT], acc[RT][VEC];
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    m[r] = -FLT_MAX; l[r] = 0.f;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[r][e] = 0.f;
+  }
+  if (k0 < k1) {
+    // the last wave instruction that holds a key of the range: later ones re-read its rows (never a row >= k1, never
+    // a block-table entry past the sequence's pages) and are masked
+    const int last_pb = (k1 - 1) & ~(KPW - 1);
+    for (int base = k0 + wave * CK; base < k1; base += NW * CK) {
+      int pbc[U], blk[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) pbc[u] = base + u * KPW < last_pb ? base + u * KPW : last_pb;
+      if ((pbc[0] >> p.lbs) == (pbc[U - 1] >> p.lbs)) {
+        const int e = bt[pbc[0] >> p.lbs];
+#pragma unroll
+        for (int u = 0; u < U; ++u) blk[u] = e;
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) blk[u] = bt[pbc[u] >> p.lbs];
+      }
+      Raw kr[U], vr[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e = blk[u] < 0 ? 0 : blk[u] < p.max_blocks ? blk[u] : p.max_blocks - 1;   // memory safety only
+        const int j = pbc[u] + g < k1 ? pbc[u] + g : k1 - 1;
+        const long long off = (((long long)e << p.lbs) + (j & (bs - 1))) * row_stride;
+        kr[u] = *reinterpret_cast<const Raw*>(kc + off);
+        vr[u] = *reinterpret_cast<const Raw*>(vc + off);
+      }
+      float kf[U][VEC], vf[U][VEC];
+      bool ok[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        CH::unpack(kr[u], kf[u]);
+        CH::unpack(vr[u], vf[u]);
+        ok[u] = base + u * KPW + g < k1;
+      }
+#pragma unroll
+      for (int r = 0; r < RT; ++r) {
+        float qf[VEC];
+        CH::unpack(q8[r], qf);
+        float sc[U], mx = m[r];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          float d = 0.f;
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) d = fmaf(qf[e], kf[u][e], d);
+          d = dec_group_sum<LPK>(lane_on ? d : 0.f) * p.scale;
+          sc[u] = ok[u] ? d : -FLT_MAX;
+          mx = fmaxf(mx, sc[u]);
+        }
+        const float alpha = __expf(m[r] - mx);
+        m[r] = mx;
+        l[r] *= alpha;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[r][e] *= alpha;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const float pv = ok[u] ? __expf(sc[u] - mx) : 0.f;
+          l[r] += pv;
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) acc[r][e] = fmaf(pv, vf[u][e], acc[r][e]);
+        }
+      }
+    }
+  }
+  // the lane groups of the workgroup to one (m, l, o) per head: maximum over the waves, every group rescaled to it
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    const float mw = dec_wave_max(m[r]);
+    if (lane == 0) red_m[r][wave] = mw;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    float M = red_m[r][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) M = fmaxf(M, red_m[r][w]);
+    const float f = __expf(m[r] - M);     // (a group without keys: l = 0 and o = 0, whatever f is)
+    const float lw = dec_wave_sum(ch == 0 ? l[r] * f : 0.f);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[r][e] = dec_stride_sum<LPK>(acc[r][e] * f);
+    if (lane == 0) red_l[r][wave] = lw;
+    if (g == 0) {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) red_o[r][wave][ch * VEC + e] = acc[r][e];
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < nr * p.dh; t += 64 * NW) {
+    const int r = t / p.dh, c = t - r * p.dh;
+    float M = red_m[r][0], L = 0.f, o = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { M = fmaxf(M, red_m[r][w]); L += red_l[r][w]; o += red_o[r][w][c]; }
+    const int head = head0 + r;
+    if (p.n_split == 1) {
+      VyT<T>::st((T*)p.out + qr * p.o_ld + (long long)head * p.dh + c, L > 0.f ? o / L : 0.f);   // seqlen 0: zeros
+    } else {
+      const long long idx = ((long long)b * p.h + head) * p.n_split + split;
+      p.ws_o[idx * p.dh + c] = o;
+      if (c == 0) { p.ws_ml[idx * 2] = M; p.ws_ml[idx * 2 + 1] = L; }
+    }
+  }
+}
+
+// out[b][head] = sum_s o_s e^(m_s - M) / sum_s l_s e^(m_s - M): one workgroup per (head, sequence)
+template <typename T>
+__global__ __launch_bounds__(64) void paged_combine_kernel(const float* __restrict__ ws_ml, const float* __restrict__ ws_o,
+                                                           T* __restrict__ out, long long o_ld,
+                                                           const int* __restrict__ q_rows, int n_split, int h, int dh) {
+  const int head = blockIdx.x, b = blockIdx.y;
+  const long long idx0 = ((long long)b * h + head) * n_split;
+  const long long qr = q_rows ? q_rows[b] : b;
+  float M = -FLT_MAX;
+  for (int s = 0; s < n_split; ++s) M = fmaxf(M, ws_ml[(idx0 + s) * 2]);
+  for (int c = threadIdx.x; c < dh; c += 64) {
+    float L = 0.f, o = 0.f;
+    for (int s = 0; s < n_split; ++s) {
+      const float f = __expf(ws_ml[(idx0 + s) * 2] - M);
+      L += ws_ml[(idx0 + s) * 2 + 1] * f;
+      o += ws_o[(idx0 + s) * dh + c] * f;
+    }
+    VyT<T>::st(out + qr * o_ld + (long long)head * dh + c, L > 0.f ? o / L : 0.f);
+  }
+}
+
+// four consecutive elements (8 bytes of bf16, 16 of fp32): half a head is a multiple of 4 elements, not of 8
+template <typename T> struct Quad;
+template <> struct Quad<float> {
+  static __device__ __forceinline__ void load(const float* p, float* v) { Chunk<float>::load(p, v); }
+  static __device__ __forceinline__ void store(float* p, const float* v) { Chunk<float>::store(p, v); }
+};
+template <> struct Quad<bf16> {
+  static __device__ __forceinline__ void load(const bf16* p, float* v) {
+    const bf16x4 t = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (float)t[e];
+  }
+  static __device__ __forceinline__ void store(bf16* p, const float* v) {
+    bf16x4 t;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[e] = (bf16)v[e];
+    *reinterpret_cast<bf16x4*>(p) = t;
+  }
+};
+
+// thread = (token, head of the packed row, 4 columns of the lower half and the same 4 of the upper half): q and k heads
+// are rotated in place with row positions[t] of the tables (the pairing d, d + dh/2 and the formula of rope2_kernel,
+// vy_misc.hip, evaluated in fp32 and rounded once), k and v heads are then stored into slot slot_mapping[t]
+template <typename T>
+__global__ __launch_bounds__(256) void paged_rope_write_kernel(T* __restrict__ qkv, long long ld,
+                                                               const int* __restrict__ positions,
+                                                               const long long* __restrict__ slots,
+                                                               const float* __restrict__ cos_tab,
+                                                               const float* __restrict__ sin_tab, long long table_rows,
+                                                               T* __restrict__ kc, T* __restrict__ vc, long long n_slots,
+                                                               long long total, int h, int hk, int dh) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int half = dh >> 1, qn = half >> 2, H3 = h + 2 * hk;
+  const int i4 = (int)(idx % qn) * 4;
+  const long long rest = idx / qn;
+  const int hd = (int)(rest % H3);
+  const long long t = rest / H3;
+  T* row = qkv + t * ld + (long long)hd * dh;
+  float lo[4], hi[4];
+  Quad<T>::load(row + i4, lo);
+  Quad<T>::load(row + half + i4, hi);
+  if (hd < h + hk) {
+    long long pos = positions[t];
+    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
+    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
+    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = lo[e], bb = hi[e];
+      lo[e] = a * c[e] - bb * s[e];
+      hi[e] = bb * c[e] + a * s[e];
+    }
+    Quad<T>::store(row + i4, lo);
+    Quad<T>::store(row + half + i4, hi);
+  }
+  if (hd < h) return;
+  const long long slot = slots[t];
+  if (slot < 0 || slot >= n_slots) return;
+  const bool isk = hd < h + hk;
+  T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
+  Quad<T>::store(dst + i4, lo);   // (k: the rotated values, rounded exactly as the in-place store rounds them)
+  Quad<T>::store(dst + half + i4, hi);
+}
+
+// thread = (K or V, key j, KV head, 16-byte chunk): out[kvh][j] = cache[block_table[j / block_size]][j % block_size][kvh]
+template <typename T>
+__global__ __launch_bounds__(256) void paged_gather_kernel(const T* __restrict__ kc, const T* __restrict__ vc,
+                                                           const int* __restrict__ bt, T* __restrict__ ko,
+                                                           T* __restrict__ vo, long long S, int lbs, int hk, int dh,
+                                                           int max_blocks) {
+  using CH = Chunk<T>;
+  const int nch = dh / CH::VEC;
+  const long long per = S * hk * nch;
+  long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= 2 * per) return;
+  const bool isv = idx >= per;
+  if (isv) idx -= per;
+  const int c = (int)(idx % nch);
+  const long long rest = idx / nch;
+  const int kvh = (int)(rest % hk);
+  const long long j = rest / hk;
+  const int blk = bt[j >> lbs];
+  typename CH::Raw v = {};
+  if (blk >= 0 && blk < max_blocks)
+    v = *reinterpret_cast<const typename CH::Raw*>((isv ? vc : kc) + ((((long long)blk << lbs) + (j & ((1 << lbs) - 1))) * hk + kvh) * dh + c * CH::VEC);
+  *reinterpret_cast<typename CH::Raw*>((isv ? vo : ko) + ((long long)kvh * S + j) * dh + c * CH::VEC) = v;
+}
+
+int log2_block_size(int block_size) {   // 8 .. 256, a power of two; else -1
+  for (int l = 3; l <= 8; ++l)
+    if (block_size == (1 << l)) return l;
+  return -1;
+}
+
+// lanes per key for a head width: the head's 16-byte chunks rounded up to a power of two, at least 8
+int pd_lpk(int dh, int dtype) {
+  const int nch = dh / (dtype == VY_BF16 ? 8 : 4);
+  int lpk = 8;
+  while (lpk < nch) lpk *= 2;
+  return lpk;
+}
+int pd_rt(int R) { return R > 4 ? 8 : R > 2 ? 4 : R; }
+
+// workgroups over the context.  A split costs a second, dependent launch: at 512-640 keys it added 1-5 us to a 10-12 us
+// unsplit call and never paid; at 4096 keys (dh = 128, 64 workgroups unsplit) it takes 68 us to 28-29 us (DESIGN.md,
+// "Paged KV cache": the table of tools/bench_paged.py --splits).  So only a context of 16 loop trips or more is split:
+// towards two workgroups per CU, at least 8 trips each.
+int pd_splits(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split, int dtype) {
+  if (n_split > 0) return n_split < PD_MAX_SPLIT ? n_split : PD_MAX_SPLIT;
+  const int R = h / hk, rt = pd_rt(R);
+  const int64_t wgs = B * hk * ((R + rt - 1) / rt);
+  const int64_t trip = (int64_t)PD_NW * PD_U * (64 / pd_lpk(dh, dtype));
+  if (max_seqlen < 16 * trip) return 1;
+  int64_t ns = PD_TARGET_WGS / wgs;
+  if (ns > max_seqlen / (8 * trip)) ns = max_seqlen / (8 * trip);
+  if (ns > PD_MAX_SPLIT) ns = PD_MAX_SPLIT;
+  return ns < 1 ? 1 : (int)ns;
+}
+
+template <typename T, int LPK>
+void paged_dec_launch(const PagedDecArgs& a, int64_t B, hipStream_t st) {
+  const int rt = pd_rt(a.R);
+  const dim3 grid((unsigned)(a.hk * ((a.R + rt - 1) / rt)), (unsigned)a.n_split, (unsigned)B), block(64 * PD_NW);
+  if (rt == 1) hipLaunchKernelGGL((paged_dec_kernel<T, LPK, 1>), grid, block, 0, st, a);
+  else if (rt == 2) hipLaunchKernelGGL((paged_dec_kernel<T, LPK, 2>), grid, block, 0, st, a);
+  else if (rt == 4) hipLaunchKernelGGL((paged_dec_kernel<T, LPK, 4>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((paged_dec_kernel<T, LPK, 8>), grid, block, 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int64_t vy_attn_paged_decode_ws_bytes(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split,
+                                                 int dtype) {
+  if (B <= 0 || h <= 0 || hk <= 0 || h % hk || dh <= 0 || dh % 8 || dh > 256 || n_split < 0) return 0;
+  const int ns = pd_splits(B, h, hk, dh, max_seqlen, n_split, dtype);
+  return ns == 1 ? 0 : B * h * ns * (int64_t)(dh + 2) * 4;
+}
+
+extern "C" int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* q_rows, const void* k_cache,
+                                    const void* v_cache, int64_t max_blocks, int block_size,
+                                    const int32_t* block_table, int64_t bt_stride, const int32_t* seqlens,
+                                    int64_t max_seqlen, void* out, int64_t o_ld, int64_t B, int h, int hk, int dh,
+                                    float scale, int n_split, void* ws, int64_t ws_bytes, int dtype, void* stream) {
+  if (!q || !k_cache || !v_cache || !block_table || !seqlens || !out) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: null operand");
+  const int lbs = log2_block_size(block_size);
+  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: block_size %d must be a power of two from 8 to 256", block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: dh %d must be a multiple of 8 up to 256", dh);
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: bad dtype %d", dtype);
+  const int vec = dtype == VY_BF16 ? 8 : 4;
+  if (B <= 0 || B > 65535 || h <= 0 || hk <= 0 || h % hk || max_blocks <= 0 || max_blocks > INT32_MAX || bt_stride <= 0 ||
+      max_seqlen < 0 || max_seqlen > (1 << 30) || n_split < 0 || q_ld % vec || o_ld < (int64_t)h * dh)
+    VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: bad shape (B %lld, h %d, hk %d, max_blocks %lld, bt_stride %lld, n_split %d)",
+            (long long)B, h, hk, (long long)max_blocks, (long long)bt_stride, n_split);
+  if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: q / caches must be 16-byte aligned");
+  int ns = pd_splits(B, h, hk, dh, max_seqlen, n_split, dtype);
+  const int64_t need = B * h * ns * (int64_t)(dh + 2) * 4;
+  if (ns > 1 && (!ws || ws_bytes < need)) {
+    if (n_split > 0) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: n_split %d needs %lld bytes of workspace", ns, (long long)need);
+    ns = 1;   // automatic split without scratch: one workgroup per (sequence, KV head)
+  }
+  PagedDecArgs a{q, q_ld, q_rows, k_cache, v_cache, block_table, bt_stride, seqlens, out, o_ld,
+                 (float*)ws, ws ? (float*)ws + B * h * ns * 2 : nullptr,
+                 h, hk, dh, h / hk, lbs, (int)max_blocks, ns, scale};
+  hipStream_t st = (hipStream_t)stream;
+  const int lpk = pd_lpk(dh, dtype);
+  if (dtype == VY_BF16) {
+    if (lpk == 8) paged_dec_launch<bf16, 8>(a, B, st);
+    else if (lpk == 16) paged_dec_launch<bf16, 16>(a, B, st);
+    else paged_dec_launch<bf16, 32>(a, B, st);
+  } else {
+    if (lpk == 8) paged_dec_launch<float, 8>(a, B, st);
+    else if (lpk == 16) paged_dec_launch<float, 16>(a, B, st);
+    else if (lpk == 32) paged_dec_launch<float, 32>(a, B, st);
+    else paged_dec_launch<float, 64>(a, B, st);
+  }
+  VY_CHECK_LAUNCH("vy_attn_paged_decode");
+  if (ns > 1) {
+    const dim3 grid((unsigned)h, (unsigned)B), block(64);
+    if (dtype == VY_BF16)
+      hipLaunchKernelGGL(paged_combine_kernel<bf16>, grid, block, 0, st, a.ws_ml, a.ws_o, (bf16*)out, o_ld, q_rows, ns, h, dh);
+    else
+      hipLaunchKernelGGL(paged_combine_kernel<float>, grid, block, 0, st, a.ws_ml, a.ws_o, (float*)out, o_ld, q_rows, ns, h, dh);
+    VY_CHECK_LAUNCH("vy_attn_paged_decode (combine)");
+  }
+  return VY_OK;
+}
+
+extern "C" int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
+                                   const float* cos_tab, const float* sin_tab, int64_t table_rows, void* k_cache,
+                                   void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh,
+                                   int dtype, void* stream) {
+  if (!qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !k_cache || !v_cache)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: null operand");
+  if (log2_block_size(block_size) < 0)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: block_size %d must be a power of two from 8 to 256", block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: dh %d must be a multiple of 8 up to 256", dh);
+  if (T <= 0 || h <= 0 || hk <= 0 || max_blocks <= 0 || table_rows <= 0 || ld < (int64_t)(h + 2 * hk) * dh)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: bad shape (T %lld, h %d, hk %d, ld %lld)", (long long)T, h, hk, (long long)ld);
+  if (ld % 4 || (((uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15))
+    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: ld must be a multiple of 4, operands 16-byte aligned");
+  const int64_t total = T * (h + 2 * hk) * (dh / 8);
+  const dim3 grid((unsigned)vy_cdiv(total, 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n_slots = max_blocks * block_size;
+  if (dtype == VY_BF16)
+    hipLaunchKernelGGL(paged_rope_write_kernel<bf16>, grid, block, 0, st, (bf16*)qkv, ld, positions,
+                       (const long long*)slot_mapping, cos_tab, sin_tab, table_rows, (bf16*)k_cache, (bf16*)v_cache, n_slots,
+                       total, h, hk, dh);
+  else if (dtype == VY_F32)
+    hipLaunchKernelGGL(paged_rope_write_kernel<float>, grid, block, 0, st, (float*)qkv, ld, positions,
+                       (const long long*)slot_mapping, cos_tab, sin_tab, table_rows, (float*)k_cache, (float*)v_cache,
+                       n_slots, total, h, hk, dh);
+  else VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: bad dtype %d", dtype);
+  VY_CHECK_LAUNCH("vy_paged_rope_write");
+  return VY_OK;
+}
+
+extern "C" int vy_paged_gather(const void* k_cache, const void* v_cache, int64_t max_blocks, int block_size,
+                               const int32_t* block_table, int64_t n_blocks, int64_t S, void* k_out, void* v_out,
+                               int hk, int dh, int dtype, void* stream) {
+  if (!k_cache || !v_cache || !block_table || !k_out || !v_out) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: null operand");
+  const int lbs = log2_block_size(block_size);
+  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: block_size %d must be a power of two from 8 to 256", block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: dh %d must be a multiple of 8 up to 256", dh);
+  if (S <= 0 || hk <= 0 || max_blocks <= 0 || max_blocks > INT32_MAX || S > n_blocks * block_size)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_gather: bad shape (S %lld, %lld blocks of %d, hk %d)", (long long)S, (long long)n_blocks, block_size, hk);
+  if (((uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_out | (uintptr_t)v_out) & 15)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_gather: operands must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == VY_BF16 ? 8 : 4;
+  const dim3 grid((unsigned)vy_cdiv(2 * S * hk * (dh / vec), 256)), block(256);
+  if (dtype == VY_BF16)
+    hipLaunchKernelGGL(paged_gather_kernel<bf16>, grid, block, 0, st, (const bf16*)k_cache, (const bf16*)v_cache, block_table,
+                       (bf16*)k_out, (bf16*)v_out, (long long)S, lbs, hk, dh, (int)max_blocks);
+  else if (dtype == VY_F32)
+    hipLaunchKernelGGL(paged_gather_kernel<float>, grid, block, 0, st, (const float*)k_cache, (const float*)v_cache,
+                       block_table, (float*)k_out, (float*)v_out, (long long)S, lbs, hk, dh, (int)max_blocks);
+  else VY_FAIL(VY_ERR_ARG, "vy_paged_gather: bad dtype %d", dtype);
+  VY_CHECK_LAUNCH("vy_paged_gather");
+  return VY_OK;
+}

@@ -459,6 +459,53 @@ class ModelForCausalLM(nn.Module):
         return losses.mean(), (pi_c - ref_c).detach().mean(), (pi_r - ref_r).detach().mean()
 
     @torch.no_grad()
+    def forward_paged(self, input_ids: torch.Tensor, positions: torch.Tensor, metadata: dict, kv_mgr) -> torch.Tensor:
+        """One step of the continuous-batching engine (serving.ContinuousBatchEngine) -> logits (sequences, vocab) of
+        the LAST row of each sequence.  input_ids (T,) are the step's packed tokens -- every unseen prompt token of a
+        prefilling sequence, one token of a decoding one -- positions (T,) int32 their positions, `metadata` what
+        ContinuousBatchEngine._prepare_inference_data built, kv_mgr the PagedKVManager whose pages are read and written.
+
+        Per layer: input_layernorm, the packed QKV projection, vy_paged_rope_write (per-token RoPE in place + the K/V
+        rows into their slots), attention -- vy_attn_paged_decode for the rows with one query token, causal vy_attn_fwd
+        per prefilling sequence (straight on its slice of the packed buffer, or with start_pos = prefix_len against its
+        gathered pages when it starts from cached prefix blocks) -- o_proj with the residual, post_attention_layernorm
+        and the MLP as in DecoderLayer.forward.  Every token attends to its sequence's whole cached context, also in a
+        step that mixes the two phases.  The final norm and the tied head see one row per sequence (the notebook of
+        Examples/simple_vllm.ipynb projects all T rows and then indexes)."""
+        _need_gpu(input_ids, "forward_paged()")
+        base = self.model
+        dev = input_ids.device
+        x = base._embed(base.embed_tokens, input_ids.view(1, -1))[0]
+        T, dt = x.shape[0], x.dtype
+        cos, sin = base._rope_slice(0, int(metadata["max_position"])).table.on(dev)
+        slots, dec = metadata["slot_mapping"], metadata["decode"]
+        for layer in base.layers[: self.config.num_hidden_layers]:
+            a = layer.self_attn
+            h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
+            kc, vc = kv_mgr.k_cache[a.layer_idx], kv_mgr.v_cache[a.layer_idx]
+            sw, sb = a._packed_shadow(dt)
+            qkv = ops.linear(layer.input_layernorm(x), sw, sb)
+            ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc)
+            o = torch.empty((T, h * dh), dtype=dt, device=dev)
+            if dec is not None:
+                ops.attention_paged_decode(qkv, kc, vc, dec["block_table"], dec["seqlens"], dec["max_seqlen"], h,
+                                           q_rows=dec["rows"], out=o)
+            for row0, rows, prefix_len, table in metadata["prefill"]:
+                seg = qkv[row0:row0 + rows]
+                q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)
+                if prefix_len:
+                    k3, v3 = ops.paged_gather(kc, vc, table, prefix_len + rows)
+                else:
+                    k3 = seg[:, h * dh:(h + hk) * dh].view(rows, hk, dh).permute(1, 0, 2)
+                    v3 = seg[:, (h + hk) * dh:].view(rows, hk, dh).permute(1, 0, 2)
+                ops.attention(q4, k3.unsqueeze(0), v3.unsqueeze(0), causal=True, start_pos=prefix_len,
+                              out=o[row0:row0 + rows].unsqueeze(0))
+            x = ops.linear(o, _shadow(a.o_proj.weight, dt), None, residual=x)
+            x = layer.mlp(layer.post_attention_layernorm(x), residual=x)
+        last = base.norm(x.index_select(0, metadata["last_rows"]))
+        return ops.linear(last, _shadow(self.lm_head.weight, dt))
+
+    @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                  max_new_tokens: int = 20, eos_token_id=None) -> torch.Tensor:
         """Greedy decoding -> (B, prompt + max_new_tokens) ids.  The prompt (left-padded when attention_mask says so) is

@@ -121,17 +121,23 @@ _WS = {}
 _WS_BYTES = 64 << 20
 
 
-def _mid_ws(rows: int) -> None:
-    """Mid-size GEMMs (32 < rows <= 4096) split K over workgroups and need scratch for their fp32 partial tiles
-    (vy_workspace_set: one buffer per stream, registered once; the library never allocates device memory)."""
-    if rows <= 32 or rows > 4096 or _Lanes.active:
-        return
+def _stream_ws() -> Tensor:
+    """The current stream's scratch buffer (vy_workspace_set: one per stream, registered once; the library never
+    allocates device memory).  Launches on one stream are ordered, so everything on it can share the buffer."""
     st = torch.cuda.current_stream()
     key = (st.device_index, st.cuda_stream)
     if key not in _WS:
         buf = torch.empty(_WS_BYTES, dtype=torch.uint8, device=torch.device("cuda", st.device_index))
         call("vy_workspace_set", st.cuda_stream, buf.data_ptr(), _WS_BYTES)
         _WS[key] = buf
+    return _WS[key]
+
+
+def _mid_ws(rows: int) -> None:
+    """Mid-size GEMMs (32 < rows <= 4096) split K over workgroups and need scratch for their fp32 partial tiles."""
+    if rows <= 32 or rows > 4096 or _Lanes.active:
+        return
+    _stream_ws()
 
 
 def _at(t: Optional[Tensor], first: int):
@@ -803,3 +809,91 @@ def gated_act_bwd(d_act: Tensor, gate_up: Tensor, act: int) -> Tensor:
     call("vy_gated_act_bwd", d2.data_ptr(), d2.stride(0), g2.data_ptr(), g2.stride(0), out.data_ptr(), out.stride(0),
          M, I, act, dtype_code(gate_up.dtype), _stream())
     return out.view(gate_up.shape)
+
+
+# ------------------------------------------------------------------------------------------
+# paged KV cache (vy_paged.hip)
+# ------------------------------------------------------------------------------------------
+
+
+def _check_pages(k_cache: Tensor, v_cache: Tensor, dtype) -> Tuple[int, int, int, int]:
+    """(max_blocks, block_size, hk, dh) of one layer's pages; the shape rules of include/vyom_hip.h as ValueErrors."""
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("k_cache / v_cache must be contiguous (max_blocks, block_size, hk, dh) tensors of one shape")
+    nb, bs, hk, dh = k_cache.shape
+    if bs < 8 or bs > 256 or bs & (bs - 1):
+        raise ValueError(f"block_size {bs} must be a power of two from 8 to 256")
+    if dh % 8 or dh > 256:
+        raise ValueError(f"head_dim {dh} must be a multiple of 8 up to 256")
+    if k_cache.dtype != dtype or v_cache.dtype != dtype:
+        raise ValueError(f"pages are {k_cache.dtype}, the step computes in {dtype}")
+    return nb, bs, hk, dh
+
+
+def paged_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos: Tensor, sin: Tensor, h: int,
+                      k_cache: Tensor, v_cache: Tensor) -> Tensor:
+    """qkv (T, (h + 2 hk) dh), the packed projection of a step's tokens: q and k heads of token t rotated in place with
+    row positions[t] (int32) of the fp32 cos / sin tables, the rotated k and the v stored into slot slot_mapping[t]
+    (int64; negative: nothing is stored) of the pages.  (vy_paged_rope_write)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype)
+    _need_gpu(qkv, positions, slot_mapping, cos, sin, k_cache, v_cache)
+    T = qkv.shape[0]
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (h + 2 * hk) * dh
+    assert positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == T
+    assert slot_mapping.dtype == torch.long and slot_mapping.is_contiguous() and slot_mapping.numel() == T
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == dh // 2 and sin.shape == cos.shape
+    call("vy_paged_rope_write", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
+         cos.data_ptr(), sin.data_ptr(), cos.shape[0], k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, T, h, hk, dh,
+         dtype_code(qkv.dtype), _stream())
+    return qkv
+
+
+def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, seqlens: Tensor,
+                           max_seqlen: int, h: int, *, q_rows: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                           n_split: int = 0, scale: Optional[float] = None) -> Tensor:
+    """One query token per sequence against its pages.  q (rows, >= h dh): sequence b's heads sit at row q_rows[b]
+    (int32; None: row b); block_table int32 (B, n), seqlens int32 (B,), keys [0, seqlens[b]) are attended.  out
+    (rows, h dh) is written at the same rows and returned.  n_split: workgroups per context (0: chosen by the library).
+    (vy_attn_paged_decode)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype)
+    _need_gpu(q, k_cache, v_cache, block_table, seqlens, q_rows, out)
+    B = seqlens.numel()
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= h * dh
+    assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1 \
+        and block_table.shape[0] == B
+    assert seqlens.dtype == torch.int32 and seqlens.is_contiguous()
+    assert max_seqlen <= block_table.shape[1] * bs
+    if q_rows is not None:
+        assert q_rows.dtype == torch.int32 and q_rows.is_contiguous() and q_rows.numel() == B
+    if out is None:
+        out = torch.empty((q.shape[0], h * dh), dtype=q.dtype, device=q.device)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h * dh and out.dtype == q.dtype
+    if scale is None:
+        scale = 1.0 / math.sqrt(dh)
+    code = dtype_code(q.dtype)
+    need = _lib.load().vy_attn_paged_decode_ws_bytes(B, h, hk, dh, int(max_seqlen), int(n_split), code)
+    ws = None
+    if need:      # split-KV partials: the stream's GEMM workspace (an automatic split that would not fit runs unsplit)
+        if need <= _WS_BYTES:
+            ws = _stream_ws()
+        elif n_split:
+            raise ValueError(f"n_split {n_split} needs {need} bytes of workspace, the stream's buffer has {_WS_BYTES}")
+    call("vy_attn_paged_decode", q.data_ptr(), q.stride(0), _ptr(q_rows), k_cache.data_ptr(), v_cache.data_ptr(), nb, bs,
+         block_table.data_ptr(), block_table.stride(0), seqlens.data_ptr(), int(max_seqlen), out.data_ptr(),
+         out.stride(0), B, h, hk, dh, float(scale), int(n_split), _ptr(ws), 0 if ws is None else ws.numel(), code,
+         _stream())
+    return out
+
+
+def paged_gather(k_cache: Tensor, v_cache: Tensor, block_table: Tensor, S: int) -> Tuple[Tensor, Tensor]:
+    """Keys [0, S) of one sequence (block_table: its int32 entries) from the pages -> contiguous k, v (hk, S, dh).
+    (vy_paged_gather)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, k_cache.dtype)
+    _need_gpu(k_cache, v_cache, block_table)
+    assert block_table.dtype == torch.int32 and block_table.dim() == 1 and block_table.is_contiguous()
+    assert 0 < S <= block_table.numel() * bs
+    k = torch.empty((hk, S, dh), dtype=k_cache.dtype, device=k_cache.device)
+    v = torch.empty_like(k)
+    call("vy_paged_gather", k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, block_table.data_ptr(), block_table.numel(),
+         S, k.data_ptr(), v.data_ptr(), hk, dh, dtype_code(k_cache.dtype), _stream())
+    return k, v

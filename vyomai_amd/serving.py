@@ -1,0 +1,334 @@
+"""Paged KV cache and continuous batching for ModelForCausalLM: the engine of the reference's
+Examples/simple_vllm.ipynb (its prefix-caching version) under the notebook's class names -- RadixNode, SequenceState,
+PagedKVManager, ContinuousBatchEngine -- serving this package's own model through vy_paged_rope_write,
+vy_attn_paged_decode, vy_paged_gather and vy_attn_fwd (ModelForCausalLM.forward_paged).  The notebook's Qwen3Model is a
+different network and is not reproduced; greedy decoding only.
+
+The bookkeeping (tokens, block tables, slot mappings, the radix tree, the queues) lives on the host: the manager and the
+scheduler run without a GPU, and a step uploads its packed metadata once and reads the step's ids back once.  Only the
+pages (PagedKVManager.k_cache / v_cache) live on `device`.
+
+Where this departs from the notebook:
+
+1. Mixed steps.  A step that holds prefilling AND decoding sequences is sent by the notebook through
+   flash_attn_varlen_func on the step's own q / k / v, so its decoding rows attend to themselves only.  Here every token
+   attends to its sequence's whole cached context (paged decode for the rows with one query token, vy_attn_fwd per
+   prefilling sequence).  Steps whose sequences are all in one phase are the same in both.
+2. A waiting request leaves nothing behind.  The notebook's get_prefix_blocks raises ref_count while the scheduler only
+   peeks at the head of the waiting room, and again on every later step.  Here match_prefix has no side effects and
+   acquire() counts the references when the request is admitted.
+3. At least one prompt token is computed: at most (len(prompt) - 1) // block_size blocks are matched.  A fully cached
+   prompt in the notebook has an empty query segment and no logits row.
+4. Evicting a block drops its subtree: the registrations of all descendants go with it and their blocks move from the
+   evictable queue to the free list (a holder of a child holds the whole chain, so every descendant has ref_count 0).
+   The notebook leaves block_to_node entries that point into a detached parent.
+5. Admission on the request's whole life.  A request enters when the blocks of prompt + max_gen_len (less the matched
+   ones) fit into what is free or evictable beyond what the running sequences may still claim, so a sequence the engine
+   admitted never meets "KV Cache full!" half way.  The notebook admits on the prompt's blocks alone and has no
+   preemption to recover with.  The price: a request that stops early on eos had blocks reserved that it never used,
+   which lowers concurrency when the cache is tight.
+
+As in the notebook: only blocks complete at allocation time (prompt blocks) are registered; free() moves registered
+blocks to the evictable queue and the others to the free list; eviction is oldest-first; RuntimeError("KV Cache full!")
+when nothing is free or evictable."""
+from __future__ import annotations
+
+import itertools
+from collections import deque
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+
+class RadixNode:
+    """One cached block: the block's id, its children keyed by their block_size token ids, the number of running
+    sequences that hold it.  `parent` / `key` are the way back up (the notebook keeps them in block_to_node)."""
+
+    def __init__(self, block_id: int, parent: Optional["RadixNode"] = None, key: Optional[tuple] = None):
+        self.block_id = block_id
+        self.children: Dict[tuple, "RadixNode"] = {}
+        self.ref_count = 0
+        self.parent, self.key = parent, key
+
+
+class SequenceState:
+    """Runtime state of one request: its tokens, the blocks that hold its keys (block_table) and the slot of every
+    token (slot_mapping), all on the host.  `prefix_len` tokens were found in the prefix cache and are not computed."""
+
+    def __init__(self, sid: int, prompt_ids: Sequence[int], max_gen_len: int, block_size: int, device="cpu",
+                 matched_blocks: Optional[Sequence[int]] = None):
+        self.id, self.device, self.block_size = sid, torch.device(device), block_size
+        matched_blocks = list(matched_blocks or [])
+        self.prefix_len = len(matched_blocks) * block_size
+        p_len = len(prompt_ids)
+        if p_len == 0 or self.prefix_len >= p_len:
+            raise ValueError("a sequence needs at least one prompt token to compute")
+        self.prompt_len = p_len
+        self.max_total_len = p_len + max_gen_len
+        self.tokens = torch.zeros(self.max_total_len, dtype=torch.long)
+        self.tokens[:p_len] = torch.as_tensor(list(prompt_ids), dtype=torch.long)
+        self.num_tokens, self.is_prefill = p_len, True
+        self.block_table = torch.zeros((self.max_total_len + block_size - 1) // block_size, dtype=torch.int32)
+        self.block_count = len(matched_blocks)
+        if matched_blocks:
+            self.block_table[:self.block_count] = torch.as_tensor(matched_blocks, dtype=torch.int32)
+        self.slot_mapping = torch.zeros(self.max_total_len, dtype=torch.long)
+
+    @property
+    def query_start(self) -> int:
+        """First token of this step's query rows: everything past the cached prefix while prefilling, then the last."""
+        return self.prefix_len if self.is_prefill else self.num_tokens - 1
+
+    def update_metadata(self) -> None:
+        """slot = block_table[i // block_size] * block_size + i % block_size for the tokens this step computes."""
+        idx = torch.arange(self.query_start, self.num_tokens)
+        self.slot_mapping[idx] = self.block_table[idx // self.block_size].long() * self.block_size + idx % self.block_size
+
+
+class PagedKVManager:
+    """The pages of every layer -- k_cache[i] / v_cache[i]: (max_blocks, block_size, num_key_value_heads, head_dim) on
+    `device` -- and who owns them: a free list, a radix tree over complete prompt blocks, and the queue of registered
+    blocks nobody holds (evictable, oldest first).  `config` is the model's Config (the notebook passes a dict)."""
+
+    def __init__(self, config, max_blocks: int, block_size: int, device="cpu", dtype=torch.float32):
+        if block_size < 8 or block_size > 256 or block_size & (block_size - 1):
+            raise ValueError(f"block_size {block_size} must be a power of two from 8 to 256")
+        if max_blocks < 1:
+            raise ValueError(f"max_blocks {max_blocks} must be positive")
+        self.config, self.max_blocks, self.block_size = config, max_blocks, block_size
+        self.device, self.dtype = torch.device(device), dtype
+        self.free_blocks = deque(range(max_blocks))
+        self.evictable_blocks: deque = deque()
+        self.radix_root = RadixNode(-1)
+        self.block_to_node: Dict[int, RadixNode] = {}
+        hk = config.num_key_value_heads
+        dh = getattr(config, "head_dim", config.hidden_size // config.num_attention_heads)
+        shape = (max_blocks, block_size, hk, dh)
+        self.k_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(config.num_hidden_layers)]
+        self.v_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(config.num_hidden_layers)]
+
+    def blocks_for(self, num_tokens: int) -> int:
+        return (num_tokens + self.block_size - 1) // self.block_size
+
+    # ---- prefix cache ----------------------------------------------------------------------------------------
+    def match_prefix(self, token_ids: Sequence[int]) -> List[int]:
+        """Block ids of the longest cached chain of whole blocks in front of token_ids, at most
+        (len - 1) // block_size of them (one token is always left to compute).  No side effects."""
+        bs, node, out = self.block_size, self.radix_root, []
+        for i in range((len(token_ids) - 1) // bs):
+            node = node.children.get(tuple(int(t) for t in token_ids[i * bs:(i + 1) * bs]))
+            if node is None:
+                break
+            out.append(node.block_id)
+        return out
+
+    def acquire(self, blocks: Sequence[int]) -> None:
+        """A sequence starts to hold these registered blocks."""
+        for b in blocks:
+            node = self.block_to_node[b]
+            if node.ref_count == 0:
+                self.evictable_blocks.remove(b)
+            node.ref_count += 1
+
+    def get_prefix_blocks(self, token_ids: Sequence[int]) -> List[int]:
+        """match_prefix + acquire: the notebook's call, for a caller that admits the request on the spot."""
+        blocks = self.match_prefix(token_ids)
+        self.acquire(blocks)
+        return blocks
+
+    def available(self, matched: Sequence[int] = ()) -> int:
+        """Blocks allocate() could hand out if `matched` were acquired first."""
+        held_back = sum(1 for b in matched if self.block_to_node[b].ref_count == 0)
+        return len(self.free_blocks) + len(self.evictable_blocks) - held_back
+
+    # ---- allocation ------------------------------------------------------------------------------------------
+    def allocate(self, state: SequenceState) -> None:
+        """Blocks for state.num_tokens tokens; a block whose tokens are all known now (a prompt block) is registered."""
+        bs = self.block_size
+        while state.block_count < self.blocks_for(state.num_tokens):
+            if not self.free_blocks:
+                if not self.evictable_blocks:
+                    raise RuntimeError("KV Cache full!")
+                self._evict(self.evictable_blocks.popleft())
+            new_block = self.free_blocks.popleft()
+            i = state.block_count
+            state.block_table[i] = new_block
+            if state.num_tokens >= (i + 1) * bs:
+                self._register_block(state, i, new_block)
+            state.block_count += 1
+
+    def _register_block(self, state: SequenceState, i: int, block_id: int) -> None:
+        """Block i of the sequence becomes a child of block i - 1's node, held once."""
+        if i and int(state.block_table[i - 1]) not in self.block_to_node:
+            return                       # the parent lost its registration: this block stays private
+        parent = self.block_to_node[int(state.block_table[i - 1])] if i else self.radix_root
+        key = tuple(state.tokens[i * self.block_size:(i + 1) * self.block_size].tolist())
+        if key in parent.children:
+            return                       # the same tokens were registered by a concurrent sequence: stays private
+        node = RadixNode(block_id, parent, key)
+        node.ref_count = 1
+        parent.children[key] = node
+        self.block_to_node[block_id] = node
+
+    def _evict(self, block_id: int) -> None:
+        """The block leaves the tree and becomes free; so does every block below it."""
+        node = self.block_to_node[block_id]
+        del node.parent.children[node.key]
+        stack = [node]
+        while stack:
+            n = stack.pop()
+            assert n.ref_count == 0, "a held block below an evicted one"
+            del self.block_to_node[n.block_id]
+            if n is not node:
+                self.evictable_blocks.remove(n.block_id)
+            self.free_blocks.append(n.block_id)
+            stack.extend(n.children.values())
+            n.children = {}
+
+    def free(self, state: SequenceState) -> None:
+        """The sequence lets go of its blocks: registered ones become evictable with their last holder, others free."""
+        for i in range(state.block_count):
+            b = int(state.block_table[i])
+            node = self.block_to_node.get(b)
+            if node is not None:
+                node.ref_count -= 1
+                if node.ref_count == 0:
+                    self.evictable_blocks.append(b)
+            else:
+                self.free_blocks.append(b)
+        state.block_count = 0
+
+
+class ContinuousBatchEngine:
+    """add_sequence() queues a request; step() admits what fits, runs ONE packed forward over every running sequence
+    (all unseen prompt tokens of the newly admitted ones, one token of the others), appends the greedy token to each and
+    returns the sequences that finished in this step as {sid: token list}.  Stop tokens: `eos_token_ids` (default: the
+    model config's eos_token_id); the notebook hard-codes Qwen's two ids.
+
+    prompt_tokens_computed[sid]: prompt tokens that went through the model (the rest came from the prefix cache).
+    record_logits=True keeps every step's last-row logits per sequence in `logits[sid]` (fp32, host): a debug aid."""
+
+    def __init__(self, model, kv_mgr: PagedKVManager, max_batch_size: int = 8, eos_token_ids=None,
+                 record_logits: bool = False):
+        self.model, self.kv_mgr = model, kv_mgr
+        if model is not None:
+            model.eval()
+        self.max_batch = max_batch_size
+        self.device = kv_mgr.device
+        if eos_token_ids is None:
+            eos = getattr(kv_mgr.config, "eos_token_id", None)
+            eos_token_ids = [] if eos is None else eos
+        self.eos_token_ids = set(eos_token_ids) if isinstance(eos_token_ids, (list, tuple, set)) else {int(eos_token_ids)}
+        self.active: Dict[int, SequenceState] = {}
+        self.waiting_room: deque = deque()
+        self.id_gen = itertools.count()
+        self.prompt_tokens_computed: Dict[int, int] = {}
+        self.record_logits = record_logits
+        self.logits: Dict[int, List[torch.Tensor]] = {}
+
+    def add_sequence(self, prompt_ids: Sequence[int], max_gen_len: int = 128) -> int:
+        prompt_ids = [int(t) for t in prompt_ids]
+        if not prompt_ids or max_gen_len < 1:
+            raise ValueError("a request needs a prompt and max_gen_len >= 1")
+        if self.kv_mgr.blocks_for(len(prompt_ids) + max_gen_len) > self.kv_mgr.max_blocks:
+            raise ValueError(f"{len(prompt_ids)} + {max_gen_len} tokens do not fit into {self.kv_mgr.max_blocks} blocks "
+                             f"of {self.kv_mgr.block_size}")
+        sid = next(self.id_gen)
+        self.waiting_room.append({"sid": sid, "prompt_ids": prompt_ids, "max_gen_len": max_gen_len})
+        return sid
+
+    def _try_schedule_waiting(self) -> None:
+        """Admit from the head of the waiting room while the batch has room and the head's whole life fits."""
+        mgr = self.kv_mgr
+        while self.waiting_room and len(self.active) < self.max_batch:
+            req = self.waiting_room[0]
+            matched = mgr.match_prefix(req["prompt_ids"])
+            need = mgr.blocks_for(len(req["prompt_ids"]) + req["max_gen_len"]) - len(matched)
+            claimed = sum(s.block_table.numel() - s.block_count for s in self.active.values())
+            if need > mgr.available(matched) - claimed:
+                break
+            self.waiting_room.popleft()
+            mgr.acquire(matched)
+            self.active[req["sid"]] = SequenceState(req["sid"], req["prompt_ids"], req["max_gen_len"], mgr.block_size,
+                                                    self.device, matched_blocks=matched)
+
+    def _prepare_inference_data(self, states: List[SequenceState]):
+        """-> (metadata, input_ids): the step's packed token ids and positions, their slots, and per phase what the
+        attention needs -- for the decoding sequences their rows, block tables and lengths, for each prefilling one
+        (first row, rows, prefix_len, its block table)."""
+        ids, pos, slots, cu, last = [], [], [], [0], []
+        dec_rows, dec_lens, dec_tables, prefill = [], [], [], []
+        width = max(s.block_table.numel() for s in states)
+        for s in states:
+            a, b = s.query_start, s.num_tokens
+            ids += s.tokens[a:b].tolist()
+            pos += range(a, b)
+            slots += s.slot_mapping[a:b].tolist()
+            table = s.block_table[:s.block_count].tolist()
+            if s.is_prefill:
+                prefill.append((cu[-1], b - a, a, table if a else None))
+            else:
+                dec_rows.append(cu[-1])
+                dec_lens.append(b)
+                dec_tables += table + [0] * (width - len(table))
+            cu.append(cu[-1] + b - a)
+            last.append(cu[-1] - 1)
+        # two uploads: everything int64 (ids | slots | last rows) and everything int32 (positions | decode rows |
+        # decode lengths | decode block tables | the block table of each prefill that starts from a cached prefix)
+        T, nd = cu[-1], len(dec_rows)
+        i32 = pos + dec_rows + dec_lens + dec_tables
+        for k, (row0, rows, prefix_len, table) in enumerate(prefill):
+            if table is not None:
+                prefill[k] = (row0, rows, prefix_len, (len(i32), len(table)))
+                i32 += table
+        l64 = torch.tensor(ids + slots + last, dtype=torch.long).to(self.device)
+        i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
+        prefill = [(r0, n, pl, None if t is None else i32[t[0]:t[0] + t[1]]) for r0, n, pl, t in prefill]
+        metadata = {
+            "positions": i32[:T],
+            "slot_mapping": l64[T:2 * T],
+            "last_rows": l64[2 * T:],
+            "max_position": max(s.num_tokens for s in states),
+            "prefill": prefill,
+            "decode": None,
+        }
+        if nd:
+            o = T + 2 * nd
+            metadata["decode"] = {"rows": i32[T:T + nd], "seqlens": i32[T + nd:o],
+                                  "block_table": i32[o:o + nd * width].view(nd, width), "max_seqlen": max(dec_lens)}
+        return metadata, l64[:T]
+
+    def step(self) -> Dict[int, List[int]]:
+        self._try_schedule_waiting()
+        if not self.active:
+            return {}
+        states = list(self.active.values())
+        for s in states:
+            self.kv_mgr.allocate(s)
+            s.update_metadata()
+            if s.is_prefill:
+                self.prompt_tokens_computed[s.id] = s.num_tokens - s.prefix_len
+        metadata, input_ids = self._prepare_inference_data(states)
+        logits = self.model.forward_paged(input_ids, metadata["positions"], metadata, self.kv_mgr)
+        next_tokens = torch.argmax(logits, dim=-1).tolist()          # the step's one device-to-host copy
+        if self.record_logits:
+            host = logits.float().cpu()
+            for i, s in enumerate(states):
+                self.logits.setdefault(s.id, []).append(host[i])
+        finished = {}
+        for s, token_id in zip(states, next_tokens):
+            s.is_prefill = False
+            s.tokens[s.num_tokens] = token_id
+            s.num_tokens += 1
+            if token_id in self.eos_token_ids or s.num_tokens >= s.max_total_len:
+                finished[s.id] = s.tokens[:s.num_tokens].tolist()
+                self.kv_mgr.free(s)
+                del self.active[s.id]
+        return finished
+
+    def run(self) -> Dict[int, List[int]]:
+        """step() until nothing is running or waiting -> every finished sequence."""
+        done = {}
+        while self.active or self.waiting_room:
+            done.update(self.step())
+        return done
