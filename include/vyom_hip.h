@@ -274,6 +274,19 @@ typedef struct vy_wgrad_desc {
 } vy_wgrad_desc;
 int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, int dtype, void* stream);
 
+/* The same launch with the column sums of up to 8 LayerNorm-backward slabs riding in it (n may be 0 when ncs > 0):
+ * out0[N] / out1[N] (fp32, added to when acc = 1, either may be NULL) = the column sums of the two [W, N] slabs
+ * vy_layernorm_bwd_partial left in ws, i.e. the dgamma / dbeta that vy_layernorm_bwd computes with two launches of
+ * its own per LayerNorm -- bit for bit, the summation order is the same.  bf16: extra workgroups of the grouped launch,
+ * on the CUs the weight-gradient tiles leave idle; fp32: the separate launches. */
+typedef struct vy_colsum_desc {
+  float* ws; int32_t W, N;
+  float* out0; float* out1;
+  int32_t acc;
+} vy_colsum_desc;
+int vy_linear_wgrad_grouped_cs(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs, int dtype,
+                               void* stream);
+
 /* LayerNorm backward: dx = rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma;
  * dgamma/dbeta fp32 [N] accumulated (beta) from per-block partials in `ws`
  * (ws: fp32, at least 2 * ws_rows * N elements; ws_rows = vy_layernorm_bwd_ws_rows(M)). */
@@ -282,6 +295,10 @@ int vy_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, c
                      const float* mean, const float* rstd, void* dx, int64_t lddx, float* dgamma,
                      float* dbeta, float beta, float* ws, int64_t M, int64_t N, int dtype,
                      void* stream);
+/* dx only: the per-block partials stay in ws ([2][ws_rows][N]) for vy_linear_wgrad_grouped_cs to sum. */
+int vy_layernorm_bwd_partial(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* gamma,
+                             const float* mean, const float* rstd, void* dx, int64_t lddx, float* ws, int64_t M,
+                             int64_t N, int dtype, void* stream);
 
 /* Flash attention backward.  dO/O are (B,L,h*dh) (strides {sb,sl}); dq/dk/dv use q/k/v layouts.
  * delta_ws: fp32 [B,h,L] scratch.  dk/dv are (B,hk,S,dh): the n_rep query heads of one kv head

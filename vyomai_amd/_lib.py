@@ -46,6 +46,8 @@ PROTOTYPES = {
     "vy_linear_dgrad": [_p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _p],
     "vy_linear_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _i64, _i, _p],
     "vy_linear_wgrad_grouped": [_p, _i, _i, _p],
+    "vy_linear_wgrad_grouped_cs": [_p, _i, _p, _i, _i, _p],
+    "vy_layernorm_bwd_partial": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i, _p],
     "vy_layernorm_bwd": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _f, _p, _i64, _i64, _i, _p],
     "vy_attn_bwd": [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64,
                     _p, _p, _i64, _i64, _p, _p,
@@ -94,6 +96,11 @@ class VyWgradDesc(C.Structure):
     """vy_wgrad_desc of include/vyom_hip.h."""
     _fields_ = [("dy", _p), ("lddy", _i64), ("x", _p), ("ldx", _i64), ("dw", _p), ("lddw", _i64), ("db", _p),
                 ("M", _i64), ("N", _i64), ("K", _i64)]
+
+
+class VyColsumDesc(C.Structure):
+    """vy_colsum_desc of include/vyom_hip.h."""
+    _fields_ = [("ws", _p), ("W", C.c_int32), ("N", C.c_int32), ("out0", _p), ("out1", _p), ("acc", C.c_int32)]
 
 
 class VyomHipError(RuntimeError):

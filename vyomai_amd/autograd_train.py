@@ -135,12 +135,14 @@ class _WgradGroup:
     and one at a time each needs M-splits -- fp32 atomic traffic -- to fill the chip.  They are collected
     here and go out as ONE launch per ~layer (vy_linear_wgrad_grouped); the parameters are reported ready
     (DDP buckets, per-bucket AdamW) when that launch has been enqueued.  Whatever is still pending when
-    the backward pass ends is flushed by an autograd-engine callback."""
+    the backward pass ends is flushed by an autograd-engine callback.
+    The column sums of a LayerNorm backward (dgamma, dbeta: two small launches of their own per LayerNorm) ride in the
+    same launch, on the CUs its tiles leave idle (add_colsum); a group may hold nothing else."""
 
     TILES = int(os.environ.get("VY_WGRAD_GROUP_TILES", "100"))   # flush once this many 256 x 256 output tiles are pending (one post-LN layer: 108)
 
     def __init__(self):
-        self.items, self.tiles, self.armed = [], 0, False
+        self.items, self.colsums, self.tiles, self.armed = [], [], 0, False
 
     def wants(self, dy, w, alpha) -> bool:
         if alpha is not None or not _GROUP_WGRADS:
@@ -160,18 +162,31 @@ class _WgradGroup:
         for p in members:
             p._vy_deferred = True
         self.tiles += -(-dw.shape[0] // 256) * -(-dw.shape[1] // 256)
-        if not self.armed:
-            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
-            self.armed = True
+        self._arm()
         if self.tiles >= self.TILES or len(self.items) == 8:
             self.flush()
 
+    def add_colsum(self, ws, dgamma, dbeta, members) -> None:
+        """ws: the slab ops.layernorm_bwd_partial left; dgamma / dbeta: the fp32 gradients its column sums are added to."""
+        self.colsums.append((ws, dgamma, dbeta, members))
+        for p in members:
+            p._vy_deferred = True
+        self._arm()
+        if len(self.colsums) == 8:
+            self.flush()
+
+    def _arm(self) -> None:
+        if not self.armed:
+            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
+            self.armed = True
+
     def flush(self) -> None:
-        items, self.items, self.tiles = self.items, [], 0
-        if not items:
+        items, colsums, self.items, self.colsums, self.tiles = self.items, self.colsums, [], [], 0
+        if not items and not colsums:
             return
-        ops.linear_wgrad_grouped([(dy, x, dw, db) for dy, x, dw, db, _ in items])
-        for *_, members in items:
+        ops.linear_wgrad_grouped([(dy, x, dw, db) for dy, x, dw, db, _ in items] +
+                                 [ops.ColSum(ws, dg, db, True, torch.bfloat16) for ws, dg, db, _ in colsums])
+        for *_, members in items + colsums:
             for p in members:
                 p._vy_deferred = False
             _notify(*members)
@@ -181,16 +196,17 @@ class _WgradGroup:
         self.flush()
 
     def discard(self) -> None:
-        for *_, members in self.items:
+        for *_, members in self.items + self.colsums:
             for p in members:
                 p._vy_deferred = False
-        self.items, self.tiles, self.armed = [], 0, False
+        self.items, self.colsums, self.tiles, self.armed = [], [], 0, False
 
 
 _GROUP_WGRADS = os.environ.get("VY_WGRAD_GROUP", "1") != "0"
 _DEFER_RESIDUALS = os.environ.get("VY_DEFER_RESIDUALS", "1") != "0"
 _GROUP_MIN_ROWS = int(os.environ.get("VY_WGRAD_GROUP_ROWS", "2048"))   # measured on configs[3] (2112 decoder rows): -6 %
 _GROUP_QKV = os.environ.get("VY_WGRAD_GROUP_QKV", "1") != "0"              # the packed QKV gradient joins the group
+_GROUP_LN_COLSUMS = os.environ.get("VY_LN_COLSUM_GROUP", "1") != "0"          # LayerNorm dgamma / dbeta sums join it too
 _wgrad_group = _WgradGroup()
 
 
@@ -212,6 +228,11 @@ def _wgrad(dy, x, w: torch.Tensor, b: Optional[torch.Tensor], alpha: Optional[to
 def _ln_bwd(dy, x, ln_w, ln_b, mean, rstd):
     dt = x.dtype
     if _direct(ln_w) and _direct(ln_b):
+        if (_GROUP_LN_COLSUMS and _GROUP_WGRADS and dt == torch.bfloat16
+                and x.numel() // x.shape[-1] >= _GROUP_MIN_ROWS):
+            dx, ws = ops.layernorm_bwd_partial(dy, x, _shadow(ln_w, dt), mean, rstd)
+            _wgrad_group.add_colsum(ws, ln_w.grad, ln_b.grad, [ln_w, ln_b])
+            return dx, None, None
         dx = ops.layernorm_bwd(dy, x, _shadow(ln_w, dt), mean, rstd, ln_w.grad, ln_b.grad, accumulate=True)
         _notify(ln_w, ln_b)
         return dx, None, None

@@ -19,6 +19,7 @@
 #include "vy_attn_tile.h"
 #include <float.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -399,9 +400,78 @@ struct WgradItem {
 };
 struct WgradGroup { WgradItem g[8]; int n; };
 
+// Column sums of LayerNorm-backward slabs riding in the same launch (vy_linear_wgrad_grouped_cs): a layer's grouped
+// launch fills 216 of 256 CUs, and its two LayerNorms' dgamma / dbeta -- 2 x 512 x 768 floats each -- were two launches of
+// their own per LayerNorm.  The workgroups behind the `items` weight-gradient ones each take a 64-column block of one
+// slab pair, all slices of it, in the summation order of vy_ln_colsum_slices (vy_common.h).
+struct ColsumItem { const float* ws; float* out0; float* out1; int W, N, rps, acc, blk0; };   // blk0: first block of this slab
+struct ColsumGroup { ColsumItem c[8]; int n; int items; };
+
+// 512 threads: column c = tid & 63, row group g = (tid >> 6) & 3, and the two halves of the workgroup take the even and
+// the odd slices, so two slices' rows are in flight at once
+__device__ __forceinline__ void colsum_slab_block(const ColsumItem& it, int blk) {
+  __shared__ float red[2][2][4][64];
+  const int tid = threadIdx.x;
+  const int c = tid & 63, g = (tid >> 6) & 3, h = tid >> 8;
+  const int n = blk * 64 + c;
+  const int W = it.W, N = it.N, rps = it.rps;
+  const float* __restrict__ ws = it.ws;
+  const bool one = rps >= W;   // one slice: its sum is the result (no 0 + sum)
+  float ta = 0.f, tb = 0.f;
+  for (int s0 = 0; s0 * rps < W; s0 += 2) {
+    const int w0 = (s0 + h) * rps, w1 = min(W, w0 + rps);
+    float a = 0.f, b = 0.f;
+    if (n < N) {
+      for (int wb = w0 + g; wb < w1; wb += 32) {
+        float av[8], bv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int w = wb + 4 * i;
+          const int wc = w < w1 ? w : wb;
+          av[i] = ws[(int64_t)wc * N + n];
+          bv[i] = ws[(int64_t)(W + wc) * N + n];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          if (wb + 4 * i < w1) { a += av[i]; b += bv[i]; }
+      }
+    }
+    red[h][0][g][c] = a; red[h][1][g][c] = b;
+    __syncthreads();
+    if (tid < 64) {
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+        if ((s0 + hh) * rps < W) {
+          const float sa = red[hh][0][0][c] + red[hh][0][1][c] + red[hh][0][2][c] + red[hh][0][3][c];
+          const float sb = red[hh][1][0][c] + red[hh][1][1][c] + red[hh][1][2][c] + red[hh][1][3][c];
+          ta = one ? sa : ta + sa;
+          tb = one ? sb : tb + sb;
+        }
+    }
+    __syncthreads();
+  }
+  if (tid < 64 && n < N) {
+    if (it.out0) it.out0[n] = (it.acc ? it.out0[n] : 0.f) + ta;
+    if (it.out1) it.out1[n] = (it.acc ? it.out1[n] : 0.f) + tb;
+  }
+}
+
 template <int BN, int BKW, int MS, int NS, bool MF16>
-__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, int diag) {
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
+__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, ColsumGroup cs, int diag) {
+  if ((int)blockIdx.x >= cs.items) {   // (workgroup-uniform) the column-sum workgroups: dispatched last, onto the idle CUs
+    const int blk = (int)blockIdx.x - cs.items;
+    int d = 0;
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+      if (i < cs.n && blk >= cs.c[i].blk0) d = i;
+    ColsumItem it = cs.c[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+      if (d == i) it = cs.c[i];
+    colsum_slab_block(it, blk - it.blk0);
+    return;
+  }
+  const int id = xcd_remap(blockIdx.x, cs.items);
   int d = 0;
 #pragma unroll
   for (int i = 1; i < 8; ++i)
@@ -910,11 +980,17 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
   return VY_OK;
 }
 
-extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, int dtype, void* stream) {
-  const char* who = "vy_linear_wgrad_grouped";
+static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
+                        int dtype, void* stream) {
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "%s: bad dtype %d", who, dtype);
-  if (!descs || n <= 0 || n > 8) VY_FAIL(VY_ERR_ARG, "%s: 1..8 descriptors", who);
+  if (n < 0 || n > 8 || (n > 0 && !descs) || ncs < 0 || ncs > 8 || (ncs > 0 && !cs) || n + ncs == 0)
+    VY_FAIL(VY_ERR_ARG, "%s: 1..8 descriptors", who);
+  for (int i = 0; i < ncs; ++i)
+    if (!cs[i].ws || cs[i].W <= 0 || cs[i].N <= 0 || (cs[i].acc != 0 && cs[i].acc != 1))
+      VY_FAIL(VY_ERR_ARG, "%s: column-sum descriptor %d: bad arguments", who, i);
   if (dtype == VY_F32) {   // the parity path: one plain launch per descriptor
+    for (int i = 0; i < ncs; ++i)
+      if (int rc = vy_ln_colsum(cs[i].ws, cs[i].W, cs[i].N, cs[i].out0, cs[i].out1, cs[i].acc, (hipStream_t)stream)) return rc;
     for (int i = 0; i < n; ++i) {
       const vy_wgrad_desc& d = descs[i];
       if (!d.dy || !d.x || !d.dw || d.M <= 0 || d.N <= 0 || d.K <= 0) VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: bad arguments", who, i);
@@ -932,12 +1008,13 @@ extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, in
   }
   static const int tgt = wgrad_env("VY_WGRAD_GROUP_TARGET", 256);
   WgradGroup grp;
+  memset(&grp, 0, sizeof(grp));   // (n == 0: column sums only)
   grp.n = n;
   int64_t items = 0;
   for (int i = 0; i < n; ++i) {
     const vy_wgrad_desc& d = descs[i];
     const int64_t tiles_k = vy_cdiv(d.K, 256), tiles = vy_cdiv(d.N, 256) * tiles_k;
-    const WgradSplit sp = wgrad_split(d.M, tgt / tiles_total);   // at most one round of workgroups
+    const WgradSplit sp = wgrad_split(d.M, tgt / tiles_total);   // at most one round of workgroups (the column sums do not count: they are short)
     WgradItem& it = grp.g[i];
     it.dY = (const bf16*)d.dy; it.X = (const bf16*)d.x; it.dW = d.dw; it.db = d.db;
     it.lddy = d.lddy; it.ldx = d.ldx; it.lddw = d.lddw;
@@ -946,10 +1023,32 @@ extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, in
     items += tiles * sp.splits;
   }
   for (int i = n; i < 8; ++i) grp.g[i] = grp.g[0];
+  ColsumGroup cg;
+  memset(&cg, 0, sizeof(cg));
+  cg.n = ncs; cg.items = (int)items;
+  int64_t blocks = 0;
+  for (int i = 0; i < ncs; ++i) {
+    ColsumItem& c = cg.c[i];
+    c.ws = cs[i].ws; c.out0 = cs[i].out0; c.out1 = cs[i].out1;
+    c.W = cs[i].W; c.N = cs[i].N; c.acc = cs[i].acc;
+    c.rps = (int)vy_cdiv(c.W, vy_ln_colsum_slices(c.W));
+    c.blk0 = (int)blocks;
+    blocks += vy_cdiv(c.N, 64);
+  }
   auto kernel = wgrad_m16() ? wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, true> : wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)items), dim3(512), 0, (hipStream_t)stream, grp, wgrad_diag());
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(items + blocks)), dim3(512), 0, (hipStream_t)stream, grp, cg, wgrad_diag());
   VY_CHECK_LAUNCH(who);
   return VY_OK;
+}
+
+extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, int dtype, void* stream) {
+  if (!descs || n <= 0 || n > 8) VY_FAIL(VY_ERR_ARG, "vy_linear_wgrad_grouped: 1..8 descriptors");
+  return wgrad_grouped("vy_linear_wgrad_grouped", descs, n, nullptr, 0, dtype, stream);
+}
+
+extern "C" int vy_linear_wgrad_grouped_cs(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
+                                          int dtype, void* stream) {
+  return wgrad_grouped("vy_linear_wgrad_grouped_cs", descs, n, cs, ncs, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------

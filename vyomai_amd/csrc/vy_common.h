@@ -102,6 +102,13 @@ void vy_set_error(const char* fmt, ...);
 
 static inline int64_t vy_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The column sums of a LayerNorm-backward slab of WB rows (dgamma, dbeta): WB is cut into this many row slices, a slice
+// is summed per row group g = 0..3 over rows w0 + g, w0 + g + 4, ..., the groups as ((p0 + p1) + p2) + p3, the slices
+// in slice order.  vy_ln_colsum (vy_misc.hip) does it in launches of its own, the grouped weight-gradient launch
+// (vy_bwd.hip) in spare workgroups -- in the same order, so both give the same bits.
+static inline int vy_ln_colsum_slices(int WB) { return WB >= 64 ? 16 : 1; }
+int vy_ln_colsum(float* ws, int WB, int N, float* dgamma, float* dbeta, int acc, hipStream_t st);
+
 // 16 zero bytes: source for out-of-range chunks of LDS-DMA loads (one copy per translation unit:
 // the library is built without relocatable device code).
 static __device__ __attribute__((aligned(16))) uint32_t vy_zero16[4] = {0, 0, 0, 0};

@@ -85,6 +85,7 @@ struct EpiPlain {
   int wt_store; // large outputs: write-through (sc1) stores from the staged epilogue
   int pre_deriv; // VY_ACT_SAVE_DERIV: `pre` receives act'(x W^T + b) / `gradpre` already holds act' (see include/vyom_hip.h)
   int act;       // the vy_act code, read by the ACT == VY_ACT_RUNTIME instantiations only (vy_act_dispatch)
+  int pf2;       // staged epilogue: request every second operand of a whole tile before its store loop (g_epi_prefetch)
 };
 
 template <typename T, int ACT, bool GRAD>
@@ -317,9 +318,16 @@ constexpr int VY_KNOB_NO_BAND = 32;   // tile_of: the plain XCD run instead of t
 // same-process A/B timing; not part of include/vyom_hip.h).  -1 = the default selection.
 int g_chains = 1;   // vy_set_concurrent_chains: launch chains the caller runs side by side
 int g_gemm_variant = -2;
+// VY_EPI_PREFETCH at first use, or vy_debug_set_epilogue_prefetch(): 0 = the staged epilogue loads its second operands
+// inside the store loop (A/B timing and tests; not part of include/vyom_hip.h)
+int g_epi_prefetch = -2;
 inline bool vy_m16_on() {   // VY_GEMM_M16=0: the two-stage 32 x 32 x 16 kernels instead of the 16 x 16 x 32 defaults
   static const int v = [] { const char* e = getenv("VY_GEMM_M16"); return e ? atoi(e) : 1; }();
   return v != 0;
+}
+inline int vy_epi_prefetch() {
+  if (g_epi_prefetch == -2) { const char* e = getenv("VY_EPI_PREFETCH"); g_epi_prefetch = e ? (atoi(e) != 0) : 1; }
+  return g_epi_prefetch;
 }
 inline int vy_gemm_variant() {
   if (g_gemm_variant == -2) { const char* e = getenv("VY_GEMM_VARIANT"); g_gemm_variant = e ? atoi(e) : -1; }
@@ -473,14 +481,18 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
     // dgrad) was requested BEFORE the accumulators were staged and is handed in as p8 -- loaded here, inside the
     // loop, every iteration waits a full memory latency for it (the residual epilogue measured 22 k cycles per
     // tile against 12 k without the residual)
+    // pf2: the operands pf does not cover -- the residual of a dgrad that also has a saved tensor (rb) and the second
+    // residual (rc) -- were requested after the staging, see below.  fast: the tile is whole and vectorisable
+    // (workgroup-uniform), so the chunk needs no bounds checks and no element-wise tail
     const bf16* pf_ptr = GRAD ? (ep.gradpre ? ep.gradpre : ep.residual) : ep.residual;
     const int64_t pf_ld = GRAD ? (ep.gradpre ? ep.ldg : ep.ldr) : ep.ldr;
     const bool pf_is_gradpre = GRAD && ep.gradpre != nullptr;
-    auto do_chunk = [&](bf16* __restrict__ dst, bool dual, int pass, int c, bool pf, const bf16x8& p8) {
+    auto do_chunk = [&](bf16* __restrict__ dst, bool dual, int pass, int c, bool pf, const bf16x8& p8, bool pf2,
+                        const bf16x8& rb, const bf16x8& rc, bool fast) __attribute__((always_inline)) {
         const int row = c / CPR, cc = c - row * CPR;
         const int64_t m = m0 + pass * RP + row;
         const int n = n0 + cc * 8;
-        if (m >= M || n >= N) return;
+        if (!fast && (m >= M || n >= N)) return;
         const bf16x8 sv = *reinterpret_cast<const bf16x8*>(et + row * EROW + cc * 16);
         float v[8];
 #pragma unroll
@@ -504,7 +516,7 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
             for (int e = 0; e < 8; ++e) v[e] = vy_drop_keep(ep.drop, lots, e) ? v[e] * ep.drop.scale : 0.f;
           }
         }
-        if (ep.vec_ok && n + 8 <= N) {
+        if (fast || (ep.vec_ok && n + 8 <= N)) {
           if constexpr (GRAD) {
             if (ep.gradpre) {
               const bf16x8 g = pf ? p8 : *reinterpret_cast<const bf16x8*>(ep.gradpre + m * ep.ldg + n);
@@ -513,12 +525,13 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
             }
           }
           if (ep.residual) {
-            const bf16x8 r = (pf && !pf_is_gradpre) ? p8 : *reinterpret_cast<const bf16x8*>(ep.residual + m * ep.ldr + n);
+            const bf16x8 r = (pf && !pf_is_gradpre) ? p8
+                             : (pf2 && GRAD) ? rb : *reinterpret_cast<const bf16x8*>(ep.residual + m * ep.ldr + n);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
           }
           if (ep.residual2) {
-            const bf16x8 r = *reinterpret_cast<const bf16x8*>(ep.residual2 + m * ep.ldr2 + n);
+            const bf16x8 r = pf2 ? rc : *reinterpret_cast<const bf16x8*>(ep.residual2 + m * ep.ldr2 + n);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
           }
@@ -544,36 +557,80 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
           }
         }
     };
-    constexpr bool PFK = PF_OK && PASSES == 1 && BM * BN == 256 * 192 && (RP * CPR) % NT == 0;   // kernels that prefetch (the 256 x 256 tile has no registers to spare: +5 % on FFN1 with them reserved)
-    constexpr int ITERS = PFK ? (RP * CPR) / NT : 1;
-    bf16x8 pre8[ITERS];
-    const bool pf_on = PFK && pf_ptr != nullptr && ep.vec_ok && m0 + BM <= M && n0 + BN <= N;   // workgroup-uniform
+    constexpr bool PFK = PF_OK && PASSES == 1 && BM * BN == 256 * 192 && (RP * CPR) % NT == 0;   // kernels that prefetch BEFORE the staging (the 256 x 256 tile has no registers to spare: +5 % on FFN1 with them reserved)
+    // Every other second operand of a whole tile is requested AFTER the staging, when the accumulator registers are
+    // dead: all ITERS chunks of each operand present, in one batch, before the barrier.  Loaded inside the store loop
+    // instead, every chunk is a load, s_waitcnt vmcnt(0) -- which also drains the store before it -- and a store: one
+    // memory round trip per 16 bytes and thread, 12-16 of them per tile.  The arithmetic per element is the same.
+    // (not with the tanh GELU or the run-time activation: their chunk body is too large for the loop to unroll fully, and
+    // a register array under a rolled loop goes to scratch.  No caller pairs them with a residual on a large tile.)
+    constexpr bool PF2K = (RP * CPR) % NT == 0 && (ACT == VY_ACT_NONE || ACT == VY_ACT_GELU_ERF);
+    constexpr int ITERS = (PFK || PF2K) ? (RP * CPR) / NT : 1;
+    bf16x8 pre8[ITERS];                    // the first operand (pf_ptr)
+    bf16x8 rb8[GRAD ? ITERS : 1];          // the residual of a dgrad whose first operand is the saved tensor
+    bf16x8 rc8[ITERS];                     // the second residual
+    const bool whole = ep.vec_ok && m0 + BM <= M && n0 + BN <= N;   // workgroup-uniform
+    const bool pf_on = PFK && pf_ptr != nullptr && whole;
+    const bool pf2_on = PF2K && ep.pf2 && pf_ptr != nullptr && whole;
+    auto pf_addr = [&](const bf16* p, int64_t ld, int pass, int it) {
+      const int c = tid + it * NT;
+      const int row = c / CPR, cc = c - row * CPR;
+      return reinterpret_cast<const bf16x8*>(p + (int64_t)(m0 + pass * RP + row) * ld + n0 + cc * 8);
+    };
     if constexpr (PFK) {
       if (pf_on) {
 #pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-          const int c = tid + it * NT;
-          const int row = c / CPR, cc = c - row * CPR;
-          pre8[it] = *reinterpret_cast<const bf16x8*>(pf_ptr + (int64_t)(m0 + row) * pf_ld + n0 + cc * 8);
-        }
+        for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, 0, it);
       }
     }
+    auto prefetch_rest = [&](int pass) {
+      if constexpr (PF2K) {
+        if (pf2_on) {
+          if (!pf_on) {
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, pass, it);
+          }
+          if constexpr (GRAD) {
+            if (pf_is_gradpre && ep.residual) {
+#pragma unroll
+              for (int it = 0; it < ITERS; ++it) rb8[it] = *pf_addr(ep.residual, ep.ldr, pass, it);
+            }
+          }
+          if (ep.residual2) {
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) rc8[it] = *pf_addr(ep.residual2, ep.ldr2, pass, it);
+          }
+        }
+      }
+    };
     auto flush_plain = [&](bf16* __restrict__ dst, bool final_pass, bool dual, int pass) {
       (void)final_pass;
-      if constexpr (PFK) {
-        if (pf_on) {
+      if constexpr (PF2K) {
+        if (pf2_on) {
 #pragma unroll
-          for (int it = 0; it < ITERS; ++it) do_chunk(dst, dual, pass, tid + it * NT, true, pre8[it]);
+          for (int it = 0; it < ITERS; ++it)
+            do_chunk(dst, dual, pass, tid + it * NT, true, pre8[it], true, rb8[GRAD ? it : 0], rc8[it], true);
           return;
         }
       }
       const bf16x8 none{};
-      for (int c = tid; c < RP * CPR; c += NT) do_chunk(dst, dual, pass, c, false, none);
+      if constexpr (PFK) {
+        if (pf_on) {
+#pragma unroll
+          for (int it = 0; it < ITERS; ++it) do_chunk(dst, dual, pass, tid + it * NT, true, pre8[it], false, none, none, false);
+          return;
+        }
+      }
+      for (int c = tid; c < RP * CPR; c += NT) do_chunk(dst, dual, pass, c, false, none, false, none, none, false);
     };
     const bool dual = !GRAD && ep.pre != nullptr;   // (the GRAD path never sets ep.pre)
 #pragma unroll 1
     for (int pass = 0; pass < PASSES; ++pass) {
       stage_all(pass);
+      // the requests stay behind the staging: above it they would be live next to the accumulators
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      prefetch_rest(pass);
       __syncthreads();
       flush_plain(ep.y, true, dual, pass);
       if (pass + 1 < PASSES) __syncthreads();
@@ -2018,6 +2075,7 @@ int linear_impl(const void* x, int64_t ldx, const void* w, int64_t ldw, const vo
   if (residual2 && !residual) VY_FAIL(VY_ERR_ARG, "%s: add_to2 without add_to", who);
   ep.gradpre = (const T*)gradpre; ep.ldg = ldg; ep.y = (T*)y; ep.ldy = ldy; ep.pre = (T*)pre_out;
   ep.drop = drop;
+  ep.pf2 = vy_epi_prefetch();
   static const int wt_env = [] { const char* e = getenv("VY_GEMM_WT_STORE"); return e ? atoi(e) : 1; }();
   ep.wt_store = (wt_env && (int64_t)M * N * (int64_t)sizeof(T) >= (16 << 20)) ? 1 : 0;
   const int ve = 16 / (int)sizeof(T);  // elements per 16-byte access (bf16: 8, f32 quads: 4)
@@ -2166,6 +2224,7 @@ extern "C" int vy_qkv_rope_fwd(const void* x, int64_t ldx, const void* w, int64_
 int64_t vy_splitk_ws_floats(int64_t N) { return 8 * 32 * N; }
 
 extern "C" int vy_debug_set_gemm_variant(int v) { g_gemm_variant = v; return 0; }
+extern "C" int vy_debug_set_epilogue_prefetch(int on) { g_epi_prefetch = on ? 1 : 0; return 0; }
 extern "C" int vy_workspace_set(void* stream, void* ws, int64_t bytes) {
   if (bytes < 0 || (ws && ((uintptr_t)ws & 255))) VY_FAIL(VY_ERR_ARG, "vy_workspace_set: bad workspace (256-byte aligned, bytes >= 0)");
   std::lock_guard<std::mutex> lk(g_ws_mu);

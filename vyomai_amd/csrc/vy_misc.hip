@@ -889,10 +889,11 @@ int ln_fwd_dispatch(const void* x, int64_t ldx, const void* gamma, const void* b
   return VY_OK;
 }
 
+// dgamma / dbeta == nullptr with partial: the slab stays in ws for the caller's column sums (vy_layernorm_bwd_partial)
 template <typename T>
 int ln_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* gamma,
                     const float* mean, const float* rstd, void* dx, int64_t lddx, float* dgamma,
-                    float* dbeta, float beta, float* ws, int64_t M, int64_t N, hipStream_t st) {
+                    float* dbeta, float beta, float* ws, int64_t M, int64_t N, hipStream_t st, bool partial = false) {
   constexpr int VEC = Chunk<T>::VEC;
   if (N % VEC || ldx % VEC || lddy % VEC || lddx % VEC) VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: N/ld must be multiples of %d", VEC);
   const int nch = (int)(N / VEC);
@@ -908,22 +909,28 @@ int ln_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, co
   else VY_FAIL(VY_ERR_UNSUPPORTED, "vy_layernorm_bwd: N=%ld too wide", (long)N);
 #undef LN_GO
   VY_CHECK_LAUNCH("vy_layernorm_bwd");
+  if (partial) return VY_OK;
   if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: beta must be 0 or 1");
-  const int acc = beta == 1.f;
-  const int slices = WB >= 64 ? 16 : 1;
+  return vy_ln_colsum(ws, WB, (int)N, dgamma, dbeta, beta == 1.f, st);
+}
+
+}  // namespace
+
+// internal: the column sums of a LayerNorm-backward slab as launches of their own (vy_layernorm_bwd, and the fp32 path
+// of vy_linear_wgrad_grouped_cs); the summation order is vy_ln_colsum_slices' (vy_common.h)
+int vy_ln_colsum(float* ws, int WB, int N, float* dgamma, float* dbeta, int acc, hipStream_t st) {
+  const int slices = vy_ln_colsum_slices(WB);
   const int rps = (int)vy_cdiv(WB, slices);
   hipLaunchKernelGGL(colsum_partials_kernel, dim3((unsigned)vy_cdiv(N, 64), (unsigned)slices), dim3(256), 0, st, ws, WB,
-                     (int)N, dgamma, dbeta, rps, acc);
+                     N, dgamma, dbeta, rps, acc);
   VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum)");
   if (slices > 1) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)vy_cdiv(N, 256)), dim3(256), 0, st, ws, WB, (int)N, dgamma,
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)vy_cdiv(N, 256)), dim3(256), 0, st, ws, WB, N, dgamma,
                        dbeta, rps, acc);
     VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum finish)");
   }
   return VY_OK;
 }
-
-}  // namespace
 
 extern "C" int vy_layernorm_fwd(const void* x, int64_t ldx, const void* gamma, const void* beta, void* y,
                                 int64_t ldy, float* mean, float* rstd, int64_t M, int64_t N, float eps,
@@ -1002,6 +1009,17 @@ extern "C" int vy_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int
   if (dtype == VY_BF16) return ln_bwd_dispatch<bf16>(dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, dgamma, dbeta, beta, ws, M, N, st);
   if (dtype == VY_F32) return ln_bwd_dispatch<float>(dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, dgamma, dbeta, beta, ws, M, N, st);
   VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: bad dtype %d", dtype);
+}
+
+extern "C" int vy_layernorm_bwd_partial(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* gamma,
+                                        const float* mean, const float* rstd, void* dx, int64_t lddx, float* ws,
+                                        int64_t M, int64_t N, int dtype, void* stream) {
+  if (!dy || !x || !gamma || !mean || !rstd || !dx || !ws || M <= 0 || N <= 0)
+    VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd_partial: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == VY_BF16) return ln_bwd_dispatch<bf16>(dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, nullptr, nullptr, 0.f, ws, M, N, st, true);
+  if (dtype == VY_F32) return ln_bwd_dispatch<float>(dy, lddy, x, ldx, gamma, mean, rstd, dx, lddx, nullptr, nullptr, 0.f, ws, M, N, st, true);
+  VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd_partial: bad dtype %d", dtype);
 }
 
 // internal (vy_qkv_rope_fwd's unfused path): RoPE on q (hq heads) and k (hk heads) in one launch

@@ -7,7 +7,7 @@ is no CPU or eager fallback.
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -367,14 +367,29 @@ def linear_wgrad(dy: Tensor, x: Tensor, dw: Tensor, db: Optional[Tensor], accumu
          dw.stride(0), _ptr(db), 1.0 if accumulate else 0.0, _ptr(alpha), M, N, K, dtype_code(dy.dtype), _stream())
 
 
+class ColSum(NamedTuple):
+    """An entry of linear_wgrad_grouped's list that is no weight gradient: the column sums of the slab `ws` that
+    layernorm_bwd_partial returned, written (accumulate: added) to the fp32 [N] tensors dgamma / dbeta.  dtype: the
+    LayerNorm's storage type (it names the path when the list holds nothing else)."""
+    ws: Tensor
+    dgamma: Tensor
+    dbeta: Tensor
+    accumulate: bool
+    dtype: torch.dtype
+
+
 def linear_wgrad_grouped(items) -> None:
     """items: up to 8 tuples (dy, x, dw, db|None): dw += dy^T @ x, db += colsum(dy), ONE launch
     (vy_linear_wgrad_grouped).  The tensors must stay alive until the launch has been enqueued (they do:
-    the caller holds them)."""
+    the caller holds them).
+    The list may also hold up to 8 ColSum entries, summed in the same launch (vy_linear_wgrad_grouped_cs), and
+    then need not hold a weight gradient at all."""
     import ctypes as C
-    n = len(items)
-    assert 1 <= n <= 8
-    arr = (_lib.VyWgradDesc * n)()
+    colsums = [it for it in items if isinstance(it, ColSum)]
+    items = [it for it in items if not isinstance(it, ColSum)]
+    n, ncs = len(items), len(colsums)
+    assert n <= 8 and ncs <= 8 and n + ncs >= 1
+    arr = (_lib.VyWgradDesc * max(n, 1))()
     dt = None
     for i, (dy, x, dw, db) in enumerate(items):
         _need_gpu(dy, x, dw, db)
@@ -389,7 +404,36 @@ def linear_wgrad_grouped(items) -> None:
         a.dy, a.lddy, a.x, a.ldx = d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0)
         a.dw, a.lddw, a.db = dw.data_ptr(), dw.stride(0), _ptr(db)
         a.M, a.N, a.K = M, N, K
-    call("vy_linear_wgrad_grouped", C.cast(arr, C.c_void_p), n, dtype_code(dt), _stream())
+    if not ncs:
+        call("vy_linear_wgrad_grouped", C.cast(arr, C.c_void_p), n, dtype_code(dt), _stream())
+        return
+    cs = (_lib.VyColsumDesc * ncs)()
+    for i, (ws, dgamma, dbeta, accumulate, cdt) in enumerate(colsums):
+        _need_gpu(ws, dgamma, dbeta)
+        dt = cdt if dt is None else dt
+        N = dgamma.numel()
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() % (2 * N) == 0
+        assert dgamma.dtype == torch.float32 and dbeta.dtype == torch.float32 and dbeta.numel() == N
+        assert dgamma.is_contiguous() and dbeta.is_contiguous()
+        c = cs[i]
+        c.ws, c.W, c.N = ws.data_ptr(), ws.numel() // (2 * N), N
+        c.out0, c.out1, c.acc = dgamma.data_ptr(), dbeta.data_ptr(), 1 if accumulate else 0
+    call("vy_linear_wgrad_grouped_cs", C.cast(arr, C.c_void_p) if n else None, n, C.cast(cs, C.c_void_p), ncs,
+         dtype_code(dt), _stream())
+
+
+def layernorm_bwd_partial(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor):
+    """-> (dx, ws): layernorm_bwd without dgamma / dbeta; their per-block partials stay in ws (fp32, [2 * ws_rows * N])
+    for a ColSum entry of linear_wgrad_grouped to sum.  (vy_layernorm_bwd_partial)"""
+    _need_gpu(dy, x, gamma, mean, rstd)
+    d2, x2 = _rows(dy), _rows(x)
+    M, N = x2.shape
+    dx = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    W = _lib.load().vy_layernorm_bwd_ws_rows(M)
+    ws = torch.empty((2 * W * N,), dtype=torch.float32, device=x.device)
+    call("vy_layernorm_bwd_partial", d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0), gamma.data_ptr(),
+         mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dx.stride(0), ws.data_ptr(), M, N, dtype_code(x.dtype), _stream())
+    return dx.view(x.shape), ws
 
 
 def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor, dgamma: Tensor,
