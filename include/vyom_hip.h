@@ -145,7 +145,7 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
 /* ------------------------------------------------------------------------------------------
  * Paged KV cache (Examples/simple_vllm.ipynb cell 2).  Per layer k_cache / v_cache are (max_blocks, block_size, hk, dh),
  * contiguous; slot = block * block_size + offset.  block_size: a power of two from 8 to 256; dh: a multiple of 8 up to
- * 256; bf16 and fp32.  Anything else is VY_ERR_ARG before a launch.  None of the three allocates.
+ * 256; bf16 and fp32.  Anything else is VY_ERR_ARG before a launch.  None of the four allocates.
  *
  * vy_paged_rope_write: after the packed QKV projection of a step's T tokens (qkv[T][ld], rows [q heads; k heads; v
  *   heads] of dh columns): token t's q and k heads are rotated IN PLACE with row positions[t] (int32, device) of the
@@ -168,6 +168,24 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
  *   replaces: flash_attn_with_kvcache(q.unsqueeze(1), k_cache, v_cache, cache_seqlens=..., block_table=...,
  *   causal=True) in the same forward.
  *
+ * vy_attn_paged_prefill: causal attention of packed, variable-length query segments against the pages, all prefilling
+ *   sequences of a step in ONE launch.  Rows cu_q[s] .. cu_q[s+1] - 1 of q (q + row * q_ld, heads of dh columns side by
+ *   side, as vy_attn_paged_decode reads it) belong to sequence s; row i of the segment sits at position ctx_lens[s] + i
+ *   and attends to keys [0, ctx_lens[s] + i] of the sequence, read through block_table[s].  ALL keys come from the pages
+ *   (vy_paged_rope_write has stored the step's own rows before), so a segment may start anywhere in its sequence:
+ *   behind cached prefix blocks, or behind an earlier chunk of the same prompt.  ctx_lens[s] is arbitrary (no multiple
+ *   of block_size).  out (row stride o_ld >= h * dh) is written at the same rows, no other row is touched.  cu_q
+ *   (n_seq + 1 entries), ctx_lens and block_table int32 [n_seq][bt_stride] live on the device; max_q (>= every segment
+ *   length) and max_kv (>= every ctx + length) are host values that only size the launch.  n_seq == 0 is VY_OK without
+ *   a launch.  bf16: 64 query rows per workgroup on the MFMA path, every admitted dh; fp32 (parity): one single-query
+ *   problem per row, online softmax in fp32, one rounding.  Key rows at or past ctx + length are never read (the tail of
+ *   a last page may hold anything).
+ *   Memory safety only, as in vy_attn_paged_decode: a key range past bt_stride * block_size is cut to it, a negative
+ *   ctx counts as 0, a block-table entry outside [0, max_blocks) is clamped into it -- silently.
+ *   replaces: flash_attn_varlen_func(q, k, v, cu_seqlens_q=..., cu_seqlens_k=..., causal=True) of
+ *   GroupedQueryAttention.forward in the same notebook -- and, with the keys coming from the pages, also serves what
+ *   that call cannot: query segments that start in the middle of a sequence (prefix hits, chunked prefill).
+ *
  * vy_paged_gather: keys [0, S) of ONE sequence (block_table: its n_blocks entries, device) copied from the pages into
  *   contiguous (hk, S, dh) buffers, K and V in one launch -- the keys of a prefill that starts from cached prefix blocks.
  *   The rows of a block-table entry outside [0, max_blocks) are written as zeros (memory safety only, silently).
@@ -182,6 +200,11 @@ int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* q_rows, con
                          int64_t max_seqlen, void* out, int64_t o_ld, int64_t B, int h, int hk, int dh,
                          float scale, int n_split, void* ws, int64_t ws_bytes, int dtype, void* stream);
 int64_t vy_attn_paged_decode_ws_bytes(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split, int dtype);
+int vy_attn_paged_prefill(const void* q, int64_t q_ld, const void* k_cache, const void* v_cache,
+                          int64_t max_blocks, int block_size, const int32_t* block_table, int64_t bt_stride,
+                          const int32_t* cu_q, const int32_t* ctx_lens, int64_t n_seq, int64_t max_q,
+                          int64_t max_kv, void* out, int64_t o_ld, int h, int hk, int dh, float scale,
+                          int dtype, void* stream);
 int vy_paged_gather(const void* k_cache, const void* v_cache, int64_t max_blocks, int block_size,
                     const int32_t* block_table, int64_t n_blocks, int64_t S, void* k_out, void* v_out,
                     int hk, int dh, int dtype, void* stream);

@@ -1,5 +1,5 @@
 """Paged decode attention against the resident-context kernel on the same keys, and the continuous-batching engine against
-generate() on the same prompts.   python tools/bench_paged.py [--iters 1000] [--splits 1 2 4] [--skip-engine]
+generate() on the same prompts.   python tools/bench_paged.py [--iters 1000] [--splits 1 2 4] [--skip-engine] [--prefill]
 
 Kernels: vy_attn_paged_decode (bf16, block_size 256, pages in shuffled physical order) and vy_attn_decode on the same keys
 in a contiguous (B, hk, S, dh) cache, each timed as a link of a captured chain of 50 calls, the chains replayed in turn;
@@ -7,6 +7,13 @@ bytes = the K and V rows each has to read.
 dh = 128 at S = 4096 has no resident-context counterpart and is reported against the 1 GiB copy ceiling measured in the
 same run (vy_debug_copy, the probe behind bench.py --full).  Engine: 6 requests of mixed lengths, generated tokens per
 second, against generate() on the prompts left-padded into one batch that runs until its longest request is done.
+--prefill (instead of the decode kernels): the attention of one layer of a prefill step, (a) the per-sequence path
+(vy_paged_gather when the sequence starts behind cached context, then vy_attn_fwd) against (b) the one
+vy_attn_paged_prefill launch, on the same pages (bf16, block_size 256, shuffled physical order), both as links of captured
+chains replayed in turn; TFLOP/s counts the causal half only (4 h dh sum_i (ctx + i + 1) per sequence); the whole
+measurement is repeated and the lowest and highest figure of each variant are printed.  The engine section then adds
+one 2048-token request arriving while 7 sequences decode, unchunked and with max_step_tokens = 256: requested tokens per
+second and the longest single step().
 Prints one JSON line per measurement."""
 import argparse
 import ctypes as C
@@ -124,6 +131,97 @@ def bench_kernels(iters, splits=()):
         print(json.dumps(rec))
 
 
+PREFILL_SHAPES = [(8, 512, 0), (8, 512, 1536), (32, 64, 0)]         # sequences, rows each, cached context
+PREFILL_HEADS = [(12, 12, 64), (16, 8, 128), (4, 2, 224)]
+
+
+def bench_prefill(iters, repeats=3):
+    bs = 256
+    for h, hk, dh in PREFILL_HEADS:
+        for n, rows, ctx in PREFILL_SHAPES:
+            g = torch.Generator().manual_seed(rows + dh + ctx)
+            S, T = ctx + rows, n * rows
+            pages = (S + bs - 1) // bs
+            nblk = n * pages
+            table = torch.randperm(nblk, generator=g).to(torch.int32).view(n, pages)
+            qkv = torch.randn(T, (h + 2 * hk) * dh, generator=g).to(BF).to(DEV)
+            kc = torch.randn(nblk, bs, hk, dh, generator=g).to(BF).to(DEV)
+            vc = torch.randn(nblk, bs, hk, dh, generator=g).to(BF).to(DEV)
+            j = torch.arange(ctx, S)
+            slot = (table[:, j // bs].long() * bs + j % bs).to(DEV)              # (n, rows): the step's own rows
+            kc.view(-1, hk, dh)[slot] = qkv[:, h * dh:(h + hk) * dh].view(n, rows, hk, dh)
+            vc.view(-1, hk, dh)[slot] = qkv[:, (h + hk) * dh:].view(n, rows, hk, dh)
+            table = table.to(DEV)
+            cu = (torch.arange(n + 1, dtype=torch.int32) * rows).to(DEV)
+            ctxs = torch.full((n,), ctx, dtype=torch.int32, device=DEV)
+            o_old = torch.empty(T, h * dh, dtype=BF, device=DEV)
+            o_new = torch.empty_like(o_old)
+
+            def old():
+                for s in range(n):
+                    seg = qkv[s * rows:(s + 1) * rows]
+                    q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)
+                    if ctx:
+                        k3, v3 = ops.paged_gather(kc, vc, table[s], S)
+                    else:
+                        k3 = seg[:, h * dh:(h + hk) * dh].view(rows, hk, dh).permute(1, 0, 2)
+                        v3 = seg[:, (h + hk) * dh:].view(rows, hk, dh).permute(1, 0, 2)
+                    ops.attention(q4, k3.unsqueeze(0), v3.unsqueeze(0), causal=True, start_pos=ctx,
+                                  out=o_old[s * rows:(s + 1) * rows].unsqueeze(0))
+
+            def new():
+                ops.attention_paged_prefill(qkv, kc, vc, table, cu, ctxs, rows, S, h, out=o_new)
+
+            runs = [timed_graph([old, new], 3, iters, reps=10) for _ in range(repeats)]
+            flops = 4.0 * h * dh * n * (rows * ctx + rows * (rows + 1) / 2)
+            t_old, t_new = [r[0] for r in runs], [r[1] for r in runs]
+            diff = (o_old.float() - o_new.float()).abs().max().item()
+            print(json.dumps({
+                "what": "prefill attention", "h": h, "hk": hk, "dh": dh, "sequences": n, "rows": rows, "ctx": ctx,
+                "launches_per_seq_path": n * (2 if ctx else 1),
+                "per_seq_us": [round(min(t_old), 1), round(max(t_old), 1)],
+                "varlen_us": [round(min(t_new), 1), round(max(t_new), 1)],
+                "per_seq_TFLOPs": round(flops / min(t_old) * 1e-6, 1), "varlen_TFLOPs": round(flops / min(t_new) * 1e-6, 1),
+                "ratio": round(min(t_new) / min(t_old), 3), "max_abs_diff": diff}))
+
+
+def bench_engine_long_arrival():
+    """7 sequences decode, then a 2048-token request arrives: unchunked, its prefill is one long step that every
+    decoding sequence waits for; with max_step_tokens = 256 it is spread over 9 steps."""
+    cfg = V.Config(vocab_size=32000, hidden_size=896, intermediate_size=4864, num_hidden_layers=4,
+                   num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=4096, pad_token_id=0)
+    torch.manual_seed(0)
+    m = V.ModelForCausalLM(cfg).to(BF).to(DEV).eval()
+    g = torch.Generator().manual_seed(2)
+    short = [torch.randint(3, cfg.vocab_size, (32,), generator=g).tolist() for _ in range(7)]
+    long = torch.randint(3, cfg.vocab_size, (2048,), generator=g).tolist()
+    requested = 7 * 128 + 32
+
+    def run(**kw):
+        mgr = V.PagedKVManager(cfg, 256, 16, DEV, BF)
+        eng = V.ContinuousBatchEngine(m, mgr, max_batch_size=8, eos_token_ids=[], **kw)
+        for p in short:
+            eng.add_sequence(p, max_gen_len=128)
+        steps = []
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while eng.active or eng.waiting_room:
+            if len(steps) == 8:
+                eng.add_sequence(long, max_gen_len=32)
+            t1 = time.perf_counter()
+            eng.step()                         # (ends with the step's device-to-host copy of the ids)
+            steps.append(time.perf_counter() - t1)
+        return time.perf_counter() - t0, max(steps), len(steps)
+
+    for name, kw in (("engine, long arrival, unchunked", {}), ("engine, long arrival, max_step_tokens 256", {"max_step_tokens": 256})):
+        run(**kw)                              # warm-up: every shape of the run
+        res = [run(**kw) for _ in range(3)]
+        dt = sorted(r[0] for r in res)[1]
+        print(json.dumps({"what": name, "requested_tokens": requested, "steps": res[0][2], "seconds": round(dt, 4),
+                          "requested_tokens_per_s": round(requested / dt, 1),
+                          "longest_step_ms": [round(min(r[1] for r in res) * 1e3, 2), round(max(r[1] for r in res) * 1e3, 2)]}))
+
+
 def bench_engine():
     cfg = V.Config(vocab_size=32000, hidden_size=896, intermediate_size=4864, num_hidden_layers=4,
                    num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=1024, pad_token_id=0)
@@ -166,10 +264,16 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=1000)
     ap.add_argument("--skip-engine", action="store_true")
+    ap.add_argument("--prefill", action="store_true", help="time the prefill attention paths instead of the decode kernels")
     ap.add_argument("--splits", type=int, nargs="*", default=[], help="also time these pinned n_split values")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_paged.py needs the MI355X: there is nothing to time without it")
-    bench_kernels(a.iters, a.splits)
+    if a.prefill:
+        bench_prefill(min(a.iters, 200))
+    else:
+        bench_kernels(a.iters, a.splits)
     if not a.skip_engine:
         bench_engine()
+        if a.prefill:
+            bench_engine_long_arrival()

@@ -36,6 +36,8 @@ PROTOTYPES = {
     "vy_paged_rope_write": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i, _i64, _i, _i, _i, _i, _p],
     "vy_attn_paged_decode": [_p, _i64, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i, _i, _i, _f, _i,
                              _p, _i64, _i, _p],
+    "vy_attn_paged_prefill": [_p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _i, _i, _i, _f,
+                              _i, _p],
     "vy_paged_gather": [_p, _p, _i64, _i, _p, _i64, _i64, _p, _p, _i, _i, _i, _p],
     "vy_layernorm_fwd": [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _f, _i, _p],
     "vy_rmsnorm_fwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _f, _f, _i, _p],

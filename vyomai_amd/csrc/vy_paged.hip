@@ -18,6 +18,7 @@ constexpr int PD_NW = 4;          // waves per workgroup
 constexpr int PD_U = 4;           // keys per lane group and loop trip: 2 * U 16-byte loads in flight per lane
 constexpr int PD_MAX_SPLIT = 32;
 constexpr int PD_TARGET_WGS = 512;   // two workgroups per CU
+constexpr float PF_LOG2E = 1.4426950408889634f;
 
 struct PagedDecArgs {
   const void* q; long long q_ld; const int* q_rows;
@@ -27,6 +28,7 @@ struct PagedDecArgs {
   float* ws_ml; float* ws_o;           // n_split > 1: [B][h][n_split]{m, l} and [B][h][n_split][dh]
   int h, hk, dh, R, lbs, max_blocks, n_split;
   float scale;
+  const int* cu_q;                     // PF kernels only: first packed row of each sequence (n_seq + 1 entries)
 };
 
 // lane = (key group g, 16-byte chunk ch of the head): LPK lanes per key (the chunks of the head, rounded up to a power of
@@ -35,7 +37,9 @@ struct PagedDecArgs {
 // in one page and the block-table entry is wave-uniform (a scalar load); where the whole trip sits in one page
 // (block_size >= CK) it is loaded once for the trip.  RT query heads per workgroup (R rounded up to 1, 2, 4 or 8; the
 // heads past R compute on head 0's query and store nothing).
-template <typename T, int LPK, int RT>
+// PF (the fp32 path of vy_attn_paged_prefill): row blockIdx.y of sequence blockIdx.z's query segment is a single-query
+// problem -- packed row cu_q[z] + y, keys [0, ctx[z] + y + 1) with seqlens = the context lengths -- and is never split.
+template <typename T, int LPK, int RT, bool PF = false>
 __global__ __launch_bounds__(64 * PD_NW) void paged_dec_kernel(const PagedDecArgs p) {
   using CH = Chunk<T>;
   using Raw = typename CH::Raw;
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(64 * PD_NW) void paged_dec_kernel(const PagedDecArg
   __shared__ float red_o[RT][NW][DHP];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.z, split = blockIdx.y;
+  const int b = blockIdx.z, split = PF ? 0 : (int)blockIdx.y;
   const int ngrp = (p.R + RT - 1) / RT;
   const int kvh = (int)blockIdx.x / ngrp, r0 = ((int)blockIdx.x - kvh * ngrp) * RT;
   const int nr = p.R - r0 < RT ? p.R - r0 : RT;
@@ -56,8 +60,17 @@ __global__ __launch_bounds__(64 * PD_NW) void paged_dec_kernel(const PagedDecArg
   const int bs = 1 << p.lbs;
   int S = p.seqlens[b];
   const long long cap = p.bt_stride << p.lbs;       // keys the row of the block table can name
-  if (S > cap) S = (int)cap;
-  const long long qr = p.q_rows ? p.q_rows[b] : b;
+  long long qr;
+  if constexpr (PF) {
+    const int row0 = p.cu_q[b], i = (int)blockIdx.y;
+    if (i >= p.cu_q[b + 1] - row0) return;          // (the whole workgroup, before any barrier)
+    const long long Sl = (long long)(S < 0 ? 0 : S) + i + 1;
+    S = Sl > cap ? (int)cap : (int)Sl;
+    qr = (long long)row0 + i;
+  } else {
+    if (S > cap) S = (int)cap;
+    qr = p.q_rows ? p.q_rows[b] : b;
+  }
   // this workgroup's keys [k0, k1): equal shares of the sequence, rounded up to whole trips
   const int per = ((S + p.n_split - 1) / p.n_split + NW * CK - 1) / (NW * CK) * (NW * CK);
   const int k0 = split * per;
@@ -331,6 +344,217 @@ void paged_dec_launch(const PagedDecArgs& a, int64_t B, hipStream_t st) {
   else hipLaunchKernelGGL((paged_dec_kernel<T, LPK, 8>), grid, block, 0, st, a);
 }
 
+// ------------------------------------------------------------------------------------------
+// vy_attn_paged_prefill, bf16: attn_fwd_gen_kernel's structure (vy_attn.hip: 64 query rows per workgroup, 16 per wave,
+// register-staged 64-key tiles, mfma_f32_16x16x32_bf16 with the swapped QK^T, P in registers, V^T through
+// ds_read_b64_tr_b16) over packed variable-length query segments, with the keys read through the block table: key kj
+// of sequence s is row table[s][kj / bs] * bs + kj % bs of the pages.  What else differs from the contiguous kernel:
+//   * the mask is always causal at offset ctx[s] and every row sees its own key: no key-padding and no "no visible
+//     key" branch;
+//   * the registers of tile t + 1 are requested right after tile t has been stored to LDS, so the two dependent loads
+//     (table entry, then the row) fly under tile t's MFMAs and softmax -- there is no LDS-DMA ring here that an
+//     ordinary load would drain (vy_attn_tile.h, fact (2));
+//   * key rows at or past ctx + len are staged as zeros, never read: the tail of a last page may hold anything and
+//     0 * NaN in the PV MFMA is NaN.
+// ------------------------------------------------------------------------------------------
+struct PagedPfArgs {
+  const bf16* q; long long q_ld;
+  const bf16* kc; const bf16* vc;
+  const int* bt; long long bt_stride;
+  const int* cu_q; const int* ctx;
+  bf16* out; long long o_ld;
+  int h, hk, dh, lbs, max_blocks;
+  float scale;
+};
+
+template <int DHP>
+__global__ __launch_bounds__(256) void paged_prefill_kernel(const PagedPfArgs p) {
+  constexpr int PITCH = (DHP + 8) * 2;       // bytes per LDS row (16 B of padding: conflict-free fragment reads)
+  constexpr int KS = DHP / 32;               // k-steps of QK^T
+  constexpr int NDB = DHP / 16;              // 16-wide d blocks of O^T
+  constexpr int CPRW = DHP / 8;              // 16-byte chunks per row
+  constexpr int CPT = 64 * CPRW / 256;       // chunks per thread and tile
+  static_assert(DHP % 32 == 0 && (64 * CPRW) % 256 == 0, "tile chunks must divide over the workgroup");
+  __shared__ __attribute__((aligned(16))) char smem[2 * 64 * PITCH];
+  char* kt = smem;
+  char* vt = smem + 64 * PITCH;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r16 = lane & 15, kq = lane >> 4;
+  // heads on x (whole heads per XCD, vy_attn.hip), long rows first
+  const int head = (int)blockIdx.x % p.h, s = (int)blockIdx.x / p.h;
+  const int kvh = head / (p.h / p.hk);
+  const int q0 = ((int)gridDim.y - 1 - (int)blockIdx.y) * 64;
+  const int row0 = p.cu_q[s], len = p.cu_q[s + 1] - row0;
+  if (q0 >= len) return;                     // (the whole workgroup, before the first barrier)
+  const int cap = (int)(p.bt_stride << p.lbs);        // keys the row of the block table can name (<= 2^30)
+  int ctx = p.ctx[s];
+  ctx = ctx < 0 ? 0 : ctx < cap ? ctx : cap;          // memory safety only
+  const int S = len < cap - ctx ? ctx + len : cap;
+  const int dh = p.dh, bs = 1 << p.lbs;
+  const int qi = q0 + wave * 16 + r16;
+  const int qrow = qi < len ? qi : len - 1;
+  const bf16* Q = p.q + ((long long)row0 + qrow) * p.q_ld + (long long)head * dh;
+  const int* bt = p.bt + (long long)s * p.bt_stride;
+  const long long row_stride = (long long)p.hk * dh;
+  const bf16* Kb = p.kc + (long long)kvh * dh;
+  const bf16* Vb = p.vc + (long long)kvh * dh;
+  const bf16x8 zero8 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+
+  bf16x8 qf[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int d0 = 32 * ks + 8 * kq;
+    qf[ks] = d0 < dh ? *reinterpret_cast<const bf16x8*>(Q + d0) : zero8;
+  }
+  f32x4 o[NDB];
+#pragma unroll
+  for (int n = 0; n < NDB; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -FLT_MAX, l_run = 0.f;
+  const float c = p.scale * PF_LOG2E;
+  const int kv_end = S < ctx + q0 + 64 ? S : ctx + q0 + 64;
+  const int nt = (kv_end + 63) / 64;         // >= 1: S >= 1
+  // transposing-read addresses of the V tile: lane j of a 16-lane group supplies row (j >> 2), columns 4 (j & 3) ..
+  const unsigned vtr = vy_lds_addr(vt) + (4 * kq + (r16 >> 2)) * PITCH + (4 * (r16 & 3)) * 2;
+
+  // the tile's 16-byte chunks -> registers: zero beyond the head width and at or beyond key S
+  bf16x8 kreg[CPT], vreg[CPT];
+  auto fetch = [&](int k0) {
+    int ent[CPT];
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int kj = k0 + (tid + 256 * i) / CPRW;
+      ent[i] = bt[(kj < S ? kj : S - 1) >> p.lbs];
+    }
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int cidx = tid + 256 * i;
+      const int row = cidx / CPRW, ch = cidx - row * CPRW;
+      const int kj = k0 + row;
+      const bool ok = ch * 8 < dh && kj < S;
+      const int kjc = kj < S ? kj : S - 1;
+      const int e = ent[i] < 0 ? 0 : ent[i] < p.max_blocks ? ent[i] : p.max_blocks - 1;   // memory safety only
+      const long long off = (((long long)e << p.lbs) + (kjc & (bs - 1))) * row_stride + (ch * 8 < dh ? ch * 8 : 0);
+      kreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Kb + off) : zero8;
+      vreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Vb + off) : zero8;
+    }
+  };
+  fetch(0);
+
+  for (int t = 0; t < nt; ++t) {
+    const int k0 = t * 64;
+    __syncthreads();   // the previous tile's fragments have been read
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int cidx = tid + 256 * i;
+      const int row = cidx / CPRW, ch = cidx - row * CPRW;
+      *reinterpret_cast<bf16x8*>(kt + row * PITCH + ch * 16) = kreg[i];
+      *reinterpret_cast<bf16x8*>(vt + row * PITCH + ch * 16) = vreg[i];
+    }
+    __syncthreads();
+    if (t + 1 < nt) fetch(k0 + 64);
+    // S^T = K Q^T: four 16-key blocks
+    f32x4 sc[4];
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+      sc[blk] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kt + (16 * blk + r16) * PITCH + (32 * ks + 8 * kq) * 2);
+        sc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], sc[blk], 0, 0, 0);
+      }
+    }
+    // causal mask: register r of block blk is key k0 + 16 blk + 4 kq + r
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int kj = k0 + 16 * blk + 4 * kq + r;
+        const float tv = kj < S && kj <= qi + ctx ? sc[blk][r] : -INFINITY;
+        sc[blk][r] = tv;
+        tmax = fmaxf(tmax, tv);
+      }
+    // the row's keys are spread over the four lane groups (lane >> 4)
+    {
+      const unsigned u = __builtin_bit_cast(unsigned, tmax);
+      auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+      tmax = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
+      const unsigned w = __builtin_bit_cast(unsigned, tmax);
+      auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+      tmax = fmaxf(__builtin_bit_cast(float, (unsigned)s32[0]), __builtin_bit_cast(float, (unsigned)s32[1]));
+    }
+    const float m_new = fmaxf(m_run, tmax * c);   // (-inf * c stays -inf; m_run is finite)
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    m_run = m_new;
+    l_run *= alpha;
+#pragma unroll
+    for (int n = 0; n < NDB; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[n][r] *= alpha;
+    float rs = 0.f;
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = __builtin_amdgcn_exp2f(fmaf(sc[blk][r], c, -m_run));
+        sc[blk][r] = e;
+        rs += e;
+      }
+    l_run += rs;   // this lane group's keys only; the four groups are added at the end
+    // O^T += V^T P^T, k-steps of 32 keys = blocks (2 tt, 2 tt + 1) in the order the scores sit in
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+      bf16x8 pf;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { pf[r] = (bf16)sc[2 * tt][r]; pf[4 + r] = (bf16)sc[2 * tt + 1][r]; }
+      vy_static_for<NDB>([&](auto n_c) {
+        constexpr int n = decltype(n_c)::value;
+        union { struct { s16x4 a, b; } h; bf16x8 v; } u;
+        u.h.a = vy_lds_tr16_off<n * 32>(vtr + (32 * tt) * PITCH);
+        u.h.b = vy_lds_tr16_off<n * 32>(vtr + (32 * tt + 16) * PITCH);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        vy_tie(u.v);
+        o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf, o[n], 0, 0, 0);
+      });
+    }
+  }
+  // row totals over the four lane groups
+  float l_tot = l_run;
+  {
+    const unsigned u = __builtin_bit_cast(unsigned, l_tot);
+    auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    l_tot = __builtin_bit_cast(float, (unsigned)s16[0]) + __builtin_bit_cast(float, (unsigned)s16[1]);
+    const unsigned w = __builtin_bit_cast(unsigned, l_tot);
+    auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+    l_tot = __builtin_bit_cast(float, (unsigned)s32[0]) + __builtin_bit_cast(float, (unsigned)s32[1]);
+  }
+  const float inv = 1.0f / l_tot;
+  if (qi < len) {
+    bf16* orow = p.out + ((long long)row0 + qi) * p.o_ld + (long long)head * dh;
+#pragma unroll
+    for (int n = 0; n < NDB; ++n) {
+      const int d0 = 16 * n + 4 * kq;
+      if (d0 < dh) {
+        bf16x4 w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = (bf16)(o[n][r] * inv);
+        *reinterpret_cast<bf16x4*>(orow + d0) = w;
+      }
+    }
+  }
+}
+
+template <int LPK>
+void paged_prefill_f32_launch(const PagedDecArgs& a, int64_t n_seq, int64_t max_q, hipStream_t st) {
+  const int rt = pd_rt(a.R);
+  const dim3 grid((unsigned)(a.hk * ((a.R + rt - 1) / rt)), (unsigned)max_q, (unsigned)n_seq), block(64 * PD_NW);
+  if (rt == 1) hipLaunchKernelGGL((paged_dec_kernel<float, LPK, 1, true>), grid, block, 0, st, a);
+  else if (rt == 2) hipLaunchKernelGGL((paged_dec_kernel<float, LPK, 2, true>), grid, block, 0, st, a);
+  else if (rt == 4) hipLaunchKernelGGL((paged_dec_kernel<float, LPK, 4, true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((paged_dec_kernel<float, LPK, 8, true>), grid, block, 0, st, a);
+}
+
 }  // namespace
 
 extern "C" int64_t vy_attn_paged_decode_ws_bytes(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split,
@@ -364,7 +588,7 @@ extern "C" int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* 
   }
   PagedDecArgs a{q, q_ld, q_rows, k_cache, v_cache, block_table, bt_stride, seqlens, out, o_ld,
                  (float*)ws, ws ? (float*)ws + B * h * ns * 2 : nullptr,
-                 h, hk, dh, h / hk, lbs, (int)max_blocks, ns, scale};
+                 h, hk, dh, h / hk, lbs, (int)max_blocks, ns, scale, nullptr};
   hipStream_t st = (hipStream_t)stream;
   const int lpk = pd_lpk(dh, dtype);
   if (dtype == VY_BF16) {
@@ -386,6 +610,52 @@ extern "C" int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* 
       hipLaunchKernelGGL(paged_combine_kernel<float>, grid, block, 0, st, a.ws_ml, a.ws_o, (float*)out, o_ld, q_rows, ns, h, dh);
     VY_CHECK_LAUNCH("vy_attn_paged_decode (combine)");
   }
+  return VY_OK;
+}
+
+extern "C" int vy_attn_paged_prefill(const void* q, int64_t q_ld, const void* k_cache, const void* v_cache,
+                                     int64_t max_blocks, int block_size, const int32_t* block_table, int64_t bt_stride,
+                                     const int32_t* cu_q, const int32_t* ctx_lens, int64_t n_seq, int64_t max_q,
+                                     int64_t max_kv, void* out, int64_t o_ld, int h, int hk, int dh, float scale,
+                                     int dtype, void* stream) {
+  // (no sequences: the three per-sequence arrays may be empty, i.e. null)
+  if (!q || !k_cache || !v_cache || !out || (n_seq > 0 && (!block_table || !cu_q || !ctx_lens)))
+    VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: null operand");
+  const int lbs = log2_block_size(block_size);
+  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: block_size %d must be a power of two from 8 to 256", block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: dh %d must be a multiple of 8 up to 256", dh);
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: bad dtype %d", dtype);
+  if (n_seq < 0 || n_seq > 65535 || h <= 0 || hk <= 0 || h % hk || max_blocks <= 0 || max_blocks > INT32_MAX || bt_stride <= 0 ||
+      bt_stride > ((int64_t)1 << 30) / block_size || max_q < 0 || max_q > 65535 * 64 || max_kv < 0 || max_kv > (1 << 30) ||
+      q_ld % (dtype == VY_BF16 ? 8 : 4) || q_ld < (int64_t)h * dh || (dtype == VY_BF16 && o_ld % 4) || o_ld < (int64_t)h * dh ||
+      (int64_t)h * n_seq > INT32_MAX)
+    VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: bad shape (n_seq %lld, max_q %lld, max_kv %lld, h %d, hk %d, max_blocks %lld, "
+            "bt_stride %lld, q_ld %lld, o_ld %lld)", (long long)n_seq, (long long)max_q, (long long)max_kv, h, hk,
+            (long long)max_blocks, (long long)bt_stride, (long long)q_ld, (long long)o_ld);
+  if ((((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) || (dtype == VY_BF16 && ((uintptr_t)out & 7)))
+    VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: q / caches must be 16-byte aligned, out 8-byte aligned");
+  if (n_seq == 0 || max_q == 0) return VY_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == VY_F32) {
+    // the parity path: every row a single-query problem of the decode kernel, online softmax in fp32, one rounding
+    if (max_q > 65535) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: fp32 segments hold at most 65535 rows, max_q is %lld", (long long)max_q);
+    PagedDecArgs a{q, q_ld, nullptr, k_cache, v_cache, block_table, bt_stride, ctx_lens, out, o_ld, nullptr, nullptr,
+                   h, hk, dh, h / hk, lbs, (int)max_blocks, 1, scale, cu_q};
+    const int lpk = pd_lpk(dh, dtype);
+    if (lpk == 8) paged_prefill_f32_launch<8>(a, n_seq, max_q, st);
+    else if (lpk == 16) paged_prefill_f32_launch<16>(a, n_seq, max_q, st);
+    else if (lpk == 32) paged_prefill_f32_launch<32>(a, n_seq, max_q, st);
+    else paged_prefill_f32_launch<64>(a, n_seq, max_q, st);
+  } else {
+    const PagedPfArgs a{(const bf16*)q, q_ld, (const bf16*)k_cache, (const bf16*)v_cache, block_table, bt_stride, cu_q,
+                        ctx_lens, (bf16*)out, o_ld, h, hk, dh, lbs, (int)max_blocks, scale};
+    const dim3 grid((unsigned)(h * n_seq), (unsigned)vy_cdiv(max_q, 64)), block(256);
+    if (dh <= 64) hipLaunchKernelGGL(paged_prefill_kernel<64>, grid, block, 0, st, a);
+    else if (dh <= 96) hipLaunchKernelGGL(paged_prefill_kernel<96>, grid, block, 0, st, a);
+    else if (dh <= 128) hipLaunchKernelGGL(paged_prefill_kernel<128>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(paged_prefill_kernel<256>, grid, block, 0, st, a);
+  }
+  VY_CHECK_LAUNCH("vy_attn_paged_prefill");
   return VY_OK;
 }
 

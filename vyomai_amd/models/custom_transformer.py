@@ -468,17 +468,19 @@ class ModelForCausalLM(nn.Module):
         Per layer: input_layernorm, the packed QKV projection, vy_paged_rope_write (per-token RoPE in place + the K/V
         rows into their slots), attention -- vy_attn_paged_decode for the rows with one query token, causal vy_attn_fwd
         per prefilling sequence (straight on its slice of the packed buffer, or with start_pos = prefix_len against its
-        gathered pages when it starts from cached prefix blocks) -- o_proj with the residual, post_attention_layernorm
-        and the MLP as in DecoderLayer.forward.  Every token attends to its sequence's whole cached context, also in a
-        step that mixes the two phases.  The final norm and the tied head see one row per sequence (the notebook of
-        Examples/simple_vllm.ipynb projects all T rows and then indexes)."""
+        gathered pages when it starts from cached prefix blocks), or, when the engine runs with varlen_prefill
+        (metadata["prefill_varlen"]), ONE vy_attn_paged_prefill launch for every prefill row of the step, read through
+        the block tables: no gather, no loop, and a segment may be a chunk in the middle of its prompt -- o_proj with the
+        residual, post_attention_layernorm and the MLP as in DecoderLayer.forward.  Every token attends to its
+        sequence's whole cached context, also in a step that mixes the two phases.  The final norm and the tied head
+        see one row per sequence (the notebook of Examples/simple_vllm.ipynb projects all T rows and then indexes)."""
         _need_gpu(input_ids, "forward_paged()")
         base = self.model
         dev = input_ids.device
         x = base._embed(base.embed_tokens, input_ids.view(1, -1))[0]
         T, dt = x.shape[0], x.dtype
         cos, sin = base._rope_slice(0, int(metadata["max_position"])).table.on(dev)
-        slots, dec = metadata["slot_mapping"], metadata["decode"]
+        slots, dec, pv = metadata["slot_mapping"], metadata["decode"], metadata.get("prefill_varlen")
         for layer in base.layers[: self.config.num_hidden_layers]:
             a = layer.self_attn
             h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
@@ -490,7 +492,10 @@ class ModelForCausalLM(nn.Module):
             if dec is not None:
                 ops.attention_paged_decode(qkv, kc, vc, dec["block_table"], dec["seqlens"], dec["max_seqlen"], h,
                                            q_rows=dec["rows"], out=o)
-            for row0, rows, prefix_len, table in metadata["prefill"]:
+            if pv is not None:
+                ops.attention_paged_prefill(qkv, kc, vc, pv["block_table"], pv["cu_q"], pv["ctx_lens"], pv["max_q"],
+                                            pv["max_kv"], h, out=o)
+            for row0, rows, prefix_len, table in (() if pv is not None else metadata["prefill"]):
                 seg = qkv[row0:row0 + rows]
                 q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)
                 if prefix_len:
@@ -502,6 +507,8 @@ class ModelForCausalLM(nn.Module):
                               out=o[row0:row0 + rows].unsqueeze(0))
             x = ops.linear(o, _shadow(a.o_proj.weight, dt), None, residual=x)
             x = layer.mlp(layer.post_attention_layernorm(x), residual=x)
+        if metadata["last_rows"].numel() == 0:    # every sequence of the step is a chunk short of its prompt's end
+            return x.new_empty((0, self.lm_head.weight.shape[0]))
         last = base.norm(x.index_select(0, metadata["last_rows"]))
         return ops.linear(last, _shadow(self.lm_head.weight, dt))
 

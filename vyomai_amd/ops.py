@@ -929,6 +929,35 @@ def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_ta
     return out
 
 
+def attention_paged_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, cu_q: Tensor,
+                            ctx_lens: Tensor, max_q: int, max_kv: int, h: int, *, out: Optional[Tensor] = None,
+                            scale: Optional[float] = None) -> Tensor:
+    """Causal attention of packed query segments against the pages, one launch for all of them.  q (rows, >= h dh): rows
+    cu_q[s] .. cu_q[s+1] - 1 (int32, n + 1 entries) are sequence s, row i of it sits at position ctx_lens[s] + i (int32,
+    (n,)) and attends to keys [0, ctx_lens[s] + i] read through block_table[s] (int32, (n, width)); the step's own K/V
+    rows are already in the pages.  max_q >= every segment length, max_kv >= every ctx + length (host values).  out
+    (rows, h dh) is written at the segments' rows and returned.  (vy_attn_paged_prefill)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype)
+    _need_gpu(q, k_cache, v_cache, block_table, cu_q, ctx_lens, out)
+    n = ctx_lens.numel()
+    assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= h * dh
+    assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1 \
+        and block_table.shape[0] == n
+    assert cu_q.dtype == torch.int32 and cu_q.is_contiguous() and cu_q.numel() == n + 1
+    assert ctx_lens.dtype == torch.int32 and ctx_lens.is_contiguous()
+    assert 0 <= max_q <= q.shape[0] and max_kv <= block_table.shape[1] * bs
+    if out is None:
+        out = torch.empty((q.shape[0], h * dh), dtype=q.dtype, device=q.device)
+    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h * dh and out.dtype == q.dtype \
+        and out.shape[0] >= q.shape[0]
+    if scale is None:
+        scale = 1.0 / math.sqrt(dh)
+    call("vy_attn_paged_prefill", q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), nb, bs,
+         block_table.data_ptr(), block_table.stride(0), cu_q.data_ptr(), ctx_lens.data_ptr(), n, int(max_q), int(max_kv),
+         out.data_ptr(), out.stride(0), h, hk, dh, float(scale), dtype_code(q.dtype), _stream())
+    return out
+
+
 def paged_gather(k_cache: Tensor, v_cache: Tensor, block_table: Tensor, S: int) -> Tuple[Tensor, Tensor]:
     """Keys [0, S) of one sequence (block_table: its int32 entries) from the pages -> contiguous k, v (hk, S, dh).
     (vy_paged_gather)"""

@@ -1,8 +1,9 @@
 """Paged KV cache and continuous batching for ModelForCausalLM: the engine of the reference's
 Examples/simple_vllm.ipynb (its prefix-caching version) under the notebook's class names -- RadixNode, SequenceState,
 PagedKVManager, ContinuousBatchEngine -- serving this package's own model through vy_paged_rope_write,
-vy_attn_paged_decode, vy_paged_gather and vy_attn_fwd (ModelForCausalLM.forward_paged).  The notebook's Qwen3Model is a
-different network and is not reproduced; greedy decoding only.
+vy_attn_paged_decode, vy_paged_gather and vy_attn_fwd, or vy_attn_paged_prefill in their place
+(ModelForCausalLM.forward_paged).  The notebook's Qwen3Model is a different network and is not reproduced; greedy
+decoding only.
 
 The bookkeeping (tokens, block tables, slot mappings, the radix tree, the queues) lives on the host: the manager and the
 scheduler run without a GPU, and a step uploads its packed metadata once and reads the step's ids back once.  Only the
@@ -30,7 +31,22 @@ Where this departs from the notebook:
 
 As in the notebook: only blocks complete at allocation time (prompt blocks) are registered; free() moves registered
 blocks to the evictable queue and the others to the free list; eviction is oldest-first; RuntimeError("KV Cache full!")
-when nothing is free or evictable."""
+when nothing is free or evictable.
+
+Beyond the notebook, both off by default (the default engine's schedule, metadata and launches are as described above):
+
+* varlen_prefill: the step's rows are ordered decoding sequences first, and all prefill rows go through ONE
+  vy_attn_paged_prefill launch per layer (metadata["prefill_varlen"]: cu_q, ctx_lens, block tables, in the step's one
+  int32 upload) -- the notebook's single flash_attn_varlen_func call, with every key read from the pages, so neither the
+  per-sequence loop nor the gather after a prefix hit remains.
+* max_step_tokens = N >= max_batch_size (chunked prefill, implies varlen_prefill): every decoding sequence takes its one
+  token first, the rest of the budget goes to the prefilling sequences in admission order, min(prompt tokens left,
+  budget left) each; one that gets nothing sits the step out.  A chunk that stops short of its prompt's end emits no
+  token and has no logits row; the sequence stays is_prefill and SequenceState.num_computed counts what the pages hold.
+  N >= max_batch_size guarantees progress (while a sequence prefills, at most max_batch_size - 1 decode).
+  Invariant: a block is in the radix tree only if its rows are written by the end of the step that registered it -- so
+  a prompt block is registered in the step whose chunk writes its last row (PagedKVManager.allocate(state, upto)), also
+  one that an earlier chunk allocated and left part filled."""
 from __future__ import annotations
 
 import itertools
@@ -73,15 +89,27 @@ class SequenceState:
         if matched_blocks:
             self.block_table[:self.block_count] = torch.as_tensor(matched_blocks, dtype=torch.int32)
         self.slot_mapping = torch.zeros(self.max_total_len, dtype=torch.long)
+        # chunked prefill: num_computed prompt tokens are in the pages (from the prefix cache or from earlier chunks),
+        # this step's chunk ends at chunk_end (None: at the end of the prompt), blocks [0, blocks_registered) have been
+        # offered to the radix tree (or came from it)
+        self.num_computed = self.prefix_len
+        self.chunk_end: Optional[int] = None
+        self.blocks_registered = len(matched_blocks)
 
     @property
     def query_start(self) -> int:
-        """First token of this step's query rows: everything past the cached prefix while prefilling, then the last."""
-        return self.prefix_len if self.is_prefill else self.num_tokens - 1
+        """First token of this step's query rows: everything past what the pages already hold while prefilling (the
+        cached prefix, and the chunks of earlier steps), then the last."""
+        return self.num_computed if self.is_prefill else self.num_tokens - 1
+
+    @property
+    def query_end(self) -> int:
+        """One past the last token of this step's query rows: the chunk's end while a prompt goes in chunks."""
+        return self.chunk_end if self.is_prefill and self.chunk_end is not None else self.num_tokens
 
     def update_metadata(self) -> None:
         """slot = block_table[i // block_size] * block_size + i % block_size for the tokens this step computes."""
-        idx = torch.arange(self.query_start, self.num_tokens)
+        idx = torch.arange(self.query_start, self.query_end)
         self.slot_mapping[idx] = self.block_table[idx // self.block_size].long() * self.block_size + idx % self.block_size
 
 
@@ -142,10 +170,20 @@ class PagedKVManager:
         return len(self.free_blocks) + len(self.evictable_blocks) - held_back
 
     # ---- allocation ------------------------------------------------------------------------------------------
-    def allocate(self, state: SequenceState) -> None:
-        """Blocks for state.num_tokens tokens; a block whose tokens are all known now (a prompt block) is registered."""
+    def allocate(self, state: SequenceState, upto: Optional[int] = None) -> None:
+        """Blocks for state.num_tokens tokens; a block whose tokens are all known now (a prompt block) is registered.
+        upto (chunked prefill): blocks for the first `upto` tokens only, and only the prompt blocks that lie wholly in
+        front of `upto` are registered -- also one that an earlier chunk allocated and left part filled.  The caller
+        computes tokens [.., upto) in this step, so a block is in the tree only if its rows are written by the end of
+        the step that registered it."""
         bs = self.block_size
-        while state.block_count < self.blocks_for(state.num_tokens):
+        end = state.num_tokens if upto is None else upto
+        whole = min(end, state.prompt_len) // bs           # prompt blocks complete once this step has run
+        while state.blocks_registered < min(state.block_count, whole):
+            i = state.blocks_registered
+            self._register_block(state, i, int(state.block_table[i]))
+            state.blocks_registered = i + 1
+        while state.block_count < self.blocks_for(end):
             if not self.free_blocks:
                 if not self.evictable_blocks:
                     raise RuntimeError("KV Cache full!")
@@ -153,8 +191,9 @@ class PagedKVManager:
             new_block = self.free_blocks.popleft()
             i = state.block_count
             state.block_table[i] = new_block
-            if state.num_tokens >= (i + 1) * bs:
+            if i < whole:
                 self._register_block(state, i, new_block)
+                state.blocks_registered = i + 1
             state.block_count += 1
 
     def _register_block(self, state: SequenceState, i: int, block_id: int) -> None:
@@ -205,11 +244,24 @@ class ContinuousBatchEngine:
     returns the sequences that finished in this step as {sid: token list}.  Stop tokens: `eos_token_ids` (default: the
     model config's eos_token_id); the notebook hard-codes Qwen's two ids.
 
-    prompt_tokens_computed[sid]: prompt tokens that went through the model (the rest came from the prefix cache).
+    max_step_tokens / varlen_prefill: chunked prefill and the one varlen prefill launch (module docstring); with both at
+    None the engine prefills a prompt in one step, one attention launch per prefilling sequence.
+
+    prompt_tokens_computed[sid]: prompt tokens that went through the model so far (the rest came from the prefix cache).
     record_logits=True keeps every step's last-row logits per sequence in `logits[sid]` (fp32, host): a debug aid."""
 
     def __init__(self, model, kv_mgr: PagedKVManager, max_batch_size: int = 8, eos_token_ids=None,
-                 record_logits: bool = False):
+                 record_logits: bool = False, max_step_tokens: Optional[int] = None,
+                 varlen_prefill: Optional[bool] = None):
+        if varlen_prefill is None:
+            varlen_prefill = max_step_tokens is not None
+        if max_step_tokens is not None:
+            if not varlen_prefill:
+                raise ValueError("max_step_tokens needs varlen_prefill: a chunk attends to pages of its own prompt")
+            if max_step_tokens < max_batch_size:
+                raise ValueError(f"max_step_tokens {max_step_tokens} must be at least max_batch_size {max_batch_size}: "
+                                 "every decoding sequence takes a token and a prefilling one must still progress")
+        self.max_step_tokens, self.varlen_prefill = max_step_tokens, bool(varlen_prefill)
         self.model, self.kv_mgr = model, kv_mgr
         if model is not None:
             model.eval()
@@ -255,32 +307,49 @@ class ContinuousBatchEngine:
     def _prepare_inference_data(self, states: List[SequenceState]):
         """-> (metadata, input_ids): the step's packed token ids and positions, their slots, and per phase what the
         attention needs -- for the decoding sequences their rows, block tables and lengths, for each prefilling one
-        (first row, rows, prefix_len, its block table)."""
+        (first row, rows, prefix_len, its block table).  last_rows has one row per sequence whose query rows reach its
+        last token (all of them unless a prompt goes in chunks).
+
+        varlen_prefill: `states` holds the decoding sequences first, so the prefill rows are one contiguous run, and
+        metadata["prefill_varlen"] = {cu_q, ctx_lens, block_table (n, width), max_q, max_kv} describes all of them for
+        ONE vy_attn_paged_prefill launch (cu_q counts rows of the packed buffer); metadata["prefill"] is then empty."""
         ids, pos, slots, cu, last = [], [], [], [0], []
         dec_rows, dec_lens, dec_tables, prefill = [], [], [], []
+        pf_cu, pf_ctx, pf_tables, pf_max_q, pf_max_kv = [], [], [], 0, 0
         width = max(s.block_table.numel() for s in states)
         for s in states:
-            a, b = s.query_start, s.num_tokens
+            a, b = s.query_start, s.query_end
             ids += s.tokens[a:b].tolist()
             pos += range(a, b)
             slots += s.slot_mapping[a:b].tolist()
             table = s.block_table[:s.block_count].tolist()
-            if s.is_prefill:
-                prefill.append((cu[-1], b - a, a, table if a else None))
-            else:
+            if not s.is_prefill:
+                assert not pf_cu, "decoding sequences come first"
                 dec_rows.append(cu[-1])
                 dec_lens.append(b)
                 dec_tables += table + [0] * (width - len(table))
+            elif self.varlen_prefill:
+                pf_cu.append(cu[-1])
+                pf_ctx.append(a)
+                pf_tables += table + [0] * (width - len(table))
+                pf_max_q, pf_max_kv = max(pf_max_q, b - a), max(pf_max_kv, b)
+            else:
+                prefill.append((cu[-1], b - a, a, table if a else None))
             cu.append(cu[-1] + b - a)
-            last.append(cu[-1] - 1)
+            if b == s.num_tokens:
+                last.append(cu[-1] - 1)
         # two uploads: everything int64 (ids | slots | last rows) and everything int32 (positions | decode rows |
-        # decode lengths | decode block tables | the block table of each prefill that starts from a cached prefix)
-        T, nd = cu[-1], len(dec_rows)
+        # decode lengths | decode block tables | the block table of each prefill that starts from a cached prefix, or
+        # with varlen_prefill: cu_q | ctx_lens | the prefill block tables)
+        T, nd, npf = cu[-1], len(dec_rows), len(pf_cu)
         i32 = pos + dec_rows + dec_lens + dec_tables
         for k, (row0, rows, prefix_len, table) in enumerate(prefill):
             if table is not None:
                 prefill[k] = (row0, rows, prefix_len, (len(i32), len(table)))
                 i32 += table
+        pf0 = len(i32)
+        if npf:
+            i32 += pf_cu + [T] + pf_ctx + pf_tables
         l64 = torch.tensor(ids + slots + last, dtype=torch.long).to(self.device)
         i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
         prefill = [(r0, n, pl, None if t is None else i32[t[0]:t[0] + t[1]]) for r0, n, pl, t in prefill]
@@ -296,27 +365,58 @@ class ContinuousBatchEngine:
             o = T + 2 * nd
             metadata["decode"] = {"rows": i32[T:T + nd], "seqlens": i32[T + nd:o],
                                   "block_table": i32[o:o + nd * width].view(nd, width), "max_seqlen": max(dec_lens)}
+        if npf:
+            o = pf0 + 2 * npf + 1
+            metadata["prefill_varlen"] = {"cu_q": i32[pf0:pf0 + npf + 1], "ctx_lens": i32[pf0 + npf + 1:o],
+                                          "block_table": i32[o:o + npf * width].view(npf, width),
+                                          "max_q": pf_max_q, "max_kv": pf_max_kv}
         return metadata, l64[:T]
+
+    def _schedule_step(self) -> List[SequenceState]:
+        """The sequences of this step, in the order of their rows.  Default: every running sequence, in admission
+        order, a prefilling one with all its unseen prompt tokens.  varlen_prefill: the decoding sequences first (one
+        token each), then the prefilling ones in admission order; under max_step_tokens each of those gets
+        min(prompt tokens left, budget left) and one that gets nothing sits the step out."""
+        states = list(self.active.values())
+        if not self.varlen_prefill:
+            return states
+        run = [s for s in states if not s.is_prefill]
+        budget = None if self.max_step_tokens is None else self.max_step_tokens - len(run)
+        for s in states:
+            if not s.is_prefill:
+                continue
+            left = s.prompt_len - s.num_computed
+            n = left if budget is None else min(left, budget)
+            if n <= 0:
+                continue
+            if budget is not None:
+                budget -= n
+            s.chunk_end = s.num_computed + n
+            run.append(s)
+        return run
 
     def step(self) -> Dict[int, List[int]]:
         self._try_schedule_waiting()
         if not self.active:
             return {}
-        states = list(self.active.values())
+        states = self._schedule_step()
         for s in states:
-            self.kv_mgr.allocate(s)
+            self.kv_mgr.allocate(s, s.query_end)
             s.update_metadata()
             if s.is_prefill:
-                self.prompt_tokens_computed[s.id] = s.num_tokens - s.prefix_len
+                self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
         metadata, input_ids = self._prepare_inference_data(states)
         logits = self.model.forward_paged(input_ids, metadata["positions"], metadata, self.kv_mgr)
         next_tokens = torch.argmax(logits, dim=-1).tolist()          # the step's one device-to-host copy
+        emitting = [s for s in states if s.query_end == s.num_tokens]   # (a chunk short of its prompt's end: no token)
         if self.record_logits:
             host = logits.float().cpu()
-            for i, s in enumerate(states):
+            for i, s in enumerate(emitting):
                 self.logits.setdefault(s.id, []).append(host[i])
+        for s in states:
+            s.num_computed, s.chunk_end = s.query_end, None
         finished = {}
-        for s, token_id in zip(states, next_tokens):
+        for s, token_id in zip(emitting, next_tokens):
             s.is_prefill = False
             s.tokens[s.num_tokens] = token_id
             s.num_tokens += 1
