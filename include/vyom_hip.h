@@ -145,7 +145,7 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
 /* ------------------------------------------------------------------------------------------
  * Paged KV cache (Examples/simple_vllm.ipynb cell 2).  Per layer k_cache / v_cache are (max_blocks, block_size, hk, dh),
  * contiguous; slot = block * block_size + offset.  block_size: a power of two from 8 to 256; dh: a multiple of 8 up to
- * 256; bf16 and fp32.  Anything else is VY_ERR_ARG before a launch.  None of the four allocates.
+ * 256; bf16 and fp32.  Anything else is VY_ERR_ARG before a launch.  None of these entry points allocates.
  *
  * vy_paged_rope_write: after the packed QKV projection of a step's T tokens (qkv[T][ld], rows [q heads; k heads; v
  *   heads] of dh columns): token t's q and k heads are rotated IN PLACE with row positions[t] (int32, device) of the
@@ -154,6 +154,16 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
  *   (or one past the pages) writes nothing; a position outside the table is clamped into it.
  *   replaces: apply_rope on q and k with the gathered metadata['cos'] / ['sin'] rows and the
  *   `k_cache[b_idx, o_idx] = k`, `v_cache[b_idx, o_idx] = v` scatters of GroupedQueryAttention.forward.
+ *
+ * vy_paged_qknorm_rope_write: vy_paged_rope_write with the per-head RMSNorm of Qwen3's qk_norm in front of the rotation,
+ *   in the same launch: every q head is replaced by n = x * rsqrt(mean_d(x^2) + eps) * q_scale, every k head by the same
+ *   with k_scale (fp32 [dh], device, 16-byte aligned, shared by all heads of their kind; eps >= 0), and n is what gets
+ *   rotated, stored in place and, for k, stored into the slot.  Everything between the load and the one store is fp32.
+ *   v heads are neither normalised nor rotated.  An all-zero head stays zero (0 * rsqrt(eps)).  Shapes, alignment, slot
+ *   and position rules are those of vy_paged_rope_write.
+ *   replaces: `q, k = self.q_norm(q), self.k_norm(k)` (RMSNorm.forward on the (tokens, heads, head_dim) views) plus
+ *   everything vy_paged_rope_write replaces.  The notebook's bf16 model rounds to bf16 after the norm and rotates in
+ *   bf16 with bf16 tables; here there is one rounding, at the store.
  *
  * vy_attn_paged_decode: one query token per sequence against its pages.  q row of sequence b: q + row * q_ld with
  *   row = q_rows ? q_rows[b] : b (int32, device), heads of dh columns side by side; out (row stride o_ld >= h * dh) is
@@ -194,6 +204,11 @@ int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positions, const i
                         const float* cos_tab, const float* sin_tab, int64_t table_rows, void* k_cache,
                         void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh,
                         int dtype, void* stream);
+int vy_paged_qknorm_rope_write(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
+                               const float* cos_tab, const float* sin_tab, int64_t table_rows,
+                               const float* q_scale, const float* k_scale, float eps, void* k_cache,
+                               void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh,
+                               int dtype, void* stream);
 int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* q_rows, const void* k_cache,
                          const void* v_cache, int64_t max_blocks, int block_size,
                          const int32_t* block_table, int64_t bt_stride, const int32_t* seqlens,

@@ -14,6 +14,8 @@ from .models.multimodel import VisionLanguageModel  # noqa: F401
 from .models.encoder_decoder import EncoderDecoderModel  # noqa: F401
 from .models.custom_transformer import (Config, MLP, Attention, RMSNorm, DecoderLayer, BaseModel,  # noqa: F401
                                          ModelForCausalLM)
+from .models import qwen3  # noqa: F401
+from .models.qwen3 import Qwen3Model, load_weights_into_qwen  # noqa: F401
 from .serving import RadixNode, SequenceState, PagedKVManager, ContinuousBatchEngine  # noqa: F401
 from .generation_utils import generate, generate_multimodel, generate_seq2seq  # noqa: F401
 from .logits_processors import (LogitsProcessor, GreedyProcessor, MultinomialProcessor, TopKProcessor,  # noqa: F401

@@ -34,6 +34,8 @@ PROTOTYPES = {
     "vy_attn_decode": [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64,
                        _p, _i64, _i64, _i, _i, _i64, _i, _f, _i, _p],
     "vy_paged_rope_write": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _i, _i64, _i, _i, _i, _i, _p],
+    "vy_paged_qknorm_rope_write": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _f, _p, _p, _i64, _i, _i64, _i, _i, _i, _i,
+                                   _p],
     "vy_attn_paged_decode": [_p, _i64, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i, _i, _i, _f, _i,
                              _p, _i64, _i, _p],
     "vy_attn_paged_prefill": [_p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _i, _i, _i, _f,

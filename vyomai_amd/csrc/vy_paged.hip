@@ -279,6 +279,89 @@ __global__ __launch_bounds__(256) void paged_rope_write_kernel(T* __restrict__ q
   Quad<T>::store(dst + half + i4, hi);
 }
 
+// sum over the 1 << lg lanes of a lane group (aligned to its size inside the wave, at most 32 lanes), in every lane of
+// it.  lg is wave-uniform, so the steps are scalar branches; the DPP steps and the row swap read neighbouring lanes,
+// so EVERY lane of the wave must arrive here (no early return, no divergent branch around the call).
+__device__ __forceinline__ float pow2_group_sum(float v, int lg) {
+  if (lg >= 1) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+  if (lg >= 2) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
+  if (lg >= 3) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false));  // row_half_mirror
+  if (lg >= 4) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
+  if (lg >= 5) {   // the neighbouring row of 16
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    v = __builtin_bit_cast(float, (unsigned)s16[0]) + __builtin_bit_cast(float, (unsigned)s16[1]);
+  }
+  return v;
+}
+
+// paged_rope_write_kernel with the per-head RMSNorm of q and k in front of the rotation (Qwen3's qk_norm).  A (token,
+// head) unit is a group of 1 << lg lanes -- the head's dh / 8 column pairs of the mapping above, rounded up to a power of
+// two, so a group never straddles a wave; the surplus lanes (4 of 16 at dh = 96, 4 of 32 at dh = 224) and the lanes past
+// the last unit load nothing, take part in the reduction with zeros and store nothing.  Per q / k head, all in fp32:
+// sum of squares (8 per lane as an fma chain, then the group sum), r = rsqrt(sum / dh + eps), n = x * r * scale, the
+// rotation of n, ONE rounding at the store.  An all-zero head gives 0 * rsqrt(eps) = 0.  v heads are neither normalised
+// nor rotated; they go through the page store as before.
+template <typename T>
+__global__ __launch_bounds__(256) void paged_qknorm_rope_write_kernel(T* __restrict__ qkv, long long ld,
+                                                                      const int* __restrict__ positions,
+                                                                      const long long* __restrict__ slots,
+                                                                      const float* __restrict__ cos_tab,
+                                                                      const float* __restrict__ sin_tab, long long table_rows,
+                                                                      const float* __restrict__ q_scale,
+                                                                      const float* __restrict__ k_scale, float eps,
+                                                                      float inv_dh, T* __restrict__ kc, T* __restrict__ vc,
+                                                                      long long n_slots, long long units, int lg, int h,
+                                                                      int hk, int dh) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int half = dh >> 1, qn = half >> 2, H3 = h + 2 * hk;
+  const long long unit = idx >> lg;
+  const int ch = (int)(idx & ((1 << lg) - 1));
+  const bool on = unit < units && ch < qn;
+  const long long uc = on ? unit : 0;                 // (an idle lane computes on unit 0's indices and touches no memory)
+  const int i4 = on ? ch * 4 : 0;
+  const int hd = (int)(uc % H3);
+  const long long t = uc / H3;
+  T* row = qkv + t * ld + (long long)hd * dh;
+  float lo[4] = {0.f, 0.f, 0.f, 0.f}, hi[4] = {0.f, 0.f, 0.f, 0.f};
+  if (on) {
+    Quad<T>::load(row + i4, lo);
+    Quad<T>::load(row + half + i4, hi);
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ss = fmaf(lo[e], lo[e], ss);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ss = fmaf(hi[e], hi[e], ss);
+  ss = pow2_group_sum(ss, lg);                        // every lane of the wave, also the idle ones
+  if (!on) return;
+  if (hd < h + hk) {
+    const float r = rsqrtf(fmaf(ss, inv_dh, eps));
+    const float* sc = hd < h ? q_scale : k_scale;
+    const f32x4 wl = *reinterpret_cast<const f32x4*>(sc + i4);
+    const f32x4 wh = *reinterpret_cast<const f32x4*>(sc + half + i4);
+    long long pos = positions[t];
+    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
+    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
+    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = lo[e] * r * wl[e], bb = hi[e] * r * wh[e];
+      lo[e] = a * c[e] - bb * s[e];
+      hi[e] = bb * c[e] + a * s[e];
+    }
+    Quad<T>::store(row + i4, lo);
+    Quad<T>::store(row + half + i4, hi);
+  }
+  if (hd < h) return;
+  const long long slot = slots[t];
+  if (slot < 0 || slot >= n_slots) return;
+  const bool isk = hd < h + hk;
+  T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
+  Quad<T>::store(dst + i4, lo);   // (k: rounded exactly as the in-place store rounds them; v: the loaded bits)
+  Quad<T>::store(dst + half + i4, hi);
+}
+
 // thread = (K or V, key j, KV head, 16-byte chunk): out[kvh][j] = cache[block_table[j / block_size]][j % block_size][kvh]
 template <typename T>
 __global__ __launch_bounds__(256) void paged_gather_kernel(const T* __restrict__ kc, const T* __restrict__ vc,
@@ -686,6 +769,44 @@ extern "C" int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positio
                        n_slots, total, h, hk, dh);
   else VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: bad dtype %d", dtype);
   VY_CHECK_LAUNCH("vy_paged_rope_write");
+  return VY_OK;
+}
+
+extern "C" int vy_paged_qknorm_rope_write(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
+                                          const float* cos_tab, const float* sin_tab, int64_t table_rows,
+                                          const float* q_scale, const float* k_scale, float eps, void* k_cache,
+                                          void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk,
+                                          int dh, int dtype, void* stream) {
+  if (!qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !q_scale || !k_scale || !k_cache || !v_cache)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: null operand");
+  if (log2_block_size(block_size) < 0)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: block_size %d must be a power of two from 8 to 256", block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: dh %d must be a multiple of 8 up to 256", dh);
+  if (T <= 0 || h <= 0 || hk <= 0 || max_blocks <= 0 || table_rows <= 0 || ld < (int64_t)(h + 2 * hk) * dh)
+    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: bad shape (T %lld, h %d, hk %d, ld %lld)", (long long)T, h, hk, (long long)ld);
+  if (!(eps >= 0.f)) VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: eps %g must not be negative", (double)eps);
+  if (ld % 4 || (((uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)q_scale | (uintptr_t)k_scale | (uintptr_t)qkv |
+                  (uintptr_t)k_cache | (uintptr_t)v_cache) & 15))
+    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: ld must be a multiple of 4, operands 16-byte aligned");
+  int lg = 0;                                         // lanes per (token, head): dh / 8 rounded up to a power of two
+  while ((1 << lg) < dh / 8) ++lg;
+  const int64_t units = T * (h + 2 * hk);
+  const int64_t blocks = vy_cdiv(units << lg, 256);
+  if (blocks > INT32_MAX) VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: T %lld is more than one launch holds", (long long)T);
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n_slots = max_blocks * block_size;
+  const float inv_dh = 1.0f / (float)dh;
+  if (dtype == VY_BF16)
+    hipLaunchKernelGGL(paged_qknorm_rope_write_kernel<bf16>, grid, block, 0, st, (bf16*)qkv, ld, positions,
+                       (const long long*)slot_mapping, cos_tab, sin_tab, table_rows, q_scale, k_scale, eps, inv_dh,
+                       (bf16*)k_cache, (bf16*)v_cache, n_slots, units, lg, h, hk, dh);
+  else if (dtype == VY_F32)
+    hipLaunchKernelGGL(paged_qknorm_rope_write_kernel<float>, grid, block, 0, st, (float*)qkv, ld, positions,
+                       (const long long*)slot_mapping, cos_tab, sin_tab, table_rows, q_scale, k_scale, eps, inv_dh,
+                       (float*)k_cache, (float*)v_cache, n_slots, units, lg, h, hk, dh);
+  else VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: bad dtype %d", dtype);
+  VY_CHECK_LAUNCH("vy_paged_qknorm_rope_write");
   return VY_OK;
 }
 

@@ -892,6 +892,28 @@ def paged_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos:
     return qkv
 
 
+def paged_qknorm_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos: Tensor, sin: Tensor,
+                             q_scale: Tensor, k_scale: Tensor, eps: float, h: int, k_cache: Tensor,
+                             v_cache: Tensor) -> Tensor:
+    """paged_rope_write_ with Qwen3's qk_norm in the same launch: every q head becomes x * rsqrt(mean x^2 + eps) *
+    q_scale, every k head the same with k_scale (fp32 (dh,), shared by all heads), and the normalised head is what is
+    rotated, stored in place and (k) stored into its slot; fp32 from the load to the one store.  v heads are only
+    stored into their slots.  (vy_paged_qknorm_rope_write)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype)
+    _need_gpu(qkv, positions, slot_mapping, cos, sin, q_scale, k_scale, k_cache, v_cache)
+    T = qkv.shape[0]
+    assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (h + 2 * hk) * dh
+    assert positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == T
+    assert slot_mapping.dtype == torch.long and slot_mapping.is_contiguous() and slot_mapping.numel() == T
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == dh // 2 and sin.shape == cos.shape
+    for s in (q_scale, k_scale):
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.shape == (dh,)
+    call("vy_paged_qknorm_rope_write", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
+         cos.data_ptr(), sin.data_ptr(), cos.shape[0], q_scale.data_ptr(), k_scale.data_ptr(), float(eps),
+         k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, T, h, hk, dh, dtype_code(qkv.dtype), _stream())
+    return qkv
+
+
 def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, seqlens: Tensor,
                            max_seqlen: int, h: int, *, q_rows: Optional[Tensor] = None, out: Optional[Tensor] = None,
                            n_split: int = 0, scale: Optional[float] = None) -> Tensor:
