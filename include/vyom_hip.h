@@ -553,6 +553,22 @@ int vy_greedy_step(const void* logits, int64_t ldl, int64_t B, int64_t V, int dt
                    const int64_t* eos_ids, int32_t n_eos, uint8_t* eos_reached, int32_t* not_done, void* stream);
 int vy_sampling_probs(const void* logits, int64_t ldl, int64_t B, int64_t V, int dtype, float temperature,
                       int32_t top_k, float top_p, float* probs, int64_t ldp, void* stream);
+/* vy_sample_rows: the processors above (reference logits_processors.py:13-16, 59-63, 73-81, 92-102) and their
+ *   torch.multinomial draw (:48-49) for the R rows of one serving step, every row with its own parameters (all five
+ *   arrays: device, length R), in ONE launch that writes nothing but tokens[r] in [0, V).
+ *   inv_temperature[r] == 0: a greedy row, tokens[r] = argmax_v logits[r, v], lowest index among equal maxima; the
+ *   row's other parameters are not read.  Otherwise tokens[r] = argmax over the kept columns v of
+ *   fmaf(logits[r, v], inv_temperature[r], noise(v)), lowest index among equal scores, where the kept set is exactly
+ *   the support of vy_sampling_probs for top_k[r] / top_p[r] (<= 0 or >= V, <= 0 or >= 1: that filter is off; the two
+ *   kernels share the selection code) and noise(v) is vy_gumbel_noise's value at row 0, column v for
+ *   (seed[r], offset = counter[r]) -- the noise row is always 0, so a draw does not depend on where the row sits in
+ *   the launch.  seed[r] carries the 64-bit seed's bit pattern.  argmax(x / T + Gumbel) is a draw from
+ *   softmax(x / T) over the kept set.  A row without a filter is read once; columns V .. ldl - 1 are never read.
+ *   inv_temperature must be >= 0 and not NaN (the caller's duty: the kernel cannot report it).
+ *   VY_ERR_ARG: a null pointer, R <= 0, V <= 0, V > 0x7ffffff0, ldl < V, an unknown dtype. */
+int vy_sample_rows(const void* logits, int64_t ldl, int64_t R, int64_t V, int dtype, const float* inv_temperature,
+                   const int32_t* top_k, const float* top_p, const int64_t* seed, const int64_t* counter,
+                   int64_t* tokens, void* stream);
 
 /* y = x converted between fp32 and bf16 (n elements). src_dtype -> dst_dtype. */
 int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);

@@ -307,7 +307,7 @@ __device__ __forceinline__ bool vy_drop_keep(const VyDrop& d, const uint32_t (&r
 struct VyNoise {
   uint32_t seed_lo, seed_hi, off_lo, off_hi;
 };
-__host__ inline VyNoise vy_make_noise(uint64_t seed, uint64_t offset) {
+__host__ __device__ inline VyNoise vy_make_noise(uint64_t seed, uint64_t offset) {
   return VyNoise{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
 }
 // the four words of columns 4 * quad .. 4 * quad + 3 of row m

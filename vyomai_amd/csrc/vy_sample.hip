@@ -1,6 +1,8 @@
 // Sampling front end of the generate loops: the per-token work after the LM head.
 //   vy_greedy_step     reference models/decoder.py:478-507 (top-1, prompt forcing, EOS bookkeeping)
 //   vy_sampling_probs  reference logits_processors.py:13-16, 59-63, 73-81, 92-102
+//   vy_sample_rows     the same processors (:13-16, 59-63, 73-81, 92-102) and their multinomial draw, per row of a
+//                      serving step: Examples/simple_vllm.ipynb decodes greedily, this is its step with sampling
 // One 1024-thread workgroup per row.  Selection (k-th largest value, nucleus cut) is a radix search over
 // 4-bit digits of an order-preserving key: every thread keeps the 16 bin counts / masses of its own
 // elements in registers and the workgroup adds them in a fixed order -- no atomics, so the result
@@ -35,6 +37,7 @@ __device__ __forceinline__ void block_sum(A (&v)[NR], A* red /* [SW][NR] */) {
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     A x = 0;
+#pragma unroll 1   // (unrolled, the SW * NR loads are all hoisted and the selection kernels spill 600 bytes a lane)
     for (int w = 0; w < SW; ++w) x += red[w * NR + r];
     v[r] = x;
   }
@@ -224,20 +227,13 @@ __global__ __launch_bounds__(64) void greedy_finish_kernel(int nch, int64_t* __r
   }
 }
 
+// ---- selection shared by vy_sampling_probs and vy_sample_rows ----------------------------------------
+// -> the key of the smallest kept value (0: the whole row is kept).  m is the row maximum and is read only when top_p is
+// on.  Every thread returns the same key; fred / ired are free again on return.
 template <typename T>
-__global__ __launch_bounds__(ST) void sampling_probs_kernel(const T* __restrict__ logits, int64_t ldl, int V,
-                                                            float inv_t, int top_k, float top_p,
-                                                            float* __restrict__ probs, int64_t ldp) {
-  __shared__ float fred[SW * 16];
-  __shared__ int ired[SW * 16];
+__device__ __forceinline__ unsigned select_keep_key(const T* __restrict__ row, int V, int top_k, float top_p, float m,
+                                                    float* fred /* [SW * 16] */, int* ired /* [SW * 16] */) {
   const int tid = threadIdx.x;
-  const T* row = logits + (int64_t)blockIdx.x * ldl;
-  float* out = probs + (int64_t)blockIdx.x * ldp;
-
-  float m = -INFINITY;
-  for (int i = tid; i < V; i += ST) m = fmaxf(m, ldf(row, i));
-  m = block_max(m, fred);
-
   // ---- top-k: key of the k-th largest value (values equal to it are all kept, reference :59-63) ----
   unsigned keep_key = 0;
   if (top_k > 0 && top_k < V) {
@@ -312,6 +308,24 @@ __global__ __launch_bounds__(ST) void sampling_probs_kernel(const T* __restrict_
     keep_key = prefix > keep_key ? prefix : keep_key;
   }
 
+  return keep_key;
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST) void sampling_probs_kernel(const T* __restrict__ logits, int64_t ldl, int V,
+                                                            float inv_t, int top_k, float top_p,
+                                                            float* __restrict__ probs, int64_t ldp) {
+  __shared__ float fred[SW * 16];
+  __shared__ int ired[SW * 16];
+  const int tid = threadIdx.x;
+  const T* row = logits + (int64_t)blockIdx.x * ldl;
+  float* out = probs + (int64_t)blockIdx.x * ldp;
+
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += ST) m = fmaxf(m, ldf(row, i));
+  m = block_max(m, fred);
+  const unsigned keep_key = select_keep_key(row, V, top_k, top_p, m, fred, ired);
+
   float zt[1] = {0.f};
   for (int i = tid; i < V; i += ST) {
     const float v = ldf(row, i);
@@ -322,6 +336,106 @@ __global__ __launch_bounds__(ST) void sampling_probs_kernel(const T* __restrict_
   for (int i = tid; i < V; i += ST) {
     const float v = ldf(row, i);
     out[i] = fkey(v) >= keep_key ? expf((v - m) * inv_t) * rz : 0.f;
+  }
+}
+
+// ---- per-request sampling of the serving engine: one launch for the step's rows ---------------------
+// Row r draws argmax over its kept columns of fmaf(logit, inv_temperature[r], gumbel(seed[r], counter[r], noise row 0,
+// column)): Gumbel-max needs no normaliser, so nothing is written but the token.  inv_temperature[r] == 0 is a greedy
+// row (plain arg-max; its other parameters are not read).  A row without a filter is read once; a filtered row runs
+// select_keep_key first (re-reading the row from L2) and pays for noise only on the columns it kept.  One workgroup per
+// row: every branch on the row's parameters is workgroup-uniform.
+template <typename T> struct Quad;
+template <> struct Quad<float> { typedef f32x4 Raw; };
+template <> struct Quad<bf16> { typedef bf16x4 Raw; };
+
+template <typename T, bool SAMPLE>
+__device__ __forceinline__ void scan_row(const T* __restrict__ row, int V, float inv_t, unsigned keep_key, const VyNoise& nz,
+                                         float& best_v, int& best_i) {
+  typedef typename Quad<T>::Raw Raw;
+  constexpr int U = 4;   // quads in flight per thread: all loads of a trip are issued before the first compare
+  const int tid = threadIdx.x, nq = (V + 3) >> 2;
+  // whole quads of an aligned row are one load; the tail quad and unaligned rows go column by column
+  const int nvec = (reinterpret_cast<uintptr_t>(row) & (sizeof(Raw) - 1)) == 0 ? V >> 2 : 0;
+  for (int q0 = 0; q0 < nq; q0 += ST * U) {
+    float v[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int q = q0 + u * ST + tid;
+      if (q < nvec) {
+        const Raw t = *reinterpret_cast<const Raw*>(row + (int64_t)q * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[u][e] = (float)t[e];
+      } else if (q < nq) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[u][e] = q * 4 + e < V ? ldf(row, q * 4 + e) : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int q = q0 + u * ST + tid;
+      if (q >= nq) continue;
+      if constexpr (SAMPLE) {
+        bool kept[4], any = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { kept[e] = q * 4 + e < V && fkey(v[u][e]) >= keep_key; any |= kept[e]; }
+        if (any) {
+          uint32_t r[4];
+          vy_noise_words(nz, 0, q, r);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (kept[e]) gp_take(fmaf(v[u][e], inv_t, vy_gumbel(r[e])), q * 4 + e, best_v, best_i);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (q * 4 + e < V) gp_take(v[u][e], q * 4 + e, best_v, best_i);
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST) void sample_rows_kernel(const T* __restrict__ logits, int64_t ldl, int V,
+                                                         const float* __restrict__ inv_temperature,
+                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                         const int64_t* __restrict__ seed, const int64_t* __restrict__ counter,
+                                                         int64_t* __restrict__ tokens) {
+  __shared__ float fred[SW * 16];
+  __shared__ int ired[SW * 16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const T* row = logits + (int64_t)r * ldl;
+  const float inv_t = inv_temperature[r];
+  int best_i = 0x7fffffff;
+  float best_v = -INFINITY;
+  if (inv_t == 0.f) {
+    scan_row<T, false>(row, V, 0.f, 0u, VyNoise{}, best_v, best_i);
+  } else {
+    const int k = top_k[r];
+    const float p = top_p[r];
+    const bool k_on = k > 0 && k < V, p_on = p > 0.f && p < 1.f;
+    unsigned keep_key = 0;
+    if (k_on || p_on) {
+      float m = -INFINITY;
+      if (p_on) {
+        for (int i = tid; i < V; i += ST) m = fmaxf(m, ldf(row, i));
+        m = block_max(m, fred);
+      }
+      keep_key = select_keep_key(row, V, k, p, m, fred, ired);
+    }
+    scan_row<T, true>(row, V, inv_t, keep_key, vy_make_noise((uint64_t)seed[r], (uint64_t)counter[r]), best_v, best_i);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best_v, o, 64);
+    const int oi = __shfl_xor(best_i, o, 64);
+    gp_merge(ov, oi, best_v, best_i);
+  }
+  if (lane == 0) { fred[wave] = best_v; ired[wave] = best_i; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < SW; ++w) gp_merge(fred[w], ired[w], best_v, best_i);
+    tokens[r] = best_i == 0x7fffffff ? 0 : best_i;   // nothing comparable in the row (NaNs): token 0, as vy_greedy_step
   }
 }
 
@@ -377,5 +491,24 @@ extern "C" int vy_sampling_probs(const void* logits, int64_t ldl, int64_t B, int
                        1.0f / temperature, (int)top_k, top_p, probs, ldp);
   else VY_FAIL(VY_ERR_ARG, "vy_sampling_probs: bad dtype %d", dtype);
   VY_CHECK_LAUNCH("vy_sampling_probs");
+  return VY_OK;
+}
+
+extern "C" int vy_sample_rows(const void* logits, int64_t ldl, int64_t R, int64_t V, int dtype,
+                              const float* inv_temperature, const int32_t* top_k, const float* top_p,
+                              const int64_t* seed, const int64_t* counter, int64_t* tokens, void* stream) {
+  if (!logits || !inv_temperature || !top_k || !top_p || !seed || !counter || !tokens)
+    VY_FAIL(VY_ERR_ARG, "vy_sample_rows: null operand");
+  if (R <= 0 || R > INT32_MAX || V <= 0 || V > 0x7ffffff0 || ldl < V)
+    VY_FAIL(VY_ERR_ARG, "vy_sample_rows: bad shape (R %lld, V %lld, ldl %lld)", (long long)R, (long long)V, (long long)ldl);
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_sample_rows: bad dtype %d", dtype);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == VY_BF16)
+    hipLaunchKernelGGL(sample_rows_kernel<bf16>, dim3((unsigned)R), dim3(ST), 0, st, (const bf16*)logits, ldl, (int)V,
+                       inv_temperature, top_k, top_p, seed, counter, tokens);
+  else
+    hipLaunchKernelGGL(sample_rows_kernel<float>, dim3((unsigned)R), dim3(ST), 0, st, (const float*)logits, ldl, (int)V,
+                       inv_temperature, top_k, top_p, seed, counter, tokens);
+  VY_CHECK_LAUNCH("vy_sample_rows");
   return VY_OK;
 }

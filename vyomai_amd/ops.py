@@ -761,6 +761,35 @@ def sampling_probs(logits: Tensor, temperature: float = 1.0, top_k: int = 0, top
     return probs.view(*logits.shape)
 
 
+def sample_rows(logits2d: Tensor, inv_temperature: Tensor, top_k: Tensor, top_p: Tensor, seed: Tensor,
+                counter: Tensor) -> Tensor:
+    """One token per row of logits2d (R, V), every row with its own parameters, in one launch (vy_sample_rows):
+    inv_temperature[r] == 0 -> the arg-max; otherwise argmax over the columns vy_sampling_probs keeps for top_k[r] /
+    top_p[r] of logit * inv_temperature[r] + gumbel_noise(1, V, seed[r], counter[r])[0].  inv_temperature / top_p fp32,
+    top_k int32, seed / counter int64 (a seed is the 64-bit pattern), each (R,) on the logits' device -> int64 (R,).
+    inv_temperature must be >= 0 and not NaN; the caller checks (the values are on the device)."""
+    if logits2d.dim() != 2 or logits2d.shape[0] < 1 or logits2d.shape[1] < 1 or logits2d.stride(1) != 1:
+        raise ValueError(f"sample_rows: logits must be (R, V) with unit column stride, got {tuple(logits2d.shape)} "
+                         f"strides {logits2d.stride()}")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"sample_rows: logits must be float32 or bfloat16, got {logits2d.dtype}")
+    R, V = logits2d.shape
+    if logits2d.stride(0) < V:
+        raise ValueError(f"sample_rows: row stride {logits2d.stride(0)} is below V = {V}")
+    for name, t, dt in (("inv_temperature", inv_temperature, torch.float32), ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float32), ("seed", seed, torch.long), ("counter", counter, torch.long)):
+        if not isinstance(t, Tensor) or t.dtype != dt or t.dim() != 1 or t.numel() != R or t.stride(0) != 1:
+            raise ValueError(f"sample_rows: {name} must be a contiguous {dt} tensor of {R} elements")
+        if t.device != logits2d.device:
+            raise ValueError(f"sample_rows: {name} is on {t.device}, the logits on {logits2d.device}")
+    _need_gpu(logits2d)
+    tokens = torch.empty(R, dtype=torch.long, device=logits2d.device)
+    call("vy_sample_rows", logits2d.data_ptr(), logits2d.stride(0), R, V, dtype_code(logits2d.dtype),
+         inv_temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), seed.data_ptr(), counter.data_ptr(),
+         tokens.data_ptr(), _stream())
+    return tokens
+
+
 def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[int]) -> None:
     """dw[ids[m], :] += dout[m, :] in fp32, skipping padding_idx  (vy_embedding_bwd)."""
     _need_gpu(dout, ids, dw)

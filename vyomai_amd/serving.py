@@ -2,8 +2,8 @@
 Examples/simple_vllm.ipynb (its prefix-caching version) under the notebook's class names -- RadixNode, SequenceState,
 PagedKVManager, ContinuousBatchEngine -- serving this package's own model through vy_paged_rope_write,
 vy_attn_paged_decode, vy_paged_gather and vy_attn_fwd, or vy_attn_paged_prefill in their place
-(ModelForCausalLM.forward_paged).  The notebook's Qwen3Model is a different network and is not reproduced; greedy
-decoding only.
+(ModelForCausalLM.forward_paged; Qwen3Model.forward_paged serves the notebook's own network).  The notebook decodes
+greedily; here every request may bring its own SamplingParams, drawn in one vy_sample_rows launch per step (below).
 
 The bookkeeping (tokens, block tables, slot mappings, the radix tree, the queues) lives on the host: the manager and the
 scheduler run without a GPU, and a step uploads its packed metadata once and reads the step's ids back once.  Only the
@@ -46,14 +46,68 @@ Beyond the notebook, both off by default (the default engine's schedule, metadat
   N >= max_batch_size guarantees progress (while a sequence prefills, at most max_batch_size - 1 decode).
   Invariant: a block is in the radix tree only if its rows are written by the end of the step that registered it -- so
   a prompt block is registered in the step whose chunk writes its last row (PagedKVManager.allocate(state, upto)), also
-  one that an earlier chunk allocated and left part filled."""
+  one that an earlier chunk allocated and left part filled.
+
+Sampling (add_sequence(..., sampling=SamplingParams(...)); None or temperature 0: greedy).  A step whose emitting
+sequences are all greedy is the greedy step: torch.argmax and one .tolist().  Otherwise ONE vy_sample_rows launch draws
+for every logits row (greedy rows ride along with inv_temperature 0) before the same single .tolist(): the token is
+argmax over the kept columns of logit / temperature + Gumbel noise, a draw from softmax(logits / temperature) over the
+set TopKProcessor / NucleusProcessor keep.  The noise of a row is keyed by (the request's seed, the position of the
+token being drawn, column) and by nothing else, so what a request generates from given logits does not depend on the
+batch around it, on its row, on prefix-cache hits or on how its prompt was chunked.  The parameters ride in the step's
+two uploads (top_k and the bit patterns of inv_temperature / top_p in the int32 one, seed and position in the int64
+one): a sampled step makes no additional copy in either direction."""
 from __future__ import annotations
 
 import itertools
+import math
 from collections import deque
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
+
+_MASK64 = (1 << 64) - 1
+
+
+class SamplingParams:
+    """How one request draws its tokens.  temperature 0: greedy (top_k / top_p / seed unused).  top_k 0 and top_p 0 or 1:
+    that filter is off; both are applied to the unscaled logits, top-k first, as the logits processors do.  seed: any
+    int, used modulo 2^64; None lets add_sequence take one from rng.next_offset()."""
+
+    def __init__(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.0, seed: Optional[int] = None):
+        temperature, top_p = float(temperature), float(top_p)
+        if not math.isfinite(temperature) or temperature < 0.0:
+            raise ValueError(f"temperature {temperature} must be finite and not negative")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"top_k {top_k} must be a non-negative integer")
+        if not 0.0 <= top_p <= 1.0:                      # (also rejects NaN)
+            raise ValueError(f"top_p {top_p} must lie in [0, 1]")
+        self.temperature, self.top_k, self.top_p = temperature, int(top_k), top_p
+        self.seed = None if seed is None else int(seed) & _MASK64
+
+    @property
+    def greedy(self) -> bool:
+        return self.temperature == 0.0
+
+    @property
+    def inv_temperature(self) -> float:
+        """What the kernel multiplies by: fp32(1 / temperature), 0 for a greedy request."""
+        return 0.0 if self.greedy else float(np.float32(1.0 / self.temperature))
+
+    def __repr__(self) -> str:
+        return (f"SamplingParams(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, "
+                f"seed={self.seed})")
+
+
+def _f32_bits(x: float) -> int:
+    """The bit pattern of fp32(x) as an int32: how a float rides in the step's int32 upload."""
+    return int(np.array([x], dtype=np.float32).view(np.int32)[0])
+
+
+def _as_i64(x: int) -> int:
+    """A 64-bit pattern as the int64 that carries it."""
+    return x - (1 << 64) if x >> 63 else x
 
 
 class RadixNode:
@@ -240,7 +294,8 @@ class PagedKVManager:
 
 class ContinuousBatchEngine:
     """add_sequence() queues a request; step() admits what fits, runs ONE packed forward over every running sequence
-    (all unseen prompt tokens of the newly admitted ones, one token of the others), appends the greedy token to each and
+    (all unseen prompt tokens of the newly admitted ones, one token of the others), appends to each the token its
+    SamplingParams draw (greedy by default; `sampling[sid]` holds the resolved parameters while the request lives) and
     returns the sequences that finished in this step as {sid: token list}.  Stop tokens: `eos_token_ids` (default: the
     model config's eos_token_id); the notebook hard-codes Qwen's two ids.
 
@@ -277,15 +332,30 @@ class ContinuousBatchEngine:
         self.prompt_tokens_computed: Dict[int, int] = {}
         self.record_logits = record_logits
         self.logits: Dict[int, List[torch.Tensor]] = {}
+        self.sampling: Dict[int, SamplingParams] = {}
 
-    def add_sequence(self, prompt_ids: Sequence[int], max_gen_len: int = 128) -> int:
+    def add_sequence(self, prompt_ids: Sequence[int], max_gen_len: int = 128,
+                     sampling: Optional[SamplingParams] = None) -> int:
+        """sampling=None: greedy.  A sampled request without a seed gets one here from the package's random stream
+        (rng.next_offset(): torch.manual_seed / rng.manual_seed govern it, every call a different one)."""
         prompt_ids = [int(t) for t in prompt_ids]
         if not prompt_ids or max_gen_len < 1:
             raise ValueError("a request needs a prompt and max_gen_len >= 1")
         if self.kv_mgr.blocks_for(len(prompt_ids) + max_gen_len) > self.kv_mgr.max_blocks:
             raise ValueError(f"{len(prompt_ids)} + {max_gen_len} tokens do not fit into {self.kv_mgr.max_blocks} blocks "
                              f"of {self.kv_mgr.block_size}")
+        if sampling is None:
+            sampling = SamplingParams()
+        elif not isinstance(sampling, SamplingParams):
+            raise ValueError(f"sampling must be a SamplingParams or None, got {type(sampling).__name__}")
+        elif not sampling.greedy and sampling.seed is None:
+            from . import rng
+            base, offset = rng.next_offset()
+            # an odd multiplier is a bijection modulo 2^64: different offsets of one base seed never collide
+            sampling = SamplingParams(sampling.temperature, sampling.top_k, sampling.top_p,
+                                      (base + 0x9E3779B97F4A7C15 * offset) & _MASK64)
         sid = next(self.id_gen)
+        self.sampling[sid] = sampling
         self.waiting_room.append({"sid": sid, "prompt_ids": prompt_ids, "max_gen_len": max_gen_len})
         return sid
 
@@ -308,12 +378,15 @@ class ContinuousBatchEngine:
         """-> (metadata, input_ids): the step's packed token ids and positions, their slots, and per phase what the
         attention needs -- for the decoding sequences their rows, block tables and lengths, for each prefilling one
         (first row, rows, prefix_len, its block table).  last_rows has one row per sequence whose query rows reach its
-        last token (all of them unless a prompt goes in chunks).
+        last token (all of them unless a prompt goes in chunks).  If one of those sequences samples,
+        metadata["sampling"] = {inv_temperature, top_k, top_p, seed, counter} holds one entry per last row, views into the
+        step's two uploads (a greedy row: inv_temperature 0; counter: the position of the token being drawn); a step
+        whose emitting sequences are all greedy has no such key and uploads what it always did.
 
         varlen_prefill: `states` holds the decoding sequences first, so the prefill rows are one contiguous run, and
         metadata["prefill_varlen"] = {cu_q, ctx_lens, block_table (n, width), max_q, max_kv} describes all of them for
         ONE vy_attn_paged_prefill launch (cu_q counts rows of the packed buffer); metadata["prefill"] is then empty."""
-        ids, pos, slots, cu, last = [], [], [], [0], []
+        ids, pos, slots, cu, last, drawn = [], [], [], [0], [], []
         dec_rows, dec_lens, dec_tables, prefill = [], [], [], []
         pf_cu, pf_ctx, pf_tables, pf_max_q, pf_max_kv = [], [], [], 0, 0
         width = max(s.block_table.numel() for s in states)
@@ -338,6 +411,7 @@ class ContinuousBatchEngine:
             cu.append(cu[-1] + b - a)
             if b == s.num_tokens:
                 last.append(cu[-1] - 1)
+                drawn.append(s)
         # two uploads: everything int64 (ids | slots | last rows) and everything int32 (positions | decode rows |
         # decode lengths | decode block tables | the block table of each prefill that starts from a cached prefix, or
         # with varlen_prefill: cu_q | ctx_lens | the prefill block tables)
@@ -350,13 +424,20 @@ class ContinuousBatchEngine:
         pf0 = len(i32)
         if npf:
             i32 += pf_cu + [T] + pf_ctx + pf_tables
-        l64 = torch.tensor(ids + slots + last, dtype=torch.long).to(self.device)
+        l64, nl, sp0 = ids + slots + last, len(last), len(i32)
+        params = [self.sampling[s.id] for s in drawn]
+        sampled = any(not sp.greedy for sp in params)
+        if sampled:
+            i32 += ([_f32_bits(sp.inv_temperature) for sp in params] + [min(sp.top_k, 0x7fffffff) for sp in params] +
+                    [_f32_bits(sp.top_p) for sp in params])
+            l64 += [_as_i64(sp.seed or 0) for sp in params] + [s.num_tokens for s in drawn]
+        l64 = torch.tensor(l64, dtype=torch.long).to(self.device)
         i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
         prefill = [(r0, n, pl, None if t is None else i32[t[0]:t[0] + t[1]]) for r0, n, pl, t in prefill]
         metadata = {
             "positions": i32[:T],
             "slot_mapping": l64[T:2 * T],
-            "last_rows": l64[2 * T:],
+            "last_rows": l64[2 * T:2 * T + nl],
             "max_position": max(s.num_tokens for s in states),
             "prefill": prefill,
             "decode": None,
@@ -370,6 +451,12 @@ class ContinuousBatchEngine:
             metadata["prefill_varlen"] = {"cu_q": i32[pf0:pf0 + npf + 1], "ctx_lens": i32[pf0 + npf + 1:o],
                                           "block_table": i32[o:o + npf * width].view(npf, width),
                                           "max_q": pf_max_q, "max_kv": pf_max_kv}
+        if sampled:
+            o = 2 * T + nl
+            metadata["sampling"] = {"inv_temperature": i32[sp0:sp0 + nl].view(torch.float32),
+                                    "top_k": i32[sp0 + nl:sp0 + 2 * nl],
+                                    "top_p": i32[sp0 + 2 * nl:sp0 + 3 * nl].view(torch.float32),
+                                    "seed": l64[o:o + nl], "counter": l64[o + nl:o + 2 * nl]}
         return metadata, l64[:T]
 
     def _schedule_step(self) -> List[SequenceState]:
@@ -395,24 +482,43 @@ class ContinuousBatchEngine:
             run.append(s)
         return run
 
-    def step(self) -> Dict[int, List[int]]:
+    def _plan_step(self):
+        """-> (states, metadata, input_ids) of the next step, its blocks allocated and its metadata uploaded; None when
+        nothing runs.  Everything a step does before the model (no GPU work but the two uploads)."""
         self._try_schedule_waiting()
         if not self.active:
-            return {}
+            return None
         states = self._schedule_step()
         for s in states:
             self.kv_mgr.allocate(s, s.query_end)
             s.update_metadata()
             if s.is_prefill:
                 self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
-        metadata, input_ids = self._prepare_inference_data(states)
+        return (states, *self._prepare_inference_data(states))
+
+    def step(self) -> Dict[int, List[int]]:
+        plan = self._plan_step()
+        if plan is None:
+            return {}
+        states, metadata, input_ids = plan
         logits = self.model.forward_paged(input_ids, metadata["positions"], metadata, self.kv_mgr)
-        next_tokens = torch.argmax(logits, dim=-1).tolist()          # the step's one device-to-host copy
-        emitting = [s for s in states if s.query_end == s.num_tokens]   # (a chunk short of its prompt's end: no token)
+        sp = metadata.get("sampling")
+        if sp is None:
+            picked = torch.argmax(logits, dim=-1)
+        else:
+            from . import ops
+            picked = ops.sample_rows(logits, sp["inv_temperature"], sp["top_k"], sp["top_p"], sp["seed"], sp["counter"])
+        next_tokens = picked.tolist()                                # the step's one device-to-host copy
         if self.record_logits:
             host = logits.float().cpu()
-            for i, s in enumerate(emitting):
+            for i, s in enumerate(s for s in states if s.query_end == s.num_tokens):
                 self.logits.setdefault(s.id, []).append(host[i])
+        return self._finish_step(states, next_tokens)
+
+    def _finish_step(self, states: List[SequenceState], next_tokens: List[int]) -> Dict[int, List[int]]:
+        """Append next_tokens (one per sequence whose query rows reached its last token, in row order) and retire what
+        finished: everything a step does after the model, on the host."""
+        emitting = [s for s in states if s.query_end == s.num_tokens]   # (a chunk short of its prompt's end: no token)
         for s in states:
             s.num_computed, s.chunk_end = s.query_end, None
         finished = {}
@@ -424,6 +530,7 @@ class ContinuousBatchEngine:
                 finished[s.id] = s.tokens[:s.num_tokens].tolist()
                 self.kv_mgr.free(s)
                 del self.active[s.id]
+                del self.sampling[s.id]
         return finished
 
     def run(self) -> Dict[int, List[int]]:
