@@ -102,10 +102,12 @@ def test_paged_prefill_vs_fp64(dh, h, hk, bs, dtype):
         assert (err <= bound).all(), f"{regime}: max err / bound {float(ratio.max()):.2f} (row {int(ratio.argmax())})"
 
 
-@pytest.mark.parametrize("dh", [64, 224])
+@pytest.mark.parametrize("dh", [64, 72, 224])
 def test_paged_prefill_agrees_with_gather_and_contiguous_attention(dh):
-    """Same pages, old path: vy_paged_gather + causal vy_attn_fwd(start_pos = ctx) per sequence, within the project's
-    bf16 attention bar (atol = rtol = 2e-2, test_attention_fwd)."""
+    """Same pages, old path: vy_paged_gather + causal vy_attn_fwd(start_pos = ctx) per sequence.  At dh = 72 and 224
+    both sides run the 16x16x32 tile core (vy_attn_gen.h) over the same 64-key tile walk from key 0 at the same padded
+    width (96 and 256), so the rows are equal bit for bit.  At dh = 64 the contiguous side is attn_fwd_mfma_kernel:
+    within the project's bf16 attention bar (atol = rtol = 2e-2, test_attention_fwd)."""
     from vyomai_amd import ops
     h, hk, bs = 4, 2, 256
     q, kc, vc, table, cu, ctx, _, _ = _prefill_case(dh, h, hk, bs, BF, "flat")
@@ -119,7 +121,12 @@ def test_paged_prefill_agrees_with_gather_and_contiguous_attention(dh):
         q4 = qd[r0:r0 + ln, :h * dh].view(ln, h, dh).permute(1, 0, 2).unsqueeze(0)
         old = torch.empty((1, ln, h * dh), dtype=BF, device=DEV)
         ops.attention(q4, k3.unsqueeze(0), v3.unsqueeze(0), causal=True, start_pos=c, out=old)
-        torch.testing.assert_close(new[r0:r0 + ln].float(), old[0].float(), atol=2e-2, rtol=2e-2)
+        if dh == 64:
+            torch.testing.assert_close(new[r0:r0 + ln].float(), old[0].float(), atol=2e-2, rtol=2e-2)
+        else:
+            diff = (new[r0:r0 + ln].float() - old[0].float()).abs().max()
+            print(f"dh {dh}, segment {SEGS[s]}: max |new - old| {float(diff):.3e}")
+            assert torch.equal(new[r0:r0 + ln], old[0]), f"segment {SEGS[s]}: max |new - old| {float(diff):.3e}"
 
 
 def test_paged_prefill_no_sequences_is_a_no_op():

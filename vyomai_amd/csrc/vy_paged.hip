@@ -8,6 +8,7 @@
 // (vy_wave.h).  What differs: the context is not bounded, so a lane group walks its keys with an fp32 online softmax (a
 // running maximum per lane group, rescaled once per U keys, no cross-lane traffic inside the loop but the dot product's
 // group sum), and a long context is split over workgroups whose fp32 (m, l, o) partials a second small launch combines.
+#include "vy_attn_gen.h"
 #include "vy_common.h"
 #include "vy_wave.h"
 #include <float.h>
@@ -234,9 +235,45 @@ template <> struct Quad<bf16> {
   }
 };
 
-// thread = (token, head of the packed row, 4 columns of the lower half and the same 4 of the upper half): q and k heads
-// are rotated in place with row positions[t] of the tables (the pairing d, d + dh/2 and the formula of rope2_kernel,
-// vy_misc.hip, evaluated in fp32 and rounded once), k and v heads are then stored into slot slot_mapping[t]
+// What follows the loads in both rope-write kernels.  The lane holds columns i4 .. i4 + 3 of the lower half (lo) and the
+// same 4 of the upper half (hi) of head hd of token t's packed row: q and k heads are rotated with row positions[t] of
+// the tables (the pairing d, d + dh/2 and the formula of rope2_kernel, vy_misc.hip, evaluated in fp32 and rounded once)
+// and stored in place, k and v heads are then stored into slot slots[t] of the pages.  pre(lo, hi) is what the caller
+// does to a q / k head in front of the rotation (the qk-norm factors, or nothing): called inside the q / k branch, so
+// its loads and the table loads are requested together.
+template <typename T, typename Pre>
+__device__ __forceinline__ void rope_store_quads(T* __restrict__ row, float (&lo)[4], float (&hi)[4], int i4, int hd,
+                                                 long long t, const int* __restrict__ positions,
+                                                 const long long* __restrict__ slots, const float* __restrict__ cos_tab,
+                                                 const float* __restrict__ sin_tab, long long table_rows,
+                                                 T* __restrict__ kc, T* __restrict__ vc, long long n_slots, int h, int hk,
+                                                 int dh, Pre pre) {
+  const int half = dh >> 1;
+  if (hd < h + hk) {
+    pre(lo, hi);
+    long long pos = positions[t];
+    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
+    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
+    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = lo[e], bb = hi[e];
+      lo[e] = a * c[e] - bb * s[e];
+      hi[e] = bb * c[e] + a * s[e];
+    }
+    Quad<T>::store(row + i4, lo);
+    Quad<T>::store(row + half + i4, hi);
+  }
+  if (hd < h) return;
+  const long long slot = slots[t];
+  if (slot < 0 || slot >= n_slots) return;
+  const bool isk = hd < h + hk;
+  T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
+  Quad<T>::store(dst + i4, lo);   // (k: rounded exactly as the in-place store rounds them; v: the loaded bits)
+  Quad<T>::store(dst + half + i4, hi);
+}
+
+// thread = (token, head of the packed row, 4 columns of the lower half and the same 4 of the upper half)
 template <typename T>
 __global__ __launch_bounds__(256) void paged_rope_write_kernel(T* __restrict__ qkv, long long ld,
                                                                const int* __restrict__ positions,
@@ -256,27 +293,8 @@ __global__ __launch_bounds__(256) void paged_rope_write_kernel(T* __restrict__ q
   float lo[4], hi[4];
   Quad<T>::load(row + i4, lo);
   Quad<T>::load(row + half + i4, hi);
-  if (hd < h + hk) {
-    long long pos = positions[t];
-    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
-    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
-    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a = lo[e], bb = hi[e];
-      lo[e] = a * c[e] - bb * s[e];
-      hi[e] = bb * c[e] + a * s[e];
-    }
-    Quad<T>::store(row + i4, lo);
-    Quad<T>::store(row + half + i4, hi);
-  }
-  if (hd < h) return;
-  const long long slot = slots[t];
-  if (slot < 0 || slot >= n_slots) return;
-  const bool isk = hd < h + hk;
-  T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
-  Quad<T>::store(dst + i4, lo);   // (k: the rotated values, rounded exactly as the in-place store rounds them)
-  Quad<T>::store(dst + half + i4, hi);
+  rope_store_quads(row, lo, hi, i4, hd, t, positions, slots, cos_tab, sin_tab, table_rows, kc, vc, n_slots, h, hk, dh,
+                   [](float (&)[4], float (&)[4]) {});
 }
 
 // sum over the 1 << lg lanes of a lane group (aligned to its size inside the wave, at most 32 lanes), in every lane of
@@ -301,7 +319,7 @@ __device__ __forceinline__ float pow2_group_sum(float v, int lg) {
 // the last unit load nothing, take part in the reduction with zeros and store nothing.  Per q / k head, all in fp32:
 // sum of squares (8 per lane as an fma chain, then the group sum), r = rsqrt(sum / dh + eps), n = x * r * scale, the
 // rotation of n, ONE rounding at the store.  An all-zero head gives 0 * rsqrt(eps) = 0.  v heads are neither normalised
-// nor rotated; they go through the page store as before.
+// nor rotated; they go through the page store as they were loaded.
 template <typename T>
 __global__ __launch_bounds__(256) void paged_qknorm_rope_write_kernel(T* __restrict__ qkv, long long ld,
                                                                       const int* __restrict__ positions,
@@ -335,31 +353,18 @@ __global__ __launch_bounds__(256) void paged_qknorm_rope_write_kernel(T* __restr
   for (int e = 0; e < 4; ++e) ss = fmaf(hi[e], hi[e], ss);
   ss = pow2_group_sum(ss, lg);                        // every lane of the wave, also the idle ones
   if (!on) return;
-  if (hd < h + hk) {
-    const float r = rsqrtf(fmaf(ss, inv_dh, eps));
-    const float* sc = hd < h ? q_scale : k_scale;
-    const f32x4 wl = *reinterpret_cast<const f32x4*>(sc + i4);
-    const f32x4 wh = *reinterpret_cast<const f32x4*>(sc + half + i4);
-    long long pos = positions[t];
-    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
-    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
-    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
+  rope_store_quads(row, lo, hi, i4, hd, t, positions, slots, cos_tab, sin_tab, table_rows, kc, vc, n_slots, h, hk, dh,
+                   [&](float (&a)[4], float (&b)[4]) {
+                     const float r = rsqrtf(fmaf(ss, inv_dh, eps));
+                     const float* sc = hd < h ? q_scale : k_scale;
+                     const f32x4 wl = *reinterpret_cast<const f32x4*>(sc + i4);
+                     const f32x4 wh = *reinterpret_cast<const f32x4*>(sc + half + i4);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a = lo[e] * r * wl[e], bb = hi[e] * r * wh[e];
-      lo[e] = a * c[e] - bb * s[e];
-      hi[e] = bb * c[e] + a * s[e];
-    }
-    Quad<T>::store(row + i4, lo);
-    Quad<T>::store(row + half + i4, hi);
-  }
-  if (hd < h) return;
-  const long long slot = slots[t];
-  if (slot < 0 || slot >= n_slots) return;
-  const bool isk = hd < h + hk;
-  T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
-  Quad<T>::store(dst + i4, lo);   // (k: rounded exactly as the in-place store rounds them; v: the loaded bits)
-  Quad<T>::store(dst + half + i4, hi);
+                     for (int e = 0; e < 4; ++e) {
+                       a[e] = a[e] * r * wl[e];
+                       b[e] = b[e] * r * wh[e];
+                     }
+                   });
 }
 
 // thread = (K or V, key j, KV head, 16-byte chunk): out[kvh][j] = cache[block_table[j / block_size]][j % block_size][kvh]
@@ -390,6 +395,28 @@ int log2_block_size(int block_size) {   // 8 .. 256, a power of two; else -1
   for (int l = 3; l <= 8; ++l)
     if (block_size == (1 << l)) return l;
   return -1;
+}
+
+// the page and head geometry every entry point of this file accepts; `fn` names the entry in the message
+int paged_check_geometry(const char* fn, int block_size, int dh, int* lbs) {
+  *lbs = log2_block_size(block_size);
+  if (*lbs < 0) VY_FAIL(VY_ERR_ARG, "%s: block_size %d must be a power of two from 8 to 256", fn, block_size);
+  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "%s: dh %d must be a multiple of 8 up to 256", fn, dh);
+  return VY_OK;
+}
+
+// the argument checks of the two rope-write entry points.  `null_operand`: one of the entry's pointers is null;
+// `ptrs`: the entry's 16-byte-aligned pointers or-ed together; eps: vy_paged_rope_write has none and passes 0
+int paged_check_rope_write(const char* fn, bool null_operand, uintptr_t ptrs, int64_t ld, int64_t table_rows, float eps,
+                           int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh) {
+  if (null_operand) VY_FAIL(VY_ERR_ARG, "%s: null operand", fn);
+  int lbs;
+  if (const int rc = paged_check_geometry(fn, block_size, dh, &lbs)) return rc;
+  if (T <= 0 || h <= 0 || hk <= 0 || max_blocks <= 0 || table_rows <= 0 || ld < (int64_t)(h + 2 * hk) * dh)
+    VY_FAIL(VY_ERR_ARG, "%s: bad shape (T %lld, h %d, hk %d, ld %lld)", fn, (long long)T, h, hk, (long long)ld);
+  if (!(eps >= 0.f)) VY_FAIL(VY_ERR_ARG, "%s: eps %g must not be negative", fn, (double)eps);
+  if (ld % 4 || (ptrs & 15)) VY_FAIL(VY_ERR_ARG, "%s: ld must be a multiple of 4, operands 16-byte aligned", fn);
+  return VY_OK;
 }
 
 // lanes per key for a head width: the head's 16-byte chunks rounded up to a power of two, at least 8
@@ -428,15 +455,16 @@ void paged_dec_launch(const PagedDecArgs& a, int64_t B, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------
-// vy_attn_paged_prefill, bf16: attn_fwd_gen_kernel's structure (vy_attn.hip: 64 query rows per workgroup, 16 per wave,
-// register-staged 64-key tiles, mfma_f32_16x16x32_bf16 with the swapped QK^T, P in registers, V^T through
-// ds_read_b64_tr_b16) over packed variable-length query segments, with the keys read through the block table: key kj
-// of sequence s is row table[s][kj / bs] * bs + kj % bs of the pages.  What else differs from the contiguous kernel:
-//   * the mask is always causal at offset ctx[s] and every row sees its own key: no key-padding and no "no visible
-//     key" branch;
-//   * the registers of tile t + 1 are requested right after tile t has been stored to LDS, so the two dependent loads
-//     (table entry, then the row) fly under tile t's MFMAs and softmax -- there is no LDS-DMA ring here that an
-//     ordinary load would drain (vy_attn_tile.h, fact (2));
+// vy_attn_paged_prefill, bf16: the 16x16x32 tile core of vy_attn_gen.h (64 query rows per workgroup, 16 per wave,
+// register-staged 64-key tiles, the swapped QK^T, P in registers, V^T through ds_read_b64_tr_b16), which
+// attn_fwd_gen_kernel (vy_attn.hip) runs over contiguous K/V, over packed variable-length query segments.  The Q
+// fragments, the tile store, one tile's step and the epilogue store are AttnGen<DHP>'s.  This kernel owns:
+//   * the fetch: key kj of sequence s is row table[s][kj / bs] * bs + kj % bs of the pages.  The registers of tile
+//     t + 1 are requested right after tile t has been stored to LDS, so the two dependent loads (table entry, then the
+//     row) fly under tile t's MFMAs and softmax -- there is no LDS-DMA ring here that an ordinary load would drain
+//     (vy_attn_tile.h, fact (2));
+//   * the predicate: always causal at offset ctx[s], and every row sees its own key -- so there is no key padding and
+//     no row without a visible key;
 //   * key rows at or past ctx + len are staged as zeros, never read: the tail of a last page may hold anything and
 //     0 * NaN in the PV MFMA is NaN.
 // ------------------------------------------------------------------------------------------
@@ -452,15 +480,10 @@ struct PagedPfArgs {
 
 template <int DHP>
 __global__ __launch_bounds__(256) void paged_prefill_kernel(const PagedPfArgs p) {
-  constexpr int PITCH = (DHP + 8) * 2;       // bytes per LDS row (16 B of padding: conflict-free fragment reads)
-  constexpr int KS = DHP / 32;               // k-steps of QK^T
-  constexpr int NDB = DHP / 16;              // 16-wide d blocks of O^T
-  constexpr int CPRW = DHP / 8;              // 16-byte chunks per row
-  constexpr int CPT = 64 * CPRW / 256;       // chunks per thread and tile
-  static_assert(DHP % 32 == 0 && (64 * CPRW) % 256 == 0, "tile chunks must divide over the workgroup");
-  __shared__ __attribute__((aligned(16))) char smem[2 * 64 * PITCH];
+  using G = AttnGen<DHP>;
+  __shared__ __attribute__((aligned(16))) char smem[G::LDS_BYTES];
   char* kt = smem;
-  char* vt = smem + 64 * PITCH;
+  char* vt = G::v_tile(smem);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, kq = lane >> 4;
@@ -482,44 +505,38 @@ __global__ __launch_bounds__(256) void paged_prefill_kernel(const PagedPfArgs p)
   const long long row_stride = (long long)p.hk * dh;
   const bf16* Kb = p.kc + (long long)kvh * dh;
   const bf16* Vb = p.vc + (long long)kvh * dh;
-  const bf16x8 zero8 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
 
-  bf16x8 qf[KS];
+  bf16x8 qf[G::KS];
+  G::load_q(qf, Q, dh, kq);
+  f32x4 o[G::NDB];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const int d0 = 32 * ks + 8 * kq;
-    qf[ks] = d0 < dh ? *reinterpret_cast<const bf16x8*>(Q + d0) : zero8;
-  }
-  f32x4 o[NDB];
-#pragma unroll
-  for (int n = 0; n < NDB; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int n = 0; n < G::NDB; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -FLT_MAX, l_run = 0.f;
   const float c = p.scale * PF_LOG2E;
   const int kv_end = S < ctx + q0 + 64 ? S : ctx + q0 + 64;
   const int nt = (kv_end + 63) / 64;         // >= 1: S >= 1
-  // transposing-read addresses of the V tile: lane j of a 16-lane group supplies row (j >> 2), columns 4 (j & 3) ..
-  const unsigned vtr = vy_lds_addr(vt) + (4 * kq + (r16 >> 2)) * PITCH + (4 * (r16 & 3)) * 2;
+  const unsigned vtr = G::vtr_addr(vt, r16, kq);
 
   // the tile's 16-byte chunks -> registers: zero beyond the head width and at or beyond key S
-  bf16x8 kreg[CPT], vreg[CPT];
+  bf16x8 kreg[G::CPT], vreg[G::CPT];
   auto fetch = [&](int k0) {
-    int ent[CPT];
+    int ent[G::CPT];
 #pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      const int kj = k0 + (tid + 256 * i) / CPRW;
+    for (int i = 0; i < G::CPT; ++i) {
+      const int kj = k0 + (tid + 256 * i) / G::CPRW;
       ent[i] = bt[(kj < S ? kj : S - 1) >> p.lbs];
     }
 #pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      const int cidx = tid + 256 * i;
-      const int row = cidx / CPRW, ch = cidx - row * CPRW;
+    for (int i = 0; i < G::CPT; ++i) {
+      int row, ch;
+      G::chunk_of(tid, i, row, ch);
       const int kj = k0 + row;
       const bool ok = ch * 8 < dh && kj < S;
       const int kjc = kj < S ? kj : S - 1;
       const int e = ent[i] < 0 ? 0 : ent[i] < p.max_blocks ? ent[i] : p.max_blocks - 1;   // memory safety only
       const long long off = (((long long)e << p.lbs) + (kjc & (bs - 1))) * row_stride + (ch * 8 < dh ? ch * 8 : 0);
-      kreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Kb + off) : zero8;
-      vreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Vb + off) : zero8;
+      kreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Kb + off) : G::zero8();
+      vreg[i] = ok ? *reinterpret_cast<const bf16x8*>(Vb + off) : G::zero8();
     }
   };
   fetch(0);
@@ -527,105 +544,14 @@ __global__ __launch_bounds__(256) void paged_prefill_kernel(const PagedPfArgs p)
   for (int t = 0; t < nt; ++t) {
     const int k0 = t * 64;
     __syncthreads();   // the previous tile's fragments have been read
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      const int cidx = tid + 256 * i;
-      const int row = cidx / CPRW, ch = cidx - row * CPRW;
-      *reinterpret_cast<bf16x8*>(kt + row * PITCH + ch * 16) = kreg[i];
-      *reinterpret_cast<bf16x8*>(vt + row * PITCH + ch * 16) = vreg[i];
-    }
+    G::store_tile(kt, vt, kreg, vreg, tid);
     __syncthreads();
     if (t + 1 < nt) fetch(k0 + 64);
-    // S^T = K Q^T: four 16-key blocks
-    f32x4 sc[4];
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk) {
-      sc[blk] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kt + (16 * blk + r16) * PITCH + (32 * ks + 8 * kq) * 2);
-        sc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], sc[blk], 0, 0, 0);
-      }
-    }
-    // causal mask: register r of block blk is key k0 + 16 blk + 4 kq + r
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kj = k0 + 16 * blk + 4 * kq + r;
-        const float tv = kj < S && kj <= qi + ctx ? sc[blk][r] : -INFINITY;
-        sc[blk][r] = tv;
-        tmax = fmaxf(tmax, tv);
-      }
-    // the row's keys are spread over the four lane groups (lane >> 4)
-    {
-      const unsigned u = __builtin_bit_cast(unsigned, tmax);
-      auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-      tmax = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
-      const unsigned w = __builtin_bit_cast(unsigned, tmax);
-      auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-      tmax = fmaxf(__builtin_bit_cast(float, (unsigned)s32[0]), __builtin_bit_cast(float, (unsigned)s32[1]));
-    }
-    const float m_new = fmaxf(m_run, tmax * c);   // (-inf * c stays -inf; m_run is finite)
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    l_run *= alpha;
-#pragma unroll
-    for (int n = 0; n < NDB; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[n][r] *= alpha;
-    float rs = 0.f;
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = __builtin_amdgcn_exp2f(fmaf(sc[blk][r], c, -m_run));
-        sc[blk][r] = e;
-        rs += e;
-      }
-    l_run += rs;   // this lane group's keys only; the four groups are added at the end
-    // O^T += V^T P^T, k-steps of 32 keys = blocks (2 tt, 2 tt + 1) in the order the scores sit in
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      bf16x8 pf;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { pf[r] = (bf16)sc[2 * tt][r]; pf[4 + r] = (bf16)sc[2 * tt + 1][r]; }
-      vy_static_for<NDB>([&](auto n_c) {
-        constexpr int n = decltype(n_c)::value;
-        union { struct { s16x4 a, b; } h; bf16x8 v; } u;
-        u.h.a = vy_lds_tr16_off<n * 32>(vtr + (32 * tt) * PITCH);
-        u.h.b = vy_lds_tr16_off<n * 32>(vtr + (32 * tt + 16) * PITCH);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        vy_tie(u.v);
-        o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf, o[n], 0, 0, 0);
-      });
-    }
+    // (& and not &&: both compares of every key are evaluated, nothing short-circuits -- the form the compiler schedules best)
+    G::step(kt, vtr, qf, o, m_run, l_run, c, k0, r16, kq, [&](int kj) { return (kj < S) & (kj <= qi + ctx); });
   }
-  // row totals over the four lane groups
-  float l_tot = l_run;
-  {
-    const unsigned u = __builtin_bit_cast(unsigned, l_tot);
-    auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    l_tot = __builtin_bit_cast(float, (unsigned)s16[0]) + __builtin_bit_cast(float, (unsigned)s16[1]);
-    const unsigned w = __builtin_bit_cast(unsigned, l_tot);
-    auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-    l_tot = __builtin_bit_cast(float, (unsigned)s32[0]) + __builtin_bit_cast(float, (unsigned)s32[1]);
-  }
-  const float inv = 1.0f / l_tot;
-  if (qi < len) {
-    bf16* orow = p.out + ((long long)row0 + qi) * p.o_ld + (long long)head * dh;
-#pragma unroll
-    for (int n = 0; n < NDB; ++n) {
-      const int d0 = 16 * n + 4 * kq;
-      if (d0 < dh) {
-        bf16x4 w;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[r] = (bf16)(o[n][r] * inv);
-        *reinterpret_cast<bf16x4*>(orow + d0) = w;
-      }
-    }
-  }
+  const float inv = 1.0f / dec_rows_sum(l_run);   // row totals over the four lane groups
+  if (qi < len) G::store_row(p.out + ((long long)row0 + qi) * p.o_ld + (long long)head * dh, o, inv, dh, kq);
 }
 
 template <int LPK>
@@ -653,9 +579,8 @@ extern "C" int vy_attn_paged_decode(const void* q, int64_t q_ld, const int32_t* 
                                     int64_t max_seqlen, void* out, int64_t o_ld, int64_t B, int h, int hk, int dh,
                                     float scale, int n_split, void* ws, int64_t ws_bytes, int dtype, void* stream) {
   if (!q || !k_cache || !v_cache || !block_table || !seqlens || !out) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: null operand");
-  const int lbs = log2_block_size(block_size);
-  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: block_size %d must be a power of two from 8 to 256", block_size);
-  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: dh %d must be a multiple of 8 up to 256", dh);
+  int lbs;
+  if (const int rc = paged_check_geometry("vy_attn_paged_decode", block_size, dh, &lbs)) return rc;
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_decode: bad dtype %d", dtype);
   const int vec = dtype == VY_BF16 ? 8 : 4;
   if (B <= 0 || B > 65535 || h <= 0 || hk <= 0 || h % hk || max_blocks <= 0 || max_blocks > INT32_MAX || bt_stride <= 0 ||
@@ -704,9 +629,8 @@ extern "C" int vy_attn_paged_prefill(const void* q, int64_t q_ld, const void* k_
   // (no sequences: the three per-sequence arrays may be empty, i.e. null)
   if (!q || !k_cache || !v_cache || !out || (n_seq > 0 && (!block_table || !cu_q || !ctx_lens)))
     VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: null operand");
-  const int lbs = log2_block_size(block_size);
-  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: block_size %d must be a power of two from 8 to 256", block_size);
-  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: dh %d must be a multiple of 8 up to 256", dh);
+  int lbs;
+  if (const int rc = paged_check_geometry("vy_attn_paged_prefill", block_size, dh, &lbs)) return rc;
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_attn_paged_prefill: bad dtype %d", dtype);
   if (n_seq < 0 || n_seq > 65535 || h <= 0 || hk <= 0 || h % hk || max_blocks <= 0 || max_blocks > INT32_MAX || bt_stride <= 0 ||
       bt_stride > ((int64_t)1 << 30) / block_size || max_q < 0 || max_q > 65535 * 64 || max_kv < 0 || max_kv > (1 << 30) ||
@@ -746,15 +670,11 @@ extern "C" int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positio
                                    const float* cos_tab, const float* sin_tab, int64_t table_rows, void* k_cache,
                                    void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk, int dh,
                                    int dtype, void* stream) {
-  if (!qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !k_cache || !v_cache)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: null operand");
-  if (log2_block_size(block_size) < 0)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: block_size %d must be a power of two from 8 to 256", block_size);
-  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: dh %d must be a multiple of 8 up to 256", dh);
-  if (T <= 0 || h <= 0 || hk <= 0 || max_blocks <= 0 || table_rows <= 0 || ld < (int64_t)(h + 2 * hk) * dh)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: bad shape (T %lld, h %d, hk %d, ld %lld)", (long long)T, h, hk, (long long)ld);
-  if (ld % 4 || (((uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15))
-    VY_FAIL(VY_ERR_ARG, "vy_paged_rope_write: ld must be a multiple of 4, operands 16-byte aligned");
+  if (const int rc = paged_check_rope_write(
+          "vy_paged_rope_write", !qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !k_cache || !v_cache,
+          (uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache, ld, table_rows,
+          0.f, max_blocks, block_size, T, h, hk, dh))
+    return rc;
   const int64_t total = T * (h + 2 * hk) * (dh / 8);
   const dim3 grid((unsigned)vy_cdiv(total, 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
@@ -777,17 +697,13 @@ extern "C" int vy_paged_qknorm_rope_write(void* qkv, int64_t ld, const int32_t* 
                                           const float* q_scale, const float* k_scale, float eps, void* k_cache,
                                           void* v_cache, int64_t max_blocks, int block_size, int64_t T, int h, int hk,
                                           int dh, int dtype, void* stream) {
-  if (!qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !q_scale || !k_scale || !k_cache || !v_cache)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: null operand");
-  if (log2_block_size(block_size) < 0)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: block_size %d must be a power of two from 8 to 256", block_size);
-  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: dh %d must be a multiple of 8 up to 256", dh);
-  if (T <= 0 || h <= 0 || hk <= 0 || max_blocks <= 0 || table_rows <= 0 || ld < (int64_t)(h + 2 * hk) * dh)
-    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: bad shape (T %lld, h %d, hk %d, ld %lld)", (long long)T, h, hk, (long long)ld);
-  if (!(eps >= 0.f)) VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: eps %g must not be negative", (double)eps);
-  if (ld % 4 || (((uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)q_scale | (uintptr_t)k_scale | (uintptr_t)qkv |
-                  (uintptr_t)k_cache | (uintptr_t)v_cache) & 15))
-    VY_FAIL(VY_ERR_ARG, "vy_paged_qknorm_rope_write: ld must be a multiple of 4, operands 16-byte aligned");
+  if (const int rc = paged_check_rope_write(
+          "vy_paged_qknorm_rope_write",
+          !qkv || !positions || !slot_mapping || !cos_tab || !sin_tab || !q_scale || !k_scale || !k_cache || !v_cache,
+          (uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)q_scale | (uintptr_t)k_scale | (uintptr_t)qkv |
+              (uintptr_t)k_cache | (uintptr_t)v_cache,
+          ld, table_rows, eps, max_blocks, block_size, T, h, hk, dh))
+    return rc;
   int lg = 0;                                         // lanes per (token, head): dh / 8 rounded up to a power of two
   while ((1 << lg) < dh / 8) ++lg;
   const int64_t units = T * (h + 2 * hk);
@@ -814,9 +730,8 @@ extern "C" int vy_paged_gather(const void* k_cache, const void* v_cache, int64_t
                                const int32_t* block_table, int64_t n_blocks, int64_t S, void* k_out, void* v_out,
                                int hk, int dh, int dtype, void* stream) {
   if (!k_cache || !v_cache || !block_table || !k_out || !v_out) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: null operand");
-  const int lbs = log2_block_size(block_size);
-  if (lbs < 0) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: block_size %d must be a power of two from 8 to 256", block_size);
-  if (dh <= 0 || dh % 8 || dh > 256) VY_FAIL(VY_ERR_ARG, "vy_paged_gather: dh %d must be a multiple of 8 up to 256", dh);
+  int lbs;
+  if (const int rc = paged_check_geometry("vy_paged_gather", block_size, dh, &lbs)) return rc;
   if (S <= 0 || hk <= 0 || max_blocks <= 0 || max_blocks > INT32_MAX || S > n_blocks * block_size)
     VY_FAIL(VY_ERR_ARG, "vy_paged_gather: bad shape (S %lld, %lld blocks of %d, hk %d)", (long long)S, (long long)n_blocks, block_size, hk);
   if (((uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k_out | (uintptr_t)v_out) & 15)

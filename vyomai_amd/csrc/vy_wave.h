@@ -1,5 +1,6 @@
-// Wave reductions on the DPP / permlane path (no LDS round trips), shared by the decode-step kernels (vy_decode.hip)
-// and the paged-cache attention (vy_paged.hip).
+// Wave reductions on the DPP / permlane path (no LDS round trips), shared by the decode-step kernels (vy_decode.hip),
+// the paged-cache attention (vy_paged.hip) and the 16x16x32 attention tile core (vy_attn_gen.h: dec_rows_max /
+// dec_rows_sum are its exchanges between the four lane groups of a query row).
 #pragma once
 #include "vy_common.h"
 
@@ -30,6 +31,15 @@ __device__ __forceinline__ float dec_rows_sum(float v) {
   const unsigned w = __builtin_bit_cast(unsigned, v);
   auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
   return __builtin_bit_cast(float, (unsigned)s32[0]) + __builtin_bit_cast(float, (unsigned)s32[1]);
+}
+// the maximum over the same four lanes, in every lane
+__device__ __forceinline__ float dec_rows_max(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  v = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
+  const unsigned w = __builtin_bit_cast(unsigned, v);
+  auto s32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+  return fmaxf(__builtin_bit_cast(float, (unsigned)s32[0]), __builtin_bit_cast(float, (unsigned)s32[1]));
 }
 __device__ __forceinline__ float dec_row16_max(float v) {
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false)));

@@ -22,6 +22,7 @@ from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
 from ..layers.kv_cache import DynamicCacheOne, StaticCacheOne
 from ..layers.mask import AttnMask
+from ..layers.paged import paged_step_attention, paged_step_logits
 from ..layers.positional_embeddings import RopeSlice, RopeTable, resolve_freqs
 from .common import PositionMixin
 
@@ -478,9 +479,9 @@ class ModelForCausalLM(nn.Module):
         base = self.model
         dev = input_ids.device
         x = base._embed(base.embed_tokens, input_ids.view(1, -1))[0]
-        T, dt = x.shape[0], x.dtype
+        dt = x.dtype
         cos, sin = base._rope_slice(0, int(metadata["max_position"])).table.on(dev)
-        slots, dec, pv = metadata["slot_mapping"], metadata["decode"], metadata.get("prefill_varlen")
+        slots = metadata["slot_mapping"]
         for layer in base.layers[: self.config.num_hidden_layers]:
             a = layer.self_attn
             h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
@@ -488,29 +489,10 @@ class ModelForCausalLM(nn.Module):
             sw, sb = a._packed_shadow(dt)
             qkv = ops.linear(layer.input_layernorm(x), sw, sb)
             ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc)
-            o = torch.empty((T, h * dh), dtype=dt, device=dev)
-            if dec is not None:
-                ops.attention_paged_decode(qkv, kc, vc, dec["block_table"], dec["seqlens"], dec["max_seqlen"], h,
-                                           q_rows=dec["rows"], out=o)
-            if pv is not None:
-                ops.attention_paged_prefill(qkv, kc, vc, pv["block_table"], pv["cu_q"], pv["ctx_lens"], pv["max_q"],
-                                            pv["max_kv"], h, out=o)
-            for row0, rows, prefix_len, table in (() if pv is not None else metadata["prefill"]):
-                seg = qkv[row0:row0 + rows]
-                q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)
-                if prefix_len:
-                    k3, v3 = ops.paged_gather(kc, vc, table, prefix_len + rows)
-                else:
-                    k3 = seg[:, h * dh:(h + hk) * dh].view(rows, hk, dh).permute(1, 0, 2)
-                    v3 = seg[:, (h + hk) * dh:].view(rows, hk, dh).permute(1, 0, 2)
-                ops.attention(q4, k3.unsqueeze(0), v3.unsqueeze(0), causal=True, start_pos=prefix_len,
-                              out=o[row0:row0 + rows].unsqueeze(0))
+            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh)
             x = ops.linear(o, _shadow(a.o_proj.weight, dt), None, residual=x)
             x = layer.mlp(layer.post_attention_layernorm(x), residual=x)
-        if metadata["last_rows"].numel() == 0:    # every sequence of the step is a chunk short of its prompt's end
-            return x.new_empty((0, self.lm_head.weight.shape[0]))
-        last = base.norm(x.index_select(0, metadata["last_rows"]))
-        return ops.linear(last, _shadow(self.lm_head.weight, dt))
+        return paged_step_logits(x, metadata["last_rows"], base.norm, self.lm_head.weight)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,

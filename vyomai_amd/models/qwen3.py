@@ -29,12 +29,8 @@ import torch.nn as nn
 from .. import ops
 from .._lib import ACT_SILU, VyomHipError
 from ..layers.attention import _shadow
-
-
-def _need_gpu(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise VyomHipError(f"vyomai_amd ops run on MI355X only: {what} got a CPU tensor (no CPU fallback exists; move "
-                           "the model and its inputs to 'cuda')")
+from ..layers.paged import paged_step_attention, paged_step_logits
+from .custom_transformer import _need_gpu
 
 
 def _packed_rows(owner: nn.Module, slot: str, linears, dtype: torch.dtype) -> torch.Tensor:
@@ -191,9 +187,9 @@ class Qwen3Model(nn.Module):
             raise ValueError(f"position {int(metadata['max_position'])} exceeds context_length {self.cfg['context_length']}")
         dev = input_ids.device
         x = ops.embedding(self.tok_emb.weight, input_ids.view(-1))
-        T, dt = x.shape[0], x.dtype
+        dt = x.dtype
         cos, sin = self._rope_tables(dev)
-        slots, dec, pv = metadata["slot_mapping"], metadata["decode"], metadata.get("prefill_varlen")
+        slots = metadata["slot_mapping"]
         for blk in self.trf_blocks:
             a = blk.att
             h, hk, dh = a.num_heads, a.num_kv_groups, a.head_dim
@@ -206,29 +202,10 @@ class Qwen3Model(nn.Module):
                                              _shadow(a.k_norm.scale, torch.float32), a.q_norm.eps, h, kc, vc)
             else:
                 ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc)
-            o = torch.empty((T, h * dh), dtype=dt, device=dev)
-            if dec is not None:
-                ops.attention_paged_decode(qkv, kc, vc, dec["block_table"], dec["seqlens"], dec["max_seqlen"], h,
-                                           q_rows=dec["rows"], out=o)
-            if pv is not None:
-                ops.attention_paged_prefill(qkv, kc, vc, pv["block_table"], pv["cu_q"], pv["ctx_lens"], pv["max_q"],
-                                            pv["max_kv"], h, out=o)
-            for row0, rows, prefix_len, table in (() if pv is not None else metadata["prefill"]):
-                seg = qkv[row0:row0 + rows]
-                q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)
-                if prefix_len:
-                    k3, v3 = ops.paged_gather(kc, vc, table, prefix_len + rows)
-                else:
-                    k3 = seg[:, h * dh:(h + hk) * dh].view(rows, hk, dh).permute(1, 0, 2)
-                    v3 = seg[:, (h + hk) * dh:].view(rows, hk, dh).permute(1, 0, 2)
-                ops.attention(q4, k3.unsqueeze(0), v3.unsqueeze(0), causal=True, start_pos=prefix_len,
-                              out=o[row0:row0 + rows].unsqueeze(0))
+            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh)
             x = ops.linear(o, _shadow(a.out_proj.weight, dt), None, residual=x)
             x = blk.ff(blk.norm2(x), residual=x)
-        if metadata["last_rows"].numel() == 0:    # every sequence of the step is a chunk short of its prompt's end
-            return x.new_empty((0, self.out_head.weight.shape[0]))
-        last = self.final_norm(x.index_select(0, metadata["last_rows"]))
-        return ops.linear(last, _shadow(self.out_head.weight, dt))
+        return paged_step_logits(x, metadata["last_rows"], self.final_norm, self.out_head.weight)
 
 
 _HF_LAYER = (
