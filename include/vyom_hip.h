@@ -199,6 +199,24 @@ int vy_attn_decode(const void* q, int64_t q_sb, int64_t q_sh,
  * vy_paged_gather: keys [0, S) of ONE sequence (block_table: its n_blocks entries, device) copied from the pages into
  *   contiguous (hk, S, dh) buffers, K and V in one launch -- the keys of a prefill that starts from cached prefix blocks.
  *   The rows of a block-table entry outside [0, max_blocks) are written as zeros (memory safety only, silently).
+ *
+ * fp8 pages (vy_paged_rope_write_fp8, vy_attn_paged_decode_fp8, vy_attn_paged_prefill_fp8): k_cache / v_cache keep their
+ *   shape and hold OCP e4m3fn codes, one byte an element; k_scale / v_scale are fp32 (max_blocks, block_size, hk), one
+ *   scale per slot and KV head, at the same indices.  The quantisation rule, for the dh values x of one head of one token
+ *   as a bf16 page would hold them (k: after the rotation's one bf16 rounding; v: as loaded):
+ *       amax = max |x|;  s = amax > 0 ? amax / 448.0f : 1.0f;  code = e4m3fn_rne(clamp(x / s, -448, 448))
+ *   with IEEE fp32 divisions; the dequantised value is float(code) * s, an fp32 product.  In torch:
+ *   (x / s).clamp(-448, 448).to(torch.float8_e4m3fn).  The three entry points are bf16 only (dtype VY_F32 is
+ *   VY_ERR_ARG), a null scale array is VY_ERR_ARG, every other argument and rule is the bf16 twin's.
+ *   vy_paged_rope_write_fp8: the arguments of vy_paged_qknorm_rope_write plus the scale arrays; q_scale and k_norm_scale
+ *     both null select the plain rotation of vy_paged_rope_write (one null alone is VY_ERR_ARG).  The in-place q / k rows
+ *     are bit for bit those of the bf16 entry points (their own kernel runs first, without a page to store to; a second
+ *     launch quantises what a bf16 page would hold); a k or v head goes to its slot as dh codes and one scale; a negative
+ *     or out-of-range slot stores neither.
+ *   vy_attn_paged_decode_fp8 (+ _ws_bytes: its own trip length, so its own automatic split): score = scale * k_s *
+ *     (q . codes), out = sum p v_s codes / sum p, fp32 throughout.  Rows at or past seqlen are never read, codes or scales.
+ *   vy_attn_paged_prefill_fp8: a fetched key row is dequantised in registers as bf16_rne(float(code) * s); from there on
+ *     it is vy_attn_paged_prefill, so it equals that entry on bf16 pages holding those values bit for bit.
  * ------------------------------------------------------------------------------------------ */
 int vy_paged_rope_write(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
                         const float* cos_tab, const float* sin_tab, int64_t table_rows, void* k_cache,
@@ -223,6 +241,22 @@ int vy_attn_paged_prefill(const void* q, int64_t q_ld, const void* k_cache, cons
 int vy_paged_gather(const void* k_cache, const void* v_cache, int64_t max_blocks, int block_size,
                     const int32_t* block_table, int64_t n_blocks, int64_t S, void* k_out, void* v_out,
                     int hk, int dh, int dtype, void* stream);
+int vy_paged_rope_write_fp8(void* qkv, int64_t ld, const int32_t* positions, const int64_t* slot_mapping,
+                            const float* cos_tab, const float* sin_tab, int64_t table_rows,
+                            const float* q_scale, const float* k_norm_scale, float eps, void* k_cache,
+                            void* v_cache, float* k_scale, float* v_scale, int64_t max_blocks, int block_size,
+                            int64_t T, int h, int hk, int dh, int dtype, void* stream);
+int vy_attn_paged_decode_fp8(const void* q, int64_t q_ld, const int32_t* q_rows, const void* k_cache,
+                             const void* v_cache, const float* k_scale, const float* v_scale, int64_t max_blocks,
+                             int block_size, const int32_t* block_table, int64_t bt_stride, const int32_t* seqlens,
+                             int64_t max_seqlen, void* out, int64_t o_ld, int64_t B, int h, int hk, int dh,
+                             float scale, int n_split, void* ws, int64_t ws_bytes, int dtype, void* stream);
+int64_t vy_attn_paged_decode_fp8_ws_bytes(int64_t B, int h, int hk, int dh, int64_t max_seqlen, int n_split, int dtype);
+int vy_attn_paged_prefill_fp8(const void* q, int64_t q_ld, const void* k_cache, const void* v_cache,
+                              const float* k_scale, const float* v_scale, int64_t max_blocks, int block_size,
+                              const int32_t* block_table, int64_t bt_stride, const int32_t* cu_q,
+                              const int32_t* ctx_lens, int64_t n_seq, int64_t max_q, int64_t max_kv, void* out,
+                              int64_t o_ld, int h, int hk, int dh, float scale, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * vy_layernorm_fwd: y = (x - mean) * rstd * gamma + beta over the last dim (biased variance).

@@ -1,5 +1,5 @@
 """Paged decode attention against the resident-context kernel on the same keys, and the continuous-batching engine against
-generate() on the same prompts.   python tools/bench_paged.py [--iters 1000] [--splits 1 2 4] [--skip-engine] [--prefill]
+generate() on the same prompts.   python tools/bench_paged.py [--iters 1000] [--splits 1 2 4] [--skip-engine] [--prefill] [--fp8]
 
 Kernels: vy_attn_paged_decode (bf16, block_size 256, pages in shuffled physical order) and vy_attn_decode on the same keys
 in a contiguous (B, hk, S, dh) cache, each timed as a link of a captured chain of 50 calls, the chains replayed in turn;
@@ -14,6 +14,10 @@ chains replayed in turn; TFLOP/s counts the causal half only (4 h dh sum_i (ctx 
 measurement is repeated and the lowest and highest figure of each variant are printed.  The engine section then adds
 one 2048-token request arriving while 7 sequences decode, unchunked and with max_step_tokens = 256: requested tokens per
 second and the longest single step().
+--fp8: the decode table gets vy_attn_paged_decode_fp8 on the same keys as e4m3 pages with per-(slot, head) scales
+(PagedKVManager(kv_cache_dtype="fp8")) as one more link of the same captured chains -- its bytes are the codes plus the
+scales, (dh + 4) / (2 dh) of the bf16 bytes -- and the engine workload runs once more over an fp8 manager, both
+engines with varlen_prefill=True (fp8 pages need it), each with its manager's kv_bytes.
 Prints one JSON line per measurement."""
 import argparse
 import ctypes as C
@@ -91,7 +95,15 @@ def copy_ceiling_gbs():
     return 2.0 * n / t * 1e-3
 
 
-def bench_kernels(iters, splits=()):
+def quantise_pages(pages):
+    """The rule of include/vyom_hip.h on bf16 pages (blocks, bs, hk, dh) -> (e4m3 codes, fp32 scales (blocks, bs, hk))."""
+    x = pages.float()
+    amax = x.abs().amax(dim=-1)
+    s = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    return (x / s.unsqueeze(-1)).clamp(-448, 448).to(torch.float8_e4m3fn), s
+
+
+def bench_kernels(iters, splits=(), fp8=False):
     ceiling = copy_ceiling_gbs()
     print(json.dumps({"what": "copy ceiling", "GBs": round(ceiling, 1)}))
     bs = 256
@@ -115,6 +127,10 @@ def bench_kernels(iters, splits=()):
         fns = [lambda: ops.attention_paged_decode(q, kc, vc, table, seqlens, S, h, out=out)]
         for n in splits:
             fns.append(lambda n=n: ops.attention_paged_decode(q, kc, vc, table, seqlens, S, h, out=out, n_split=n))
+        if fp8:
+            (kq, ks), (vq, vs) = quantise_pages(kc), quantise_pages(vc)
+            out8 = torch.empty_like(out)
+            fns.append(lambda: ops.attention_paged_decode(q, kq, vq, table, seqlens, S, h, out=out8, k_scale=ks, v_scale=vs))
         if dense:
             fns.append(lambda: ops.attention_decode(q4, k, v, S))
         t = timed_graph(fns, 20, iters)
@@ -125,6 +141,14 @@ def bench_kernels(iters, splits=()):
                "paged_share_of_copy_ceiling": round(nbytes / t[0] * 1e-3 / ceiling, 3)}
         for n, us in zip(splits, t[1:]):
             rec[f"paged_n_split_{n}_us"] = round(us, 2)
+        if fp8:
+            us = t[1 + len(splits)]
+            nb8 = 2 * B * hk * S * (dh + 4)
+            ns8 = (_lib.load().vy_attn_paged_decode_fp8_ws_bytes(B, h, hk, dh, S, 0, 1) // (B * h * (dh + 2) * 4)) or 1
+            fns[0]()
+            rec.update(fp8_us=round(us, 2), fp8_n_split=ns8, fp8_GBs=round(nb8 / us * 1e-3, 1),
+                       fp8_share_of_copy_ceiling=round(nb8 / us * 1e-3 / ceiling, 3), fp8_bytes_ratio=round(nb8 / nbytes, 3),
+                       fp8_time_ratio=round(us / t[0], 3), fp8_max_abs_diff=(out8.float() - out.float()).abs().max().item())
         if dense:
             diff = (out.float() - ops.attention_decode(q4, k, v, S).view(B, -1).float()).abs().max().item()
             rec.update(contiguous_us=round(t[-1], 2), ratio=round(t[0] / t[-1], 3), max_abs_diff=diff)
@@ -222,7 +246,7 @@ def bench_engine_long_arrival():
                           "longest_step_ms": [round(min(r[1] for r in res) * 1e3, 2), round(max(r[1] for r in res) * 1e3, 2)]}))
 
 
-def bench_engine():
+def bench_engine(fp8=False):
     cfg = V.Config(vocab_size=32000, hidden_size=896, intermediate_size=4864, num_hidden_layers=4,
                    num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=1024, pad_token_id=0)
     torch.manual_seed(0)
@@ -231,12 +255,13 @@ def bench_engine():
     plen, glen = [12, 40, 96, 24, 160, 64], [64, 32, 128, 16, 96, 48]
     prompts = [torch.randint(3, cfg.vocab_size, (n,), generator=g).tolist() for n in plen]
 
-    def run_engine():
-        mgr = V.PagedKVManager(cfg, 64, 16, DEV, BF)
-        eng = V.ContinuousBatchEngine(m, mgr, max_batch_size=8, eos_token_ids=[])
+    def run_engine(kv_cache_dtype=None, **kw):
+        mgr = V.PagedKVManager(cfg, 64, 16, DEV, BF, kv_cache_dtype=kv_cache_dtype)
+        eng = V.ContinuousBatchEngine(m, mgr, max_batch_size=8, eos_token_ids=[], **kw)
         for p, n in zip(prompts, glen):
             eng.add_sequence(p, max_gen_len=n)
-        return eng.run()
+        eng.run()
+        return mgr.kv_bytes
 
     def run_generate():
         L = max(plen)
@@ -247,8 +272,12 @@ def bench_engine():
             mask[r, L - len(p):] = 1
         return m.generate(ids.to(DEV), attention_mask=mask.to(DEV), max_new_tokens=max(glen))
 
-    for name, fn in (("engine", run_engine), ("generate", run_generate)):
-        fn()                                   # warm-up: every shape of the run
+    runs = [("engine", run_engine), ("generate", run_generate)]
+    if fp8:
+        runs = [("engine, varlen prefill, bf16 pages", lambda: run_engine(varlen_prefill=True)),
+                ("engine, varlen prefill, fp8 pages", lambda: run_engine("fp8", varlen_prefill=True))]
+    for name, fn in runs:
+        kv_bytes = fn()                        # warm-up: every shape of the run
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         reps = 3
@@ -256,8 +285,11 @@ def bench_engine():
             fn()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / reps
-        print(json.dumps({"what": name, "requests": len(prompts), "requested_tokens": sum(glen),
-                          "seconds": round(dt, 4), "requested_tokens_per_s": round(sum(glen) / dt, 1)}))
+        rec = {"what": name, "requests": len(prompts), "requested_tokens": sum(glen),
+               "seconds": round(dt, 4), "requested_tokens_per_s": round(sum(glen) / dt, 1)}
+        if fp8:
+            rec["kv_bytes"] = kv_bytes
+        print(json.dumps(rec))
 
 
 if __name__ == "__main__":
@@ -265,6 +297,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=1000)
     ap.add_argument("--skip-engine", action="store_true")
     ap.add_argument("--prefill", action="store_true", help="time the prefill attention paths instead of the decode kernels")
+    ap.add_argument("--fp8", action="store_true", help="add the fp8-page decode kernel and the engine over an fp8 manager")
     ap.add_argument("--splits", type=int, nargs="*", default=[], help="also time these pinned n_split values")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -272,8 +305,8 @@ if __name__ == "__main__":
     if a.prefill:
         bench_prefill(min(a.iters, 200))
     else:
-        bench_kernels(a.iters, a.splits)
+        bench_kernels(a.iters, a.splits, a.fp8)
     if not a.skip_engine:
-        bench_engine()
+        bench_engine(a.fp8)
         if a.prefill:
             bench_engine_long_arrival()

@@ -41,6 +41,12 @@ PROTOTYPES = {
     "vy_attn_paged_prefill": [_p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _i, _i, _i, _f,
                               _i, _p],
     "vy_paged_gather": [_p, _p, _i64, _i, _p, _i64, _i64, _p, _p, _i, _i, _i, _p],
+    "vy_paged_rope_write_fp8": [_p, _i64, _p, _p, _p, _p, _i64, _p, _p, _f, _p, _p, _p, _p, _i64, _i, _i64, _i, _i, _i,
+                                _i, _p],
+    "vy_attn_paged_decode_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i, _i, _i,
+                                 _f, _i, _p, _i64, _i, _p],
+    "vy_attn_paged_prefill_fp8": [_p, _i64, _p, _p, _p, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _i,
+                                  _i, _i, _f, _i, _p],
     "vy_layernorm_fwd": [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64, _i64, _f, _i, _p],
     "vy_rmsnorm_fwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _f, _f, _i, _p],
     "vy_gated_act_fwd": [_p, _i64, _p, _i64, _i64, _i64, _i, _i, _p],
@@ -93,7 +99,8 @@ PROTOTYPES = {
     "vy_workspace_set": [_p, _p, _i64],
 }
 OTHER_SYMBOLS = ["vy_last_error", "vy_abi_version", "vy_layernorm_bwd_ws_rows", "vy_decode_ws_bytes",
-                 "vy_gemma_ws_bytes", "vy_ddp_world", "vy_ddp_rank", "vy_attn_paged_decode_ws_bytes"]
+                 "vy_gemma_ws_bytes", "vy_ddp_world", "vy_ddp_rank", "vy_attn_paged_decode_ws_bytes",
+                 "vy_attn_paged_decode_fp8_ws_bytes"]
 ALL_SYMBOLS = list(PROTOTYPES) + OTHER_SYMBOLS
 
 
@@ -139,6 +146,8 @@ def load() -> C.CDLL:
     lib.vy_decode_ws_bytes.argtypes = [C.c_int32] * 7
     lib.vy_attn_paged_decode_ws_bytes.restype = C.c_int64
     lib.vy_attn_paged_decode_ws_bytes.argtypes = [_i64, _i, _i, _i, _i64, _i, _i]
+    lib.vy_attn_paged_decode_fp8_ws_bytes.restype = C.c_int64
+    lib.vy_attn_paged_decode_fp8_ws_bytes.argtypes = [_i64, _i, _i, _i, _i64, _i, _i]
     _lib = lib
     return lib
 

@@ -9,21 +9,31 @@ from .. import ops
 from .attention import _shadow
 
 
+def page_scales(kv_mgr, layer: int) -> dict:
+    """The keywords the paged attention ops take for layer `layer` of an fp8 manager; none for an unquantised one."""
+    if getattr(kv_mgr, "k_scale", None) is None:
+        return {}
+    return {"k_scale": kv_mgr.k_scale[layer], "v_scale": kv_mgr.v_scale[layer]}
+
+
 def paged_step_attention(qkv: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, metadata: dict, h: int, hk: int,
-                         dh: int) -> torch.Tensor:
+                         dh: int, **scales) -> torch.Tensor:
     """Attention of one layer over the step's packed rows qkv (T, (h + 2 hk) dh), rotated and already written to the
     pages kc / vc -> o (T, h dh).  vy_attn_paged_decode serves the rows with one query token; the prefill rows take ONE
     vy_attn_paged_prefill through the block tables (metadata["prefill_varlen"]: no gather, no loop, a segment may be a
     chunk in the middle of its prompt) or else causal vy_attn_fwd per sequence, straight on its slice of the packed
-    buffer or with start_pos = prefix_len against its gathered pages when it starts from cached prefix blocks."""
+    buffer or with start_pos = prefix_len against its gathered pages when it starts from cached prefix blocks.
+    scales: k_scale= / v_scale= of fp8 pages (page_scales), which only the two paged kernels read."""
     o = torch.empty((qkv.shape[0], h * dh), dtype=qkv.dtype, device=qkv.device)
     dec, pv = metadata["decode"], metadata.get("prefill_varlen")
     if dec is not None:
         ops.attention_paged_decode(qkv, kc, vc, dec["block_table"], dec["seqlens"], dec["max_seqlen"], h,
-                                   q_rows=dec["rows"], out=o)
+                                   q_rows=dec["rows"], out=o, **scales)
     if pv is not None:
         ops.attention_paged_prefill(qkv, kc, vc, pv["block_table"], pv["cu_q"], pv["ctx_lens"], pv["max_q"],
-                                    pv["max_kv"], h, out=o)
+                                    pv["max_kv"], h, out=o, **scales)
+    elif scales and metadata["prefill"]:
+        raise ValueError("fp8 KV pages are read by the varlen prefill only (ContinuousBatchEngine(varlen_prefill=True))")
     for row0, rows, prefix_len, table in (() if pv is not None else metadata["prefill"]):
         seg = qkv[row0:row0 + rows]
         q4 = seg[:, :h * dh].view(rows, h, dh).permute(1, 0, 2).unsqueeze(0)

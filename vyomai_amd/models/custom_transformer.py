@@ -22,7 +22,7 @@ from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
 from ..layers.kv_cache import DynamicCacheOne, StaticCacheOne
 from ..layers.mask import AttnMask
-from ..layers.paged import paged_step_attention, paged_step_logits
+from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
 from ..layers.positional_embeddings import RopeSlice, RopeTable, resolve_freqs
 from .common import PositionMixin
 
@@ -488,8 +488,9 @@ class ModelForCausalLM(nn.Module):
             kc, vc = kv_mgr.k_cache[a.layer_idx], kv_mgr.v_cache[a.layer_idx]
             sw, sb = a._packed_shadow(dt)
             qkv = ops.linear(layer.input_layernorm(x), sw, sb)
-            ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc)
-            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh)
+            sc = page_scales(kv_mgr, a.layer_idx)      # fp8 pages: their scales; else nothing
+            ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc, **sc)
+            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh, **sc)
             x = ops.linear(o, _shadow(a.o_proj.weight, dt), None, residual=x)
             x = layer.mlp(layer.post_attention_layernorm(x), residual=x)
         return paged_step_logits(x, metadata["last_rows"], base.norm, self.lm_head.weight)

@@ -29,7 +29,7 @@ import torch.nn as nn
 from .. import ops
 from .._lib import ACT_SILU, VyomHipError
 from ..layers.attention import _shadow
-from ..layers.paged import paged_step_attention, paged_step_logits
+from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
 from .custom_transformer import _need_gpu
 
 
@@ -195,14 +195,16 @@ class Qwen3Model(nn.Module):
             h, hk, dh = a.num_heads, a.num_kv_groups, a.head_dim
             kc, vc = kv_mgr.k_cache[a.layer_idx], kv_mgr.v_cache[a.layer_idx]
             qkv = ops.linear(blk.norm1(x), a._packed_qkv(dt))
+            sc = page_scales(kv_mgr, a.layer_idx)      # fp8 pages: their scales; else nothing
             if a.q_norm is not None:
                 if a.q_norm.eps != a.k_norm.eps:
                     raise ValueError("q_norm and k_norm share one eps in vy_paged_qknorm_rope_write")
                 ops.paged_qknorm_rope_write_(qkv, positions, slots, cos, sin, _shadow(a.q_norm.scale, torch.float32),
-                                             _shadow(a.k_norm.scale, torch.float32), a.q_norm.eps, h, kc, vc)
+                                             _shadow(a.k_norm.scale, torch.float32), a.q_norm.eps, h, kc, vc,
+                                             k_page_scale=sc.get("k_scale"), v_page_scale=sc.get("v_scale"))
             else:
-                ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc)
-            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh)
+                ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc, **sc)
+            o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh, **sc)
             x = ops.linear(o, _shadow(a.out_proj.weight, dt), None, residual=x)
             x = blk.ff(blk.norm2(x), residual=x)
         return paged_step_logits(x, metadata["last_rows"], self.final_norm, self.out_head.weight)

@@ -889,8 +889,15 @@ def gated_act_bwd(d_act: Tensor, gate_up: Tensor, act: int) -> Tensor:
 # ------------------------------------------------------------------------------------------
 
 
-def _check_pages(k_cache: Tensor, v_cache: Tensor, dtype) -> Tuple[int, int, int, int]:
-    """(max_blocks, block_size, hk, dh) of one layer's pages; the shape rules of include/vyom_hip.h as ValueErrors."""
+def _is_fp8_pages(t: Tensor) -> bool:
+    return t.dtype == torch.float8_e4m3fn
+
+
+def _check_pages(k_cache: Tensor, v_cache: Tensor, dtype, k_scale: Optional[Tensor] = None,
+                 v_scale: Optional[Tensor] = None) -> Tuple[int, int, int, int]:
+    """(max_blocks, block_size, hk, dh) of one layer's pages; the shape rules of include/vyom_hip.h as ValueErrors.
+    fp8 (torch.float8_e4m3fn) pages come with their fp32 (max_blocks, block_size, hk) scales and a bf16 step; pages of
+    the step's dtype come without scales."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("k_cache / v_cache must be contiguous (max_blocks, block_size, hk, dh) tensors of one shape")
     nb, bs, hk, dh = k_cache.shape
@@ -898,23 +905,43 @@ def _check_pages(k_cache: Tensor, v_cache: Tensor, dtype) -> Tuple[int, int, int
         raise ValueError(f"block_size {bs} must be a power of two from 8 to 256")
     if dh % 8 or dh > 256:
         raise ValueError(f"head_dim {dh} must be a multiple of 8 up to 256")
+    if _is_fp8_pages(k_cache) or _is_fp8_pages(v_cache):
+        if k_cache.dtype != v_cache.dtype or dtype != torch.bfloat16:
+            raise ValueError(f"fp8 pages serve a bfloat16 step with fp8 k and v pages, got {k_cache.dtype} / "
+                             f"{v_cache.dtype} pages and a {dtype} step")
+        if k_scale is None or v_scale is None:
+            raise ValueError("fp8 pages need k_scale= and v_scale=")
+        for sc in (k_scale, v_scale):
+            if sc.dtype != torch.float32 or sc.shape != (nb, bs, hk) or not sc.is_contiguous():
+                raise ValueError(f"k_scale / v_scale must be contiguous float32 {(nb, bs, hk)} tensors")
+        return nb, bs, hk, dh
+    if k_scale is not None or v_scale is not None:
+        raise ValueError(f"k_scale / v_scale belong to fp8 pages, these pages are {k_cache.dtype}")
     if k_cache.dtype != dtype or v_cache.dtype != dtype:
         raise ValueError(f"pages are {k_cache.dtype}, the step computes in {dtype}")
     return nb, bs, hk, dh
 
 
 def paged_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos: Tensor, sin: Tensor, h: int,
-                      k_cache: Tensor, v_cache: Tensor) -> Tensor:
+                      k_cache: Tensor, v_cache: Tensor, *, k_scale: Optional[Tensor] = None,
+                      v_scale: Optional[Tensor] = None) -> Tensor:
     """qkv (T, (h + 2 hk) dh), the packed projection of a step's tokens: q and k heads of token t rotated in place with
     row positions[t] (int32) of the fp32 cos / sin tables, the rotated k and the v stored into slot slot_mapping[t]
-    (int64; negative: nothing is stored) of the pages.  (vy_paged_rope_write)"""
-    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype)
-    _need_gpu(qkv, positions, slot_mapping, cos, sin, k_cache, v_cache)
+    (int64; negative: nothing is stored) of the pages.  (vy_paged_rope_write)
+    fp8 pages (k_scale= / v_scale=, fp32 (max_blocks, block_size, hk)): the same in-place rows, every k / v head stored
+    as e4m3 codes and one scale -- the rule of include/vyom_hip.h.  (vy_paged_rope_write_fp8)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype, k_scale, v_scale)
+    _need_gpu(qkv, positions, slot_mapping, cos, sin, k_cache, v_cache, k_scale, v_scale)
     T = qkv.shape[0]
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (h + 2 * hk) * dh
     assert positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == T
     assert slot_mapping.dtype == torch.long and slot_mapping.is_contiguous() and slot_mapping.numel() == T
     assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == dh // 2 and sin.shape == cos.shape
+    if k_scale is not None:
+        call("vy_paged_rope_write_fp8", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
+             cos.data_ptr(), sin.data_ptr(), cos.shape[0], None, None, 0.0, k_cache.data_ptr(), v_cache.data_ptr(),
+             k_scale.data_ptr(), v_scale.data_ptr(), nb, bs, T, h, hk, dh, dtype_code(qkv.dtype), _stream())
+        return qkv
     call("vy_paged_rope_write", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
          cos.data_ptr(), sin.data_ptr(), cos.shape[0], k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, T, h, hk, dh,
          dtype_code(qkv.dtype), _stream())
@@ -923,13 +950,16 @@ def paged_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos:
 
 def paged_qknorm_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tensor, cos: Tensor, sin: Tensor,
                              q_scale: Tensor, k_scale: Tensor, eps: float, h: int, k_cache: Tensor,
-                             v_cache: Tensor) -> Tensor:
+                             v_cache: Tensor, *, k_page_scale: Optional[Tensor] = None,
+                             v_page_scale: Optional[Tensor] = None) -> Tensor:
     """paged_rope_write_ with Qwen3's qk_norm in the same launch: every q head becomes x * rsqrt(mean x^2 + eps) *
     q_scale, every k head the same with k_scale (fp32 (dh,), shared by all heads), and the normalised head is what is
     rotated, stored in place and (k) stored into its slot; fp32 from the load to the one store.  v heads are only
-    stored into their slots.  (vy_paged_qknorm_rope_write)"""
-    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype)
-    _need_gpu(qkv, positions, slot_mapping, cos, sin, q_scale, k_scale, k_cache, v_cache)
+    stored into their slots.  (vy_paged_qknorm_rope_write)
+    fp8 pages: their scales come as k_page_scale= / v_page_scale= (k_scale is the norm weight here), otherwise as
+    paged_rope_write_.  (vy_paged_rope_write_fp8)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, qkv.dtype, k_page_scale, v_page_scale)
+    _need_gpu(qkv, positions, slot_mapping, cos, sin, q_scale, k_scale, k_cache, v_cache, k_page_scale, v_page_scale)
     T = qkv.shape[0]
     assert qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (h + 2 * hk) * dh
     assert positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == T
@@ -937,6 +967,12 @@ def paged_qknorm_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tenso
     assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == dh // 2 and sin.shape == cos.shape
     for s in (q_scale, k_scale):
         assert s.dtype == torch.float32 and s.is_contiguous() and s.shape == (dh,)
+    if k_page_scale is not None:
+        call("vy_paged_rope_write_fp8", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
+             cos.data_ptr(), sin.data_ptr(), cos.shape[0], q_scale.data_ptr(), k_scale.data_ptr(), float(eps),
+             k_cache.data_ptr(), v_cache.data_ptr(), k_page_scale.data_ptr(), v_page_scale.data_ptr(), nb, bs, T, h, hk,
+             dh, dtype_code(qkv.dtype), _stream())
+        return qkv
     call("vy_paged_qknorm_rope_write", qkv.data_ptr(), qkv.stride(0), positions.data_ptr(), slot_mapping.data_ptr(),
          cos.data_ptr(), sin.data_ptr(), cos.shape[0], q_scale.data_ptr(), k_scale.data_ptr(), float(eps),
          k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, T, h, hk, dh, dtype_code(qkv.dtype), _stream())
@@ -945,13 +981,15 @@ def paged_qknorm_rope_write_(qkv: Tensor, positions: Tensor, slot_mapping: Tenso
 
 def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, seqlens: Tensor,
                            max_seqlen: int, h: int, *, q_rows: Optional[Tensor] = None, out: Optional[Tensor] = None,
-                           n_split: int = 0, scale: Optional[float] = None) -> Tensor:
+                           n_split: int = 0, scale: Optional[float] = None, k_scale: Optional[Tensor] = None,
+                           v_scale: Optional[Tensor] = None) -> Tensor:
     """One query token per sequence against its pages.  q (rows, >= h dh): sequence b's heads sit at row q_rows[b]
     (int32; None: row b); block_table int32 (B, n), seqlens int32 (B,), keys [0, seqlens[b]) are attended.  out
     (rows, h dh) is written at the same rows and returned.  n_split: workgroups per context (0: chosen by the library).
-    (vy_attn_paged_decode)"""
-    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype)
-    _need_gpu(q, k_cache, v_cache, block_table, seqlens, q_rows, out)
+    (vy_attn_paged_decode)  fp8 pages: k_scale= / v_scale=, the keys are read as code * scale.
+    (vy_attn_paged_decode_fp8)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype, k_scale, v_scale)
+    _need_gpu(q, k_cache, v_cache, block_table, seqlens, q_rows, out, k_scale, v_scale)
     B = seqlens.numel()
     assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= h * dh
     assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1 \
@@ -966,13 +1004,21 @@ def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_ta
     if scale is None:
         scale = 1.0 / math.sqrt(dh)
     code = dtype_code(q.dtype)
-    need = _lib.load().vy_attn_paged_decode_ws_bytes(B, h, hk, dh, int(max_seqlen), int(n_split), code)
+    fp8 = k_scale is not None
+    ws_bytes = _lib.load().vy_attn_paged_decode_fp8_ws_bytes if fp8 else _lib.load().vy_attn_paged_decode_ws_bytes
+    need = ws_bytes(B, h, hk, dh, int(max_seqlen), int(n_split), code)
     ws = None
     if need:      # split-KV partials: the stream's GEMM workspace (an automatic split that would not fit runs unsplit)
         if need <= _WS_BYTES:
             ws = _stream_ws()
         elif n_split:
             raise ValueError(f"n_split {n_split} needs {need} bytes of workspace, the stream's buffer has {_WS_BYTES}")
+    if fp8:
+        call("vy_attn_paged_decode_fp8", q.data_ptr(), q.stride(0), _ptr(q_rows), k_cache.data_ptr(), v_cache.data_ptr(),
+             k_scale.data_ptr(), v_scale.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0),
+             seqlens.data_ptr(), int(max_seqlen), out.data_ptr(), out.stride(0), B, h, hk, dh, float(scale), int(n_split),
+             _ptr(ws), 0 if ws is None else ws.numel(), code, _stream())
+        return out
     call("vy_attn_paged_decode", q.data_ptr(), q.stride(0), _ptr(q_rows), k_cache.data_ptr(), v_cache.data_ptr(), nb, bs,
          block_table.data_ptr(), block_table.stride(0), seqlens.data_ptr(), int(max_seqlen), out.data_ptr(),
          out.stride(0), B, h, hk, dh, float(scale), int(n_split), _ptr(ws), 0 if ws is None else ws.numel(), code,
@@ -982,14 +1028,16 @@ def attention_paged_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_ta
 
 def attention_paged_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor, cu_q: Tensor,
                             ctx_lens: Tensor, max_q: int, max_kv: int, h: int, *, out: Optional[Tensor] = None,
-                            scale: Optional[float] = None) -> Tensor:
+                            scale: Optional[float] = None, k_scale: Optional[Tensor] = None,
+                            v_scale: Optional[Tensor] = None) -> Tensor:
     """Causal attention of packed query segments against the pages, one launch for all of them.  q (rows, >= h dh): rows
     cu_q[s] .. cu_q[s+1] - 1 (int32, n + 1 entries) are sequence s, row i of it sits at position ctx_lens[s] + i (int32,
     (n,)) and attends to keys [0, ctx_lens[s] + i] read through block_table[s] (int32, (n, width)); the step's own K/V
     rows are already in the pages.  max_q >= every segment length, max_kv >= every ctx + length (host values).  out
-    (rows, h dh) is written at the segments' rows and returned.  (vy_attn_paged_prefill)"""
-    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype)
-    _need_gpu(q, k_cache, v_cache, block_table, cu_q, ctx_lens, out)
+    (rows, h dh) is written at the segments' rows and returned.  (vy_attn_paged_prefill)  fp8 pages: k_scale= /
+    v_scale=, a key row enters as bf16(code * scale).  (vy_attn_paged_prefill_fp8)"""
+    nb, bs, hk, dh = _check_pages(k_cache, v_cache, q.dtype, k_scale, v_scale)
+    _need_gpu(q, k_cache, v_cache, block_table, cu_q, ctx_lens, out, k_scale, v_scale)
     n = ctx_lens.numel()
     assert q.dim() == 2 and q.stride(1) == 1 and q.shape[1] >= h * dh
     assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1 \
@@ -1003,6 +1051,12 @@ def attention_paged_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, block_t
         and out.shape[0] >= q.shape[0]
     if scale is None:
         scale = 1.0 / math.sqrt(dh)
+    if k_scale is not None:
+        call("vy_attn_paged_prefill_fp8", q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+             k_scale.data_ptr(), v_scale.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0),
+             cu_q.data_ptr(), ctx_lens.data_ptr(), n, int(max_q), int(max_kv), out.data_ptr(), out.stride(0), h, hk, dh,
+             float(scale), dtype_code(q.dtype), _stream())
+        return out
     call("vy_attn_paged_prefill", q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), nb, bs,
          block_table.data_ptr(), block_table.stride(0), cu_q.data_ptr(), ctx_lens.data_ptr(), n, int(max_q), int(max_kv),
          out.data_ptr(), out.stride(0), h, hk, dh, float(scale), dtype_code(q.dtype), _stream())

@@ -170,9 +170,15 @@ class SequenceState:
 class PagedKVManager:
     """The pages of every layer -- k_cache[i] / v_cache[i]: (max_blocks, block_size, num_key_value_heads, head_dim) on
     `device` -- and who owns them: a free list, a radix tree over complete prompt blocks, and the queue of registered
-    blocks nobody holds (evictable, oldest first).  `config` is the model's Config (the notebook passes a dict)."""
+    blocks nobody holds (evictable, oldest first).  `config` is the model's Config (the notebook passes a dict).
 
-    def __init__(self, config, max_blocks: int, block_size: int, device="cpu", dtype=torch.float32):
+    kv_cache_dtype="fp8" ("fp8_e4m3", torch.float8_e4m3fn): the pages hold OCP e4m3 codes, one byte an element, and
+    k_scale[i] / v_scale[i] -- fp32 (max_blocks, block_size, num_key_value_heads) -- one scale per slot and KV head, at
+    the block's own indices (the rule: include/vyom_hip.h).  Blocks, the tree, eviction and admission do not change.
+    None: pages in `dtype`, k_scale / v_scale are None.  kv_bytes: what pages and scales hold."""
+
+    def __init__(self, config, max_blocks: int, block_size: int, device="cpu", dtype=torch.float32,
+                 kv_cache_dtype=None):
         if block_size < 8 or block_size > 256 or block_size & (block_size - 1):
             raise ValueError(f"block_size {block_size} must be a power of two from 8 to 256")
         if max_blocks < 1:
@@ -186,8 +192,32 @@ class PagedKVManager:
         hk = config.num_key_value_heads
         dh = getattr(config, "head_dim", config.hidden_size // config.num_attention_heads)
         shape = (max_blocks, block_size, hk, dh)
-        self.k_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(config.num_hidden_layers)]
-        self.v_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(config.num_hidden_layers)]
+        layers = range(config.num_hidden_layers)
+        if kv_cache_dtype is None:
+            self.kv_cache_dtype = None
+            self.k_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in layers]
+            self.v_cache = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in layers]
+            self.k_scale = self.v_scale = None
+        elif kv_cache_dtype in ("fp8", "fp8_e4m3", torch.float8_e4m3fn):
+            self.kv_cache_dtype = torch.float8_e4m3fn
+            self.k_cache = [self._fp8_zeros(shape) for _ in layers]
+            self.v_cache = [self._fp8_zeros(shape) for _ in layers]
+            self.k_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=self.device) for _ in layers]
+            self.v_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=self.device) for _ in layers]
+        else:
+            raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: None, 'fp8', 'fp8_e4m3' or torch.float8_e4m3fn")
+
+    def _fp8_zeros(self, shape) -> torch.Tensor:
+        try:
+            return torch.zeros(shape, dtype=torch.float8_e4m3fn, device=self.device)
+        except (RuntimeError, TypeError):      # an allocator that refuses the dtype: the same bytes, viewed
+            return torch.zeros(shape, dtype=torch.uint8, device=self.device).view(torch.float8_e4m3fn)
+
+    @property
+    def kv_bytes(self) -> int:
+        """Bytes held by the pages of every layer, plus their scales."""
+        held = self.k_cache + self.v_cache + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in held)
 
     def blocks_for(self, num_tokens: int) -> int:
         return (num_tokens + self.block_size - 1) // self.block_size
@@ -292,6 +322,12 @@ class PagedKVManager:
         state.block_count = 0
 
 
+def _compute_dtype(model) -> torch.dtype:
+    """The dtype of the model's packed QKV rows: compute_dtype where a model keeps fp32 masters, else its parameters'."""
+    inner = getattr(model, "model", model)
+    return getattr(inner, "compute_dtype", None) or next(model.parameters()).dtype
+
+
 class ContinuousBatchEngine:
     """add_sequence() queues a request; step() admits what fits, runs ONE packed forward over every running sequence
     (all unseen prompt tokens of the newly admitted ones, one token of the others), appends to each the token its
@@ -317,6 +353,14 @@ class ContinuousBatchEngine:
                 raise ValueError(f"max_step_tokens {max_step_tokens} must be at least max_batch_size {max_batch_size}: "
                                  "every decoding sequence takes a token and a prefilling one must still progress")
         self.max_step_tokens, self.varlen_prefill = max_step_tokens, bool(varlen_prefill)
+        if getattr(kv_mgr, "k_scale", None) is not None:
+            if not varlen_prefill:
+                raise ValueError("fp8 KV pages need varlen_prefill=True: the per-sequence prefill attends to the "
+                                 "step's own unquantised rows and gathers bf16 pages")
+            computes = kv_mgr.dtype if model is None else _compute_dtype(model)
+            if computes != torch.bfloat16 or kv_mgr.dtype != torch.bfloat16:
+                raise ValueError(f"fp8 KV pages serve a model that computes in bfloat16: the model computes in "
+                                 f"{computes}, the manager was built for {kv_mgr.dtype}")
         self.model, self.kv_mgr = model, kv_mgr
         if model is not None:
             model.eval()
