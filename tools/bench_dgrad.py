@@ -1,11 +1,9 @@
-"""The three dgrad launches of a layer + the FFN2 dgrad with the GELU derivative (B=32 x 512 rows, d=768), per
-GEMM variant:  python tools/bench_dgrad.py [variants...]   (VY_GEMM_VARIANT values; -1 = default selection)"""
-import ctypes as C, math, os, sys
+"""The three dgrad launches of a layer + the FFN2 dgrad with the GELU derivative (B=32 x 512 rows, d=768):
+python tools/bench_dgrad.py"""
+import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vyomai_amd import ops, _lib
-lib = _lib.load()
-lib.vy_debug_set_gemm_variant.argtypes = [C.c_int]
+from vyomai_amd import ops
 M, d = 16384, 768
 bf, dev = torch.bfloat16, "cuda"
 g = torch.Generator().manual_seed(0)
@@ -33,10 +31,8 @@ cases = {
     "ffn1 dgrad (N 768, K 3072, + residual)": (lambda: ops.linear_dgrad(dy_4d, w1_t, add_to=res, out=outs["d"]), 2.0 * M * d * 4 * d),
     "ffn2 dgrad (N 3072, K 768, * gelu'(pre))": (lambda: ops.linear_dgrad(dy_d, w2_t, pre=pre, act=1, out=outs["4d"]), 2.0 * M * d * 4 * d),
 }
-for v in [int(x) for x in sys.argv[1:]] or [-1]:
-    lib.vy_debug_set_gemm_variant(v)
-    line = [f"variant {v:3d}:"]
-    for name, (fn, fl) in cases.items():
-        us = t(fn)
-        line.append(f"{name} {us:6.1f} us {fl / us * 1e-6:5.0f} TF")
-    print("  |  ".join(line))
+line = []
+for name, (fn, fl) in cases.items():
+    us = t(fn)
+    line.append(f"{name} {us:6.1f} us {fl / us * 1e-6:5.0f} TF")
+print("  |  ".join(line))

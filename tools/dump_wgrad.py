@@ -1,5 +1,5 @@
 """dW and db of the bf16 weight-gradient calls, for comparing two builds of the library bit for bit (tools/ab_lib.sh,
-VY_LIB_PATH; one fresh process per library, VY_WGRAD_M16 as wanted, the other VY_WGRAD_* knobs unset):
+VY_LIB_PATH; one fresh process per library):
   python tools/dump_wgrad.py OUT.npz          the bf16 shapes of tests.test_bwd_kernels_gpu.test_wgrad_exact, each through
                                               linear_wgrad (overwrite, accumulate, accumulate with alpha = 0.5) and the
                                               grouped entry point, and the six-item strided group of test_wgrad_grouped;
@@ -26,7 +26,7 @@ def cdiv(a, b):
     return (a + b - 1) // b
 
 
-# the launchers' M-split arithmetic under the default selection (vy_bwd.hip: wgrad_split and its two callers)
+# the launchers' M-split arithmetic (vy_bwd.hip: wgrad_split and its two callers)
 def m_splits(M, want):
     want = max(1, min(want, cdiv(M, 256)))
     return cdiv(M, cdiv(cdiv(M, want), 64) * 64)
@@ -50,8 +50,6 @@ def tag(kind, addends, zero_start):
 
 
 def dump(path):
-    for knob in ("VY_WGRAD_VARIANT", "VY_WGRAD_TARGET", "VY_WGRAD_GROUP_TARGET", "VY_WGRAD_DIAG"):
-        assert knob not in os.environ, f"{knob} is set: the addend counts below are those of the default selection"
     from tests import test_bwd_kernels_gpu as T
     from tests.test_kernels_gpu import ints, rnd
     from vyomai_amd import ops

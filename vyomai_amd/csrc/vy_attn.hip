@@ -40,7 +40,6 @@ struct AttnParams {
   int B, h, hk, L, S;
   float scale;
   const int* pos_dev;  // decode under a hipGraph: S = *pos_dev + 1 (else NULL)
-  int diag;            // timing experiments only (VY_ATTN_DIAG): 1 = no output store, 2 = no tile loop
 };
 
 // ------------------------------------------------------------------------------------------
@@ -244,7 +243,7 @@ __global__ __launch_bounds__(256, DH == 64 ? 3 : 1) void attn_fwd_mfma_kernel(At
   for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(Q + ks * 16 + fh * 8);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(qf[ks]));
-  for (int t = 0; t < (p.diag == 2 ? 0 : nt); ++t) {
+  for (int t = 0; t < nt; ++t) {
     Ring::arrive(t, nt);
     if (t + Ring::AHEAD < nt) stage(t + Ring::AHEAD, (t + Ring::AHEAD) % NS);
     compute(t, t % NS);
@@ -617,9 +616,8 @@ int launch_rowwise(const AttnParams& p, int dh, hipStream_t st, const char* who)
   int cpr = 1;
   while (cpr * VEC < dh) cpr <<= 1;  // lanes per key row, rounded up to a power of two
   const dim3 grid(p.L, p.h, p.B), block(256);
-  static const int wide_wg = [] { const char* e = getenv("VY_DECODE_WIDE_WG"); return e ? atoi(e) : 1; }();
-  static const int wide_rows = [] { const char* e = getenv("VY_DECODE_WIDE_ROWS"); return e ? atoi(e) : 128; }();
-  if (p.L == 1 && wide_wg && (int64_t)p.B * p.h <= wide_rows && p.S > 64 && std::is_same<T, bf16>::value && (cpr == 8 || cpr == 32)) {
+  constexpr int wide_rows = 128;   // single-token rows (B * h) up to which a row gets a 16-wave workgroup
+  if (p.L == 1 && (int64_t)p.B * p.h <= wide_rows && p.S > 64 && std::is_same<T, bf16>::value && (cpr == 8 || cpr == 32)) {
     const dim3 block16(1024);
     if (cpr == 8) hipLaunchKernelGGL((attn_rowwise_kernel<T, 8, 16>), grid, block16, 0, st, p, dh);
     else hipLaunchKernelGGL((attn_rowwise_kernel<T, 32, 16>), grid, block16, 0, st, p, dh);
@@ -675,8 +673,6 @@ extern "C" int vy_attn_fwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
   p.mask_kind = mask_kind; p.start_pos = (int)start_pos;
   p.keypad = keypad; p.kp_sb = kp_sb; p.addmask = addmask; p.am_sb = am_sb; p.am_sl = am_sl;
   p.B = (int)B; p.h = h; p.hk = hk; p.L = (int)L; p.S = (int)S; p.scale = scale; p.pos_dev = nullptr;
-  static const int diag = [] { const char* e = getenv("VY_ATTN_DIAG"); return e ? atoi(e) : 0; }();
-  p.diag = diag;
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "%s: bad dtype %d", who, dtype);
   if (int rc = check_attn(who, p, dh, dtype)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -688,8 +684,7 @@ extern "C" int vy_attn_fwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
     VY_CHECK_LAUNCH(who);
     return VY_OK;
   }
-  static const int gen_on = [] { const char* e = getenv("VY_ATTN_GEN"); return e ? atoi(e) : 1; }();
-  if (gen_on && dtype == VY_BF16 && L > 1 && dh % 8 == 0 && dh <= 256 && !(mask_kind & VY_MASK_ADDITIVE)) {
+  if (dtype == VY_BF16 && L > 1 && dh % 8 == 0 && dh <= 256 && !(mask_kind & VY_MASK_ADDITIVE)) {
     // other head widths (72 -> 96 columns, ... 256): the general MFMA kernel, 64 query rows per workgroup
     const dim3 grid((unsigned)(h * B), (unsigned)((L + 63) / 64), 1), block(256);
     if (dh <= 96) hipLaunchKernelGGL(attn_fwd_gen_kernel<96>, grid, block, 0, st, p, dh);

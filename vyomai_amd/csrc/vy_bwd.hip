@@ -18,7 +18,6 @@
 // (dS = P o (dP - rowsum(dO o O))).
 #include "vy_attn_tile.h"
 #include <float.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -45,7 +44,8 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* base, int row_bytes) {
 // 256 x 256 with 32-row stages in a 4-deep ring (128 KiB, one workgroup per CU).
 // The kernel is three parts: WgradTile (the LDS image of a stage and its writer), one ring in wgrad_tn_bf16_body
 // (when a stage is requested, which vmcnt is waited for, where the barrier sits) and a fragment policy per MFMA
-// shape, WgradMma32 / WgradMma16 (accumulators, the k-step schedule of one stage, bias gradient, atomic epilogue).
+// shape, WgradMma32 / WgradMma16 (accumulators, the k-step schedule of one stage, bias gradient, atomic epilogue):
+// the 128 x 128 tile runs on mfma_f32_32x32x16_bf16, the 256 x 256 tile on mfma_f32_16x16x32_bf16.
 // ------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
@@ -335,13 +335,17 @@ struct WgradMma16 {
 
 // The ring: NS stages of LDS, the loads of the next NS-1 stages in flight while a stage is multiplied; a stage is
 // waited for with a COUNTED vmcnt (its 2 PP LDS-DMA instructions are the wave's oldest) and one raw s_barrier.
-template <int BN, int BKW, int MS, int NS, bool MF16>
+template <int BN, int BKW, int MS, int NS>
 __device__ __forceinline__ void wgrad_tn_bf16_body(
     const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
     float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
-    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int diag, int wg) {
+    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int wg) {
   static_assert(BN == BKW && ((BN == 128 && MS == 64 && NS == 2) || (BN == 256 && MS == 32 && NS == 4)),
                 "built shapes: 128 x 128 x 64 in 2 stages, 256 x 256 x 32 in 4");
+  // 16 x 16 x 32 MFMAs: 3 % faster on the 256 x 256 tiles (vocabulary projection 1.62 -> 1.57 ms, +0.25 % on the training
+  // step), 2-8 % SLOWER on the 128 x 128 tiles (these kernels are bound by the transposing LDS reads and the atomic
+  // epilogue, not by the matrix pipe) -- so the MFMA shape follows the tile
+  constexpr bool MF16 = BN == 256;
   typedef WgradTile<BN, MS, MF16> Tile;
   typedef std::conditional_t<MF16, WgradMma16<Tile>, WgradMma32<Tile>> Mma;
   constexpr int STAGE = Tile::STAGE, PS = 2 * Tile::PP;   // LDS-DMA instructions per wave and stage
@@ -373,21 +377,17 @@ __device__ __forceinline__ void wgrad_tn_bf16_body(
     if (s + NS - 1 < nst) t.stage(s + NS - 1, smem + (s + NS - 1) % NS * STAGE);  // the buffer stage s-1 was read from
     mma.mma_stage(s % NS * STAGE, do_db);
   }
-  if (diag == 1) {  // timing-only: no atomic epilogue (results wrong)
-    if (mma.acc[0][0][0] == 12345.678f) dW[0] = 1.f;
-    return;
-  }
   const float alpha = alpha_dev ? *alpha_dev : 1.0f;
   mma.epilogue(dW, lddw, db, do_db, alpha, n0 + wn * 64, k0 + wk * Tile::WKT, N, K);
 }
 
-template <int BN, int BKW, int MS, int NS, bool MF16>
+template <int BN, int BKW, int MS, int NS>
 __global__ __launch_bounds__(BN * 2, BN == 128 ? 2 : 1) void wgrad_tn_bf16_kernel(
     const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
     float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
-    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, int diag) {
-  wgrad_tn_bf16_body<BN, BKW, MS, NS, MF16>(dY, lddy, X, ldx, dW, lddw, db, alpha_dev, M, N, K, tiles_k, tiles_nk, m_chunk,
-                                            diag, xcd_remap(blockIdx.x, gridDim.x));
+    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk) {
+  wgrad_tn_bf16_body<BN, BKW, MS, NS>(dY, lddy, X, ldx, dW, lddw, db, alpha_dev, M, N, K, tiles_k, tiles_nk, m_chunk,
+                                      xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Several weight gradients in ONE launch (vy_linear_wgrad_grouped): the four GEMMs of a transformer layer
@@ -456,8 +456,8 @@ __device__ __forceinline__ void colsum_slab_block(const ColsumItem& it, int blk)
   }
 }
 
-template <int BN, int BKW, int MS, int NS, bool MF16>
-__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, ColsumGroup cs, int diag) {
+template <int BN, int BKW, int MS, int NS>
+__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, ColsumGroup cs) {
   if ((int)blockIdx.x >= cs.items) {   // (workgroup-uniform) the column-sum workgroups: dispatched last, onto the idle CUs
     const int blk = (int)blockIdx.x - cs.items;
     int d = 0;
@@ -481,8 +481,8 @@ __global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradG
 #pragma unroll
   for (int i = 1; i < 8; ++i)
     if (d == i) it = grp.g[i];
-  wgrad_tn_bf16_body<BN, BKW, MS, NS, MF16>(it.dY, it.lddy, it.X, it.ldx, it.dW, it.lddw, it.db, nullptr, it.M, it.N, it.K,
-                                            it.tiles_k, it.tiles_nk, it.m_chunk, diag, id - it.item0);
+  wgrad_tn_bf16_body<BN, BKW, MS, NS>(it.dY, it.lddy, it.X, it.ldx, it.dW, it.lddw, it.db, nullptr, it.M, it.N, it.K,
+                                      it.tiles_k, it.tiles_nk, it.m_chunk, id - it.item0);
 }
 
 // db[n] += sum_m dY[m,n]: block = 64 lanes x 8 columns, 256 rows per block
@@ -923,14 +923,6 @@ WgradSplit wgrad_split(int64_t M, int64_t want) {
   return {vy_cdiv(M, m_chunk), m_chunk};
 }
 
-int wgrad_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
-// VY_WGRAD_M16, 16 x 16 x 32 MFMAs: 3 % faster on the 256 x 256 tiles (vocabulary projection 1.62 -> 1.57 ms, +0.25 % on
-// the training step), 2-8 % SLOWER on the 128 x 128 tiles (these kernels are bound by the transposing LDS reads and the
-// atomic epilogue, not by the matrix pipe): 1 = the wide tiles only (default), 2 = everywhere, 0 = off
-int wgrad_m16() { static const int v = wgrad_env("VY_WGRAD_M16", 1); return v; }
-int wgrad_diag() { static const int v = wgrad_env("VY_WGRAD_DIAG", 0); return v; }
-
 }  // namespace
 
 extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
@@ -946,11 +938,6 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
   if (!wgrad_bf16_operands_ok(dy, lddy, x, ldx, N, K))
     VY_FAIL(VY_ERR_ARG, "%s: K and leading dimensions must be multiples of 8 (lddy >= roundup8(N)), operands 16-byte aligned", who);
   if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "%s: beta must be 0 or 1", who);
-  // VY_WGRAD_VARIANT: 0 = the 128 x 128 tile, 8 = the 256 x 256 tile, unset = by shape (below)
-  static const int wv = wgrad_env("VY_WGRAD_VARIANT", -1);
-  static const int tgt = wgrad_env("VY_WGRAD_TARGET", 0);
-  if (wv != -1 && wv != 0 && wv != 8)
-    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: VY_WGRAD_VARIANT=%d was removed (the values left are 0 and 8; unset selects by shape)", who, wv);
   hipStream_t st = (hipStream_t)stream;
   if (beta == 0.f) {
     if (hipMemset2DAsync(dw, lddw * sizeof(float), 0, K * sizeof(float), N, st) != hipSuccess)
@@ -966,16 +953,14 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
   // The vocabulary projection (N = 50265: every tile reduces all M rows, so the 256 KiB atomic epilogue of a
   // 256 x 256 tile is paid once per 512 stages) takes the 256 x 256 tile, 32-row stages, 4-deep ring, one workgroup
   // per CU (7.8 instead of 15.6 LDS-DMA bytes per kFLOP): +9 %
-  const bool big = wv < 0 ? (N >= 8192 && M >= 4096) : wv == 8;
+  const bool big = N >= 8192 && M >= 4096;
   const int BT = big ? 256 : 128;
   const int tiles_k = (int)vy_cdiv(K, BT), tiles = (int)vy_cdiv(N, BT) * tiles_k;
   // 128 x 128: ~1.5 workgroups per CU; 256 x 256: at most one round of 256 workgroups
-  const WgradSplit sp = wgrad_split(M, tgt > 0 ? vy_cdiv(tgt, tiles) : big ? 256 / tiles : vy_cdiv(384, tiles));
-  const int w16 = wgrad_m16();
-  auto kernel = big ? (w16 ? wgrad_tn_bf16_kernel<256, 256, 32, 4, true> : wgrad_tn_bf16_kernel<256, 256, 32, 4, false>)
-                    : (w16 >= 2 ? wgrad_tn_bf16_kernel<128, 128, 64, 2, true> : wgrad_tn_bf16_kernel<128, 128, 64, 2, false>);
+  const WgradSplit sp = wgrad_split(M, big ? 256 / tiles : vy_cdiv(384, tiles));
+  auto kernel = big ? wgrad_tn_bf16_kernel<256, 256, 32, 4> : wgrad_tn_bf16_kernel<128, 128, 64, 2>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * sp.splits)), dim3(BT * 2), 0, st, (const bf16*)dy, lddy, (const bf16*)x,
-                     ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, (int)K, tiles_k, tiles, (int)sp.m_chunk, wgrad_diag());
+                     ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, (int)K, tiles_k, tiles, (int)sp.m_chunk);
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }
@@ -1006,7 +991,6 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
       VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: K and leading dimensions must be multiples of 8, operands 16-byte aligned", who, i);
     tiles_total += vy_cdiv(d.N, 256) * vy_cdiv(d.K, 256);
   }
-  static const int tgt = wgrad_env("VY_WGRAD_GROUP_TARGET", 256);
   WgradGroup grp;
   memset(&grp, 0, sizeof(grp));   // (n == 0: column sums only)
   grp.n = n;
@@ -1014,7 +998,7 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
   for (int i = 0; i < n; ++i) {
     const vy_wgrad_desc& d = descs[i];
     const int64_t tiles_k = vy_cdiv(d.K, 256), tiles = vy_cdiv(d.N, 256) * tiles_k;
-    const WgradSplit sp = wgrad_split(d.M, tgt / tiles_total);   // at most one round of workgroups (the column sums do not count: they are short)
+    const WgradSplit sp = wgrad_split(d.M, 256 / tiles_total);   // at most one round of workgroups (the column sums do not count: they are short)
     WgradItem& it = grp.g[i];
     it.dY = (const bf16*)d.dy; it.X = (const bf16*)d.x; it.dW = d.dw; it.db = d.db;
     it.lddy = d.lddy; it.ldx = d.ldx; it.lddw = d.lddw;
@@ -1035,8 +1019,8 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
     c.blk0 = (int)blocks;
     blocks += vy_cdiv(c.N, 64);
   }
-  auto kernel = wgrad_m16() ? wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, true> : wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4, false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(items + blocks)), dim3(512), 0, (hipStream_t)stream, grp, cg, wgrad_diag());
+  hipLaunchKernelGGL((wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4>), dim3((unsigned)(items + blocks)), dim3(512), 0,
+                     (hipStream_t)stream, grp, cg);
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }

@@ -3,11 +3,12 @@
 // bf16 kernels (the product path): MFMA, fp32 accumulate, LDS-DMA staging, by size of M:
 //   * M > ~2304 (training, prefill): 256 x 192 tiles with the X operand in a three-deep ring (gemm_nt_bf16_x3m16_kernel) or
 //     256 x 256 two-stage tiles where N >= 3072 (gemm_nt_bf16_m16_kernel), both on mfma_f32_16x16x32_bf16, 8 waves, one
-//     workgroup per CU; gemm_nt_bf16_kernel is the same tile family on mfma_f32_32x32x16_bf16 (A/B knob, 32 x 128 fallback);
+//     workgroup per CU;
 //   * 32 < M <= ~2304: 128 x 128 tiles (two workgroups per CU) or ONE all-rows tile of 256 / 320 x 128 for 128 < M <= 320,
 //     split over K when the tile grid leaves CUs idle (gemm_nt_bf16_m16_splitk_kernel + gemm_splitk_finish_kernel);
 //   * M <= 32 (decode): weight-streaming kernels without LDS staging (gemm_skinny*), M <= 4: one wave per output column
-//     (gemv_bf16_kernel); the decode driver's straight-line versions are in vy_decode.hip;
+//     (gemv_bf16_kernel), wide N or odd K: 32 x 128 tiles on mfma_f32_32x32x16_bf16 (gemm_nt_bf16_kernel); the decode
+//     driver's straight-line versions are in vy_decode.hip;
 //   * both operands are K-contiguous ("NT"), so both MFMA fragments are 16-byte row reads
 //     (ds_read_b128) from a [rows][64] bf16 LDS image; the image is XOR-swizzled on the 16-B
 //     chunk index with (row>>1)&7, applied on the *source address* of the
@@ -289,49 +290,13 @@ __device__ __forceinline__ void epi_qkv_quad(const EpiQkv<T>& e, float (&v)[4], 
   Quad<T>::store(qkv_dest(e, b, l, n), v);
 }
 
-// measurement aid (VY_GEMM_ROT bit 16): workgroup 0 accumulates its shader-clock cycles (s_memtime)
-// and 100 MHz ticks (s_memrealtime) here; vy_debug_gemm_clock() reads and clears them
-// (tools/gemm_clock.py): cycles / ticks * 100 = the shader clock in MHz the GEMMs really ran at.
-__device__ unsigned long long vy_gemm_clk[6];   // cycles, ticks, launches, prologue / k-loop / epilogue cycles
-// bits of the knob the launchers hand to the tile kernels (the value of VY_GEMM_ROT)
-constexpr int VY_KNOB_ROT = 1;        // per-tile rotated k order (32 x 32 x 16 kernel only)
-constexpr int VY_KNOB_CLK = 16;       // the clock probe above (32 x 32 x 16 kernel only)
-constexpr int VY_KNOB_NO_BAND = 32;   // tile_of: the plain XCD run instead of the band walk
-#define VY_CLK_BEGIN(on)                                                         \
-  const bool clk_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0;              \
-  unsigned long long clk_c0_ = 0, clk_w0_ = 0, clk_m_ = 0;                       \
-  if (clk_on_) { clk_c0_ = clk_m_ = __builtin_readcyclecounter(); clk_w0_ = wall_clock64(); }
-#define VY_CLK_MARK(i)                                                           \
-  if (clk_on_) {                                                                 \
-    const unsigned long long now_ = __builtin_readcyclecounter();                \
-    atomicAdd(&vy_gemm_clk[3 + (i)], now_ - clk_m_);                             \
-    clk_m_ = now_;                                                               \
-  }
-#define VY_CLK_END()                                                             \
-  if (clk_on_) {                                                                 \
-    atomicAdd(&vy_gemm_clk[0], __builtin_readcyclecounter() - clk_c0_);          \
-    atomicAdd(&vy_gemm_clk[1], wall_clock64() - clk_w0_);                        \
-    atomicAdd(&vy_gemm_clk[2], 1ull);                                            \
-  }
-
-// large-M kernel selection knob: VY_GEMM_VARIANT at first use, or vy_debug_set_gemm_variant() (tests and
-// same-process A/B timing; not part of include/vyom_hip.h).  -1 = the default selection.
 int g_chains = 1;   // vy_set_concurrent_chains: launch chains the caller runs side by side
-int g_gemm_variant = -2;
 // VY_EPI_PREFETCH at first use, or vy_debug_set_epilogue_prefetch(): 0 = the staged epilogue loads its second operands
 // inside the store loop (A/B timing and tests; not part of include/vyom_hip.h)
 int g_epi_prefetch = -2;
-inline bool vy_m16_on() {   // VY_GEMM_M16=0: the two-stage 32 x 32 x 16 kernels instead of the 16 x 16 x 32 defaults
-  static const int v = [] { const char* e = getenv("VY_GEMM_M16"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
 inline int vy_epi_prefetch() {
   if (g_epi_prefetch == -2) { const char* e = getenv("VY_EPI_PREFETCH"); g_epi_prefetch = e ? (atoi(e) != 0) : 1; }
   return g_epi_prefetch;
-}
-inline int vy_gemm_variant() {
-  if (g_gemm_variant == -2) { const char* e = getenv("VY_GEMM_VARIANT"); g_gemm_variant = e ? atoi(e) : -1; }
-  return g_gemm_variant;
 }
 
 // XCD-aware bijective block remap: blocks b, b+8, ... share an XCD (round-robin dispatch), give
@@ -347,9 +312,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // L2): 113 MB of weight re-fetch per launch against 30 MB of algorithmic reads (PMC, profiles/r01_gemm_pmc.json).
 // Here an XCD keeps ONE band of W (half the matrix) in its L2 for the whole launch and streams its row panels
 // past it; every X panel is read by two XCDs instead of one: fetch ~ 2 X + 8 * W/2 = 69 MB instead of 138 MB.
-__device__ __forceinline__ void tile_of(int bid, int nwg, int tiles_n, int band_on, int& tile_m, int& tile_n) {
+__device__ __forceinline__ void tile_of(int bid, int nwg, int tiles_n, int& tile_m, int& tile_n) {
   const int tiles_m = nwg / tiles_n;
-  if (band_on && tiles_n >= 8 && (tiles_n & 1) == 0 && (tiles_m & 3) == 0 && tiles_m * tiles_n == nwg) {
+  if (tiles_n >= 8 && (tiles_n & 1) == 0 && (tiles_m & 3) == 0 && tiles_m * tiles_n == nwg) {
     const int xcd = bid & 7, i = bid >> 3;
     const int band = xcd & 1, grp = xcd >> 1;
     const int bw = tiles_n >> 1, pg = tiles_m >> 2;
@@ -368,40 +333,35 @@ __device__ __forceinline__ void tile_of(int bid, int nwg, int tiles_n, int band_
 constexpr int BK = 64;            // k elements per stage
 constexpr int ROWB = BK * 2;      // bytes per LDS row (128)
 
-// LDS bytes of the staged epilogue: the bf16 tile band (rows padded by 16 B) and, for the QKV epilogue, the
-// rotary table of the band's rows (cos | sin, 32 + 32 bf16 = 128 B per row) when both fit in 160 KiB
-constexpr int epi_tile_bytes(int BM, int BN, int PASSES) { return (BM / PASSES) * (BN * 2 + 16); }
-constexpr bool epi_has_rope_tab(int BM, int BN, int EPI, int PASSES) {
-  return EPI == 1 && epi_tile_bytes(BM, BN, PASSES) + (BM / PASSES) * 128 <= 160 * 1024;
+// LDS bytes of the staged epilogue: the bf16 tile (rows padded by 16 B) and, for the QKV epilogue, the
+// rotary table of the tile's rows (cos | sin, 32 + 32 bf16 = 128 B per row) when both fit in 160 KiB
+constexpr int epi_tile_bytes(int BM, int BN) { return BM * (BN * 2 + 16); }
+constexpr bool epi_has_rope_tab(int BM, int BN, int EPI) {
+  return EPI == 1 && epi_tile_bytes(BM, BN) + BM * 128 <= 160 * 1024;
 }
-constexpr int epi_lds_bytes(int BM, int BN, int EPI, int PASSES) {
-  return epi_tile_bytes(BM, BN, PASSES) + (epi_has_rope_tab(BM, BN, EPI, PASSES) ? (BM / PASSES) * 128 : 0);
+constexpr int epi_lds_bytes(int BM, int BN, int EPI) {
+  return epi_tile_bytes(BM, BN) + (epi_has_rope_tab(BM, BN, EPI) ? BM * 128 : 0);
 }
 constexpr int vy_cmax(int a, int b) { return a > b ? a : b; }
 
 // ---- shared epilogue of the bf16 kernels ------------------------------------------------------
-// PASSES > 1: the staged tile does not fit next to a second resident workgroup's LDS, so it goes out in
-// PASSES row bands of BM / PASSES rows (each band is owned by whole wave rows: WGM % PASSES == 0).
-// the wave's accumulators: 32 x 32 blocks of mfma_f32_32x32x16 (f32x16 each), or -- MF16 -- 16 x 16 blocks of
-// mfma_f32_16x16x32 (f32x4 each: a lane owns output row lane & 15 of the block and the 4 consecutive columns
-// 4 * (lane >> 4) .. + 3).  Either way a lane holds QUADS of 4 consecutive columns of one row, which is all the
-// staged epilogue needs to know.
+// the wave's accumulators: MF16 -- every tile but one -- 16 x 16 blocks of mfma_f32_16x16x32 (f32x4 each: a lane owns
+// output row lane & 15 of the block and the 4 consecutive columns 4 * (lane >> 4) .. + 3); else (the 32 x 128 skinny
+// fallback of gemm_nt_bf16_kernel) 32 x 32 blocks of mfma_f32_32x32x16 (f32x16 each).  Either way a lane holds QUADS of
+// 4 consecutive columns of one row, which is all the staged epilogue needs to know.
 template <int BM, int BN, int WGM, int WGN, bool MF16> struct AccTile {
   typedef f32x16 T32[BN / (32 * WGN)][BM / (32 * WGM)];
   typedef f32x4 T16[BN / (16 * WGN)][BM / (16 * WGM)];
   typedef std::conditional_t<MF16, T16, T32> type;
 };
 
-template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD, int PASSES = 1, bool PF_OK = true, bool MF16 = false>
+template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD, bool MF16>
 __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN, MF16>::type& acc, char* smem,
                                               int m0, int n0, int M, int N, const EpiPlain<bf16>& ep,
                                               const EpiQkv<bf16>& eq) {
-  static_assert(!MF16 || PASSES == 1, "the 16 x 16 accumulator layout is staged in one pass");
   constexpr int NW = WGM * WGN, NT = 64 * NW;
   constexpr int TM = BM / (32 * WGM), TN = BN / (32 * WGN);
   constexpr int EROW = BN * 2 + 16;
-  constexpr int RP = BM / PASSES;   // rows per pass
-  static_assert(WGM % PASSES == 0, "a pass must be whole wave rows");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WGN, wn = wave % WGN;
@@ -415,12 +375,11 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
   constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
   char* et = smem;
 
-  const int my_pass = (wm * 32 * TM) / RP;   // the row band this wave's sub-tile belongs to
   auto stage_quad = [&](int row, int col, const float (&v)[4]) {
     bf16x4 w;
 #pragma unroll
     for (int e = 0; e < 4; ++e) w[e] = (bf16)v[e];
-    *reinterpret_cast<bf16x4*>(et + (row - my_pass * RP) * EROW + col * 2) = w;
+    *reinterpret_cast<bf16x4*>(et + row * EROW + col * 2) = w;
   };
   // bias of a register quad (depends on the lane half only); loaded at use, not kept live
   const bf16* biasp = EPI == 0 ? ep.bias : eq.bias;
@@ -435,25 +394,23 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
       for (int e = 0; e < 4; ++e) bq[e] = (biasp && n + e < N) ? (float)biasp[n + e] : 0.f;
     }
   };
-  // phase 1 of a pass: every quad of the wave's sub-tile that lies in the pass's row band, + bias, -> LDS
-  auto stage_all = [&](int pass) {
+  // phase 1: every quad of the wave's sub-tile, + bias, -> LDS
+  auto stage_all = [&]() {
     if constexpr (!MF16) {
-      if (PASSES == 1 || pass == my_pass) {
 #pragma unroll
-        for (int i = 0; i < TN; ++i)
+      for (int i = 0; i < TN; ++i)
 #pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            float bq[4];
-            bias_quad(n0 + wn * 32 * TN + i * 32 + 8 * rg + 4 * fh, bq);
+        for (int rg = 0; rg < 4; ++rg) {
+          float bq[4];
+          bias_quad(n0 + wn * 32 * TN + i * 32 + 8 * rg + 4 * fh, bq);
 #pragma unroll
-            for (int j = 0; j < TM; ++j) {
-              float v[4];
+          for (int j = 0; j < TM; ++j) {
+            float v[4];
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * rg + e] + bq[e];
-              stage_quad(wm * 32 * TM + j * 32 + fr, wn * 32 * TN + i * 32 + 8 * rg + 4 * fh, v);
-            }
+            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * rg + e] + bq[e];
+            stage_quad(wm * 32 * TM + j * 32 + fr, wn * 32 * TN + i * 32 + 8 * rg + 4 * fh, v);
           }
-      }
+        }
     } else {
       constexpr int TM16 = BM / (16 * WGM), TN16 = BN / (16 * WGN);
       const int r16 = lane & 15, kq = lane >> 4;
@@ -477,7 +434,7 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
     // values -- what the reference's bf16 Linear -> GELU computes -- and, when the caller wants the
     // pre-activation saved for backward (dual), it is stored from the same chunk: one pass over the
     // tile, no second staging pass, no GELU chains among the accumulator registers.
-    // one 16-byte chunk of the staged band.  pf: the chunk's second operand (residual, or the pre-activation of a
+    // one 16-byte chunk of the staged tile.  pf: the chunk's second operand (residual, or the pre-activation of a
     // dgrad) was requested BEFORE the accumulators were staged and is handed in as p8 -- loaded here, inside the
     // loop, every iteration waits a full memory latency for it (the residual epilogue measured 22 k cycles per
     // tile against 12 k without the residual)
@@ -487,10 +444,10 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
     const bf16* pf_ptr = GRAD ? (ep.gradpre ? ep.gradpre : ep.residual) : ep.residual;
     const int64_t pf_ld = GRAD ? (ep.gradpre ? ep.ldg : ep.ldr) : ep.ldr;
     const bool pf_is_gradpre = GRAD && ep.gradpre != nullptr;
-    auto do_chunk = [&](bf16* __restrict__ dst, bool dual, int pass, int c, bool pf, const bf16x8& p8, bool pf2,
+    auto do_chunk = [&](bf16* __restrict__ dst, bool dual, int c, bool pf, const bf16x8& p8, bool pf2,
                         const bf16x8& rb, const bf16x8& rc, bool fast) __attribute__((always_inline)) {
         const int row = c / CPR, cc = c - row * CPR;
-        const int64_t m = m0 + pass * RP + row;
+        const int64_t m = m0 + row;
         const int n = n0 + cc * 8;
         if (!fast && (m >= M || n >= N)) return;
         const bf16x8 sv = *reinterpret_cast<const bf16x8*>(et + row * EROW + cc * 16);
@@ -557,59 +514,58 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
           }
         }
     };
-    constexpr bool PFK = PF_OK && PASSES == 1 && BM * BN == 256 * 192 && (RP * CPR) % NT == 0;   // kernels that prefetch BEFORE the staging (the 256 x 256 tile has no registers to spare: +5 % on FFN1 with them reserved)
+    constexpr bool PFK = BM * BN == 256 * 192 && (BM * CPR) % NT == 0;   // kernels that prefetch BEFORE the staging (the 256 x 256 tile has no registers to spare: +5 % on FFN1 with them reserved)
     // Every other second operand of a whole tile is requested AFTER the staging, when the accumulator registers are
     // dead: all ITERS chunks of each operand present, in one batch, before the barrier.  Loaded inside the store loop
     // instead, every chunk is a load, s_waitcnt vmcnt(0) -- which also drains the store before it -- and a store: one
     // memory round trip per 16 bytes and thread, 12-16 of them per tile.  The arithmetic per element is the same.
     // (not with the tanh GELU or the run-time activation: their chunk body is too large for the loop to unroll fully, and
     // a register array under a rolled loop goes to scratch.  No caller pairs them with a residual on a large tile.)
-    constexpr bool PF2K = (RP * CPR) % NT == 0 && (ACT == VY_ACT_NONE || ACT == VY_ACT_GELU_ERF);
-    constexpr int ITERS = (PFK || PF2K) ? (RP * CPR) / NT : 1;
+    constexpr bool PF2K = (BM * CPR) % NT == 0 && (ACT == VY_ACT_NONE || ACT == VY_ACT_GELU_ERF);
+    constexpr int ITERS = (PFK || PF2K) ? (BM * CPR) / NT : 1;
     bf16x8 pre8[ITERS];                    // the first operand (pf_ptr)
     bf16x8 rb8[GRAD ? ITERS : 1];          // the residual of a dgrad whose first operand is the saved tensor
     bf16x8 rc8[ITERS];                     // the second residual
     const bool whole = ep.vec_ok && m0 + BM <= M && n0 + BN <= N;   // workgroup-uniform
     const bool pf_on = PFK && pf_ptr != nullptr && whole;
     const bool pf2_on = PF2K && ep.pf2 && pf_ptr != nullptr && whole;
-    auto pf_addr = [&](const bf16* p, int64_t ld, int pass, int it) {
+    auto pf_addr = [&](const bf16* p, int64_t ld, int it) {
       const int c = tid + it * NT;
       const int row = c / CPR, cc = c - row * CPR;
-      return reinterpret_cast<const bf16x8*>(p + (int64_t)(m0 + pass * RP + row) * ld + n0 + cc * 8);
+      return reinterpret_cast<const bf16x8*>(p + (int64_t)(m0 + row) * ld + n0 + cc * 8);
     };
     if constexpr (PFK) {
       if (pf_on) {
 #pragma unroll
-        for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, 0, it);
+        for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, it);
       }
     }
-    auto prefetch_rest = [&](int pass) {
+    auto prefetch_rest = [&]() {
       if constexpr (PF2K) {
         if (pf2_on) {
           if (!pf_on) {
 #pragma unroll
-            for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, pass, it);
+            for (int it = 0; it < ITERS; ++it) pre8[it] = *pf_addr(pf_ptr, pf_ld, it);
           }
           if constexpr (GRAD) {
             if (pf_is_gradpre && ep.residual) {
 #pragma unroll
-              for (int it = 0; it < ITERS; ++it) rb8[it] = *pf_addr(ep.residual, ep.ldr, pass, it);
+              for (int it = 0; it < ITERS; ++it) rb8[it] = *pf_addr(ep.residual, ep.ldr, it);
             }
           }
           if (ep.residual2) {
 #pragma unroll
-            for (int it = 0; it < ITERS; ++it) rc8[it] = *pf_addr(ep.residual2, ep.ldr2, pass, it);
+            for (int it = 0; it < ITERS; ++it) rc8[it] = *pf_addr(ep.residual2, ep.ldr2, it);
           }
         }
       }
     };
-    auto flush_plain = [&](bf16* __restrict__ dst, bool final_pass, bool dual, int pass) {
-      (void)final_pass;
+    auto flush_plain = [&](bf16* __restrict__ dst, bool dual) {
       if constexpr (PF2K) {
         if (pf2_on) {
 #pragma unroll
           for (int it = 0; it < ITERS; ++it)
-            do_chunk(dst, dual, pass, tid + it * NT, true, pre8[it], true, rb8[GRAD ? it : 0], rc8[it], true);
+            do_chunk(dst, dual, tid + it * NT, true, pre8[it], true, rb8[GRAD ? it : 0], rc8[it], true);
           return;
         }
       }
@@ -617,45 +573,39 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
       if constexpr (PFK) {
         if (pf_on) {
 #pragma unroll
-          for (int it = 0; it < ITERS; ++it) do_chunk(dst, dual, pass, tid + it * NT, true, pre8[it], false, none, none, false);
+          for (int it = 0; it < ITERS; ++it) do_chunk(dst, dual, tid + it * NT, true, pre8[it], false, none, none, false);
           return;
         }
       }
-      for (int c = tid; c < RP * CPR; c += NT) do_chunk(dst, dual, pass, c, false, none, false, none, none, false);
+      for (int c = tid; c < BM * CPR; c += NT) do_chunk(dst, dual, c, false, none, false, none, none, false);
     };
     const bool dual = !GRAD && ep.pre != nullptr;   // (the GRAD path never sets ep.pre)
-#pragma unroll 1
-    for (int pass = 0; pass < PASSES; ++pass) {
-      stage_all(pass);
-      // the requests stay behind the staging: above it they would be live next to the accumulators
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      prefetch_rest(pass);
-      __syncthreads();
-      flush_plain(ep.y, true, dual, pass);
-      if (pass + 1 < PASSES) __syncthreads();
-    }
+    stage_all();
+    // the requests stay behind the staging: above it they would be live next to the accumulators
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    prefetch_rest();
+    __syncthreads();
+    flush_plain(ep.y, dual);
   } else {
     // QKV: bias in registers; RoPE and the head-split scatter in phase 2, where a rotary pair
     // (d, d+32) is two 16-byte chunks 64 bytes apart in the same staged row.  The staged values
     // are the bf16-rounded projections, so the rotation reproduces the reference's op order
     // (Linear output in q.dtype, then q*cos + rotate_half(q)*sin with every op rounded:
     // VyomAI/layers/positional_embeddings.py:173-181) exactly.
-    // The rotary factors of the band's rows go through LDS: cos | sin of one position, rounded to bf16 once, are
-    // 128 bytes next to the staged tile, filled by 2 x 16-byte loads per thread and pass while the accumulators
+    // The rotary factors of the tile's rows go through LDS: cos | sin of one position, rounded to bf16 once, are
+    // 128 bytes next to the staged tile, filled by 2 x 16-byte loads per thread while the accumulators
     // are being staged -- read per chunk from the fp32 tables they were 4 more loads per 16-byte store in a phase
     // that is bound by the CU's vector-memory path (24 k cycles against 13 k for the same tile without RoPE).
-    constexpr bool TAB = epi_has_rope_tab(BM, BN, 1, PASSES);
-    char* rt = smem + RP * EROW;   // rotary table of the band: [RP][64] bf16
+    constexpr bool TAB = epi_has_rope_tab(BM, BN, 1);
+    char* rt = smem + BM * EROW;   // rotary table of the tile: [BM][64] bf16
     const bool use_tab = TAB && eq.rope && n0 < eq.nq + eq.nkv;
     // row -> (batch, position) without 64-bit divisions: the tile's first row once, then 32-bit arithmetic
     const unsigned Lu = (unsigned)eq.L;
     const unsigned b0 = (unsigned)m0 / Lu, l0 = (unsigned)m0 - b0 * Lu;
     const int64_t pdev = eq.pos_dev ? (int64_t)*eq.pos_dev : 0;
     const int64_t pbase = eq.pos_dev ? pdev : eq.pos0;
-#pragma unroll 1
-    for (int pass = 0; pass < PASSES; ++pass) {
-    constexpr int TIT = (RP * 8 + NT - 1) / NT;   // table chunks (8 bf16) per thread
+    constexpr int TIT = (BM * 8 + NT - 1) / NT;   // table chunks (8 bf16) per thread
     f32x4 tv[TAB ? TIT : 1][2];
     if constexpr (TAB) {
       if (use_tab) {
@@ -663,8 +613,8 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
         for (int it = 0; it < TIT; ++it) {
           const int idx = tid + it * NT;
           const int row = idx >> 3, ch = idx & 7;
-          if (RP * 8 % NT == 0 || idx < RP * 8) {
-            const unsigned t = l0 + (unsigned)(pass * RP + row);
+          if (BM * 8 % NT == 0 || idx < BM * 8) {
+            const unsigned t = l0 + (unsigned)row;
             const unsigned l = t - (t / Lu) * Lu;
             const float* src = (ch < 4 ? eq.cos_tab : eq.sin_tab) + (pbase + l) * 32 + (ch & 3) * 8;
             tv[it][0] = *reinterpret_cast<const f32x4*>(src);
@@ -673,13 +623,13 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
         }
       }
     }
-    stage_all(pass);
+    stage_all();
     if constexpr (TAB) {
       if (use_tab) {
 #pragma unroll
         for (int it = 0; it < TIT; ++it) {
           const int idx = tid + it * NT;
-          if (RP * 8 % NT == 0 || idx < RP * 8) {
+          if (BM * 8 % NT == 0 || idx < BM * 8) {
             bf16x8 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { o[e] = (bf16)tv[it][0][e]; o[4 + e] = (bf16)tv[it][1][e]; }
@@ -689,12 +639,12 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
       }
     }
     __syncthreads();
-    for (int c = tid; c < RP * CPR; c += NT) {
+    for (int c = tid; c < BM * CPR; c += NT) {
       const int row = c / CPR, cc = c - row * CPR;
-      const int64_t m = m0 + pass * RP + row;
+      const int64_t m = m0 + row;
       const int n = n0 + cc * 8;
       if (m >= M || n >= N) continue;
-      const unsigned t = l0 + (unsigned)(pass * RP + row);
+      const unsigned t = l0 + (unsigned)row;
       const unsigned tq = t / Lu;
       const int64_t b = b0 + tq, l = t - tq * Lu;
       bf16x8 sv = *reinterpret_cast<const bf16x8*>(et + row * EROW + cc * 16);
@@ -731,8 +681,6 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
         for (int e = 0; e < 8 && n + e < N; ++e) *qkv_dest(eq, b, l, n + e) = sv[e];
       }
     }
-    if (pass + 1 < PASSES) __syncthreads();
-    }
   }
 }
 
@@ -742,9 +690,9 @@ __device__ __forceinline__ void gemm_epilogue(typename AccTile<BM, BN, WGM, WGN,
 // writer (per-lane global_load_lds sources, one piece per wave-instruction, wave w owns pieces w, w + NW, ...)
 // and its reader (the MFMA fragment addresses), plus the wave's accumulators and the MFMA block.  WHEN a stage
 // is requested, which vmcnt is waited for and where the barrier sits is the schedule -- that is the kernels'.
-// MF16: 16 x 16 blocks of mfma_f32_16x16x32_bf16 (fragment rows lane & 15, chunk 4 ks + (lane >> 4), 2 k-steps
-// per stage); else 32 x 32 blocks of mfma_f32_32x32x16_bf16 (rows lane & 31, chunk 2 ks + (lane >> 5), 4 k-steps).
-// The swizzle is conflict-free for both.
+// MF16 (the x3m16, m16 and split-K kernels): 16 x 16 blocks of mfma_f32_16x16x32_bf16 (fragment rows lane & 15, chunk
+// 4 ks + (lane >> 4), 2 k-steps per stage); else (gemm_nt_bf16_kernel's 32 x 128 tile only) 32 x 32 blocks of
+// mfma_f32_32x32x16_bf16 (rows lane & 31, chunk 2 ks + (lane >> 5), 4 k-steps).  The swizzle is conflict-free for both.
 template <int BM, int BN, int WGM, int WGN, bool MF16>
 struct GemmTile {
   static constexpr int NW = WGM * WGN;
@@ -848,41 +796,29 @@ struct GemmTile {
   }
 };
 
-// tile BM x BN x 64 with WGM x WGN waves, each owning a (BM/WGM) x (BN/WGN) sub-tile as
-// TN x TM blocks of 32x32.  Shapes in use:
-//   256 x 192, 4x2 waves (512 threads, 1 workgroup per CU, 112 KiB LDS): the training shapes.  Loads
-//       per FLOP are (BM+BN)/(BM*BN) = 9.1 B/kFLOP -- a 128^2 tile needs 15.6 and is bound by the
-//       ~70 GB/s a CU can pull from L2, not by MFMA; 192 columns make N in {768, 2304, 3072} with
-//       M = 16384 give 256 / 768 / 1024 tiles, whole multiples of the 256 CUs;
-//   128 x 128, 2x2 waves (2 workgroups per CU): mid-size M;   32 x 128, 1x4 waves: skinny M.
+// tile BM x BN x 64 with WGM x WGN waves, each owning a (BM/WGM) x (BN/WGN) sub-tile as TN x TM blocks of 32 x 32
+// (mfma_f32_32x32x16_bf16), two whole stages.  One shape is in use: 32 x 128, 1 x 4 waves -- the fallback for M <= 32
+// where no weight-streaming kernel applies (the vocabulary projection of a decode step, K % 16 != 0).
 template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
-    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
+    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq) {
   typedef GemmTile<BM, BN, WGM, WGN, false> Tile;
   constexpr int TM = Tile::TM, TN = Tile::TN;
-  VY_CLK_BEGIN(knob & VY_KNOB_CLK)
   constexpr int STAGE = (BM + BN) * ROWB;
-  constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI, 1));
+  constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, BM * ROWB);
   const int KT = (K + BK - 1) / BK;
 
-  // optional (VY_GEMM_ROT=1) per-tile rotated k order, an experiment: workgroups that share an operand
-  // run in lockstep and request the same not-yet-resident lines at once.  tools/probe/ldsdma_probe
-  // shows the L2 merges such requests well (72 GB/s per CU for a 4-way shared stream against 28
-  // unshared), and the rotation measured 1-5 % slower -- kept off.
-  const int rot = (knob & VY_KNOB_ROT) ? (tile_n * 2 + tile_m) % KT : 0;
   auto stage = [&](int kt, int buf) {
-    int kr = kt + rot;
-    kr = kr >= KT ? kr - KT : kr;
-    t.issue_x(kr, smem + buf * STAGE);
-    t.issue_w(kr, smem + buf * STAGE + BM * ROWB);
+    t.issue_x(kt, smem + buf * STAGE);
+    t.issue_w(kt, smem + buf * STAGE + BM * ROWB);
   };
 
   typename Tile::WFrag wf[2];   // fragments of k-step ks + 1 are read before the MFMAs of k-step ks
@@ -916,8 +852,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_kernel(
     if (kt + 1 < KT) t.read_frags(t.wa[0] + (STAGE - boff), t.xa[0] + (STAGE - boff), wf[0], xf[0]);
   }
   // the epilogue reuses the stage buffers: every LDS read above has been retired (last k-step: lgkmcnt(0))
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD>(t.acc, smem, m0, n0, M, N, ep, eq);
-  VY_CLK_END()
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, false>(t.acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -942,19 +877,19 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_kernel(
 template <int BN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(512) void gemm_nt_bf16_x3m16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
-    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
+    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq) {
   constexpr int BM = 256, WGM = 4, WGN = 2;
   typedef GemmTile<BM, BN, WGM, WGN, true> Tile;
   constexpr int TM = Tile::TM, TN = Tile::TN, GX = Tile::GX;   // 4, 6 (BN = 192), 4
   static_assert(Tile::PX % Tile::NW == 0 && Tile::PW % Tile::NW == 0, "pieces must divide over the waves");
   constexpr int XT = BM * ROWB, WT = BN * ROWB;
   constexpr int WOFF = 3 * XT;
-  constexpr int LDS_BYTES = vy_cmax(3 * XT + 2 * WT, epi_lds_bytes(BM, BN, EPI, 1));
+  constexpr int LDS_BYTES = vy_cmax(3 * XT + 2 * WT, epi_lds_bytes(BM, BN, EPI));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, WOFF);
   const int KT = (K + BK - 1) / BK;
@@ -990,7 +925,7 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_x3m16_kernel(
     xbuf = xbuf == 2 ? 0 : xbuf + 1;
     if (kt + 1 < KT) t.read_frags(t.wa[0] + (WT - wo), t.xa[0] + xbuf * XT, wf[0], xf[0]);
   }
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(t.acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, true>(t.acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1002,17 +937,17 @@ __global__ __launch_bounds__(512) void gemm_nt_bf16_x3m16_kernel(
 template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
-    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int knob) {
+    int K, int tiles_n, EpiPlain<bf16> ep, EpiQkv<bf16> eq) {
   typedef GemmTile<BM, BN, WGM, WGN, true> Tile;
   constexpr int TM = Tile::TM, TN = Tile::TN;   // 256 x 256, 4 x 2 waves: 4, 8;  128 x 128, 2 x 2 waves: 4, 4
   static_assert(Tile::PX % Tile::NW == 0 && Tile::PW % Tile::NW == 0, "pieces must divide over the waves");
   constexpr int STAGE = (BM + BN) * ROWB;
-  constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI, 1));
+  constexpr int LDS_BYTES = vy_cmax(2 * STAGE, epi_lds_bytes(BM, BN, EPI));
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile_m, tile_n;
-  tile_of(blockIdx.x, gridDim.x, tiles_n, !(knob & VY_KNOB_NO_BAND), tile_m, tile_n);
+  tile_of(blockIdx.x, gridDim.x, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   Tile t(X, ldx, W, ldw, m0, n0, M, N, K, wave, smem, BM * ROWB);
   const int KT = (K + BK - 1) / BK;
@@ -1044,7 +979,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_nt_bf16_m16_kernel(
     asm volatile("" ::: "memory");
     if (kt + 1 < KT) t.read_frags(t.wa[0] + (STAGE - boff), t.xa[0] + (STAGE - boff), wf[0], xf[0]);
   }
-  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, 1, true, true>(t.acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<BM, BN, WGM, WGN, EPI, ACT, GRAD, true>(t.acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1152,7 +1087,7 @@ __global__ __launch_bounds__(64) void gemm_splitk_finish_kernel(
   constexpr int TM = BM / (16 * WGM), TN = BN / (16 * WGN);
   constexpr int SM = BM / WGM, SN = BN / WGN;   // the wave's sub-tile
   constexpr int SMAX = 16;
-  __shared__ __attribute__((aligned(16))) char smem[epi_lds_bytes(16, SN, EPI, 1)];
+  __shared__ __attribute__((aligned(16))) char smem[epi_lds_bytes(16, SN, EPI)];
   const int lane = threadIdx.x;
   const int tile = blockIdx.x / (NW * TM);
   const int rem = blockIdx.x - tile * (NW * TM);
@@ -1178,7 +1113,7 @@ __global__ __launch_bounds__(64) void gemm_splitk_finish_kernel(
 #pragma unroll
       for (int i = 0; i < TN; ++i) acc[i][0] = acc[i][0] + part[sidx][i];   // slice order: deterministic
     }
-  gemm_epilogue<16, SN, 1, 1, EPI, ACT, GRAD, 1, true, true>(acc, smem, m0, n0, M, N, ep, eq);
+  gemm_epilogue<16, SN, 1, 1, EPI, ACT, GRAD, true>(acc, smem, m0, n0, M, N, ep, eq);
 }
 
 // Workspaces for the split-K launches, registered per stream by the caller (the library never allocates device memory):
@@ -1196,10 +1131,9 @@ inline float* splitk_ws(hipStream_t st, int64_t need) {
 // slices for a tile grid: `target` workgroups in all (two per CU for the 128 x 128 tiles, one for the all-rows tiles), at least
 // two 64-deep stages per slice
 inline int splitk_slices(int64_t tiles, int KT, int target) {
-  static const int on = [] { const char* e = getenv("VY_SPLITK"); return e ? atoi(e) : 1; }();
   // (measured, same box: 2 stages per slice at least -- configs[4] prefill 7.09 -> 6.88 ms, configs[3] step 19.1 -> 18.5 ms against 4)
-  static const int min_stages = [] { const char* e = getenv("VY_SPLITK_MIN_STAGES"); return e ? atoi(e) : 2; }();
-  if (!on || tiles * 3 >= target * 2 || g_chains != 1) return 1;
+  constexpr int min_stages = 2;
+  if (tiles * 3 >= target * 2 || g_chains != 1) return 1;
   int S = (int)((target + tiles / 2) / tiles);
   if (S > KT / min_stages) S = KT / min_stages;
   if (S > 16) S = 16;
@@ -1214,7 +1148,7 @@ inline int splitk_slices(int64_t tiles, int KT, int target) {
 // mid-size M launch on BM x BN tiles: split over K when the tile grid leaves CUs idle and the stream has a workspace
 template <int BM, int BN, int WGM, int WGN, int EPI, int ACT, bool GRAD>
 void launch_mid(const bf16* X, int64_t ldx, const bf16* W, int64_t ldw, int64_t M, int64_t N, int64_t K,
-                const EpiPlain<bf16>& ep, const EpiQkv<bf16>& eq, hipStream_t st, int target, int rot) {
+                const EpiPlain<bf16>& ep, const EpiQkv<bf16>& eq, hipStream_t st, int target) {
   constexpr int NT = 64 * WGM * WGN;
   const int tn = (int)vy_cdiv(N, BN), tm = (int)vy_cdiv(M, BM);
   const int KT = (int)vy_cdiv(K, 64);
@@ -1230,7 +1164,7 @@ void launch_mid(const bf16* X, int64_t ldx, const bf16* W, int64_t ldw, int64_t 
                        st, ws, (int)M, (int)N, tn, tiles, S, ep, eq);
   } else {
     hipLaunchKernelGGL((gemm_nt_bf16_m16_kernel<BM, BN, WGM, WGN, EPI, ACT, GRAD>), dim3(tiles), dim3(NT), 0,
-                       st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
+                       st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq);
   }
 }
 
@@ -1330,7 +1264,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_bf16_kernel(
 // ---- split-K weight streaming for M <= 32 and narrow N (decode: N = hidden size) --------------
 // A skinny GEMM has N/32 workgroups: 24 for N = 768, on a 256-CU chip.  Here grid.y slices of K
 // each produce an fp32 partial tile part[ks][32][N] (plain stores: deterministic, no atomics); the
-// consumer (splitk_finish_ln_kernel) adds them in slice order with bias and residual.
+// consumer (splitk_finish_ln_row_kernel) adds them in slice order with bias and residual.
 __global__ __launch_bounds__(256) void gemm_skinny_splitk_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
     int K, int steps_per_wg, float* __restrict__ part) {
@@ -1394,88 +1328,6 @@ __global__ __launch_bounds__(256) void gemm_skinny_splitk_kernel(
   }
 }
 
-// y = LayerNorm(bf16(sum_ks part[ks] + bias + residual)): the epilogue of the split-K GEMM above fused
-// with the LayerNorm that follows it in the block (AttentionSelfOutput / FeedForward).  One wave per
-// row, the same arithmetic as gemm epilogue + layernorm_fwd_kernel (sum rounded to bf16 first).
-template <int CH>
-__global__ __launch_bounds__(256) void splitk_finish_ln_kernel(const float* __restrict__ part, int ksplit, int M,
-                                                               int N, const bf16* __restrict__ bias,
-                                                               const bf16* __restrict__ residual, int64_t ldr,
-                                                               const bf16* __restrict__ gamma,
-                                                               const bf16* __restrict__ beta, bf16* __restrict__ y,
-                                                               int64_t ldy, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const int nch = N / 8;
-  float v[CH][8];
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = lane + 64 * c;
-    if (ch < nch) {
-      float a[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a[e] = 0.f;
-      // all (<= 8) partial tiles are requested before the first add: one memory latency, not ksplit
-      f32x4 p0[8], p1[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float* pp = part + ((int64_t)(k < ksplit ? k : 0) * 32 + row) * N + ch * 8;
-        p0[k] = *reinterpret_cast<const f32x4*>(pp);
-        p1[k] = *reinterpret_cast<const f32x4*>(pp + 4);
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (k < ksplit) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { a[e] += p0[k][e]; a[4 + e] += p1[k][e]; }
-        }
-      }
-      if (bias) {
-        const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(bias + ch * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] += (float)b8[e];
-      }
-      if (residual) {
-        const bf16x8 r8 = *reinterpret_cast<const bf16x8*>(residual + (int64_t)row * ldr + ch * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] += (float)r8[e];
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { v[c][e] = vy_round_bf16(a[e]); s += v[c][e]; }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[c][e] = 0.f;
-    }
-  }
-  const float mean = vy_wave_sum(s) / (float)N;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = lane + 64 * c;
-    if (ch < nch) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    }
-  }
-  const float var = vy_wave_sum(q) / (float)N;
-  const float rstd = rsqrtf(var + eps);
-  const float rstd_r = rstd * (1.5f - 0.5f * (var + eps) * rstd * rstd);
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    const int ch = lane + 64 * c;
-    if (ch < nch) {
-      const bf16x8 g8 = *reinterpret_cast<const bf16x8*>(gamma + ch * 8);
-      const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(beta + ch * 8);
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (bf16)((v[c][e] - mean) * rstd_r * (float)g8[e] + (float)b8[e]);
-      *reinterpret_cast<bf16x8*>(y + (int64_t)row * ldy + ch * 8) = o;
-    }
-  }
-}
-
 // (A one-launch form of the split-K GEMM + combine + LayerNorm -- the workgroup that delivers the last K-slice
 // of a tile combines it, the one that finishes the last tile normalises the rows; sc1 write-through hand-offs,
 // no spinning -- was built, was bit-identical, and made the decode step 1.5x SLOWER (1.03 vs 0.69 ms): two
@@ -1483,9 +1335,11 @@ __global__ __launch_bounds__(256) void splitk_finish_ln_kernel(const float* __re
 // cost ~15 us against ~1.7 us for a kernel boundary.  On this chip a chain of short dependent phases is
 // cheapest as launches in a graph, and each launch is made as short as possible instead.)
 
-// y = LayerNorm(bf16(sum_ks part[ks] + bias + residual)), ONE WORKGROUP PER ROW: every thread requests its
-// 4 columns of all partial tiles, bias, residual, gamma and beta at once (one memory round trip), then two
-// block reductions.  (splitk_finish_ln_kernel walks a row with one wave: 6.4 us per launch against ~2.5.)
+// y = LayerNorm(bf16(sum_ks part[ks] + bias + residual)): the epilogue of the split-K GEMM above fused with the
+// LayerNorm that follows it in the block (AttentionSelfOutput / FeedForward), the same arithmetic as gemm epilogue +
+// layernorm_fwd_kernel (sum rounded to bf16 first).  ONE WORKGROUP PER ROW: every thread requests its 4 columns of
+// all partial tiles, bias, residual, gamma and beta at once (one memory round trip), then two block reductions.
+// (Walking a row with one wave measured 6.4 us per launch against ~2.5.)
 template <int QPT>
 __global__ __launch_bounds__(256) void splitk_finish_ln_row_kernel(const float* __restrict__ part, int ksplit, int M,
                                                                    int N, const bf16* __restrict__ bias,
@@ -1574,7 +1428,7 @@ __global__ __launch_bounds__(256) void splitk_finish_ln_row_kernel(const float* 
 template <int EPI, int ACT>
 __global__ __launch_bounds__(256) void gemm_skinny16_bf16_kernel(
     const bf16* __restrict__ X, int64_t ldx, const bf16* __restrict__ W, int64_t ldw, int M, int N,
-    int K, EpiPlain<bf16> ep, EpiQkv<bf16> eq, int dbg) {
+    int K, EpiPlain<bf16> ep, EpiQkv<bf16> eq) {
   __shared__ float red[3][8][64];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1588,11 +1442,6 @@ __global__ __launch_bounds__(256) void gemm_skinny16_bf16_kernel(
   const bf16* wp = W + (int64_t)wr * ldw + kq * 8;
   const bf16* xp0 = X + (int64_t)m0r * ldx + kq * 8;
   const bf16* xp1 = X + (int64_t)m1r * ldx + kq * 8;
-  // measurement knobs (VY_SKINNY_DBG; wrong results): 1 = every lane reads X row 0, 2 = every workgroup reads the
-  // weight rows of tile 0, 4 = one k-step only, 8 = no epilogue, 16 = return at once
-  if (dbg & 16) return;
-  if (dbg & 1) { xp0 = X + kq * 8; xp1 = xp0; }
-  if (dbg & 2) wp = W + (int64_t)r16 * ldw + kq * 8;
   const bool two = M > 16;   // (wave-uniform) a second block of batch rows exists
   // the epilogue's operands that do not depend on the product (bias, residual, rotary cos / sin) are requested
   // up front, under the weight stream: loaded after the reduction they are one more dependent memory round
@@ -1619,7 +1468,7 @@ __global__ __launch_bounds__(256) void gemm_skinny16_bf16_kernel(
       sin4[blk] = *reinterpret_cast<const f32x4*>(eq.sin_tab + pp * 32 + dcol);
     }
   }
-  const int nsteps = (dbg & 4) ? 4 : K >> 5;
+  const int nsteps = K >> 5;
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   int s = wave;
   constexpr int U = 6;   // K = 768: the wave's 6 k-steps in one trip, 18 loads in flight per lane
@@ -1651,7 +1500,6 @@ __global__ __launch_bounds__(256) void gemm_skinny16_bf16_kernel(
   }
   __syncthreads();
   if (wave != 0) return;
-  if (dbg & 8) { if (acc0[0] == 12345.678f) ep.y[0] = (bf16)acc1[0]; return; }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     acc0[r] += red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
@@ -1944,89 +1792,53 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16* __restrict__
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-// the large-M kernel: a forced variant (8 / 9 / 40 / 41) wins, else the MFMA shape by VY_GEMM_M16 and the tile by width
-enum class LargeM { K32_256x256, K32_256x192, M16_256x256, X3M16_256x192 };
-inline LargeM large_m_kernel(int var, bool m16, bool wide) {
-  switch (var) {
-    case 8: return LargeM::K32_256x256;
-    case 9: return LargeM::K32_256x192;
-    case 40: return LargeM::X3M16_256x192;
-    case 41: return LargeM::M16_256x256;
-  }
-  if (m16) return wide ? LargeM::M16_256x256 : LargeM::X3M16_256x192;
-  return wide ? LargeM::K32_256x256 : LargeM::K32_256x192;
-}
-
 template <int EPI, int ACT, bool GRAD>
 int launch_bf16(const bf16* X, int64_t ldx, const bf16* W, int64_t ldw, int64_t M, int64_t N,
                 int64_t K, const EpiPlain<bf16>& ep, const EpiQkv<bf16>& eq, hipStream_t st) {
-  static const int rot = [] { const char* e = getenv("VY_GEMM_ROT"); return e ? atoi(e) : 0; }();  // rotated k order: measured 1-5 % slower
-  static const int mid_tiles = [] { const char* e = getenv("VY_GEMM_MID"); return e ? atoi(e) : 1; }();
-  static const int gemv_on = [] { const char* e = getenv("VY_GEMV"); return e ? atoi(e) : 1; }();
-  static const int skinny16_on = [] { const char* e = getenv("VY_SKINNY16"); return e ? atoi(e) : 1; }();
-  static const int64_t skinny_max_n = [] { const char* e = getenv("VY_SKINNY_MAXN"); return e ? (int64_t)atoll(e) : (int64_t)8192; }();   // wider (the vocabulary): 32 x 128 tiles with X staged once per workgroup -- 15.5 vs 31.1 us at N = 50265
-  if (M <= 4 && (EPI == 0 || !eq.rope) && !GRAD && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && gemv_on &&
+  // wider (the vocabulary): 32 x 128 tiles with X staged once per workgroup -- 15.5 vs 31.1 us at N = 50265
+  constexpr int64_t skinny_max_n = 8192;
+  if (M <= 4 && (EPI == 0 || !eq.rope) && !GRAD && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
       ((uintptr_t)X % 16 == 0) && ((uintptr_t)W % 16 == 0)) {
     if constexpr (!GRAD && (EPI == 1 ? ACT == 0 : true))
       hipLaunchKernelGGL((gemv_bf16_kernel<EPI, ACT, 4>), dim3((unsigned)vy_cdiv(N, 4)), dim3(256), 0, st, X, ldx, W, ldw,
                          (int)M, (int)N, (int)K, ep, eq, (const bf16*)nullptr, 0.f);
-  } else if (M <= 32 && K % 32 == 0 && !GRAD && N % 16 == 0 && N / 32 < 200 && skinny16_on &&
+  } else if (M <= 32 && K % 32 == 0 && !GRAD && N % 16 == 0 && N / 32 < 200 &&
              (EPI == 0 || !eq.rope || (N % 64 == 0 && eq.dh == 64))) {
     // few 32-column workgroups: 16-column ones, so that twice as many CUs stream weights
-    static const int sk_dbg = [] { const char* e = getenv("VY_SKINNY_DBG"); return e ? atoi(e) : 0; }();
     hipLaunchKernelGGL((gemm_skinny16_bf16_kernel<EPI, ACT>), dim3((unsigned)(N / 16)), dim3(256), 0, st, X, ldx,
-                       W, ldw, (int)M, (int)N, (int)K, ep, eq, sk_dbg);
+                       W, ldw, (int)M, (int)N, (int)K, ep, eq);
   } else if (M <= 32 && K % 16 == 0 && !GRAD && (EPI == 0 || !eq.rope || N % 64 == 0) && N <= skinny_max_n) {
     hipLaunchKernelGGL((gemm_skinny_bf16_kernel<EPI, ACT>), dim3((unsigned)vy_cdiv(N, 32)), dim3(256), 0, st, X, ldx,
                        W, ldw, (int)M, (int)N, (int)K, ep, eq);
   } else if (M <= 32) {  // skinny fallback: 32 x 128 tiles
     const int tn = (int)vy_cdiv(N, 128), tm = (int)vy_cdiv(M, 32);
     hipLaunchKernelGGL((gemm_nt_bf16_kernel<32, 128, 1, 4, EPI, ACT, GRAD>), dim3(tm * tn), dim3(256), 0,
-                       st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
-  } else if (M <= 1024 || (mid_tiles && vy_cdiv(M, 256) * vy_cdiv(N, 192) * g_chains < 160)) {
+                       st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq);
+  } else if (M <= 1024 || vy_cdiv(M, 256) * vy_cdiv(N, 192) * g_chains < 160) {
     // mid-size M: also whenever the 256 x 192 grid would leave more than a third of the CUs without a tile
     // (M = 2112 rows of a captioning decoder x N = 768: 36 tiles of 256 x 192, 102 of 128 x 128)
-    const int tn = (int)vy_cdiv(N, 128), tm = (int)vy_cdiv(M, 128);
-    static const int mid16 = [] { const char* e = getenv("VY_GEMM_MID16"); return e ? atoi(e) : 1; }();
     // 128 < M <= 320 (a 256-patch vision tower, a 264-row PaliGemma prefill): ONE row tile holds every row, so each weight
     // element crosses L2 -> LDS once per launch and the 8 rows past 256 do not cost a third row of 128 x 128 tiles
-    // (all-rows tiles of 256 or 320 x 128, 8 waves, one workgroup per CU; VY_GEMM_ROWS=0: the 128 x 128 tiles)
-    static const int rows_on = [] { const char* e = getenv("VY_GEMM_ROWS"); return e ? atoi(e) : 1; }();
-    if (mid16 && rows_on && M > 128 && M <= 320) {
-      if (M <= 256) launch_mid<256, 128, 4, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 256, rot);
-      else launch_mid<320, 128, 4, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 256, rot);
-    } else if (mid16)
-      launch_mid<128, 128, 2, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 448, rot);
-    else
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, 128, 2, 2, EPI, ACT, GRAD>), dim3(tm * tn), dim3(256), 0,
-                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
+    // (all-rows tiles of 256 or 320 x 128, 8 waves, one workgroup per CU)
+    if (M > 128 && M <= 256) launch_mid<256, 128, 4, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 256);
+    else if (M > 128 && M <= 320) launch_mid<320, 128, 4, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 256);
+    else launch_mid<128, 128, 2, 2, EPI, ACT, GRAD>(X, ldx, W, ldw, M, N, K, ep, eq, st, 448);
   } else {
-    const int tn = (int)vy_cdiv(N, 192), tm = (int)vy_cdiv(M, 256);
+    const int tm = (int)vy_cdiv(M, 256);
     // Large M.  256 x 192 tiles divide N in {768, 2304} x M = 16384 into whole multiples of the 256 CUs (X operand in a
     // three-deep ring: gemm_nt_bf16_x3m16_kernel); 256 x 256 (fewer L2 bytes per FLOP) where N is wide enough for whole
     // rounds anyway (FFN1, the dgrad of FFN2, the vocabulary projection).  Both on mfma_f32_16x16x32_bf16.
-    // VY_GEMM_VARIANT (A/B runs in one process, tools/exp_gemm.py): 8 / 9 force the 256 x 256 / 256 x 192 tiles of the
-    // two-stage 32 x 32 x 16 kernel, 40 / 41 force the two default kernels whatever N.  The experimental kernels of rounds
-    // 1-2 (persistent pipelined epilogue, two 4-wave workgroups per CU, 4- and 5-slot rings of 32-wide slices, the
-    // 32 x 32 x 16 X-ring) measured level or behind these on every box and were removed in round 3.
-    const int tn2 = (int)vy_cdiv(N, 256);
-    switch (large_m_kernel(vy_gemm_variant(), vy_m16_on(), N >= 3072)) {
-      case LargeM::K32_256x256:
-        hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
-                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
-        break;
-      case LargeM::K32_256x192:
-        hipLaunchKernelGGL((gemm_nt_bf16_kernel<256, 192, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
-                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
-        break;
-      case LargeM::M16_256x256:
-        hipLaunchKernelGGL((gemm_nt_bf16_m16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn2), dim3(512), 0,
-                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn2, ep, eq, rot);
-        break;
-      case LargeM::X3M16_256x192:
-        hipLaunchKernelGGL((gemm_nt_bf16_x3m16_kernel<192, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
-                           st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq, rot);
-        break;
+    // The experimental kernels of rounds 1-2 (persistent pipelined epilogue, two 4-wave workgroups per CU, 4- and 5-slot
+    // rings of 32-wide slices, the 32 x 32 x 16 X-ring) and the two-stage 32 x 32 x 16 kernel at these tiles measured level
+    // or behind these on every box and were removed.
+    if (N >= 3072) {
+      const int tn = (int)vy_cdiv(N, 256);
+      hipLaunchKernelGGL((gemm_nt_bf16_m16_kernel<256, 256, 4, 2, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
+                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq);
+    } else {
+      const int tn = (int)vy_cdiv(N, 192);
+      hipLaunchKernelGGL((gemm_nt_bf16_x3m16_kernel<192, EPI, ACT, GRAD>), dim3(tm * tn), dim3(512), 0,
+                         st, X, ldx, W, ldw, (int)M, (int)N, (int)K, tn, ep, eq);
     }
   }
   return 0;
@@ -2076,8 +1888,7 @@ int linear_impl(const void* x, int64_t ldx, const void* w, int64_t ldw, const vo
   ep.gradpre = (const T*)gradpre; ep.ldg = ldg; ep.y = (T*)y; ep.ldy = ldy; ep.pre = (T*)pre_out;
   ep.drop = drop;
   ep.pf2 = vy_epi_prefetch();
-  static const int wt_env = [] { const char* e = getenv("VY_GEMM_WT_STORE"); return e ? atoi(e) : 1; }();
-  ep.wt_store = (wt_env && (int64_t)M * N * (int64_t)sizeof(T) >= (16 << 20)) ? 1 : 0;
+  ep.wt_store = (int64_t)M * N * (int64_t)sizeof(T) >= (16 << 20) ? 1 : 0;   // outputs of 16 MiB and more: see EpiPlain
   const int ve = 16 / (int)sizeof(T);  // elements per 16-byte access (bf16: 8, f32 quads: 4)
   ep.vec_ok = (ldy % ve == 0) && aligned_to(y, 16) && (!bias || aligned_to(bias, 4 * sizeof(T))) &&
               (!residual || (ldr % ve == 0 && aligned_to(residual, 16))) &&
@@ -2223,7 +2034,6 @@ extern "C" int vy_qkv_rope_fwd(const void* x, int64_t ldx, const void* w, int64_
 // `part` is an fp32 scratch of vy_splitk_ws_floats(N) elements.  Internal to the decode driver.
 int64_t vy_splitk_ws_floats(int64_t N) { return 8 * 32 * N; }
 
-extern "C" int vy_debug_set_gemm_variant(int v) { g_gemm_variant = v; return 0; }
 extern "C" int vy_debug_set_epilogue_prefetch(int on) { g_epi_prefetch = on ? 1 : 0; return 0; }
 extern "C" int vy_workspace_set(void* stream, void* ws, int64_t bytes) {
   if (bytes < 0 || (ws && ((uintptr_t)ws & 255))) VY_FAIL(VY_ERR_ARG, "vy_workspace_set: bad workspace (256-byte aligned, bytes >= 0)");
@@ -2249,12 +2059,6 @@ extern "C" int vy_set_concurrent_chains(int n) {
   return VY_OK;
 }
 
-// measurement aid, not part of include/vyom_hip.h: {shader cycles, 10 ns ticks, launches} since the last call
-extern "C" int vy_debug_gemm_clock(unsigned long long* out3) {   // out3: 6 values
-  unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(out3, HIP_SYMBOL(vy_gemm_clk), sizeof(z)) != hipSuccess) return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(vy_gemm_clk), z, sizeof(z)) != hipSuccess;
-}
 int vy_linear_res_ln_skinny(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias,
                             const void* residual, int64_t ldr, const void* gamma, const void* beta, float eps,
                             void* y, int64_t ldy, float* part, int64_t M, int64_t N, int64_t K, void* stream) {
@@ -2274,31 +2078,15 @@ int vy_linear_res_ln_skinny(const void* x, int64_t ldx, const void* w, int64_t l
   hipLaunchKernelGGL(gemm_skinny_splitk_kernel, dim3((unsigned)nwg, (unsigned)ksplit), dim3(256), 0, st, (const bf16*)x,
                      ldx, (const bf16*)w, ldw, (int)M, (int)N, (int)K, spw, part);
   VY_CHECK_LAUNCH(who);
-  static const int row_fin = [] { const char* e = getenv("VY_DECODE_ROW_FINISH"); return e ? atoi(e) : 1; }();
-  if (row_fin && N % 4 == 0) {   // one workgroup per row
-    const int qpt = (int)vy_cdiv(N / 4, 256);
+  const int qpt = (int)vy_cdiv(N / 4, 256);   // one workgroup per row
 #define ROW_GO(Q)                                                                                               \
-    hipLaunchKernelGGL((splitk_finish_ln_row_kernel<Q>), dim3((unsigned)M), dim3(256), 0, st, part, ksplit, (int)M, (int)N, \
-                       (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps)
-    if (qpt <= 1) ROW_GO(1);
-    else if (qpt <= 2) ROW_GO(2);
-    else if (qpt <= 4) ROW_GO(4);
-    else ROW_GO(8);
+  hipLaunchKernelGGL((splitk_finish_ln_row_kernel<Q>), dim3((unsigned)M), dim3(256), 0, st, part, ksplit, (int)M, (int)N, \
+                     (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps)
+  if (qpt <= 1) ROW_GO(1);
+  else if (qpt <= 2) ROW_GO(2);
+  else if (qpt <= 4) ROW_GO(4);
+  else ROW_GO(8);
 #undef ROW_GO
-    VY_CHECK_LAUNCH(who);
-    return VY_OK;
-  }
-  const int nch = (int)(N / 8);
-  const dim3 grid((unsigned)((M + 3) / 4)), block(256);
-#define FIN_GO(CH)                                                                                               \
-  hipLaunchKernelGGL((splitk_finish_ln_kernel<CH>), grid, block, 0, st, part, ksplit, (int)M, (int)N, (const bf16*)bias, \
-                     (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps)
-  if (nch <= 64) FIN_GO(1);
-  else if (nch <= 128) FIN_GO(2);
-  else if (nch <= 256) FIN_GO(4);
-  else if (nch <= 512) FIN_GO(8);
-  else FIN_GO(16);
-#undef FIN_GO
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }

@@ -994,7 +994,7 @@ extern "C" int vy_gated_act_fwd(const void* gate_up, int64_t ldg, void* out, int
 }
 
 extern "C" int64_t vy_layernorm_bwd_ws_rows(int64_t M) {
-  static const int64_t cap = [] { const char* e = getenv("VY_LNBWD_WB"); return e ? (int64_t)atoi(e) : (int64_t)512; }();   // measured at M = 16384, N = 768: 256: 27.8 us, 512: 24.3, 1024: 27.6, 2048: 36.3
+  constexpr int64_t cap = 512;   // measured at M = 16384, N = 768: 256: 27.8 us, 512: 24.3, 1024: 27.6, 2048: 36.3
   const int64_t b = (M + 3) / 4;  // one wave per row at least
   return b < 1 ? 1 : (b > cap ? cap : b);
 }
