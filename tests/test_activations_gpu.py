@@ -201,8 +201,6 @@ def test_unknown_activation_is_an_error_everywhere():
     part = torch.zeros(12 * 32 * N, dtype=torch.float32, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
     p, i, f = C.c_void_p, C.c_int, C.c_float
-    dec_linear = getattr(lib, "_Z13vy_dec_linearPKviS0_S0_PviiiiiP12ihipStream_t")
-    dec_linear.argtypes, dec_linear.restype = [p, i, p, p, p, i, i, i, i, i, p], i
     dec_linear_ex = getattr(lib, "_Z16vy_dec_linear_exPKviS0_S0_S0_iS0_S0_fPviiiiiP12ihipStream_t")
     dec_linear_ex.argtypes, dec_linear_ex.restype = [p, i, p, p, p, i, p, p, f, p, i, i, i, i, i, p], i
     dec_res_ln = getattr(lib, "_Z20vy_dec_linear_res_lnPKviS0_S0_S0_iS0_S0_fPviPfiiiiP12ihipStream_t")
@@ -211,13 +209,14 @@ def test_unknown_activation_is_an_error_everywhere():
     want = (x.double() @ w.double().t() + b.double()).cpu()
     for code, rc_want in ((0, 0), (3, 0), (99, VY_ERR_ARG), (8, VY_ERR_ARG)):
         y.fill_(7.0)
-        rc = dec_linear(x.data_ptr(), K, w.data_ptr(), b.data_ptr(), y.data_ptr(), N, B, N, K, code, st)
-        assert rc == rc_want, ("vy_dec_linear", code, rc, lib.vy_last_error())
+        # the plain projection: no residual, no LayerNorm operands
+        rc = dec_linear_ex(x.data_ptr(), K, w.data_ptr(), b.data_ptr(), None, 0, None, None, 0.0, y.data_ptr(), N, B, N, K, code, st)
+        assert rc == rc_want, ("vy_dec_linear_ex plain", code, rc, lib.vy_last_error())
         torch.cuda.synchronize()
         if rc_want:
             assert float((y.float() - 7.0).abs().max()) == 0, "a refused call must not launch"
         else:
-            check(y, want if code == 0 else F.silu(want), 3e-2, 1e-2, f"vy_dec_linear act {code}")
+            check(y, want if code == 0 else F.silu(want), 3e-2, 1e-2, f"vy_dec_linear_ex plain act {code}")
         rc = dec_linear_ex(x.data_ptr(), K, w.data_ptr(), b.data_ptr(), None, 0, g.data_ptr(), be.data_ptr(), 1e-5,
                            y.data_ptr(), N, B, N, K, code, st)
         assert rc == rc_want, ("vy_dec_linear_ex", code, rc, lib.vy_last_error())
@@ -555,7 +554,7 @@ def _decode_model(name, dtype=BF):
 def test_lean_decode_step_matches_general_and_fp32(name, B):
     """test_decode_lean_gpu.test_lean_step_matches_general_and_fp32, same bars, per activation.  The general step runs
     vy_linear_fwd, which refuses codes it does not know; a lean kernel that sent a new code to the identity (what
-    vy_dec_linear did before it knew them) is far outside these bars."""
+    the decode projection did before it knew them) is far outside these bars."""
     from tests.test_decode_lean_gpu import _plan, _step
     torch.manual_seed(1)
     cfg, m = _decode_model(name)

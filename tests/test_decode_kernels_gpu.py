@@ -339,27 +339,45 @@ def test_step_at_the_benchmark_shape_against_fp64(attn, pos):
     _assert_ratios(_step_ratios(768, 3072, 12, 12 if attn == "mha" else 4, 32, pos, cap=640), 32)
 
 
+# ---- the step does not depend on the environment ---------------------------------------------------------------
+# The variables that once selected a decode kernel, a chain of the step or a measurement aid, each at its former
+# non-default value.  Nothing reads them any more.
+STALE_ENV = {"VY_DEC_WT": "1", "VY_DEC_P64": "0", "VY_DEC_LNFOLD": "0", "VY_DEC_ATTN": "0", "VY_DEC_ATTN_NT": "0",
+             "VY_DEC_ATTN_GQ": "0", "VY_DECODE_LEAN": "0", "VY_GEMMA_LEAN": "0", "VY_GEMMA_FUSED": "2",
+             "VY_GEMMA_ROPE_FUSED": "0", "VY_GEMMA_PRESCALE": "0", "VY_GREEDY_TWO_STAGE": "0"}
+
+
+def _first_attn_case(dh, h, hk, nt):
+    """The case of Part A with the smallest context (all of them in the first NP bucket) for these heads and K/V policy."""
+    case = next(c for c in ATTN_CASES if c[:3] == (dh, h, hk) and c[4] == nt)
+    assert expected_tuple(dh, h, hk, case[3], case[5])[1] == NP_BUCKETS[0]
+    return case
+
+
 def _child_main():
-    """The (768, 3072), B = 32 step check, run as `python -m tests.test_decode_kernels_gpu` in a fresh process by
-    test_step_under_env_switches (VY_DEC_LNFOLD / VY_DEC_P64 are read once per process)."""
-    import os
-    tag = " ".join(f"{k}=0" for k in ("VY_DEC_LNFOLD", "VY_DEC_P64") if os.environ.get(k) == "0")
+    """The (768, 3072), B = 32 step check and one Part-A case per family (each asserts which instantiation ran before it
+    compares numbers), run as `python -m tests.test_decode_kernels_gpu` in a fresh process by
+    test_step_does_not_depend_on_the_environment (such variables were read once per process)."""
     for hk in (12, 3):
-        _assert_ratios(_step_ratios(768, 3072, 2, hk, 32, 37, cap=96,
-                                    what=f"{tag} 2L d=768 ffn=3072 h/hk=12/{hk} B=32 pos=37"), 32)
+        _assert_ratios(_step_ratios(768, 3072, 2, hk, 32, 37, cap=96), 32)
+    for dh, h, hk, nt in ((64, 8, 2, 1),       # R = 4, streamed
+                          (64, 12, 12, 0),     # small cache: default loads
+                          (256, 8, 1, 0)):
+        case = _first_attn_case(dh, h, hk, nt)
+        assert expected_tuple(dh, h, hk, case[3], case[5]) == (dh, NP_BUCKETS[0], nt, 4 if nt and dh == 64 else 1)
+        test_decode_attention_every_instantiation(*case)
     print("child ok")
 
 
-@pytest.mark.parametrize("env", ["VY_DEC_LNFOLD", "VY_DEC_P64"])
-def test_step_under_env_switches(env):
-    """VY_DEC_LNFOLD=0 (the seven-link layer: out-projection as partial tiles + finish with LayerNorm, FFN1 plain) and
-    VY_DEC_P64=0 (dec_gemm16<DEC_PART> at d = 768) select shipped code the default run never reaches."""
+def test_step_does_not_depend_on_the_environment():
+    """With the old library every one of these would have changed what runs: the seven-link layer, dec_gemm16<DEC_PART>
+    at d = 768, the general launchers, and FALLBACK or another tuple from vy_debug_decode_attn_last."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     e = dict(os.environ)
-    e[env] = "0"
+    e.update(STALE_ENV)
     r = subprocess.run([sys.executable, "-m", "tests.test_decode_kernels_gpu"], cwd=root, env=e, timeout=300,
                        capture_output=True, text=True)
     print(r.stdout)

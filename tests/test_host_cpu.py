@@ -325,3 +325,30 @@ def test_wrapped_projection_is_refused_not_ignored():
         layer.attention._packed()
     with pytest.raises(VyomHipError, match="merge the low-rank update"):
         layer.attention._params()
+
+
+# vy_decode_ws_bytes (h = d / 64, hk = h / 4, dh = 64) and vy_gemma_ws_bytes (h = 8, dh = 256) as the library returned them
+# before the step and the size query shared one layout: plans sized by an earlier build must stay valid.
+# Rows: (d, ffn) = (512, 2048), (768, 3072), (1024, 6144); columns: B = 1, 7, 32.
+WS_SHAPES = ((512, 2048), (768, 3072), (1024, 6144))
+WS_BATCHES = (1, 7, 32)
+WS_DECODE = {"f32": ((1597440, 1720320, 2232320), (2394112, 2578432, 3346432), (3198976, 3493888, 4722688)),
+             "bf16": ((1587200, 1648640, 1904640), (2378752, 2470912, 2854912), (3174400, 3321856, 3936256))}
+WS_GEMMA = {"f32": ((53248, 348160, 1576960), (69632, 462848, 2101248), (110592, 749568, 3411968)),
+            "bf16": ((28672, 176128, 790528), (36864, 233472, 1052672), (57344, 376832, 1708032))}
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_decode_workspace_sizes_are_unchanged(dtype):
+    from vyomai_amd import _lib
+    lib = _lib.load()
+    lib.vy_decode_ws_bytes.restype = ctypes.c_int64
+    lib.vy_decode_ws_bytes.argtypes = [ctypes.c_int32] * 7
+    lib.vy_gemma_ws_bytes.restype = ctypes.c_int64
+    lib.vy_gemma_ws_bytes.argtypes = [ctypes.c_int32] * 6
+    code = _lib.dtype_code(torch.float32 if dtype == "f32" else torch.bfloat16)
+    for i, (d, ffn) in enumerate(WS_SHAPES):
+        for j, B in enumerate(WS_BATCHES):
+            h = d // 64
+            assert lib.vy_decode_ws_bytes(B, d, h, h // 4, 64, ffn, code) == WS_DECODE[dtype][i][j], (B, d, ffn)
+            assert lib.vy_gemma_ws_bytes(B, d, 8, 256, ffn, code) == WS_GEMMA[dtype][i][j], (B, d, ffn)

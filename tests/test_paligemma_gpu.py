@@ -205,7 +205,7 @@ def test_model_and_cached_greedy_loop_fp32_vs_notebook(golden):
     assert torch.allclose(m.norm.weight, before + 1.0)
 
 
-def test_single_sequence_step_lean_kernels_vs_general_and_fp32(monkeypatch):
+def test_single_sequence_step_lean_kernels_vs_general_and_fp32():
     """B = 1 bf16 decode at the true Gemma-2B widths (d 2048, 8 x 256 query heads on one KV head, MLP 16384): the
     straight-line matrix-vector kernels with the RMSNorms folded into pre-scaled weights and the rotary embedding
     fused into the QKV product (vy_decode.hip) against the general chain (RMSNorm / QKV / RoPE launches), and both
@@ -236,11 +236,10 @@ def test_single_sequence_step_lean_kernels_vs_general_and_fp32(monkeypatch):
     m16, m32 = model(torch.bfloat16), model(torch.float32)
     res = {}
     try:
-        for name, lean, prescale in (("lean", 1, "1"), ("lean_noscale", 1, "0"), ("general", 0, "0")):
-            monkeypatch.setenv("VY_GEMMA_PRESCALE", prescale)
+        for name, lean, prescale in (("lean", 1, True), ("lean_noscale", 1, False), ("general", 0, False)):
             lib.vy_debug_set_gemma_lean(lean)
             cs = caches(torch.bfloat16)
-            plan = GemmaDecodePlan(m16, cs, 1)
+            plan = GemmaDecodePlan(m16, cs, 1, prescale=prescale)
             res[name] = (plan.step(x.to(torch.bfloat16).to(DEV), pos).float().clone(),
                          [c[0][:, :, pos].float().clone() for c in cs])
             torch.cuda.synchronize()

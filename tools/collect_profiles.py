@@ -32,11 +32,6 @@ if all(os.path.isdir(d) for d in dirs):
         print("wrote", f"{R}_gemm_pmc.json")
     else:
         print(out.stderr[-2000:])
-tl = os.path.join(src, "decode_timeline.log")
-if os.path.exists(tl):
-    keep = [l for l in open(tl).read().splitlines() if l[:1] in " lf" and ("|" in l or "stamped" in l)]
-    open(os.path.join(dst, f"{R}_decode_timeline.txt"), "w").write("\n".join(keep) + "\n")
-    print("wrote", f"{R}_decode_timeline.txt")
 for log in ("roofline.log", "decode.log", "paligemma.log", "prefill.log", "vlm.log", "train.log"):
     p = os.path.join(src, log)
     if os.path.exists(p):

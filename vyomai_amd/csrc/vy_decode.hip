@@ -18,25 +18,11 @@
 // eager / graph / prefill comparisons in the tests hold unchanged.
 #include "vy_common.h"
 #include "vy_wave.h"
-#include <stdlib.h>
 #include <float.h>
 
 namespace {
 
 enum { DEC_STORE = 0, DEC_PART = 1, DEC_QKV = 2 };
-
-// measurement aid (vy_debug_set_decode_stamps, tools/decode_timeline.py): lane 0 of every workgroup's wave 0 writes
-// the 100 MHz wall clock (s_memrealtime) at five points of the kernel into stamps[launch][workgroup][8]
-struct DecDbg { unsigned long long* buf; int slot; int max_wg; };
-#define DEC_STAMP(i)                                                                                          \
-  if constexpr (DBG) { __builtin_amdgcn_sched_barrier(0); dbg_t[i] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); }
-#define DEC_STAMP_FLUSH()                                                                                     \
-  if constexpr (DBG) {                                                                                        \
-    if (threadIdx.x == 0 && (int)(blockIdx.x + gridDim.x * blockIdx.y) < dbg.max_wg) {                        \
-      for (int i_ = 0; i_ < 8; ++i_)                                                                          \
-        dbg.buf[((long long)dbg.slot * dbg.max_wg + blockIdx.x + gridDim.x * blockIdx.y) * 8 + i_] = dbg_t[i_]; \
-    }                                                                                                         \
-  }
 
 // 16 bytes of a stream too large to stay on chip until it is read again: the non-temporal policy
 // (`global_load_dwordx4 ... nt`).  Used for the K/V rows of a LARGE cache only (dec_attn_kernel<..., NT>): at B = 32 the
@@ -57,22 +43,15 @@ struct DecGemmArgs {
   long long c_sb, c_sh, c_sl;          //   element strides of the caches (batch, head, token)
   const float* cos_tab; const float* sin_tab; const int* pos_dev;
   int pos0, nq, nkv, rope;
-  int wt;                              // write-through stores
   const bf16* residual; int ldr;       // DEC_STORE: y = bf16(act(x W^T + b) + residual)
   const bf16* ln_g; const bf16* ln_b; float ln_eps;   // LNP kernels: the rows of X are LayerNorm'ed on the way in
   int act;                             // the vy_act code, read by the ACT == VY_ACT_RUNTIME instantiations only
 };
 
-// stores of the step's small outputs.  wt: write-through (sc0 sc1) -- the line does not stay dirty in this XCD's L2,
-// so the write-back at the end of the kernel (every launch boundary releases at agent scope) finds nothing to do
+// one 8- or 16-byte vector store of the step's small outputs
 template <typename V>
-__device__ __forceinline__ void dec_store(void* p, const V& v, int wt) {
-  if (wt) {
-    if constexpr (sizeof(V) == 16) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-    else asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-  } else {
-    *reinterpret_cast<V*>(p) = v;
-  }
+__device__ __forceinline__ void dec_store(void* p, const V& v) {
+  *reinterpret_cast<V*>(p) = v;
 }
 
 // the value of lane ^ 32 (v_permlane32_swap instead of a ds_bpermute round trip); upper = this lane is >= 32
@@ -96,14 +75,10 @@ __device__ __forceinline__ float dec_swap32(float v, bool upper) {
 // through LDS (one barrier each: mean, then the sum of squared deviations -- the two-pass form of dec_finish_ln_kernel,
 // same rsqrt refinement, the normalised value rounded to bf16 exactly where that kernel stores it).  The launch this
 // saves is a ~4.3 us link of the step's dependent chain; every workgroup redoes the statistics (25 k elements: noise).
-template <int EPI, int ACT, int U, bool DBG, bool LNP = false>
-__global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, const DecDbg dbg) {
+template <int EPI, int ACT, int U, bool LNP = false>
+__global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p) {
   __shared__ float red[3][8][64];
   __shared__ float lnred[2][4][32];
-  unsigned long long dbg_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DEC_STAMP(0)
-  if constexpr (DBG) { asm volatile("" ::"s"(p.M), "s"(p.ldw)); }
-  DEC_STAMP(5)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, kq = lane >> 4;
@@ -116,8 +91,6 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
   const bf16* wp = p.W + (long long)col * p.ldw + kbase;
   const bf16* xp0 = p.X + (long long)m0 * p.ldx + kbase;
   const bf16* xp1 = p.X + (long long)m1 * p.ldx + kbase;
-  if constexpr (DBG) { asm volatile("" ::"v"(wp), "v"(xp0), "v"(xp1)); }
-  DEC_STAMP(6)
   // this lane's output quad: columns nq0 .. nq0 + 3
   const int nq0 = rope_map ? (nb >> 2) * 64 + (nb & 3) * 8 + 4 * (kq & 1) + (kq >= 2 ? 32 : 0) : nb * 16 + 4 * kq;
 
@@ -155,7 +128,6 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
       sin4 = *reinterpret_cast<const f32x4*>(p.sin_tab + pp);
     }
   }
-  DEC_STAMP(1)
   if constexpr (LNP) {
     const float inv_n = 1.0f / (float)(128 * U);   // K = 4 waves x U k-steps x 32
     float s0 = 0.f, s1 = 0.f;
@@ -199,15 +171,12 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
     acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b0[u], acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b1[u], acc1, 0, 0, 0);
   }
-  if constexpr (DBG) { asm volatile("" :: "v"(acc0), "v"(acc1)); }
-  DEC_STAMP(2)
   if (wave > 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) { red[wave - 1][r][lane] = acc0[r]; red[wave - 1][4 + r][lane] = acc1[r]; }
   }
   __syncthreads();
   if (wave != 0) return;
-  DEC_STAMP(3)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     acc0[r] += red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
@@ -215,8 +184,8 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
   }
   if constexpr (EPI == DEC_PART) {
     float* dst = p.part + ((long long)blockIdx.y * 32 + r16) * p.N + nq0;
-    if (r16 < p.M) dec_store(dst, acc0, p.wt);
-    if (16 + r16 < p.M) dec_store(dst + 16ll * p.N, acc1, p.wt);
+    if (r16 < p.M) dec_store(dst, acc0);
+    if (16 + r16 < p.M) dec_store(dst + 16ll * p.N, acc1);
   } else if constexpr (EPI == DEC_STORE) {
     bf16x4 o0, o1;
     vy_act_dispatch<ACT>(p.act, [&](auto ac) __attribute__((always_inline)) {
@@ -228,8 +197,8 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
       }
     });
     bf16* dst = p.y + (long long)r16 * p.ldy + nq0;
-    if (r16 < p.M) dec_store(dst, o0, p.wt);
-    if (16 + r16 < p.M) dec_store(dst + 16ll * p.ldy, o1, p.wt);
+    if (r16 < p.M) dec_store(dst, o0);
+    if (16 + r16 < p.M) dec_store(dst + 16ll * p.ldy, o1);
   } else {
     // head and offset inside the head of this lane's quad; section q / k / v is workgroup-uniform
     const int hd = nb >> 2;                       // 64-wide heads: 4 workgroups per head under either column map
@@ -259,28 +228,23 @@ __global__ __launch_bounds__(256) void dec_gemm16_kernel(const DecGemmArgs p, co
     if (hd < hq) { base = p.q + hd * 64 + dcol; rs = p.nq; }
     else if (hd < hq + hkv) { base = p.k + (hd - hq) * p.c_sh + (long long)pos * p.c_sl + dcol; rs = p.c_sb; }
     else { base = p.v + (hd - hq - hkv) * p.c_sh + (long long)pos * p.c_sl + dcol; rs = p.c_sb; }
-    if (r16 < p.M) dec_store(base + r16 * rs, o0, p.wt);
-    if (16 + r16 < p.M) dec_store(base + (16 + r16) * rs, o1, p.wt);
+    if (r16 < p.M) dec_store(base + r16 * rs, o0);
+    if (16 + r16 < p.M) dec_store(base + (16 + r16) * rs, o1);
   }
-  if constexpr (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  DEC_STAMP(4)
-  DEC_STAMP_FLUSH()
 }
 
 // ------------------------------------------------------------------------------------------
 // Partial tiles of the two N = d projections (out-projection, FFN2) for the split-K finish below: 64 output
 // columns x 32 rows x a SHORT K range (U k-steps of 32) per workgroup, one 16-column block per WAVE, all four
-// waves on the same K range.  The timeline (tools/decode_timeline.py) shows what a launch of dec_gemm16_kernel
+// waves on the same K range.  The recorded timelines (profiles/*_decode_timeline.txt) show what a launch of dec_gemm16_kernel
 // waits for: its 73 KB per workgroup (49 KB of it the activations, re-read by every workgroup) arrive at the
 // ~30 GB/s one CU takes in -- 2.4 us.  Bytes per workgroup for a (c columns, k range) tile are 2k(32 + c) against
 // k c of work: wide and short is cheapest, and costs nothing here because these projections are split over K
 // anyway.  12 KB of activations (shared by the four waves through L1) + 24 KB of weights per workgroup, no
 // cross-wave reduction, no LDS, no barrier.  part[gridDim.y][32][N] as in dec_gemm16_kernel<DEC_PART>.
 // ------------------------------------------------------------------------------------------
-template <int U, bool DBG>
-__global__ __launch_bounds__(256) void dec_gemm64p_kernel(const DecGemmArgs p, const DecDbg dbg) {
-  unsigned long long dbg_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DEC_STAMP(0)
+template <int U>
+__global__ __launch_bounds__(256) void dec_gemm64p_kernel(const DecGemmArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, kq = lane >> 4;
@@ -297,21 +261,15 @@ __global__ __launch_bounds__(256) void dec_gemm64p_kernel(const DecGemmArgs p, c
     b0[u] = *reinterpret_cast<const bf16x8*>(xp0 + 32 * u);
     b1[u] = *reinterpret_cast<const bf16x8*>(xp1 + 32 * u);
   }
-  DEC_STAMP(1)
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b0[u], acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b1[u], acc1, 0, 0, 0);
   }
-  if constexpr (DBG) { asm volatile("" :: "v"(acc0), "v"(acc1)); }
-  DEC_STAMP(2)
   float* dst = p.part + ((long long)blockIdx.y * 32 + r16) * p.N + (int)blockIdx.x * 64 + wave * 16 + 4 * kq;
-  if (r16 < p.M) dec_store(dst, acc0, p.wt);
-  if (16 + r16 < p.M) dec_store(dst + 16ll * p.N, acc1, p.wt);
-  if constexpr (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  DEC_STAMP(4)
-  DEC_STAMP_FLUSH()
+  if (r16 < p.M) dec_store(dst, acc0);
+  if (16 + r16 < p.M) dec_store(dst + 16ll * p.N, acc1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -319,172 +277,109 @@ __global__ __launch_bounds__(256) void dec_gemm64p_kernel(const DecGemmArgs p, c
 // 4 columns of every partial tile, bias, residual, gamma and beta at once (one memory round trip), then two
 // block reductions (the arithmetic of splitk_finish_ln_row_kernel, vy_gemm.hip).
 // ------------------------------------------------------------------------------------------
-template <int KS, int QPT, int ACT, bool DBG>
+template <int KS, int ACT>
 __global__ __launch_bounds__(256) void dec_finish_ln_kernel(const float* __restrict__ part, int ksplit, int N,
                                                             const bf16* __restrict__ bias,
                                                             const bf16* __restrict__ residual, int ldr,
                                                             const bf16* __restrict__ gamma,
                                                             const bf16* __restrict__ beta, bf16* __restrict__ y,
-                                                            int ldy, float eps, int wt, const DecDbg dbg, int act) {
+                                                            int ldy, float eps, int act) {
   __shared__ float red[2][4];
-  unsigned long long dbg_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DEC_STAMP(0)
-  if constexpr (DBG) { asm volatile("" ::"s"(N), "s"(ksplit)); }
-  DEC_STAMP(5)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = blockIdx.x;
-  const int nq = N >> 2;
-  f32x4 pk[QPT][KS];
-  bf16x4 b4[QPT], r4[QPT], g4[QPT], be4[QPT];
+  const bool ok = tid < (N >> 2);   // N <= 1024: one quad of columns per thread
+  const int n = (ok ? tid : 0) * 4;
+  f32x4 pk[KS];
 #pragma unroll
-  for (int i = 0; i < QPT; ++i) {
-    const int q = tid + 256 * i;
-    const int n = (q < nq ? q : 0) * 4;
+  for (int k = 0; k < KS; ++k)
+    pk[k] = *reinterpret_cast<const f32x4*>(part + ((long long)(k < ksplit ? k : 0) * 32 + row) * N + n);
+  bf16x4 b4 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f}, r4 = b4;
+  if (bias) b4 = *reinterpret_cast<const bf16x4*>(bias + n);
+  if (residual) r4 = *reinterpret_cast<const bf16x4*>(residual + (long long)row * ldr + n);
+  const bf16x4 g4 = *reinterpret_cast<const bf16x4*>(gamma + n);
+  const bf16x4 be4 = *reinterpret_cast<const bf16x4*>(beta + n);
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < KS; ++k)
-      pk[i][k] = *reinterpret_cast<const f32x4*>(part + ((long long)(k < ksplit ? k : 0) * 32 + row) * N + n);
-    b4[i] = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
-    r4[i] = b4[i];
-    if (bias) b4[i] = *reinterpret_cast<const bf16x4*>(bias + n);
-    if (residual) r4[i] = *reinterpret_cast<const bf16x4*>(residual + (long long)row * ldr + n);
-    g4[i] = *reinterpret_cast<const bf16x4*>(gamma + n);
-    be4[i] = *reinterpret_cast<const bf16x4*>(beta + n);
+  for (int k = 0; k < KS; ++k) {
+    if (k < ksplit) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a[e] += pk[k][e];
+    }
   }
-  DEC_STAMP(1)
-  float v[QPT][4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a[e] += (float)b4[e];
+  if constexpr (ACT != VY_ACT_NONE) {
+    vy_act_dispatch<ACT>(act, [&](auto ac) __attribute__((always_inline)) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a[e] = vy_act_fwd_fast<decltype(ac)::value>(a[e]);
+    });
+  }
+  float v[4];
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < QPT; ++i) {
-    const bool ok = tid + 256 * i < nq;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      if (k < ksplit) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] += pk[i][k][e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] += (float)b4[i][e];
-    if constexpr (ACT != VY_ACT_NONE) {
-      vy_act_dispatch<ACT>(act, [&](auto ac) __attribute__((always_inline)) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] = vy_act_fwd_fast<decltype(ac)::value>(a[e]);
-      });
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      a[e] += (float)r4[i][e];
-      v[i][e] = ok ? vy_round_bf16(a[e]) : 0.f;
-      s += v[i][e];
-    }
+  for (int e = 0; e < 4; ++e) {
+    a[e] += (float)r4[e];
+    v[e] = ok ? vy_round_bf16(a[e]) : 0.f;
+    s += v[e];
   }
-  DEC_STAMP(2)
   s = dec_wave_sum(s);
   if (lane == 0) red[0][wave] = s;
   __syncthreads();
   const float mean = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (float)N;
   float qv = 0.f;
+  if (ok) {
 #pragma unroll
-  for (int i = 0; i < QPT; ++i) {
-    if (tid + 256 * i < nq) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; qv += d * d; }
-    }
+    for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; qv += d * d; }
   }
   qv = dec_wave_sum(qv);
   if (lane == 0) red[1][wave] = qv;
   __syncthreads();
-  DEC_STAMP(3)
   const float var = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (float)N;
   const float rstd = rsqrtf(var + eps);
   const float rstd_r = rstd * (1.5f - 0.5f * (var + eps) * rstd * rstd);
+  if (ok) {
+    bf16x4 o;
 #pragma unroll
-  for (int i = 0; i < QPT; ++i) {
-    const int q = tid + 256 * i;
-    if (q < nq) {
-      bf16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (bf16)((v[i][e] - mean) * rstd_r * (float)g4[i][e] + (float)be4[i][e]);
-      dec_store(y + (long long)row * ldy + q * 4, o, wt);
-    }
+    for (int e = 0; e < 4; ++e) o[e] = (bf16)((v[e] - mean) * rstd_r * (float)g4[e] + (float)be4[e]);
+    dec_store(y + (long long)row * ldy + tid * 4, o);
   }
-  if constexpr (DBG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  DEC_STAMP(4)
-  DEC_STAMP_FLUSH()
 }
 
-DecDbg g_dbg{nullptr, 0, 0};
-int g_dbg_launches = 0;
-
-int dec_wt() {
-  static const int v = [] { const char* e = getenv("VY_DEC_WT"); return e ? atoi(e) : 0; }();
-  return v;
-}
-
-template <int EPI, int ACT>
-int dec_gemm_go(DecGemmArgs a, int K, int chunks, hipStream_t st) {
-  a.wt = dec_wt();
-  const int u4 = K / chunks / 128;   // k-steps per wave
-  const dim3 grid((unsigned)(a.N / 16), (unsigned)chunks), block(256);
-  if constexpr (EPI == DEC_STORE) {
-    if (a.ln_g) {   // LayerNorm prologue: the workgroup must hold whole rows (one K chunk)
-      if (chunks != 1) return 1;
-      if (u4 == 6) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 6, false, true>), grid, block, 0, st, a, g_dbg);
-      else if (u4 == 8) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 8, false, true>), grid, block, 0, st, a, g_dbg);
-      else if (u4 == 4) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 4, false, true>), grid, block, 0, st, a, g_dbg);
-      else return 1;
-      return 0;
-    }
-  }
-  if (g_dbg.buf && g_dbg.slot < g_dbg_launches) {
-    if (u4 == 6) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 6, true>), grid, block, 0, st, a, g_dbg);
-    else if (u4 == 8) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 8, true>), grid, block, 0, st, a, g_dbg);
-    else if (u4 == 4) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 4, true>), grid, block, 0, st, a, g_dbg);
-    else return 1;
-    ++g_dbg.slot;
-    return 0;
-  }
-  if (u4 == 6) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 6, false>), grid, block, 0, st, a, g_dbg);
-  else if (u4 == 8) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 8, false>), grid, block, 0, st, a, g_dbg);
-  else if (u4 == 4) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 4, false>), grid, block, 0, st, a, g_dbg);
+// k-steps per wave u4 in {6, 8, 4}: K / chunks = 128 * u4.  Returns nonzero (nothing launched) for any other K
+template <int EPI, int ACT, bool LNP>
+int dec_gemm16_launch(const DecGemmArgs& a, int u4, dim3 grid, hipStream_t st) {
+  if (u4 == 6) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 6, LNP>), grid, dim3(256), 0, st, a);
+  else if (u4 == 8) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 8, LNP>), grid, dim3(256), 0, st, a);
+  else if (u4 == 4) hipLaunchKernelGGL((dec_gemm16_kernel<EPI, ACT, 4, LNP>), grid, dim3(256), 0, st, a);
   else return 1;
   return 0;
 }
 
+template <int EPI, int ACT>
+int dec_gemm_go(const DecGemmArgs& a, int K, int chunks, hipStream_t st) {
+  const int u4 = K / chunks / 128;
+  const dim3 grid((unsigned)(a.N / 16), (unsigned)chunks);
+  if constexpr (EPI == DEC_STORE) {
+    // LayerNorm prologue: the workgroup must hold whole rows (one K chunk)
+    if (a.ln_g) return chunks != 1 ? 1 : dec_gemm16_launch<EPI, ACT, true>(a, u4, grid, st);
+  }
+  return dec_gemm16_launch<EPI, ACT, false>(a, u4, grid, st);
+}
+
 // partial tiles with 64-column workgroups: k-steps per workgroup U in {6, 8, 4}; returns the number of K chunks or 0
-int dec_part64_go(DecGemmArgs a, int K, hipStream_t st) {
-  a.wt = dec_wt();
+int dec_part64_go(const DecGemmArgs& a, int K, hipStream_t st) {
   int u = 0;
   for (int c : {6, 8, 4})
     if (K % (32 * c) == 0 && K / (32 * c) <= 24) { u = c; break; }
   if (!u || a.N % 64) return 0;
   const int chunks = K / (32 * u);
   const dim3 grid((unsigned)(a.N / 64), (unsigned)chunks), block(256);
-  const bool dbg_on = g_dbg.buf && g_dbg.slot < g_dbg_launches;
-#define P64(UU)                                                                                   \
-  do {                                                                                            \
-    if (dbg_on) hipLaunchKernelGGL((dec_gemm64p_kernel<UU, true>), grid, block, 0, st, a, g_dbg);  \
-    else hipLaunchKernelGGL((dec_gemm64p_kernel<UU, false>), grid, block, 0, st, a, g_dbg);        \
-  } while (0)
-  if (u == 6) P64(6); else if (u == 8) P64(8); else P64(4);
-#undef P64
-  if (dbg_on) ++g_dbg.slot;
+  if (u == 6) hipLaunchKernelGGL((dec_gemm64p_kernel<6>), grid, block, 0, st, a);
+  else if (u == 8) hipLaunchKernelGGL((dec_gemm64p_kernel<8>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((dec_gemm64p_kernel<4>), grid, block, 0, st, a);
   return chunks;
 }
 
-// ------------------------------------------------------------------------------------------
-// Single-sequence matrix-vector products (Gemma-style decode, B = 1: BASELINE configs[4]).  One wave per output
-// column, the row of the weight matrix in 16-byte pieces (1 KiB contiguous per wave instruction).  The general
-// gemv_bf16_kernel (vy_gemm.hip) serves up to 4 rows with run-time row guards, and its ISA shows what that costs:
-// the activation chunk of every k-piece is requested and waited for (vmcnt(0)) in the middle of the dot products,
-// one dependent round trip per piece.  Here the row count is 1 and the piece count a template constant: straight-
-// line code, the loads of batch b + 1 issued before the dot products of batch b, waits counted by the compiler.
-//   NORM: the weights carry the preceding RMSNorm's (1 + w) along K; the wave accumulates sum x^2 from the chunks
-//         it holds anyway and scales its result by rsqrt(mean x^2 + eps)              (no RMSNorm launch)
-//   GV_QKV: rotary embedding fused: the four waves of a workgroup take the columns {d, d+1, d+dh/2, d+1+dh/2} of one
-//         head and swap partners through LDS (rope2_kernel's arithmetic, vy_misc.hip)   (no RoPE launch)
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // Single-query attention against the KV cache (reference models/decoder.py:107 / layers/attention.py with L = 1 and
 // mask = None): one workgroup per (batch row, query head), every K and V chunk of the row's context requested
@@ -613,6 +508,18 @@ int dec_attn_go(const DecAttnArgs& a, int B, int Smax, hipStream_t st) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Single-sequence matrix-vector products (Gemma-style decode, B = 1: BASELINE configs[4]).  One wave per output
+// column, the row of the weight matrix in 16-byte pieces (1 KiB contiguous per wave instruction).  The general
+// gemv_bf16_kernel (vy_gemm.hip) serves up to 4 rows with run-time row guards, and its ISA shows what that costs:
+// the activation chunk of every k-piece is requested and waited for (vmcnt(0)) in the middle of the dot products,
+// one dependent round trip per piece.  Here the row count is 1 and the piece count a template constant: straight-
+// line code, the loads of batch b + 1 issued before the dot products of batch b, waits counted by the compiler.
+//   NORM: the weights carry the preceding RMSNorm's (1 + w) along K; the wave accumulates sum x^2 from the chunks
+//         it holds anyway and scales its result by rsqrt(mean x^2 + eps)              (no RMSNorm launch)
+//   GV_QKV: rotary embedding fused: the four waves of a workgroup take the columns {d, d+1, d+dh/2, d+1+dh/2} of one
+//         head and swap partners through LDS (rope2_kernel's arithmetic, vy_misc.hip)   (no RoPE launch)
+// ------------------------------------------------------------------------------------------
 enum { GV_PLAIN = 0, GV_GATED = 1, GV_QKV = 2 };
 struct DecGemvArgs {
   const bf16* x; const bf16* w; const bf16* bias; const bf16* residual; bf16* y;
@@ -790,68 +697,38 @@ int vy_dec_linear_ex(const void* x, int ldx, const void* w, const void* bias, co
   return VY_OK;
 }
 
-// y[B][N] = act(x W^T + b), K one chunk
-int vy_dec_linear(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int B, int N, int K, int act,
-                  hipStream_t st) {
-  DecGemmArgs a{};
-  a.X = (const bf16*)x; a.W = (const bf16*)w; a.bias = (const bf16*)bias;
-  a.ldx = ldx; a.ldw = K; a.M = B; a.N = N; a.y = (bf16*)y; a.ldy = ldy;
-  int rc;
-  if (dec_store_go(a, K, act, st, &rc)) VY_FAIL(VY_ERR_ARG, "vy_dec_linear: unknown activation %d", act);
-  if (rc) VY_FAIL(VY_ERR_UNSUPPORTED, "vy_dec_linear: K = %d", K);
-  VY_CHECK_LAUNCH("vy_dec_linear");
-  return VY_OK;
-}
-
 // y = LayerNorm(bf16(act(x W^T + b) + residual)): split-K partial tiles, then one workgroup per row
 int vy_dec_linear_res_ln(const void* x, int ldx, const void* w, const void* bias, const void* residual, int ldr,
                          const void* gamma, const void* beta, float eps, void* y, int ldy, float* part, int B, int N, int K,
                          int act, hipStream_t st) {
   const char* who = "vy_dec_linear_res_ln";
   if (!dec_act_known(act)) VY_FAIL(VY_ERR_ARG, "%s: unknown activation %d", who, act);
-  if (N % 16 || N % 4 || N > 8192) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: N = %d", who, N);
+  // the finish kernel holds one quad of columns per thread: N <= 1024 (the driver calls with N = d in {512, 768, 1024})
+  if (N % 16 || N > 1024) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: N = %d (needs a multiple of 16, at most 1024)", who, N);
   DecGemmArgs a{};
   a.X = (const bf16*)x; a.W = (const bf16*)w; a.ldx = ldx; a.ldw = K; a.M = B; a.N = N; a.part = part;
-  static const int p64_env = [] { const char* e = getenv("VY_DEC_P64"); return e ? atoi(e) : 1; }();
-  int chunks = p64_env ? dec_part64_go(a, K, st) : 0;
+  // 64-column partial tiles where K and N allow them, else the 16-column kernel with a split K (K = 9216)
+  int chunks = dec_part64_go(a, K, st);
   if (!chunks) {
     chunks = dec_chunks(K, true);
     if (!chunks) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: N = %d, K = %d", who, N, K);
     if (dec_gemm_go<DEC_PART, VY_ACT_NONE>(a, K, chunks, st)) VY_FAIL(VY_ERR_UNSUPPORTED, "%s: K = %d", who, K);
   }
   VY_CHECK_LAUNCH(who);
-  const int qpt = (int)vy_cdiv(N / 4, 256);
-  const bool dbg_on = g_dbg.buf && g_dbg.slot < g_dbg_launches;
-#define FIN(KS, Q, A)                                                                                                  \
-  do {                                                                                                                 \
-    if (dbg_on)                                                                                                        \
-      hipLaunchKernelGGL((dec_finish_ln_kernel<KS, Q, A, true>), dim3((unsigned)B), dim3(256), 0, st, part, chunks, N, \
-                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg, act); \
-    else                                                                                                               \
-      hipLaunchKernelGGL((dec_finish_ln_kernel<KS, Q, A, false>), dim3((unsigned)B), dim3(256), 0, st, part, chunks, N, \
-                         (const bf16*)bias, (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, dec_wt(), g_dbg, act); \
-  } while (0)
-#define FIN_Q(KS, A)                                                                                                   \
-  do { if (qpt <= 1) FIN(KS, 1, A); else if (qpt <= 2) FIN(KS, 2, A); else if (qpt <= 4) FIN(KS, 4, A); else FIN(KS, 8, A); } while (0)
-#define FIN_K(A)                                                                                                       \
-  do { if (chunks <= 1) FIN_Q(1, A); else if (chunks <= 4) FIN_Q(4, A); else if (chunks <= 8) FIN_Q(8, A); else if (chunks <= 16) FIN_Q(16, A); else FIN_Q(24, A); } while (0)
+  // KS = the partial tiles a thread requests at once: the smallest instantiation that holds `chunks` (<= 24)
+#define FIN(KS, A)                                                                                                  \
+  hipLaunchKernelGGL((dec_finish_ln_kernel<KS, A>), dim3((unsigned)B), dim3(256), 0, st, part, chunks, N, (const bf16*)bias, \
+                     (const bf16*)residual, ldr, (const bf16*)gamma, (const bf16*)beta, (bf16*)y, ldy, eps, act)
+#define FIN_K(A)                                                                                                    \
+  do { if (chunks <= 4) FIN(4, A); else if (chunks <= 8) FIN(8, A); else if (chunks <= 16) FIN(16, A); else FIN(24, A); } while (0)
   if (act == VY_ACT_GELU_ERF) FIN_K(VY_ACT_GELU_ERF);
   else if (act == VY_ACT_GELU_TANH) FIN_K(VY_ACT_GELU_TANH);
   else if (act == VY_ACT_NONE) FIN_K(VY_ACT_NONE);
   else FIN_K(VY_ACT_RUNTIME);   // checked on entry: one of the run-time codes
 #undef FIN_K
-#undef FIN_Q
 #undef FIN
-  if (dbg_on) ++g_dbg.slot;
   VY_CHECK_LAUNCH(who);
   return VY_OK;
-}
-
-// measurement aid, not part of include/vyom_hip.h: the next `launches` launches of the kernels in this file write
-// their stamps into buf[launches][max_wg][8] (device memory, 64-bit words); buf = NULL switches it off
-extern "C" int vy_debug_set_decode_stamps(void* buf, int launches, int max_wg) {
-  g_dbg.buf = (unsigned long long*)buf; g_dbg.slot = 0; g_dbg.max_wg = max_wg; g_dbg_launches = launches;
-  return 0;
 }
 
 // ---- single-sequence (B = 1) products of the Gemma-style decode step; return VY_ERR_UNSUPPORTED (without an error
@@ -896,9 +773,8 @@ int vy_dec_gemv1_qkv(const void* x, const void* w, const void* bias, void* q, vo
 int vy_dec_attn(const void* q, int64_t q_sb, const void* k, const void* v, int64_t c_sb, int64_t c_sh, int64_t c_sl, void* out,
                 int64_t o_sb, int B, int h, int hk, int64_t S, int64_t smax, const int* pos_dev, int dh, float scale,
                 hipStream_t st) {
-  static const int on = [] { const char* e = getenv("VY_DEC_ATTN"); return e ? atoi(e) : 1; }();
   g_attn_last[0] = g_attn_last[1] = g_attn_last[2] = g_attn_last[3] = 0;
-  if (!on || (dh != 64 && dh != 256) || hk < 1 || h % hk || S < 1 || c_sl % 8 || c_sh % 8 || c_sb % 8 || q_sb % 8 ||
+  if ((dh != 64 && dh != 256) || hk < 1 || h % hk || S < 1 || c_sl % 8 || c_sh % 8 || c_sb % 8 || q_sb % 8 ||
       ((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)v % 16))
     return VY_ERR_UNSUPPORTED;
   DecAttnArgs a{};
@@ -909,19 +785,17 @@ int vy_dec_attn(const void* q, int64_t q_sb, const void* k, const void* v, int64
   // d = 768 decoder, whose 170 MB of weights can stay in the Infinity Cache if the K/V stream does not push them out: nt is
   // ahead at every batch (B = 1 / 2 / 4 / 8 / 32: 349 / 360 / 380 / 368 / 485 us against 355 / 363 / 388 / 399 / 515); on
   // configs[4] (0.3 MB per layer, 5.8 GB of weights streaming through anyway) the default policy is 5 % ahead.
-  // VY_DEC_ATTN_NT = 0 / 1 forces it
-  static const int nt_env = [] { const char* e = getenv("VY_DEC_ATTN_NT"); return e ? atoi(e) : -1; }();
-  const int64_t layer_bytes = 2ll * B * hk * (pos_dev ? smax : S) * dh * 2;
-  const bool nt = nt_env < 0 ? layer_bytes > (1ll << 20) : nt_env != 0;
-  int rc;
-  // grouped-query heads of a 64-wide model: the query heads of one KV head in one workgroup (K/V read once, not h / hk times)
-  static const int gq_env = [] { const char* e = getenv("VY_DEC_ATTN_GQ"); return e ? atoi(e) : 1; }();
+  const bool nt = 2ll * B * hk * bound * dh * 2 > (1ll << 20);
+  // streamed grouped-query heads of a 64-wide model: the 2 / 3 / 4 query heads of one KV head in one workgroup (K/V read
+  // once, not h / hk times)
   const int rep = h / hk;
-  if (dh == 64 && gq_env && nt && rep == 2) rc = dec_attn_go<64, 8, true, 2>(a, B, bound, st);
-  else if (dh == 64 && gq_env && nt && rep == 3) rc = dec_attn_go<64, 8, true, 3>(a, B, bound, st);
-  else if (dh == 64 && gq_env && nt && rep == 4) rc = dec_attn_go<64, 8, true, 4>(a, B, bound, st);
-  else if (dh == 64) rc = nt ? dec_attn_go<64, 8, true>(a, B, bound, st) : dec_attn_go<64, 8, false>(a, B, bound, st);
-  else rc = nt ? dec_attn_go<256, 16, true>(a, B, bound, st) : dec_attn_go<256, 16, false>(a, B, bound, st);
+  int rc;
+  if (dh == 256) rc = nt ? dec_attn_go<256, 16, true>(a, B, bound, st) : dec_attn_go<256, 16, false>(a, B, bound, st);
+  else if (!nt) rc = dec_attn_go<64, 8, false>(a, B, bound, st);
+  else if (rep == 2) rc = dec_attn_go<64, 8, true, 2>(a, B, bound, st);
+  else if (rep == 3) rc = dec_attn_go<64, 8, true, 3>(a, B, bound, st);
+  else if (rep == 4) rc = dec_attn_go<64, 8, true, 4>(a, B, bound, st);
+  else rc = dec_attn_go<64, 8, true>(a, B, bound, st);
   if (rc) return VY_ERR_UNSUPPORTED;
   VY_CHECK_LAUNCH("vy_dec_attn");
   return VY_OK;

@@ -8,7 +8,6 @@
 // elements in registers and the workgroup adds them in a fixed order -- no atomics, so the result
 // does not depend on scheduling.  The row is re-read from L2 for every pass (V = 50265 bf16 = 100 KB).
 #include "vy_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -450,9 +449,9 @@ extern "C" int vy_greedy_step(const void* logits, int64_t ldl, int64_t B, int64_
     VY_FAIL(VY_ERR_ARG, "vy_greedy_step: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_greedy_step: bad dtype %d", dtype);
-  static const int two_stage = [] { const char* e = getenv("VY_GREEDY_TWO_STAGE"); return e ? atoi(e) : 1; }();
+  // wide rows: two stages (see greedy_part_kernel); small V or B > GP_MAXB: one workgroup per row
   const int64_t nch = (V + GP_CHUNK - 1) / GP_CHUNK;
-  if (two_stage && V >= 2 * GP_CHUNK && nch <= GP_MAXCH && B <= GP_MAXB) {
+  if (V >= 2 * GP_CHUNK && nch <= GP_MAXCH && B <= GP_MAXB) {
     const dim3 grid((unsigned)nch, (unsigned)B);
     if (dtype == VY_BF16)
       hipLaunchKernelGGL(greedy_part_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)logits, ldl, (int)V, (int)nch, text_mask,

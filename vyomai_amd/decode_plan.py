@@ -170,9 +170,13 @@ GEMMA_PRESCALED = 1
 class GemmaDecodePlan:
     """vy_gemma_plan of a models.paligemma.PaliGemmaForConditionalGeneration and its per-layer (k, v) cache
     buffers: `step(x, pos)` runs one token through all layers, the final norm and the tied vocabulary
-    projection in ONE C call (vy_gemma_decoder_step)."""
+    projection in ONE C call (vy_gemma_decoder_step).
 
-    def __init__(self, model, caches, batch: int):
+    prescale: fold the RMSNorm weights into the projections that follow them, so the step needs no RMSNorm launch.
+    None = wherever the step runs the fused matrix-vector chain (bf16, batch <= 4, widths multiples of 8); False = a plan
+    with the weights as they are (separate RMSNorm launches); True where that chain cannot run is an error."""
+
+    def __init__(self, model, caches, batch: int, prescale=None):
         from .models.paligemma import _packed
         lib = _lib.load()
         t = model.shape.text
@@ -190,12 +194,15 @@ class GemmaDecodePlan:
 
         layers = list(model.layers)
         arr = (VyGemmaLayer * len(layers))()
-        # single-sequence bf16 decode: RMSNorm folded into the weights (VY_GEMMA_PRESCALE=0: separate RMSNorm launches)
-        # -- only where the step will run the chain that skips them (the same predicate as vy_gemma_decoder_step's `fused`;
-        # the C side refuses a pre-scaled plan on any other chain)
+        # single-sequence bf16 decode: RMSNorm folded into the weights -- only where the step will run the chain that
+        # skips the RMSNorm launches (the same predicate as vy_gemma_decoder_step's `fused`; the C side refuses a
+        # pre-scaled plan on any other chain)
         widths_ok = t.hidden_size % 8 == 0 and t.intermediate_size % 8 == 0 and (t.num_attention_heads * t.head_dim) % 8 == 0
-        prescale = (dt == torch.bfloat16 and batch <= 4 and widths_ok and os.environ.get("VY_GEMMA_PRESCALE", "1") != "0"
-                    and os.environ.get("VY_GEMMA_FUSED", "1") != "0")
+        fused = dt == torch.bfloat16 and batch <= 4 and widths_ok
+        if prescale is None:
+            prescale = fused
+        elif prescale and not fused:
+            raise ValueError("prescale=True needs the fused matrix-vector chain: bf16, batch <= 4, widths multiples of 8")
         for i, layer in enumerate(layers):
             a, m = layer.self_attn, layer.mlp
             wqkv, bqkv = _packed([a.q_proj, a.k_proj, a.v_proj], layer, "_qkv")
