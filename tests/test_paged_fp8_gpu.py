@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+from tests.attn_range import GAINS, paged_decode_period, stair_levels
 from tests.golden import cases_causal_lm as C
 from tests.test_causal_lm_gpu import rel_err
 from tests.test_paged_gpu import DH128, SEQLENS, drain, model
@@ -141,7 +142,11 @@ def _fp8_decode_case(dh, h, hk, bs, regime, seed):
         table[b, :pages[b]] = torch.tensor(blocks, dtype=torch.int32)
         slot = torch.tensor([blocks[j // bs] * bs + j % bs for j in range(S)])
         for dst, dsc, keep in ((kc, ksc, ks), (vc, vsc, vs)):
-            x = (torch.randn(S, hk, dh, generator=g) * head_factors((S, hk), g)[..., None]).to(BF).float()
+            x = torch.randn(S, hk, dh, generator=g) * head_factors((S, hk), g)[..., None]
+            if regime == "staircase" and dst is kc:   # tests/attn_range.py; the level dominates the row's amax
+                x *= 0.5
+                x[..., 0] = stair_levels(S, paged_decode_period(dh, BF, fp8=True))[:, None]
+            x = x.to(BF).float()
             codes, s = quantise(x)
             dst.view(-1, hk, dh)[slot] = u8(codes)
             dsc.view(-1, hk)[slot] = s
@@ -151,6 +156,9 @@ def _fp8_decode_case(dh, h, hk, bs, regime, seed):
     for b, S in enumerate(SEQLENS):
         if regime == "flat":
             q = torch.randn(h, dh, generator=g)
+        elif regime == "staircase":
+            q = torch.randn(h, dh, generator=g)
+            q[:, 0] = math.sqrt(dh) * GAINS[(S - 1) % len(GAINS)]
         else:      # peaked: q = 6 k[j*], j* in the sequence's last page
             jstar = torch.randint((S - 1) // bs * bs, S, (h,), generator=g)
             q = 6.0 * ks[b][jstar, kvh].float()
@@ -178,7 +186,7 @@ def test_fp8_paged_decode_vs_fp64(dh, h, hk, bs):
     for the scales, far inside the S * 2^-24 accumulation term the bound carries.  Finite outputs (no row >= seqlen, no
     spare page, codes or scales, took part); rows outside q_rows keep their 3.25."""
     from vyomai_amd import ops
-    for regime in ("flat", "peaked"):
+    for regime in ("flat", "peaked", "staircase"):
         q, q_rows, kc, vc, ksc, vsc, table, seqlens, want, vmax = _fp8_decode_case(dh, h, hk, bs, regime, seed=dh + 7 * hk + bs)
         qd, rd, kd, vd, ksd, vsd, td, sd = (t.to(DEV) for t in (q, q_rows, kc, vc, ksc, vsc, table, seqlens))
         for n_split in (1, 2, 5, 0):
@@ -230,7 +238,7 @@ def test_fp8_paged_prefill_equals_bf16_kernel_on_dequantised_pages(dh, bs):
     from vyomai_amd import ops
     h, hk = 4, 2
     g = torch.Generator().manual_seed(dh + bs)
-    for regime in ("flat", "peaked"):
+    for regime in ("flat", "peaked", "staircase"):
         q, kc, vc, table, cu, ctx, _, _ = _prefill_case(dh, h, hk, bs, BF, regime)
         rows = q.shape[0] - EXTRA
         args = (table.to(DEV), cu.to(DEV), ctx.to(DEV), max(l for _, l in SEGS), max(c + l for c, l in SEGS), h)

@@ -6,6 +6,7 @@ import math
 import pytest
 import torch
 
+from tests.attn_range import GAINS, paged_decode_period, stair_levels
 from tests.golden import cases_causal_lm as C
 from tests.test_causal_lm_gpu import build, rel_err
 
@@ -133,7 +134,11 @@ def _decode_case(dh, h, hk, bs, dtype, regime, seed):
     for b, S in enumerate(SEQLENS):
         blocks = [order.pop() for _ in range(pages[b])]
         table[b, :pages[b]] = torch.tensor(blocks, dtype=torch.int32)
-        k = torch.randn(S, hk, dh, generator=g).to(dtype).float()
+        k = torch.randn(S, hk, dh, generator=g)
+        if regime == "staircase":   # tests/attn_range.py: a score ramp of one level per trip of the workgroup
+            k *= 0.5
+            k[..., 0] = stair_levels(S, paged_decode_period(dh, dtype))[:, None]
+        k = k.to(dtype).float()
         v = torch.randn(S, hk, dh, generator=g).to(dtype).float()
         slot = torch.tensor([blocks[j // bs] * bs + j % bs for j in range(S)])
         kc.view(-1, hk, dh)[slot] = k
@@ -145,6 +150,9 @@ def _decode_case(dh, h, hk, bs, dtype, regime, seed):
     for b, S in enumerate(SEQLENS):
         if regime == "flat":
             q = torch.randn(h, dh, generator=g)
+        elif regime == "staircase":   # the query row sits at position S - 1: its gain, 4 / 6 / 12 nat a level
+            q = torch.randn(h, dh, generator=g)
+            q[:, 0] = math.sqrt(dh) * GAINS[(S - 1) % len(GAINS)]
         else:      # peaked: q = 6 k[j*], j* in the sequence's last page (tests/test_decode_kernels_gpu.py's regime)
             jstar = torch.randint((S - 1) // bs * bs, S, (h,), generator=g)
             q = 6.0 * ks[b][jstar, kvh]
@@ -177,7 +185,7 @@ def test_paged_decode_vs_fp64(dh, h, hk, bs, dtype):
     each meet the bound (they are not compared with each other)."""
     from vyomai_amd import ops
     rel = 2.0 ** -8 if dtype == BF else 2.0 ** -20
-    for regime in ("flat", "peaked"):
+    for regime in ("flat", "peaked", "staircase"):
         q, q_rows, kc, vc, table, seqlens, want, vmax = _decode_case(dh, h, hk, bs, dtype, regime, seed=dh + 7 * hk + bs)
         qd, rd, kd, vd, td, sd = (t.to(DEV) for t in (q, q_rows, kc, vc, table, seqlens))
         for n_split in (1, 2, 5, 0):

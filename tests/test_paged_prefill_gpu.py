@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+from tests.attn_range import paged_decode_period, row_gains, stair_levels
 from tests.golden import cases_causal_lm as C
 from tests.test_causal_lm_gpu import rel_err
 from tests.test_paged_gpu import DH128, drain, engine, model
@@ -21,13 +22,15 @@ SEGS = [(0, 1), (0, 63), (0, 64), (0, 65), (0, 130), (5, 1), (16, 3), (61, 70), 
 EXTRA = 3
 
 
-@functools.lru_cache(maxsize=2)
+@functools.lru_cache(maxsize=3)
 def _prefill_case(dh, h, hk, bs, dtype, regime):
     """One batch of the eleven segments, in the manner of test_paged_gpu._decode_case: pages in shuffled physical order,
     NaN in the key rows >= ctx + len of every last page and in a spare page that every block-table entry past a
     sequence's pages points at; q rows inside a buffer shaped like the packed QKV rows, with 3 extra rows at the end.
     -> inputs (host) and the float64 result of every row."""
-    g = torch.Generator().manual_seed(dh + 7 * hk + bs + (1 if regime == "peaked" else 0))
+    g = torch.Generator().manual_seed(dh + 7 * hk + bs + {"flat": 0, "peaked": 1, "staircase": 2}[regime])
+    # keys per online-softmax step: the 64-key tile of the bf16 kernel, a trip of paged_dec_kernel on the fp32 path
+    period = 64 if dtype == BF else paged_decode_period(dh, dtype)
     n = len(SEGS)
     pages = [(c + l + bs - 1) // bs for c, l in SEGS]
     nblk = sum(pages) + 1
@@ -45,7 +48,11 @@ def _prefill_case(dh, h, hk, bs, dtype, regime):
         S = ctx + ln
         blocks = [order.pop() for _ in range(pages[s])]
         table[s, :pages[s]] = torch.tensor(blocks, dtype=torch.int32)
-        k = torch.randn(S, hk, dh, generator=g).to(dtype).float()
+        k = torch.randn(S, hk, dh, generator=g)
+        if regime == "staircase":   # tests/attn_range.py: one score level per step, gain by the row's position
+            k *= 0.5
+            k[..., 0] = stair_levels(S, period)[:, None]
+        k = k.to(dtype).float()
         v = torch.randn(S, hk, dh, generator=g).to(dtype).float()
         slot = torch.tensor([blocks[j // bs] * bs + j % bs for j in range(S)])
         kc.view(-1, hk, dh)[slot] = k
@@ -53,6 +60,9 @@ def _prefill_case(dh, h, hk, bs, dtype, regime):
         vmax = max(vmax, float(v.abs().max()))
         if regime == "flat":
             q = torch.randn(ln, h, dh, generator=g)
+        elif regime == "staircase":
+            q = torch.randn(ln, h, dh, generator=g)
+            q[..., 0] = math.sqrt(dh) * row_gains(ln, start_pos=ctx)[:, None]
         else:      # peaked: q = 6 k[j*], j* among the row's visible keys [0, ctx + i]
             hi = (ctx + torch.arange(ln) + 1).view(ln, 1).double()
             jstar = (torch.rand(ln, h, generator=g, dtype=torch.float64) * hi).long().clamp_max(hi.long() - 1)
@@ -84,7 +94,7 @@ def test_paged_prefill_vs_fp64(dh, h, hk, bs, dtype):
     The output is finite (no key row >= ctx + len and no poison page took part) and the extra rows keep their 3.25."""
     from vyomai_amd import ops
     rel, ab = (2.0 ** -8, 2.0 ** -8) if dtype == BF else (2.0 ** -20, 1e-4)
-    for regime in ("flat", "peaked"):
+    for regime in ("flat", "peaked", "staircase"):
         q, kc, vc, table, cu, ctx, want, vmax = _prefill_case(dh, h, hk, bs, dtype, regime)
         rows = want.shape[0]
         out = torch.full((q.shape[0], h * dh), 3.25, dtype=dtype, device=DEV)
