@@ -603,6 +603,37 @@ int vy_sampling_probs(const void* logits, int64_t ldl, int64_t B, int64_t V, int
 int vy_sample_rows(const void* logits, int64_t ldl, int64_t R, int64_t V, int dtype, const float* inv_temperature,
                    const int32_t* top_k, const float* top_p, const int64_t* seed, const int64_t* counter,
                    int64_t* tokens, void* stream);
+/* vy_spec_verify: the accept / reject / resample rule of speculative decoding (reference speculative_decoding.py:73-83
+ *   norm_fn, :195-230 the rejection loop and the adjusted draw; the processors logits_processors.py:13-16, 59-63, 73-81,
+ *   92-102 and their multinomial draw :48-49) for every drafted token of every sequence of one serving step, every
+ *   sequence with its own parameters, in ONE launch: grid (S, gamma + 1), one workgroup per (sequence s, row i).  No
+ *   probability tensor is written.
+ *   target_logits: (t_rows, V), leading dimension ldt; sequence s owns rows t_row0[s] .. t_row0[s] + n_draft[s].
+ *   draft_logits: row (i, s) starts at i * ldd_i + s * ldd_s elements; rows with i >= n_draft[s] are never read.
+ *   draft_tokens: (gamma, S) int64, contiguous.  Per sequence (device, length S): n_draft int32 in [0, gamma],
+ *   inv_temperature, top_k, top_p, seed as for vy_sample_rows, position0 = the position of the first drafted token.
+ *   accept: (S, gamma + 1) int32, alt: (S, gamma + 1) int64 -- the token to emit if the round ends at row i.
+ *   Row i < n_draft[s], x = draft_tokens[i][s], t / d the target / draft row:
+ *     greedy (inv_temperature[s] == 0): a = argmax t, lowest index among equal maxima; accept = (a == x); alt = a.
+ *     sampled: p(c) = [c in Kp] exp((t_c - max t) inv_t) / Zp and q(c) likewise from d, Kp / Kq the kept sets of
+ *       vy_sampling_probs for top_k[s] / top_p[s], Zp summed as vy_sampling_probs sums it.  u = the top 24 bits of
+ *       word 0 of quad 0 of noise row 1 for (seed[s], offset = position0[s] + i), times 2^-24.  Rejected iff x lies
+ *       outside Kp or u q(x) > p(x) (the reference's r > p / q without the division).  A rejected row's alt = argmax
+ *       over the columns with p(c) > q(c) of log(p(c) - q(c)) + noise(row 2, column c, same seed and offset), lowest
+ *       index among equal scores: a Gumbel-max draw from norm_fn(p - q); if no column has p > q (rounding only), the
+ *       draw is from p with the same noise.  An accepted row writes alt = -1.
+ *   Row i == n_draft[s]: accept = 0 and alt = exactly vy_sample_rows' token for that target row with
+ *     counter = position0[s] + n_draft[s] (the same code, noise row 0), so n_draft[s] == 0 is the plain step's draw.
+ *   Rows i > n_draft[s], and every row of a sequence with n_draft outside [0, gamma] or rows outside [0, t_rows):
+ *     accept = 0, alt = -1, nothing is read.
+ *   Noise rows 1 and 2 are Philox counters disjoint from row 0, which drew the draft at that position.
+ *   VY_ERR_ARG: a null pointer, S <= 0, gamma < 1, gamma > 16, t_rows <= 0, V <= 0, V > 0x7ffffff0, ldt < V,
+ *   ldd_s < V, ldd_i < 0, an unknown dtype. */
+int vy_spec_verify(const void* target_logits, int64_t ldt, int64_t t_rows, const void* draft_logits, int64_t ldd_i,
+                   int64_t ldd_s, int64_t S, int64_t gamma, int64_t V, int dtype, const int64_t* draft_tokens,
+                   const int32_t* t_row0, const int32_t* n_draft, const float* inv_temperature, const int32_t* top_k,
+                   const float* top_p, const int64_t* seed, const int64_t* position0, int32_t* accept, int64_t* alt,
+                   void* stream);
 
 /* y = x converted between fp32 and bf16 (n elements). src_dtype -> dst_dtype. */
 int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);

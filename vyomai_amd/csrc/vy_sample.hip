@@ -3,6 +3,8 @@
 //   vy_sampling_probs  reference logits_processors.py:13-16, 59-63, 73-81, 92-102
 //   vy_sample_rows     the same processors (:13-16, 59-63, 73-81, 92-102) and their multinomial draw, per row of a
 //                      serving step: Examples/simple_vllm.ipynb decodes greedily, this is its step with sampling
+//   vy_spec_verify     reference speculative_decoding.py:73-83, 195-230 (accept / reject / resample of a round's drafts)
+//                      with the same processors, for every drafted token of a serving step in one launch
 // One 1024-thread workgroup per row.  Selection (k-th largest value, nucleus cut) is a radix search over
 // 4-bit digits of an order-preserving key: every thread keeps the 16 bin counts / masses of its own
 // elements in registers and the workgroup adds them in a fixed order -- no atomics, so the result
@@ -350,7 +352,7 @@ template <> struct Quad<bf16> { typedef bf16x4 Raw; };
 
 template <typename T, bool SAMPLE>
 __device__ __forceinline__ void scan_row(const T* __restrict__ row, int V, float inv_t, unsigned keep_key, const VyNoise& nz,
-                                         float& best_v, int& best_i) {
+                                         int64_t nrow, float& best_v, int& best_i) {
   typedef typename Quad<T>::Raw Raw;
   constexpr int U = 4;   // quads in flight per thread: all loads of a trip are issued before the first compare
   const int tid = threadIdx.x, nq = (V + 3) >> 2;
@@ -380,7 +382,7 @@ __device__ __forceinline__ void scan_row(const T* __restrict__ row, int V, float
         for (int e = 0; e < 4; ++e) { kept[e] = q * 4 + e < V && fkey(v[u][e]) >= keep_key; any |= kept[e]; }
         if (any) {
           uint32_t r[4];
-          vy_noise_words(nz, 0, q, r);
+          vy_noise_words(nz, nrow, q, r);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (kept[e]) gp_take(fmaf(v[u][e], inv_t, vy_gumbel(r[e])), q * 4 + e, best_v, best_i);
@@ -394,21 +396,41 @@ __device__ __forceinline__ void scan_row(const T* __restrict__ row, int V, float
   }
 }
 
+// the workgroup's best (value, index): highest value, lowest index among equal ones -> the index (0x7fffffff: nothing
+// comparable in the row).  ALL: every thread gets it and fred / ired are free again on return; else thread 0 alone.
+template <bool ALL>
+__device__ __forceinline__ int block_best(float best_v, int best_i, float* fred, int* ired) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best_v, o, 64);
+    const int oi = __shfl_xor(best_i, o, 64);
+    gp_merge(ov, oi, best_v, best_i);
+  }
+  if (lane == 0) { fred[wave] = best_v; ired[wave] = best_i; }
+  __syncthreads();
+  if (ALL || threadIdx.x == 0) {
+    if (ALL) { best_v = fred[0]; best_i = ired[0]; }
+    for (int w = 1; w < SW; ++w) gp_merge(fred[w], ired[w], best_v, best_i);
+  }
+  if (ALL) __syncthreads();
+  return best_i;
+}
+
+// One row's draw with the parameters of entry r (vy_sample_rows' rule; vy_spec_verify's row after the last draft is
+// this very code, so the two give the same token bit for bit).  The noise offset is counter[r] + counter_add.  Thread 0
+// holds the token.
 template <typename T>
-__global__ __launch_bounds__(ST) void sample_rows_kernel(const T* __restrict__ logits, int64_t ldl, int V,
-                                                         const float* __restrict__ inv_temperature,
-                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
-                                                         const int64_t* __restrict__ seed, const int64_t* __restrict__ counter,
-                                                         int64_t* __restrict__ tokens) {
-  __shared__ float fred[SW * 16];
-  __shared__ int ired[SW * 16];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const T* row = logits + (int64_t)r * ldl;
+__device__ __forceinline__ int draw_row(const T* __restrict__ row, int V, int r, const float* __restrict__ inv_temperature,
+                                        const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                        const int64_t* __restrict__ seed, const int64_t* __restrict__ counter,
+                                        int64_t counter_add, float* fred, int* ired) {
+  const int tid = threadIdx.x;
   const float inv_t = inv_temperature[r];
   int best_i = 0x7fffffff;
   float best_v = -INFINITY;
   if (inv_t == 0.f) {
-    scan_row<T, false>(row, V, 0.f, 0u, VyNoise{}, best_v, best_i);
+    scan_row<T, false>(row, V, 0.f, 0u, VyNoise{}, 0, best_v, best_i);
   } else {
     const int k = top_k[r];
     const float p = top_p[r];
@@ -422,20 +444,139 @@ __global__ __launch_bounds__(ST) void sample_rows_kernel(const T* __restrict__ l
       }
       keep_key = select_keep_key(row, V, k, p, m, fred, ired);
     }
-    scan_row<T, true>(row, V, inv_t, keep_key, vy_make_noise((uint64_t)seed[r], (uint64_t)counter[r]), best_v, best_i);
+    scan_row<T, true>(row, V, inv_t, keep_key, vy_make_noise((uint64_t)seed[r], (uint64_t)(counter[r] + counter_add)), 0,
+                      best_v, best_i);
   }
+  const int best = block_best<false>(best_v, best_i, fred, ired);
+  return best == 0x7fffffff ? 0 : best;   // nothing comparable in the row (NaNs): token 0, as vy_greedy_step
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST) void sample_rows_kernel(const T* __restrict__ logits, int64_t ldl, int V,
+                                                         const float* __restrict__ inv_temperature,
+                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                         const int64_t* __restrict__ seed, const int64_t* __restrict__ counter,
+                                                         int64_t* __restrict__ tokens) {
+  __shared__ float fred[SW * 16];
+  __shared__ int ired[SW * 16];
+  const int r = blockIdx.x;
+  const int tok = draw_row(logits + (int64_t)r * ldl, V, r, inv_temperature, top_k, top_p, seed, counter, 0, fred, ired);
+  if (threadIdx.x == 0) tokens[r] = tok;
+}
+
+// ---- speculative decoding: accept / reject / resample for every drafted token of a step ---------------
+// Workgroup (s, i) judges row i of sequence s: target row t = target[t_row0[s] + i], draft row d = draft[i][s], draft token
+// x = draft_tokens[i][s].  The rows of a sequence are independent (the first rejection is a scan the host does).
+//   i <  n_draft[s], greedy:  a = argmax t;  accept iff a == x;  alt = a.
+//   i <  n_draft[s], sampled: p / q = the softmax of t / d at the request's temperature over the set its top_k / top_p keep
+//                             (the values vy_sampling_probs would write, never stored);  reject iff x is outside p's set or
+//                             u q(x) > p(x), u from noise row 1;  alt = Gumbel-max draw from max(p - q, 0) with noise row 2
+//                             (from p if no column has p > q);  an accepted row writes alt = -1.
+//   i == n_draft[s]:          alt = draw_row on t with counter position0[s] + n_draft[s] -- vy_sample_rows' token.
+//   i >  n_draft[s], or a sequence whose rows would leave the target buffer: accept 0, alt -1, nothing read.
+// Every branch is on values all threads hold alike (block_sum / block_max / block_best<true> hand every thread the same
+// result).
+template <typename T>
+__device__ __forceinline__ float kept_prob(const T* __restrict__ row, int c, float m, float inv_t, unsigned key, float rz) {
+  const float v = ldf(row, c);
+  return fkey(v) >= key ? expf((v - m) * inv_t) * rz : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST) void spec_verify_kernel(const T* __restrict__ target, int64_t ldt, int64_t t_rows,
+                                                         const T* __restrict__ draft, int64_t ldd_i, int64_t ldd_s, int S,
+                                                         int gamma, int V, const int64_t* __restrict__ draft_tokens,
+                                                         const int32_t* __restrict__ t_row0, const int32_t* __restrict__ n_draft,
+                                                         const float* __restrict__ inv_temperature,
+                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                         const int64_t* __restrict__ seed, const int64_t* __restrict__ position0,
+                                                         int32_t* __restrict__ accept, int64_t* __restrict__ alt) {
+  __shared__ float fred[SW * 16];
+  __shared__ int ired[SW * 16];
+  const int s = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+  const int n = n_draft[s];
+  const int64_t r0 = t_row0[s];
+  const int64_t out = (int64_t)s * (gamma + 1) + i;
+  if (n < 0 || n > gamma || i > n || r0 < 0 || r0 + n >= t_rows) {
+    if (tid == 0) { accept[out] = 0; alt[out] = -1; }
+    return;
+  }
+  const T* trow = target + (r0 + i) * ldt;
+  if (i == n) {
+    const int tok = draw_row(trow, V, s, inv_temperature, top_k, top_p, seed, position0, n, fred, ired);
+    if (tid == 0) { accept[out] = 0; alt[out] = tok; }
+    return;
+  }
+  const int64_t x = draft_tokens[(int64_t)i * S + s];
+  const float inv_t = inv_temperature[s];
+  int best_i = 0x7fffffff;
+  float best_v = -INFINITY;
+  if (inv_t == 0.f) {
+    scan_row<T, false>(trow, V, 0.f, 0u, VyNoise{}, 0, best_v, best_i);
+    const int best = block_best<false>(best_v, best_i, fred, ired);
+    const int a = best == 0x7fffffff ? 0 : best;
+    if (tid == 0) { accept[out] = a == x; alt[out] = a; }
+    return;
+  }
+  const T* drow = draft + i * ldd_i + s * ldd_s;
+  const int k = top_k[s];
+  const float tp = top_p[s];
+  float mt = 0.f, md = 0.f, rzt = 0.f, rzd = 0.f;
+  unsigned keyt = 0, keyd = 0;
+#pragma unroll 1   // (one copy of the selection code serves both rows)
+  for (int w = 0; w < 2; ++w) {
+    const T* row = w ? drow : trow;
+    float m = -INFINITY;
+    for (int c = tid; c < V; c += ST) m = fmaxf(m, ldf(row, c));
+    m = block_max(m, fred);
+    const unsigned key = select_keep_key(row, V, k, tp, m, fred, ired);
+    float z[1] = {0.f};
+    for (int c = tid; c < V; c += ST) {
+      const float v = ldf(row, c);
+      if (fkey(v) >= key) z[0] += expf((v - m) * inv_t);
+    }
+    block_sum<1, float>(z, fred);
+    if (w) { md = m; keyd = key; rzd = 1.0f / z[0]; }
+    else { mt = m; keyt = key; rzt = 1.0f / z[0]; }
+  }
+  const bool in_range = x >= 0 && x < V;
+  const bool in_kp = in_range && fkey(ldf(trow, in_range ? (int)x : 0)) >= keyt;
+  const float px = in_range ? kept_prob(trow, (int)x, mt, inv_t, keyt, rzt) : 0.f;
+  const float qx = in_range ? kept_prob(drow, (int)x, md, inv_t, keyd, rzd) : 0.f;
+  const VyNoise nz = vy_make_noise((uint64_t)seed[s], (uint64_t)(position0[s] + i));
+  uint32_t uw[4];
+  vy_noise_words(nz, 1, 0, uw);
+  const float u = (float)(uw[0] >> 8) * 5.9604644775390625e-8f;
+  if (in_kp && !(u * qx > px)) {
+    if (tid == 0) { accept[out] = 1; alt[out] = -1; }
+    return;
+  }
+  // rejected: Gumbel-max over the columns with p > q of log(p - q) + noise row 2
+  const int nq = (V + 3) >> 2;
+  for (int q = tid; q < nq; q += ST) {
+    float diff[4];
+    bool any = false;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best_v, o, 64);
-    const int oi = __shfl_xor(best_i, o, 64);
-    gp_merge(ov, oi, best_v, best_i);
+    for (int e = 0; e < 4; ++e) {
+      const int c = q * 4 + e;
+      diff[e] = c < V ? kept_prob(trow, c, mt, inv_t, keyt, rzt) - kept_prob(drow, c, md, inv_t, keyd, rzd) : 0.f;
+      any |= diff[e] > 0.f;
+    }
+    if (any) {
+      uint32_t r[4];
+      vy_noise_words(nz, 2, q, r);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (diff[e] > 0.f) gp_take(logf(diff[e]) + vy_gumbel(r[e]), q * 4 + e, best_v, best_i);
+    }
   }
-  if (lane == 0) { fred[wave] = best_v; ired[wave] = best_i; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < SW; ++w) gp_merge(fred[w], ired[w], best_v, best_i);
-    tokens[r] = best_i == 0x7fffffff ? 0 : best_i;   // nothing comparable in the row (NaNs): token 0, as vy_greedy_step
+  int best = block_best<true>(best_v, best_i, fred, ired);
+  if (best == 0x7fffffff) {   // p <= q everywhere (rounding only: both sum to one): draw from p
+    best_v = -INFINITY;
+    scan_row<T, true>(trow, V, inv_t, keyt, nz, 2, best_v, best_i);
+    best = block_best<false>(best_v, best_i, fred, ired);
   }
+  if (tid == 0) { accept[out] = 0; alt[out] = best == 0x7fffffff ? 0 : best; }
 }
 
 }  // namespace
@@ -509,5 +650,34 @@ extern "C" int vy_sample_rows(const void* logits, int64_t ldl, int64_t R, int64_
     hipLaunchKernelGGL(sample_rows_kernel<float>, dim3((unsigned)R), dim3(ST), 0, st, (const float*)logits, ldl, (int)V,
                        inv_temperature, top_k, top_p, seed, counter, tokens);
   VY_CHECK_LAUNCH("vy_sample_rows");
+  return VY_OK;
+}
+
+extern "C" int vy_spec_verify(const void* target_logits, int64_t ldt, int64_t t_rows, const void* draft_logits, int64_t ldd_i,
+                              int64_t ldd_s, int64_t S, int64_t gamma, int64_t V, int dtype, const int64_t* draft_tokens,
+                              const int32_t* t_row0, const int32_t* n_draft, const float* inv_temperature,
+                              const int32_t* top_k, const float* top_p, const int64_t* seed, const int64_t* position0,
+                              int32_t* accept, int64_t* alt, void* stream) {
+  if (!target_logits || !draft_logits || !draft_tokens || !t_row0 || !n_draft || !inv_temperature || !top_k || !top_p ||
+      !seed || !position0 || !accept || !alt)
+    VY_FAIL(VY_ERR_ARG, "vy_spec_verify: null operand");
+  if (S <= 0 || S > INT32_MAX || gamma < 1 || gamma > 16 || t_rows <= 0 || t_rows > INT32_MAX)
+    VY_FAIL(VY_ERR_ARG, "vy_spec_verify: bad shape (S %lld, gamma %lld, target rows %lld)", (long long)S, (long long)gamma,
+            (long long)t_rows);
+  if (V <= 0 || V > 0x7ffffff0 || ldt < V || ldd_s < V || ldd_i < 0)
+    VY_FAIL(VY_ERR_ARG, "vy_spec_verify: bad shape (V %lld, ldt %lld, ldd %lld / %lld)", (long long)V, (long long)ldt,
+            (long long)ldd_i, (long long)ldd_s);
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_spec_verify: bad dtype %d", dtype);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, (unsigned)gamma + 1);
+  if (dtype == VY_BF16)
+    hipLaunchKernelGGL(spec_verify_kernel<bf16>, grid, dim3(ST), 0, st, (const bf16*)target_logits, ldt, t_rows,
+                       (const bf16*)draft_logits, ldd_i, ldd_s, (int)S, (int)gamma, (int)V, draft_tokens, t_row0, n_draft,
+                       inv_temperature, top_k, top_p, seed, position0, accept, alt);
+  else
+    hipLaunchKernelGGL(spec_verify_kernel<float>, grid, dim3(ST), 0, st, (const float*)target_logits, ldt, t_rows,
+                       (const float*)draft_logits, ldd_i, ldd_s, (int)S, (int)gamma, (int)V, draft_tokens, t_row0, n_draft,
+                       inv_temperature, top_k, top_p, seed, position0, accept, alt);
+  VY_CHECK_LAUNCH("vy_spec_verify");
   return VY_OK;
 }

@@ -790,6 +790,53 @@ def sample_rows(logits2d: Tensor, inv_temperature: Tensor, top_k: Tensor, top_p:
     return tokens
 
 
+def spec_verify(target_logits: Tensor, draft_logits: Tensor, draft_tokens: Tensor, t_row0: Tensor, n_draft: Tensor,
+                inv_temperature: Tensor, top_k: Tensor, top_p: Tensor, seed: Tensor, position0: Tensor):
+    """The accept / reject / resample rule of speculative decoding for every drafted token of a step, in one launch
+    (vy_spec_verify; the rule: include/vyom_hip.h) -> (accept int32 (S, gamma + 1), alt int64 (S, gamma + 1)).
+    target_logits (rows, V): sequence s owns rows t_row0[s] .. t_row0[s] + n_draft[s].  draft_logits (gamma, S, V) of
+    the same dtype, unit column stride; draft_tokens (gamma, S) int64, contiguous.  t_row0 / n_draft / top_k int32,
+    inv_temperature / top_p fp32, seed / position0 int64, each (S,) on the logits' device.  n_draft[s] in [0, gamma]
+    and inv_temperature >= 0 are the caller's duty (the values are on the device); a sequence whose rows would leave
+    target_logits is not read and gets accept 0, alt -1."""
+    if target_logits.dim() != 2 or target_logits.shape[0] < 1 or target_logits.shape[1] < 1 or target_logits.stride(1) != 1:
+        raise ValueError(f"spec_verify: target logits must be (rows, V) with unit column stride, got "
+                         f"{tuple(target_logits.shape)} strides {target_logits.stride()}")
+    if target_logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"spec_verify: logits must be float32 or bfloat16, got {target_logits.dtype}")
+    Rt, V = target_logits.shape
+    if target_logits.stride(0) < V:
+        raise ValueError(f"spec_verify: target row stride {target_logits.stride(0)} is below V = {V}")
+    if not isinstance(draft_logits, Tensor) or draft_logits.dim() != 3 or draft_logits.shape[2] != V or \
+            not 1 <= draft_logits.shape[0] <= 16 or draft_logits.shape[1] < 1 or draft_logits.stride(2) != 1 or \
+            draft_logits.stride(1) < V or draft_logits.stride(0) < 0:
+        raise ValueError(f"spec_verify: draft logits must be (gamma, S, {V}) with 1 <= gamma <= 16, unit column stride and "
+                         f"a row stride of at least V, got {tuple(getattr(draft_logits, 'shape', ()))}")
+    if draft_logits.dtype != target_logits.dtype:
+        raise ValueError(f"spec_verify: draft logits are {draft_logits.dtype}, target logits {target_logits.dtype}")
+    gamma, S = draft_logits.shape[:2]
+    if not isinstance(draft_tokens, Tensor) or draft_tokens.dtype != torch.long or tuple(draft_tokens.shape) != (gamma, S) \
+            or not draft_tokens.is_contiguous():
+        raise ValueError(f"spec_verify: draft_tokens must be a contiguous int64 tensor of shape ({gamma}, {S})")
+    per_seq = (("t_row0", t_row0, torch.int32), ("n_draft", n_draft, torch.int32),
+               ("inv_temperature", inv_temperature, torch.float32), ("top_k", top_k, torch.int32),
+               ("top_p", top_p, torch.float32), ("seed", seed, torch.long), ("position0", position0, torch.long))
+    for name, t, dt in per_seq:
+        if not isinstance(t, Tensor) or t.dtype != dt or t.dim() != 1 or t.numel() != S or t.stride(0) != 1:
+            raise ValueError(f"spec_verify: {name} must be a contiguous {dt} tensor of {S} elements")
+    for name, t in (("draft_logits", draft_logits), ("draft_tokens", draft_tokens)) + tuple(x[:2] for x in per_seq):
+        if t.device != target_logits.device:
+            raise ValueError(f"spec_verify: {name} is on {t.device}, the target logits on {target_logits.device}")
+    _need_gpu(target_logits)
+    accept = torch.empty((S, gamma + 1), dtype=torch.int32, device=target_logits.device)
+    alt = torch.empty((S, gamma + 1), dtype=torch.long, device=target_logits.device)
+    call("vy_spec_verify", target_logits.data_ptr(), target_logits.stride(0), Rt, draft_logits.data_ptr(),
+         draft_logits.stride(0), draft_logits.stride(1), S, gamma, V, dtype_code(target_logits.dtype),
+         draft_tokens.data_ptr(), t_row0.data_ptr(), n_draft.data_ptr(), inv_temperature.data_ptr(), top_k.data_ptr(),
+         top_p.data_ptr(), seed.data_ptr(), position0.data_ptr(), accept.data_ptr(), alt.data_ptr(), _stream())
+    return accept, alt
+
+
 def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[int]) -> None:
     """dw[ids[m], :] += dout[m, :] in fp32, skipping padding_idx  (vy_embedding_bwd)."""
     _need_gpu(dout, ids, dw)

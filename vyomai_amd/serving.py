@@ -56,7 +56,37 @@ set TopKProcessor / NucleusProcessor keep.  The noise of a row is keyed by (the 
 token being drawn, column) and by nothing else, so what a request generates from given logits does not depend on the
 batch around it, on its row, on prefix-cache hits or on how its prompt was chunked.  The parameters ride in the step's
 two uploads (top_k and the bit patterns of inv_temperature / top_p in the int32 one, seed and position in the int64
-one): a sampled step makes no additional copy in either direction."""
+one): a sampled step makes no additional copy in either direction.
+
+Speculative decoding (ContinuousBatchEngine(..., draft_model=, draft_kv_mgr=, num_speculative_tokens=g); off by default,
+and then the engine's schedule, metadata, uploads and launches are the ones above).  A step lets the drafter propose up
+to g tokens for every decoding sequence and the target judge them all in ONE forward: the reference's
+speculative_generate (speculative_decoding.py:86-245) for every sequence of the batch at once, with each request's own
+SamplingParams, on the pages.  One step:
+
+1. schedule, allocate, upload -- once: positions and slots of all g draft rounds and of the verification are known on
+   the host in advance and ride in the step's two uploads; draft token ids stay on the device from round to round.
+   The decoding sequences come first, those with the most drafts in front (g_s = min(g, max_total_len - num_tokens -
+   1), the reference's corrected_gamma), so the sequences of round j are always the first n_j.  Under max_step_tokens a
+   decoding sequence takes 1 + g_s rows of the budget.
+2. draft round 0: one draft_model.forward_paged over the step's prompt chunks (the target's segments, no logits rows)
+   and, per decoding sequence, a varlen segment of the tokens the drafter has not computed yet (1, or 2 after a round
+   whose drafts were all accepted: draft_computed[sid] counts what its pages hold); one vy_sample_rows, counter =
+   position.
+3. draft rounds 1 .. g - 1: plain decode rows, one vy_sample_rows each; a sequence with g_s <= j sits round j out.
+4. verify: one target forward_paged over the prompt chunks and, per decoding sequence, the varlen segment [last token,
+   d_0 .. d_{g_s - 1}] with ctx_len = num_tokens - 1, all of its rows in last_rows; then ONE vy_spec_verify launch
+   (accept / reject / resample, include/vyom_hip.h) in which prompts that finish prefilling ride along with n_draft = 0
+   -- their row is vy_sample_rows' draw, so a step without drafts emits what the plain engine emits.
+5. ONE device-to-host copy carries accept, alt and the draft tokens; the host finds the first rejection, appends the
+   accepted drafts and alt, cuts at the first stop token among them (reference :210-214), and retires what finished.
+
+Only the pages (and scales) of draft_kv_mgr are used, indexed by the target manager's block tables and slots; its own
+free list and tree stay idle.  Invariant: both models write the same slots in the same step, so a block the prefix
+cache hands out holds valid rows of both models, and eviction and reuse overwrite both.  Speculative rows land only at
+positions >= prompt_len, in blocks that are never registered: a rejected draft never touches a shared block, its slot is
+simply overwritten later, and g_s keeps every write inside the blocks admission reserved.  The reference's
+skip_sample_adjustment is not carried over."""
 from __future__ import annotations
 
 import itertools
@@ -338,12 +368,18 @@ class ContinuousBatchEngine:
     max_step_tokens / varlen_prefill: chunked prefill and the one varlen prefill launch (module docstring); with both at
     None the engine prefills a prompt in one step, one attention launch per prefilling sequence.
 
+    draft_model / draft_kv_mgr / num_speculative_tokens: speculative decoding (module docstring).  drafts_proposed /
+    drafts_accepted count over the engine's life.
+
     prompt_tokens_computed[sid]: prompt tokens that went through the model so far (the rest came from the prefix cache).
-    record_logits=True keeps every step's last-row logits per sequence in `logits[sid]` (fp32, host): a debug aid."""
+    record_logits=True keeps every step's last-row logits per sequence in `logits[sid]` (fp32, host): a debug aid.  In a
+    speculative engine that is one row per emitted token, the target row that decided it, and `rounds[sid]` holds per
+    round {position0, draft_tokens, draft_rows, target_rows, accepted, emitted}."""
 
     def __init__(self, model, kv_mgr: PagedKVManager, max_batch_size: int = 8, eos_token_ids=None,
                  record_logits: bool = False, max_step_tokens: Optional[int] = None,
-                 varlen_prefill: Optional[bool] = None):
+                 varlen_prefill: Optional[bool] = None, draft_model=None, draft_kv_mgr: Optional[PagedKVManager] = None,
+                 num_speculative_tokens: int = 0):
         if varlen_prefill is None:
             varlen_prefill = max_step_tokens is not None
         if max_step_tokens is not None:
@@ -361,6 +397,15 @@ class ContinuousBatchEngine:
             if computes != torch.bfloat16 or kv_mgr.dtype != torch.bfloat16:
                 raise ValueError(f"fp8 KV pages serve a model that computes in bfloat16: the model computes in "
                                  f"{computes}, the manager was built for {kv_mgr.dtype}")
+        self.speculative = draft_model is not None or draft_kv_mgr is not None or num_speculative_tokens != 0
+        if self.speculative:
+            self._check_drafter(model, kv_mgr, draft_model, draft_kv_mgr, num_speculative_tokens, max_batch_size)
+            if draft_model is not None:
+                draft_model.eval()
+        self.draft_model, self.draft_kv_mgr, self.num_speculative_tokens = draft_model, draft_kv_mgr, num_speculative_tokens
+        self.draft_computed: Dict[int, int] = {}     # tokens of a decoding sequence the drafter's pages hold
+        self.drafts_proposed = self.drafts_accepted = 0
+        self.rounds: Dict[int, List[dict]] = {}
         self.model, self.kv_mgr = model, kv_mgr
         if model is not None:
             model.eval()
@@ -377,6 +422,36 @@ class ContinuousBatchEngine:
         self.record_logits = record_logits
         self.logits: Dict[int, List[torch.Tensor]] = {}
         self.sampling: Dict[int, SamplingParams] = {}
+
+    def _check_drafter(self, model, kv_mgr, draft_model, draft_kv_mgr, g, max_batch_size) -> None:
+        if not self.varlen_prefill:
+            raise ValueError("speculative decoding needs varlen_prefill=True: a verification segment of g + 1 rows "
+                             "attends to its sequence's pages through vy_attn_paged_prefill")
+        if draft_kv_mgr is None or (model is None) != (draft_model is None):
+            raise ValueError("speculative decoding needs draft_model and draft_kv_mgr, the drafter's own pages")
+        if int(g) != g or not 1 <= g <= 16:
+            raise ValueError(f"num_speculative_tokens {g} must be an integer from 1 to 16")
+        tv, dv = getattr(kv_mgr.config, "vocab_size", None), getattr(draft_kv_mgr.config, "vocab_size", None)
+        if tv != dv:
+            raise ValueError(f"drafter and target need one vocabulary: the drafter has {dv} entries, the target {tv}")
+        if (draft_kv_mgr.max_blocks, draft_kv_mgr.block_size) != (kv_mgr.max_blocks, kv_mgr.block_size):
+            raise ValueError(f"draft_kv_mgr holds {draft_kv_mgr.max_blocks} blocks of {draft_kv_mgr.block_size}, the target's "
+                             f"manager {kv_mgr.max_blocks} of {kv_mgr.block_size}: the drafter's pages are indexed by the "
+                             "target's block tables")
+        if draft_kv_mgr.device != kv_mgr.device:
+            raise ValueError(f"draft_kv_mgr is on {draft_kv_mgr.device}, the target's manager on {kv_mgr.device}")
+        computes = kv_mgr.dtype if draft_model is None else _compute_dtype(draft_model)
+        if draft_kv_mgr.dtype != computes:
+            raise ValueError(f"draft_kv_mgr was built for {draft_kv_mgr.dtype}, the drafter computes in {computes}")
+        if model is not None and _compute_dtype(model) != computes:
+            raise ValueError(f"the drafter computes in {computes}, the target in {_compute_dtype(model)}: vy_spec_verify "
+                             "compares logits of one dtype")
+        if getattr(draft_kv_mgr, "k_scale", None) is not None and computes != torch.bfloat16:
+            raise ValueError(f"fp8 KV pages serve a drafter that computes in bfloat16, not {computes}")
+        if self.max_step_tokens is not None and self.max_step_tokens < max_batch_size * (g + 1):
+            raise ValueError(f"max_step_tokens {self.max_step_tokens} must be at least max_batch_size * "
+                             f"(num_speculative_tokens + 1) = {max_batch_size * (g + 1)}: a decoding sequence takes "
+                             "1 + g rows of the budget and a prefilling one must still progress")
 
     def add_sequence(self, prompt_ids: Sequence[int], max_gen_len: int = 128,
                      sampling: Optional[SamplingParams] = None) -> int:
@@ -541,6 +616,8 @@ class ContinuousBatchEngine:
         return (states, *self._prepare_inference_data(states))
 
     def step(self) -> Dict[int, List[int]]:
+        if self.speculative:
+            return self._spec_step()
         plan = self._plan_step()
         if plan is None:
             return {}
@@ -575,6 +652,219 @@ class ContinuousBatchEngine:
                 self.kv_mgr.free(s)
                 del self.active[s.id]
                 del self.sampling[s.id]
+        return finished
+
+    # ---- speculative decoding (module docstring) -------------------------------------------------------------
+    def _plan_spec_step(self):
+        """-> the plan of one speculative step, its blocks allocated and its metadata uploaded (two uploads, as a
+        plain step); None when nothing runs.  Keys: states (row order: decoding sequences, most drafts first, then the
+        prompt chunks), emitting (the sequences vy_spec_verify judges, in its order) with n_draft / t_row0 per entry,
+        verify = (metadata, input_ids) of the target forward, draft = per round (metadata, input_ids or None, n, sampling)
+        -- round j >= 1 reads its ids from round j - 1's draws -- scatter = (rows of the verify ids, flat indices into
+        the (g, S) draft tokens) and sampling = the per-sequence arguments of vy_spec_verify."""
+        self._try_schedule_waiting()
+        if not self.active:
+            return None
+        G, bs = self.num_speculative_tokens, self.kv_mgr.block_size
+        running = list(self.active.values())
+        g_of = {s.id: max(0, min(G, s.max_total_len - s.num_tokens - 1)) for s in running if not s.is_prefill}
+        dec = sorted((s for s in running if not s.is_prefill), key=lambda s: -g_of[s.id])
+        budget = None if self.max_step_tokens is None else self.max_step_tokens - sum(1 + g for g in g_of.values())
+        prompts = []
+        for s in running:
+            if not s.is_prefill:
+                continue
+            left = s.prompt_len - s.num_computed
+            n = left if budget is None else min(left, budget)
+            if n <= 0:
+                continue
+            if budget is not None:
+                budget -= n
+            s.chunk_end = s.num_computed + n
+            prompts.append(s)
+        states = dec + prompts
+        for s in dec:
+            g, n = g_of[s.id], s.num_tokens
+            self.kv_mgr.allocate(s, n + g)
+            idx = torch.arange(min(self.draft_computed.get(s.id, n - 1), n - 1), n + g)
+            s.slot_mapping[idx] = s.block_table[idx // bs].long() * bs + idx % bs
+        for s in prompts:
+            self.kv_mgr.allocate(s, s.query_end)
+            s.update_metadata()
+            self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
+        width = max(s.block_table.numel() for s in states)
+        tables = {s.id: s.block_table[:s.block_count].tolist() + [0] * (width - s.block_count) for s in states}
+
+        def segments(segs):
+            """segs: (sequence, first position, one past the last) -> the lists of one varlen forward."""
+            ids, pos, slots, cu, ctx, tab, max_q, max_kv = [], [], [], [0], [], [], 0, 0
+            for s, a, b in segs:
+                ids += s.tokens[a:b].tolist()
+                pos += range(a, b)
+                slots += s.slot_mapping[a:b].tolist()
+                cu.append(cu[-1] + b - a)
+                ctx.append(a)
+                tab += tables[s.id]
+                max_q, max_kv = max(max_q, b - a), max(max_kv, b)
+            return ids, pos, slots, cu, ctx, tab, max_q, max_kv
+
+        chunks = [(s, s.query_start, s.query_end) for s in prompts]
+        # the verification: [last token, d_0 .. d_{g - 1}] per decoding sequence (the drafts are scattered in on the device)
+        v = segments([(s, s.num_tokens - 1, s.num_tokens + g_of[s.id]) for s in dec] + chunks)
+        emitting = dec + [s for s in prompts if s.query_end == s.num_tokens]
+        S, n_dec = len(emitting), len(dec)
+        v_last, t_row0, n_draft, v_dst, v_src = [], [], [], [], []
+        for k, s in enumerate(dec):
+            g = g_of[s.id]
+            t_row0.append(len(v_last))
+            n_draft.append(g)
+            v_last += range(v[3][k], v[3][k + 1])
+            v_dst += range(v[3][k] + 1, v[3][k + 1])
+            v_src += [i * S + k for i in range(g)]
+        for k, s in enumerate(prompts):
+            if s.query_end == s.num_tokens:
+                t_row0.append(len(v_last))
+                n_draft.append(0)
+                v_last.append(v[3][n_dec + k + 1] - 1)
+        # draft round 0: what the drafter has not computed yet of every sequence that drafts, and the prompt chunks
+        n_of = [sum(1 for s in dec if g_of[s.id] > j) for j in range(G)]
+        r0 = segments([(s, min(self.draft_computed.get(s.id, s.num_tokens - 1), s.num_tokens - 1), s.num_tokens)
+                       for s in dec[:n_of[0]]] + chunks)
+        r0_last = [c - 1 for c in r0[3][1:n_of[0] + 1]]
+        later = [(j, n_of[j]) for j in range(1, G) if n_of[j]]
+        params = [self.sampling[s.id] for s in emitting]
+        Tv, T0 = len(v[0]), len(r0[0])
+        l64, i32, at64, at32 = [], [], {}, {}
+
+        def put(buf, at, name, values):
+            at[name] = (len(buf), len(values))
+            buf += values
+
+        for name, values in (("v_ids", v[0]), ("v_slots", v[2]), ("v_last", v_last), ("v_dst", v_dst), ("v_src", v_src),
+                             ("r0_ids", r0[0]), ("r0_slots", r0[2]), ("r0_last", r0_last),
+                             ("seed", [_as_i64(sp.seed or 0) for sp in params]),
+                             ("position0", [s.num_tokens for s in emitting]), ("rows64", list(range(n_dec)))):
+            put(l64, at64, name, values)
+        for name, values in (("v_pos", v[1]), ("v_cu", v[3]), ("v_ctx", v[4]), ("v_tab", v[5]),
+                             ("r0_pos", r0[1]), ("r0_cu", r0[3]), ("r0_ctx", r0[4]), ("r0_tab", r0[5]),
+                             ("rows", list(range(n_dec))), ("t_row0", t_row0), ("n_draft", n_draft),
+                             ("inv_temperature", [_f32_bits(sp.inv_temperature) for sp in params]),
+                             ("top_k", [min(sp.top_k, 0x7fffffff) for sp in params]),
+                             ("top_p", [_f32_bits(sp.top_p) for sp in params])):
+            put(i32, at32, name, values)
+        for j, n in [(0, n_of[0])] + later:         # round j draws the token at num_tokens + j, reads position num_tokens - 1 + j
+            put(l64, at64, f"counter{j}", [s.num_tokens + j for s in dec[:n]])
+            if j:
+                put(l64, at64, f"slots{j}", [int(s.slot_mapping[s.num_tokens - 1 + j]) for s in dec[:n]])
+                put(i32, at32, f"pos{j}", [s.num_tokens - 1 + j for s in dec[:n]])
+                put(i32, at32, f"lens{j}", [s.num_tokens + j for s in dec[:n]])
+        l64 = torch.tensor(l64, dtype=torch.long).to(self.device)
+        i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
+        L = lambda name: l64[at64[name][0]:at64[name][0] + at64[name][1]]
+        I = lambda name: i32[at32[name][0]:at32[name][0] + at32[name][1]]
+        F = lambda name: I(name).view(torch.float32)
+
+        def varlen(prefix, lists, last):
+            nseg = len(lists[4])
+            return {"positions": I(prefix + "_pos"), "slot_mapping": L(prefix + "_slots"), "last_rows": last,
+                    "max_position": lists[7], "prefill": [], "decode": None,
+                    "prefill_varlen": {"cu_q": I(prefix + "_cu"), "ctx_lens": I(prefix + "_ctx"),
+                                       "block_table": I(prefix + "_tab").view(nseg, width),
+                                       "max_q": lists[6], "max_kv": lists[7]}}
+
+        def draws(j, n):
+            return {"inv_temperature": F("inv_temperature")[:n], "top_k": I("top_k")[:n], "top_p": F("top_p")[:n],
+                    "seed": L("seed")[:n], "counter": L(f"counter{j}")}
+
+        draft = []
+        if T0:
+            draft.append((varlen("r0", r0, L("r0_last")), L("r0_ids"), n_of[0], draws(0, n_of[0])))
+        dec_tab = I("v_tab").view(len(v[4]), width)      # the decoding sequences' tables lead the verification's
+        for j, n in later:
+            md = {"positions": I(f"pos{j}"), "slot_mapping": L(f"slots{j}"), "last_rows": L("rows64")[:n],
+                  "max_position": max(s.num_tokens + j for s in dec[:n]), "prefill": [],
+                  "decode": {"rows": I("rows")[:n], "seqlens": I(f"lens{j}"), "block_table": dec_tab[:n],
+                             "max_seqlen": max(s.num_tokens + j for s in dec[:n])}}
+            draft.append((md, None, n, draws(j, n)))
+        return {"states": states, "emitting": emitting, "n_draft": n_draft, "t_row0": t_row0, "S": S,
+                "verify": (varlen("v", v, L("v_last")), L("v_ids")), "draft": draft, "scatter": (L("v_dst"), L("v_src")),
+                "sampling": {"t_row0": I("t_row0"), "n_draft": I("n_draft"), "inv_temperature": F("inv_temperature"),
+                             "top_k": I("top_k"), "top_p": F("top_p"), "seed": L("seed"), "position0": L("position0")}}
+
+    def _spec_step(self) -> Dict[int, List[int]]:
+        plan = self._plan_spec_step()
+        if plan is None:
+            return {}
+        from . import ops
+        G, S = self.num_speculative_tokens, plan["S"]
+        dtok = torch.zeros((G, max(S, 1)), dtype=torch.long, device=self.device)
+        dlog = None
+        for j, (md, ids, n, sp) in enumerate(plan["draft"]):
+            rows = self.draft_model.forward_paged(dtok[j - 1, :n] if ids is None else ids, md["positions"], md,
+                                                  self.draft_kv_mgr)
+            if n:
+                if dlog is None:
+                    dlog = rows.new_empty((G, S, rows.shape[1]))
+                dlog[j, :n] = rows
+                dtok[j, :n] = ops.sample_rows(rows, sp["inv_temperature"], sp["top_k"], sp["top_p"], sp["seed"],
+                                              sp["counter"])
+        md, ids = plan["verify"]
+        dst, src = plan["scatter"]
+        if dst.numel():
+            ids[dst] = dtok.view(-1)[src]
+        target_rows = self.model.forward_paged(ids, md["positions"], md, self.kv_mgr)
+        if not S:                                       # prompt chunks only: nothing to judge
+            return self._finish_spec_step(plan, [], [], [])
+        if dlog is None:                                # no sequence drafts in this step: the rows are never read
+            dlog = target_rows.new_empty((G, S, target_rows.shape[1]))
+        sp = plan["sampling"]
+        accept, alt = ops.spec_verify(target_rows, dlog, dtok, sp["t_row0"], sp["n_draft"], sp["inv_temperature"],
+                                      sp["top_k"], sp["top_p"], sp["seed"], sp["position0"])
+        host = torch.cat([accept.view(-1).long(), alt.view(-1), dtok.view(-1)]).tolist()   # the step's one device-to-host copy
+        n = S * (G + 1)
+        accept = [host[k * (G + 1):(k + 1) * (G + 1)] for k in range(S)]
+        alt = [host[n + k * (G + 1):n + (k + 1) * (G + 1)] for k in range(S)]
+        drafts = [host[2 * n + i * S:2 * n + (i + 1) * S] for i in range(G)]
+        recorded = (target_rows.float().cpu(), dlog.float().cpu()) if self.record_logits else None
+        return self._finish_spec_step(plan, accept, alt, drafts, recorded)
+
+    def _finish_spec_step(self, plan, accept, alt, drafts, recorded=None) -> Dict[int, List[int]]:
+        """What a speculative step does after vy_spec_verify, on the host.  accept / alt: one list of g + 1 entries per
+        judged sequence, drafts: one list of S tokens per draft index.  Per sequence: the drafts before the first
+        rejection, then alt of that row; cut after the first stop token and at max_total_len; retire what finished."""
+        for s in plan["states"]:
+            s.num_computed, s.chunk_end = s.query_end, None
+        finished = {}
+        for k, s in enumerate(plan["emitting"]):
+            g, n = plan["n_draft"][k], s.num_tokens
+            mine = [int(drafts[i][k]) for i in range(g)]
+            a = 0
+            while a < g and accept[k][a]:
+                a += 1
+            emitted = (mine[:a] + [int(alt[k][a])])[:s.max_total_len - n]
+            for c, token_id in enumerate(emitted):
+                if token_id in self.eos_token_ids:
+                    emitted = emitted[:c + 1]
+                    break
+            self.drafts_proposed += g
+            self.drafts_accepted += a
+            if s.is_prefill or g:                       # what the drafter's pages hold of the tokens that stay
+                self.draft_computed[s.id] = n if s.is_prefill else n + min(a, g - 1)
+            s.is_prefill = False
+            s.tokens[n:n + len(emitted)] = torch.as_tensor(emitted, dtype=torch.long)
+            s.num_tokens = n + len(emitted)
+            if recorded is not None:
+                r0 = plan["t_row0"][k]
+                self.logits.setdefault(s.id, []).extend(recorded[0][r0 + c] for c in range(len(emitted)))
+                self.rounds.setdefault(s.id, []).append({
+                    "position0": n, "draft_tokens": mine, "draft_rows": recorded[1][:g, k].clone(),
+                    "target_rows": recorded[0][r0:r0 + g + 1].clone(), "accepted": a, "emitted": list(emitted)})
+            if emitted[-1] in self.eos_token_ids or s.num_tokens >= s.max_total_len:
+                finished[s.id] = s.tokens[:s.num_tokens].tolist()
+                self.kv_mgr.free(s)
+                del self.active[s.id]
+                del self.sampling[s.id]
+                self.draft_computed.pop(s.id, None)
         return finished
 
     def run(self) -> Dict[int, List[int]]:
