@@ -464,7 +464,7 @@ class ModelForCausalLM(nn.Module):
         """One step of the continuous-batching engine (serving.ContinuousBatchEngine) -> logits (sequences, vocab) of
         the LAST row of each sequence.  input_ids (T,) are the step's packed tokens -- every unseen prompt token of a
         prefilling sequence, one token of a decoding one -- positions (T,) int32 their positions, `metadata` what
-        ContinuousBatchEngine._prepare_inference_data built, kv_mgr the PagedKVManager whose pages are read and written.
+        ContinuousBatchEngine._plan_step built, kv_mgr the PagedKVManager whose pages are read and written.
 
         Per layer: input_layernorm, the packed QKV projection, vy_paged_rope_write (per-token RoPE in place + the K/V
         rows into their slots), attention -- vy_attn_paged_decode for the rows with one query token, causal vy_attn_fwd

@@ -54,9 +54,14 @@ for every logits row (greedy rows ride along with inv_temperature 0) before the 
 argmax over the kept columns of logit / temperature + Gumbel noise, a draw from softmax(logits / temperature) over the
 set TopKProcessor / NucleusProcessor keep.  The noise of a row is keyed by (the request's seed, the position of the
 token being drawn, column) and by nothing else, so what a request generates from given logits does not depend on the
-batch around it, on its row, on prefix-cache hits or on how its prompt was chunked.  The parameters ride in the step's
-two uploads (top_k and the bit patterns of inv_temperature / top_p in the int32 one, seed and position in the int64
-one): a sampled step makes no additional copy in either direction.
+batch around it, on its row, on prefix-cache hits or on how its prompt was chunked.  A sampled step makes no additional
+copy in either direction.
+
+What a step uploads: two tensors, one int64 and one int32, whatever the step holds (_StepUploads).  A planner appends
+named lists to them -- per forward (_PackedRows) ids and slots to the int64 one, positions, decode rows / lengths / block
+tables and cu_q / ctx_lens / block tables of the varlen segments to the int32 one; then the logits rows, and the
+sampling parameters of a step that draws (top_k and the bit patterns of inv_temperature / top_p as int32, seed and
+position as int64) -- and every tensor of the step's metadata is a view into one of the two.
 
 Speculative decoding (ContinuousBatchEngine(..., draft_model=, draft_kv_mgr=, num_speculative_tokens=g); off by default,
 and then the engine's schedule, metadata, uploads and launches are the ones above).  A step lets the drafter propose up
@@ -64,11 +69,11 @@ to g tokens for every decoding sequence and the target judge them all in ONE for
 speculative_generate (speculative_decoding.py:86-245) for every sequence of the batch at once, with each request's own
 SamplingParams, on the pages.  One step:
 
-1. schedule, allocate, upload -- once: positions and slots of all g draft rounds and of the verification are known on
-   the host in advance and ride in the step's two uploads; draft token ids stay on the device from round to round.
-   The decoding sequences come first, those with the most drafts in front (g_s = min(g, max_total_len - num_tokens -
-   1), the reference's corrected_gamma), so the sequences of round j are always the first n_j.  Under max_step_tokens a
-   decoding sequence takes 1 + g_s rows of the budget.
+1. schedule, allocate, upload -- once: all g draft rounds and the verification are planned on the host in advance and
+   ride in the step's two uploads; draft token ids stay on the device from round to round.  The decoding sequences
+   come first, those with the most drafts in front (g_s = min(g, max_total_len - num_tokens - 1), the reference's
+   corrected_gamma), so the sequences of round j are always the first n_j.  Under max_step_tokens a decoding
+   sequence takes 1 + g_s rows of the budget.
 2. draft round 0: one draft_model.forward_paged over the step's prompt chunks (the target's segments, no logits rows)
    and, per decoding sequence, a varlen segment of the tokens the drafter has not computed yet (1, or 2 after a round
    whose drafts were all accepted: draft_computed[sid] counts what its pages hold); one vy_sample_rows, counter =
@@ -103,7 +108,7 @@ _MASK64 = (1 << 64) - 1
 class SamplingParams:
     """How one request draws its tokens.  temperature 0: greedy (top_k / top_p / seed unused).  top_k 0 and top_p 0 or 1:
     that filter is off; both are applied to the unscaled logits, top-k first, as the logits processors do.  seed: any
-    int, used modulo 2^64; None lets add_sequence take one from rng.next_offset()."""
+    int, used modulo 2^64; None lets add_sequence take one from rng.next_offset().  Fixed at construction."""
 
     def __init__(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 0.0, seed: Optional[int] = None):
         temperature, top_p = float(temperature), float(top_p)
@@ -115,6 +120,10 @@ class SamplingParams:
             raise ValueError(f"top_p {top_p} must lie in [0, 1]")
         self.temperature, self.top_k, self.top_p = temperature, int(top_k), top_p
         self.seed = None if seed is None else int(seed) & _MASK64
+        # how the parameters ride in a step's uploads, fixed here: top_k and the bit patterns of inv_temperature /
+        # top_p as int32, the seed as the int64 that carries its 64 bits
+        self.wire = (_f32_bits(self.inv_temperature), min(self.top_k, 0x7fffffff), _f32_bits(self.top_p),
+                     _as_i64(self.seed or 0))
 
     @property
     def greedy(self) -> bool:
@@ -191,10 +200,14 @@ class SequenceState:
         """One past the last token of this step's query rows: the chunk's end while a prompt goes in chunks."""
         return self.chunk_end if self.is_prefill and self.chunk_end is not None else self.num_tokens
 
-    def update_metadata(self) -> None:
-        """slot = block_table[i // block_size] * block_size + i % block_size for the tokens this step computes."""
-        idx = torch.arange(self.query_start, self.query_end)
+    def map_slots(self, a: int, b: int) -> None:
+        """slot = block_table[i // block_size] * block_size + i % block_size for the tokens [a, b)."""
+        idx = torch.arange(a, b)
         self.slot_mapping[idx] = self.block_table[idx // self.block_size].long() * self.block_size + idx % self.block_size
+
+    def update_metadata(self) -> None:
+        """The slots of the tokens this step computes."""
+        self.map_slots(self.query_start, self.query_end)
 
 
 class PagedKVManager:
@@ -358,6 +371,133 @@ def _compute_dtype(model) -> torch.dtype:
     return getattr(inner, "compute_dtype", None) or next(model.parameters()).dtype
 
 
+class _StepUploads:
+    """The step's two host-to-device copies (module docstring): named lists are collected for one int64 and one int32
+    buffer, in the order they are put, and upload() builds and moves each buffer once and splits it -> {name: the
+    entry's view of the device tensor}, in the dtype it was put in (the _f32_bits() patterns of a float entry:
+    .view(torch.float32)).  An entry without values is an empty view; a name that was never put is not in the dict."""
+
+    def __init__(self):
+        self._l64, self._l32 = {}, {}
+
+    def put64(self, name: str, values) -> None:
+        assert name not in self._l64 and name not in self._l32, f"{name} is already in the step's uploads"
+        self._l64[name] = values
+
+    def put32(self, name: str, values) -> None:
+        assert name not in self._l64 and name not in self._l32, f"{name} is already in the step's uploads"
+        self._l32[name] = values
+
+    def upload(self, device) -> Dict[str, torch.Tensor]:
+        views = {}
+        for entries, dtype in ((self._l64, torch.long), (self._l32, torch.int32)):
+            buf = torch.tensor(list(itertools.chain.from_iterable(entries.values())), dtype=dtype).to(device)
+            views.update(zip(entries, buf.split([len(values) for values in entries.values()])))
+        return views
+
+
+def _put_sampling(up: _StepUploads, params: List[SamplingParams]) -> None:
+    """One entry per row of SamplingParams.wire: inv_temperature, top_k and top_p in the int32 upload, the seed in the
+    int64 one (a greedy row: inv_temperature 0)."""
+    up.put32("inv_temperature", [sp.wire[0] for sp in params])
+    up.put32("top_k", [sp.wire[1] for sp in params])
+    up.put32("top_p", [sp.wire[2] for sp in params])
+    up.put64("seed", [sp.wire[3] for sp in params])
+
+
+def _sampling_views(at: Dict[str, torch.Tensor], n: Optional[int] = None, **more) -> dict:
+    """What _put_sampling uploaded (n: the first n rows of it), as vy_sample_rows / vy_spec_verify take it; `more`: the
+    caller's own per-row entries (counter: the position of the token being drawn)."""
+    views = {"inv_temperature": at["inv_temperature"].view(torch.float32), "top_k": at["top_k"],
+             "top_p": at["top_p"].view(torch.float32), "seed": at["seed"]}
+    if n is not None:
+        views = {name: view[:n] for name, view in views.items()}
+    return {**views, **more}
+
+
+def _metadata(positions, slot_mapping, last_rows, max_position: int, prefill=(), decode=None, prefill_varlen=None) -> dict:
+    """The dict forward_paged and layers/paged.py read.  last_rows: the rows that get logits; prefill: the default
+    engine's per-sequence list; decode / prefill_varlen: what the paged decode launch and the ONE varlen prefill
+    launch read, None / no such key when the forward has no such rows."""
+    md = {"positions": positions, "slot_mapping": slot_mapping, "last_rows": last_rows, "max_position": max_position,
+          "prefill": list(prefill), "decode": decode}
+    if prefill_varlen is not None:
+        md["prefill_varlen"] = prefill_varlen
+    return md
+
+
+def _padded_tables(states: List[SequenceState]):
+    """-> (width, {sid: the sequence's block table padded with zeros to width})."""
+    width = max(s.block_table.numel() for s in states)
+    return width, {s.id: s.block_table[:s.block_count].tolist() + [0] * (width - s.block_count) for s in states}
+
+
+class _PackedRows:
+    """One packed forward, built segment by segment in row order: ids, positions and slots of every row, the rows that
+    get logits (the last n_last of a segment), and per kind of segment what its attention launch reads.  decode(s): the
+    one query row of a decoding sequence, for vy_attn_paged_decode.  varlen(s, a, b, n_last): tokens [a, b) as a segment
+    of the ONE vy_attn_paged_prefill launch (cu_q counts rows of the packed buffer, ctx_len = a).  per_sequence(s, a, b,
+    n_last): the default engine's prefill (first row, rows, prefix_len, its block table after a prefix hit).
+    put() appends all of it to the step's uploads under `prefix`, metadata() builds the dict from the views."""
+
+    def __init__(self, width: int, tables: Dict[int, List[int]], prefix: str = ""):
+        self.width, self.tables, self.prefix = width, tables, prefix
+        self.ids, self.pos, self.slots, self.last = [], [], [], []
+        self.dec_rows, self.dec_lens, self.dec_tables, self.prefill = [], [], [], []
+        self.seg_rows, self.ctx, self.seg_tables, self.max_q, self.max_kv = [], [], [], 0, 0
+
+    def _rows(self, s: SequenceState, a: int, b: int, n_last: int) -> int:
+        row0 = len(self.ids)
+        self.ids += s.tokens[a:b].tolist()
+        self.pos += range(a, b)
+        self.slots += s.slot_mapping[a:b].tolist()
+        self.last += range(row0 + b - a - n_last, row0 + b - a)
+        return row0
+
+    def decode(self, s: SequenceState) -> None:
+        assert not self.ctx, "decoding sequences come first"
+        self.dec_rows.append(self._rows(s, s.num_tokens - 1, s.num_tokens, 1))
+        self.dec_lens.append(s.num_tokens)
+        self.dec_tables += self.tables[s.id]
+
+    def varlen(self, s: SequenceState, a: int, b: int, n_last: int) -> None:
+        self.seg_rows.append(self._rows(s, a, b, n_last))
+        self.ctx.append(a)
+        self.seg_tables += self.tables[s.id]
+        self.max_q, self.max_kv = max(self.max_q, b - a), max(self.max_kv, b)
+
+    def per_sequence(self, s: SequenceState, a: int, b: int, n_last: int) -> None:
+        self.prefill.append((self._rows(s, a, b, n_last), b - a, a, self.tables[s.id][:s.block_count] if a else None))
+
+    def put(self, up: _StepUploads) -> None:
+        p = self.prefix
+        for name, values in (("ids", self.ids), ("slots", self.slots), ("last", self.last)):
+            up.put64(p + name, values)
+        for name, values in (("pos", self.pos), ("dec_rows", self.dec_rows), ("dec_lens", self.dec_lens),
+                             ("dec_tables", self.dec_tables)):
+            up.put32(p + name, values)
+        for k, (_, _, _, table) in enumerate(self.prefill):
+            if table is not None:
+                up.put32(f"{p}prefill{k}", table)
+        if self.ctx or not self.ids:             # (a draft round 0 without rows still has its cu_q = [0])
+            up.put32(p + "cu", self.seg_rows + [len(self.ids)])      # the varlen segments end the forward
+            up.put32(p + "ctx", self.ctx)
+            up.put32(p + "tab", self.seg_tables)
+
+    def metadata(self, at: Dict[str, torch.Tensor], max_position: int) -> dict:
+        """at: what upload() returned."""
+        p, decode, varlen = self.prefix, None, None
+        if self.dec_rows:
+            decode = {"rows": at[p + "dec_rows"], "seqlens": at[p + "dec_lens"], "max_seqlen": max(self.dec_lens),
+                      "block_table": at[p + "dec_tables"].view(len(self.dec_rows), self.width)}
+        if self.ctx:
+            varlen = {"cu_q": at[p + "cu"], "ctx_lens": at[p + "ctx"], "max_q": self.max_q, "max_kv": self.max_kv,
+                      "block_table": at[p + "tab"].view(len(self.ctx), self.width)}
+        prefill = [(row0, n, prefix_len, None if table is None else at[f"{p}prefill{k}"])
+                   for k, (row0, n, prefix_len, table) in enumerate(self.prefill)]
+        return _metadata(at[p + "pos"], at[p + "slots"], at[p + "last"], max_position, prefill, decode, varlen)
+
+
 class ContinuousBatchEngine:
     """add_sequence() queues a request; step() admits what fits, runs ONE packed forward over every running sequence
     (all unseen prompt tokens of the newly admitted ones, one token of the others), appends to each the token its
@@ -493,127 +633,66 @@ class ContinuousBatchEngine:
             self.active[req["sid"]] = SequenceState(req["sid"], req["prompt_ids"], req["max_gen_len"], mgr.block_size,
                                                     self.device, matched_blocks=matched)
 
-    def _prepare_inference_data(self, states: List[SequenceState]):
-        """-> (metadata, input_ids): the step's packed token ids and positions, their slots, and per phase what the
-        attention needs -- for the decoding sequences their rows, block tables and lengths, for each prefilling one
-        (first row, rows, prefix_len, its block table).  last_rows has one row per sequence whose query rows reach its
-        last token (all of them unless a prompt goes in chunks).  If one of those sequences samples,
-        metadata["sampling"] = {inv_temperature, top_k, top_p, seed, counter} holds one entry per last row, views into the
-        step's two uploads (a greedy row: inv_temperature 0; counter: the position of the token being drawn); a step
-        whose emitting sequences are all greedy has no such key and uploads what it always did.
-
-        varlen_prefill: `states` holds the decoding sequences first, so the prefill rows are one contiguous run, and
-        metadata["prefill_varlen"] = {cu_q, ctx_lens, block_table (n, width), max_q, max_kv} describes all of them for
-        ONE vy_attn_paged_prefill launch (cu_q counts rows of the packed buffer); metadata["prefill"] is then empty."""
-        ids, pos, slots, cu, last, drawn = [], [], [], [0], [], []
-        dec_rows, dec_lens, dec_tables, prefill = [], [], [], []
-        pf_cu, pf_ctx, pf_tables, pf_max_q, pf_max_kv = [], [], [], 0, 0
-        width = max(s.block_table.numel() for s in states)
-        for s in states:
-            a, b = s.query_start, s.query_end
-            ids += s.tokens[a:b].tolist()
-            pos += range(a, b)
-            slots += s.slot_mapping[a:b].tolist()
-            table = s.block_table[:s.block_count].tolist()
-            if not s.is_prefill:
-                assert not pf_cu, "decoding sequences come first"
-                dec_rows.append(cu[-1])
-                dec_lens.append(b)
-                dec_tables += table + [0] * (width - len(table))
-            elif self.varlen_prefill:
-                pf_cu.append(cu[-1])
-                pf_ctx.append(a)
-                pf_tables += table + [0] * (width - len(table))
-                pf_max_q, pf_max_kv = max(pf_max_q, b - a), max(pf_max_kv, b)
-            else:
-                prefill.append((cu[-1], b - a, a, table if a else None))
-            cu.append(cu[-1] + b - a)
-            if b == s.num_tokens:
-                last.append(cu[-1] - 1)
-                drawn.append(s)
-        # two uploads: everything int64 (ids | slots | last rows) and everything int32 (positions | decode rows |
-        # decode lengths | decode block tables | the block table of each prefill that starts from a cached prefix, or
-        # with varlen_prefill: cu_q | ctx_lens | the prefill block tables)
-        T, nd, npf = cu[-1], len(dec_rows), len(pf_cu)
-        i32 = pos + dec_rows + dec_lens + dec_tables
-        for k, (row0, rows, prefix_len, table) in enumerate(prefill):
-            if table is not None:
-                prefill[k] = (row0, rows, prefix_len, (len(i32), len(table)))
-                i32 += table
-        pf0 = len(i32)
-        if npf:
-            i32 += pf_cu + [T] + pf_ctx + pf_tables
-        l64, nl, sp0 = ids + slots + last, len(last), len(i32)
-        params = [self.sampling[s.id] for s in drawn]
-        sampled = any(not sp.greedy for sp in params)
-        if sampled:
-            i32 += ([_f32_bits(sp.inv_temperature) for sp in params] + [min(sp.top_k, 0x7fffffff) for sp in params] +
-                    [_f32_bits(sp.top_p) for sp in params])
-            l64 += [_as_i64(sp.seed or 0) for sp in params] + [s.num_tokens for s in drawn]
-        l64 = torch.tensor(l64, dtype=torch.long).to(self.device)
-        i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
-        prefill = [(r0, n, pl, None if t is None else i32[t[0]:t[0] + t[1]]) for r0, n, pl, t in prefill]
-        metadata = {
-            "positions": i32[:T],
-            "slot_mapping": l64[T:2 * T],
-            "last_rows": l64[2 * T:2 * T + nl],
-            "max_position": max(s.num_tokens for s in states),
-            "prefill": prefill,
-            "decode": None,
-        }
-        if nd:
-            o = T + 2 * nd
-            metadata["decode"] = {"rows": i32[T:T + nd], "seqlens": i32[T + nd:o],
-                                  "block_table": i32[o:o + nd * width].view(nd, width), "max_seqlen": max(dec_lens)}
-        if npf:
-            o = pf0 + 2 * npf + 1
-            metadata["prefill_varlen"] = {"cu_q": i32[pf0:pf0 + npf + 1], "ctx_lens": i32[pf0 + npf + 1:o],
-                                          "block_table": i32[o:o + npf * width].view(npf, width),
-                                          "max_q": pf_max_q, "max_kv": pf_max_kv}
-        if sampled:
-            o = 2 * T + nl
-            metadata["sampling"] = {"inv_temperature": i32[sp0:sp0 + nl].view(torch.float32),
-                                    "top_k": i32[sp0 + nl:sp0 + 2 * nl],
-                                    "top_p": i32[sp0 + 2 * nl:sp0 + 3 * nl].view(torch.float32),
-                                    "seed": l64[o:o + nl], "counter": l64[o + nl:o + 2 * nl]}
-        return metadata, l64[:T]
-
-    def _schedule_step(self) -> List[SequenceState]:
-        """The sequences of this step, in the order of their rows.  Default: every running sequence, in admission
-        order, a prefilling one with all its unseen prompt tokens.  varlen_prefill: the decoding sequences first (one
-        token each), then the prefilling ones in admission order; under max_step_tokens each of those gets
-        min(prompt tokens left, budget left) and one that gets nothing sits the step out."""
-        states = list(self.active.values())
-        if not self.varlen_prefill:
-            return states
-        run = [s for s in states if not s.is_prefill]
-        budget = None if self.max_step_tokens is None else self.max_step_tokens - len(run)
-        for s in states:
-            if not s.is_prefill:
-                continue
-            left = s.prompt_len - s.num_computed
-            n = left if budget is None else min(left, budget)
-            if n <= 0:
-                continue
-            if budget is not None:
+    def _schedule_prompts(self, decode_rows: int) -> List[SequenceState]:
+        """The prefilling sequences that run in this step, in admission order, their chunk_end set.  Under
+        max_step_tokens the decoding sequences took decode_rows of the budget; each prompt gets min(prompt tokens left,
+        budget left) and one that gets nothing sits the step out."""
+        budget = math.inf if self.max_step_tokens is None else self.max_step_tokens - decode_rows
+        run = []
+        for s in self.active.values():
+            n = min(s.prompt_len - s.num_computed, budget) if s.is_prefill else 0
+            if n > 0:
                 budget -= n
-            s.chunk_end = s.num_computed + n
-            run.append(s)
+                s.chunk_end = s.num_computed + n
+                run.append(s)
         return run
+
+    def _allocate(self, s: SequenceState) -> None:
+        """Blocks and slots of the tokens this step computes of its sequence."""
+        self.kv_mgr.allocate(s, s.query_end)
+        s.update_metadata()
+        if s.is_prefill:
+            self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
 
     def _plan_step(self):
         """-> (states, metadata, input_ids) of the next step, its blocks allocated and its metadata uploaded; None when
-        nothing runs.  Everything a step does before the model (no GPU work but the two uploads)."""
+        nothing runs.  Everything a step does before the model (no GPU work but the two uploads).  states, in the order
+        of their rows: every running sequence in admission order, a prefilling one with all its unseen prompt tokens
+        through its own attention launch (metadata["prefill"]); varlen_prefill: the decoding sequences first, then the
+        prompts _schedule_prompts() lets run, as segments of ONE launch (metadata["prefill_varlen"]).  last_rows has one
+        row per sequence whose query rows reach its last token; if one of those sequences samples, metadata["sampling"]
+        holds one entry per last row, else the step uploads no sampling entries and has no such key."""
         self._try_schedule_waiting()
         if not self.active:
             return None
-        states = self._schedule_step()
+        states = list(self.active.values())
+        if self.varlen_prefill:
+            dec = [s for s in states if not s.is_prefill]
+            states = dec + self._schedule_prompts(len(dec))
         for s in states:
-            self.kv_mgr.allocate(s, s.query_end)
-            s.update_metadata()
-            if s.is_prefill:
-                self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
-        return (states, *self._prepare_inference_data(states))
+            self._allocate(s)
+        rows = _PackedRows(*_padded_tables(states))
+        for s in states:
+            a, b = s.query_start, s.query_end
+            if not s.is_prefill:
+                rows.decode(s)
+            elif self.varlen_prefill:
+                rows.varlen(s, a, b, int(b == s.num_tokens))
+            else:
+                rows.per_sequence(s, a, b, int(b == s.num_tokens))
+        drawn = [s for s in states if s.query_end == s.num_tokens]
+        params = [self.sampling[s.id] for s in drawn]
+        sampled = any(not sp.greedy for sp in params)
+        up = _StepUploads()
+        rows.put(up)
+        if sampled:
+            _put_sampling(up, params)
+            up.put64("counter", [s.num_tokens for s in drawn])
+        at = up.upload(self.device)
+        metadata = rows.metadata(at, max(s.num_tokens for s in states))
+        if sampled:
+            metadata["sampling"] = _sampling_views(at, counter=at["counter"])
+        return states, metadata, at["ids"]
 
     def step(self) -> Dict[int, List[int]]:
         if self.speculative:
@@ -636,22 +715,32 @@ class ContinuousBatchEngine:
                 self.logits.setdefault(s.id, []).append(host[i])
         return self._finish_step(states, next_tokens)
 
+    @staticmethod
+    def _end_step(states: List[SequenceState]) -> None:
+        """The step's rows are in the pages: what it computed counts, and the next step cuts its own chunks."""
+        for s in states:
+            s.num_computed, s.chunk_end = s.query_end, None
+
+    def _retire(self, s: SequenceState, finished: Dict[int, List[int]]) -> None:
+        """A sequence that met a stop token or its length leaves: its tokens go to `finished`, its blocks back."""
+        finished[s.id] = s.tokens[:s.num_tokens].tolist()
+        self.kv_mgr.free(s)
+        del self.active[s.id]
+        del self.sampling[s.id]
+        self.draft_computed.pop(s.id, None)
+
     def _finish_step(self, states: List[SequenceState], next_tokens: List[int]) -> Dict[int, List[int]]:
         """Append next_tokens (one per sequence whose query rows reached its last token, in row order) and retire what
         finished: everything a step does after the model, on the host."""
         emitting = [s for s in states if s.query_end == s.num_tokens]   # (a chunk short of its prompt's end: no token)
-        for s in states:
-            s.num_computed, s.chunk_end = s.query_end, None
+        self._end_step(states)
         finished = {}
         for s, token_id in zip(emitting, next_tokens):
             s.is_prefill = False
             s.tokens[s.num_tokens] = token_id
             s.num_tokens += 1
             if token_id in self.eos_token_ids or s.num_tokens >= s.max_total_len:
-                finished[s.id] = s.tokens[:s.num_tokens].tolist()
-                self.kv_mgr.free(s)
-                del self.active[s.id]
-                del self.sampling[s.id]
+                self._retire(s, finished)
         return finished
 
     # ---- speculative decoding (module docstring) -------------------------------------------------------------
@@ -665,131 +754,72 @@ class ContinuousBatchEngine:
         self._try_schedule_waiting()
         if not self.active:
             return None
-        G, bs = self.num_speculative_tokens, self.kv_mgr.block_size
-        running = list(self.active.values())
-        g_of = {s.id: max(0, min(G, s.max_total_len - s.num_tokens - 1)) for s in running if not s.is_prefill}
-        dec = sorted((s for s in running if not s.is_prefill), key=lambda s: -g_of[s.id])
-        budget = None if self.max_step_tokens is None else self.max_step_tokens - sum(1 + g for g in g_of.values())
-        prompts = []
-        for s in running:
-            if not s.is_prefill:
-                continue
-            left = s.prompt_len - s.num_computed
-            n = left if budget is None else min(left, budget)
-            if n <= 0:
-                continue
-            if budget is not None:
-                budget -= n
-            s.chunk_end = s.num_computed + n
-            prompts.append(s)
+        G = self.num_speculative_tokens
+        dec = [s for s in self.active.values() if not s.is_prefill]
+        g_of = {s.id: max(0, min(G, s.max_total_len - s.num_tokens - 1)) for s in dec}
+        dec.sort(key=lambda s: -g_of[s.id])
+        prompts = self._schedule_prompts(sum(1 + g for g in g_of.values()))
         states = dec + prompts
+        seen = {}                     # first token of a decoding sequence that the drafter has not computed yet
         for s in dec:
-            g, n = g_of[s.id], s.num_tokens
-            self.kv_mgr.allocate(s, n + g)
-            idx = torch.arange(min(self.draft_computed.get(s.id, n - 1), n - 1), n + g)
-            s.slot_mapping[idx] = s.block_table[idx // bs].long() * bs + idx % bs
+            seen[s.id] = min(self.draft_computed.get(s.id, s.num_tokens - 1), s.num_tokens - 1)
+            self.kv_mgr.allocate(s, s.num_tokens + g_of[s.id])
+            s.map_slots(seen[s.id], s.num_tokens + g_of[s.id])
         for s in prompts:
-            self.kv_mgr.allocate(s, s.query_end)
-            s.update_metadata()
-            self.prompt_tokens_computed[s.id] = s.query_end - s.prefix_len
-        width = max(s.block_table.numel() for s in states)
-        tables = {s.id: s.block_table[:s.block_count].tolist() + [0] * (width - s.block_count) for s in states}
-
-        def segments(segs):
-            """segs: (sequence, first position, one past the last) -> the lists of one varlen forward."""
-            ids, pos, slots, cu, ctx, tab, max_q, max_kv = [], [], [], [0], [], [], 0, 0
-            for s, a, b in segs:
-                ids += s.tokens[a:b].tolist()
-                pos += range(a, b)
-                slots += s.slot_mapping[a:b].tolist()
-                cu.append(cu[-1] + b - a)
-                ctx.append(a)
-                tab += tables[s.id]
-                max_q, max_kv = max(max_q, b - a), max(max_kv, b)
-            return ids, pos, slots, cu, ctx, tab, max_q, max_kv
-
-        chunks = [(s, s.query_start, s.query_end) for s in prompts]
-        # the verification: [last token, d_0 .. d_{g - 1}] per decoding sequence (the drafts are scattered in on the device)
-        v = segments([(s, s.num_tokens - 1, s.num_tokens + g_of[s.id]) for s in dec] + chunks)
+            self._allocate(s)
+        # the verification: [last token, d_0 .. d_{g - 1}] per decoding sequence (the drafts are scattered in on the
+        # device), every row with logits; draft round 0: what the drafter has not computed yet of every sequence that
+        # drafts, its last row with logits; both: the prompt chunks, the target's with a logits row where a prompt ends
+        width, tables = _padded_tables(states)
+        v, r0 = _PackedRows(width, tables, "v_"), _PackedRows(width, tables, "r0_")
+        for s in dec:
+            v.varlen(s, s.num_tokens - 1, s.num_tokens + g_of[s.id], g_of[s.id] + 1)
+            if g_of[s.id]:
+                r0.varlen(s, seen[s.id], s.num_tokens, 1)
+        for s in prompts:
+            v.varlen(s, s.query_start, s.query_end, int(s.query_end == s.num_tokens))
+            r0.varlen(s, s.query_start, s.query_end, 0)
         emitting = dec + [s for s in prompts if s.query_end == s.num_tokens]
-        S, n_dec = len(emitting), len(dec)
-        v_last, t_row0, n_draft, v_dst, v_src = [], [], [], [], []
-        for k, s in enumerate(dec):
-            g = g_of[s.id]
-            t_row0.append(len(v_last))
-            n_draft.append(g)
-            v_last += range(v[3][k], v[3][k + 1])
-            v_dst += range(v[3][k] + 1, v[3][k + 1])
-            v_src += [i * S + k for i in range(g)]
-        for k, s in enumerate(prompts):
-            if s.query_end == s.num_tokens:
-                t_row0.append(len(v_last))
-                n_draft.append(0)
-                v_last.append(v[3][n_dec + k + 1] - 1)
-        # draft round 0: what the drafter has not computed yet of every sequence that drafts, and the prompt chunks
-        n_of = [sum(1 for s in dec if g_of[s.id] > j) for j in range(G)]
-        r0 = segments([(s, min(self.draft_computed.get(s.id, s.num_tokens - 1), s.num_tokens - 1), s.num_tokens)
-                       for s in dec[:n_of[0]]] + chunks)
-        r0_last = [c - 1 for c in r0[3][1:n_of[0] + 1]]
+        S, n_dec, cu = len(emitting), len(dec), v.seg_rows + [len(v.ids)]
+        # the decoding sequences lead the verification, so the first logits row of sequence k is its first row, cu[k]
+        n_draft = [g_of[s.id] for s in dec] + [0] * (S - n_dec)
+        t_row0 = cu[:n_dec] + list(range(cu[n_dec], cu[n_dec] + S - n_dec))
+        v_dst = [row for k in range(n_dec) for row in range(cu[k] + 1, cu[k + 1])]
+        v_src = [i * S + k for k in range(n_dec) for i in range(n_draft[k])]
+        n_of = [sum(1 for g in n_draft[:n_dec] if g > j) for j in range(G)]    # the sequences of round j: the first n_of[j]
         later = [(j, n_of[j]) for j in range(1, G) if n_of[j]]
-        params = [self.sampling[s.id] for s in emitting]
-        Tv, T0 = len(v[0]), len(r0[0])
-        l64, i32, at64, at32 = [], [], {}, {}
-
-        def put(buf, at, name, values):
-            at[name] = (len(buf), len(values))
-            buf += values
-
-        for name, values in (("v_ids", v[0]), ("v_slots", v[2]), ("v_last", v_last), ("v_dst", v_dst), ("v_src", v_src),
-                             ("r0_ids", r0[0]), ("r0_slots", r0[2]), ("r0_last", r0_last),
-                             ("seed", [_as_i64(sp.seed or 0) for sp in params]),
-                             ("position0", [s.num_tokens for s in emitting]), ("rows64", list(range(n_dec)))):
-            put(l64, at64, name, values)
-        for name, values in (("v_pos", v[1]), ("v_cu", v[3]), ("v_ctx", v[4]), ("v_tab", v[5]),
-                             ("r0_pos", r0[1]), ("r0_cu", r0[3]), ("r0_ctx", r0[4]), ("r0_tab", r0[5]),
-                             ("rows", list(range(n_dec))), ("t_row0", t_row0), ("n_draft", n_draft),
-                             ("inv_temperature", [_f32_bits(sp.inv_temperature) for sp in params]),
-                             ("top_k", [min(sp.top_k, 0x7fffffff) for sp in params]),
-                             ("top_p", [_f32_bits(sp.top_p) for sp in params])):
-            put(i32, at32, name, values)
+        up = _StepUploads()
+        v.put(up)
+        up.put64("v_dst", v_dst)
+        up.put64("v_src", v_src)
+        r0.put(up)
+        up.put32("rows", list(range(n_dec)))
+        up.put32("t_row0", t_row0)
+        up.put32("n_draft", n_draft)
+        _put_sampling(up, [self.sampling[s.id] for s in emitting])
+        up.put64("position0", [s.num_tokens for s in emitting])
+        up.put64("rows64", list(range(n_dec)))
         for j, n in [(0, n_of[0])] + later:         # round j draws the token at num_tokens + j, reads position num_tokens - 1 + j
-            put(l64, at64, f"counter{j}", [s.num_tokens + j for s in dec[:n]])
+            up.put64(f"counter{j}", [s.num_tokens + j for s in dec[:n]])
             if j:
-                put(l64, at64, f"slots{j}", [int(s.slot_mapping[s.num_tokens - 1 + j]) for s in dec[:n]])
-                put(i32, at32, f"pos{j}", [s.num_tokens - 1 + j for s in dec[:n]])
-                put(i32, at32, f"lens{j}", [s.num_tokens + j for s in dec[:n]])
-        l64 = torch.tensor(l64, dtype=torch.long).to(self.device)
-        i32 = torch.tensor(i32, dtype=torch.int32).to(self.device)
-        L = lambda name: l64[at64[name][0]:at64[name][0] + at64[name][1]]
-        I = lambda name: i32[at32[name][0]:at32[name][0] + at32[name][1]]
-        F = lambda name: I(name).view(torch.float32)
-
-        def varlen(prefix, lists, last):
-            nseg = len(lists[4])
-            return {"positions": I(prefix + "_pos"), "slot_mapping": L(prefix + "_slots"), "last_rows": last,
-                    "max_position": lists[7], "prefill": [], "decode": None,
-                    "prefill_varlen": {"cu_q": I(prefix + "_cu"), "ctx_lens": I(prefix + "_ctx"),
-                                       "block_table": I(prefix + "_tab").view(nseg, width),
-                                       "max_q": lists[6], "max_kv": lists[7]}}
-
-        def draws(j, n):
-            return {"inv_temperature": F("inv_temperature")[:n], "top_k": I("top_k")[:n], "top_p": F("top_p")[:n],
-                    "seed": L("seed")[:n], "counter": L(f"counter{j}")}
-
+                up.put64(f"slots{j}", [int(s.slot_mapping[s.num_tokens - 1 + j]) for s in dec[:n]])
+                up.put32(f"pos{j}", [s.num_tokens - 1 + j for s in dec[:n]])
+                up.put32(f"lens{j}", [s.num_tokens + j for s in dec[:n]])
+        at = up.upload(self.device)
         draft = []
-        if T0:
-            draft.append((varlen("r0", r0, L("r0_last")), L("r0_ids"), n_of[0], draws(0, n_of[0])))
-        dec_tab = I("v_tab").view(len(v[4]), width)      # the decoding sequences' tables lead the verification's
+        if r0.ids:
+            draft.append((r0.metadata(at, r0.max_kv), at["r0_ids"], n_of[0],
+                          _sampling_views(at, n_of[0], counter=at["counter0"])))
+        dec_tab = at["v_tab"].view(len(v.ctx), width)      # the decoding sequences' tables lead the verification's
         for j, n in later:
-            md = {"positions": I(f"pos{j}"), "slot_mapping": L(f"slots{j}"), "last_rows": L("rows64")[:n],
-                  "max_position": max(s.num_tokens + j for s in dec[:n]), "prefill": [],
-                  "decode": {"rows": I("rows")[:n], "seqlens": I(f"lens{j}"), "block_table": dec_tab[:n],
-                             "max_seqlen": max(s.num_tokens + j for s in dec[:n])}}
-            draft.append((md, None, n, draws(j, n)))
+            longest = max(s.num_tokens + j for s in dec[:n])
+            md = _metadata(at[f"pos{j}"], at[f"slots{j}"], at["rows64"][:n], longest,
+                           decode={"rows": at["rows"][:n], "seqlens": at[f"lens{j}"], "block_table": dec_tab[:n],
+                                   "max_seqlen": longest})
+            draft.append((md, None, n, _sampling_views(at, n, counter=at[f"counter{j}"])))
         return {"states": states, "emitting": emitting, "n_draft": n_draft, "t_row0": t_row0, "S": S,
-                "verify": (varlen("v", v, L("v_last")), L("v_ids")), "draft": draft, "scatter": (L("v_dst"), L("v_src")),
-                "sampling": {"t_row0": I("t_row0"), "n_draft": I("n_draft"), "inv_temperature": F("inv_temperature"),
-                             "top_k": I("top_k"), "top_p": F("top_p"), "seed": L("seed"), "position0": L("position0")}}
+                "verify": (v.metadata(at, v.max_kv), at["v_ids"]), "draft": draft, "scatter": (at["v_dst"], at["v_src"]),
+                "sampling": _sampling_views(at, t_row0=at["t_row0"], n_draft=at["n_draft"], position0=at["position0"])}
 
     def _spec_step(self) -> Dict[int, List[int]]:
         plan = self._plan_spec_step()
@@ -832,8 +862,7 @@ class ContinuousBatchEngine:
         """What a speculative step does after vy_spec_verify, on the host.  accept / alt: one list of g + 1 entries per
         judged sequence, drafts: one list of S tokens per draft index.  Per sequence: the drafts before the first
         rejection, then alt of that row; cut after the first stop token and at max_total_len; retire what finished."""
-        for s in plan["states"]:
-            s.num_computed, s.chunk_end = s.query_end, None
+        self._end_step(plan["states"])
         finished = {}
         for k, s in enumerate(plan["emitting"]):
             g, n = plan["n_draft"][k], s.num_tokens
@@ -860,12 +889,9 @@ class ContinuousBatchEngine:
                     "position0": n, "draft_tokens": mine, "draft_rows": recorded[1][:g, k].clone(),
                     "target_rows": recorded[0][r0:r0 + g + 1].clone(), "accepted": a, "emitted": list(emitted)})
             if emitted[-1] in self.eos_token_ids or s.num_tokens >= s.max_total_len:
-                finished[s.id] = s.tokens[:s.num_tokens].tolist()
-                self.kv_mgr.free(s)
-                del self.active[s.id]
-                del self.sampling[s.id]
-                self.draft_computed.pop(s.id, None)
+                self._retire(s, finished)
         return finished
+
 
     def run(self) -> Dict[int, List[int]]:
         """step() until nothing is running or waiting -> every finished sequence."""
