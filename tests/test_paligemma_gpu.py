@@ -205,11 +205,20 @@ def test_model_and_cached_greedy_loop_fp32_vs_notebook(golden):
     assert torch.allclose(m.norm.weight, before + 1.0)
 
 
-def test_single_sequence_step_lean_kernels_vs_general_and_fp32():
-    """B = 1 bf16 decode at the true Gemma-2B widths (d 2048, 8 x 256 query heads on one KV head, MLP 16384): the
-    straight-line matrix-vector kernels with the RMSNorms folded into pre-scaled weights and the rotary embedding
-    fused into the QKV product (vy_decode.hip) against the general chain (RMSNorm / QKV / RoPE launches), and both
-    against the fp32 step on the same weights and cache contents: same error level."""
+def gemma_last():
+    import ctypes as C
+    from vyomai_amd import _lib
+    out = (C.c_int * 4)()
+    _lib.load().vy_debug_gemma_last(out)
+    return tuple(out)
+
+
+def _lean_general_fp32(txt_cfg, prefix, B, lean_layers):
+    """One decode step of a Gemma stack in bf16 on three plans -- pre-scaled weights, plain weights, and plain weights
+    with the B = 1 kernels switched off -- and in fp32 on the same weights and cache contents.  lean_layers: how many
+    layers must report the straight-line B = 1 kernels while they are on (vy_debug_gemma_last; 0 where no lean kernel
+    serves the shape: the fused matrix-vector chain of vy_gemm.hip runs instead and meets the same bars)."""
+    import copy
     import ctypes as C
     from vyomai_amd import _lib
     from vyomai_amd.decode_plan import GemmaDecodePlan
@@ -217,36 +226,40 @@ def test_single_sequence_step_lean_kernels_vs_general_and_fp32():
     lib = _lib.load()
     lib.vy_debug_set_gemma_lean.argtypes = [C.c_int]
     vis = P.SiglipVisionConfig(**dict(cases.SIGLIP, num_hidden_layers=1))
-    txt = types.SimpleNamespace(**dict(cases.GEMMA, num_hidden_layers=2, vocab_size=4096))
+    txt = types.SimpleNamespace(**txt_cfg)
+    nl, hk, dh = txt.num_hidden_layers, txt.num_key_value_heads, txt.head_dim
 
-    def model(dt):
-        m = P.PaliGemmaForConditionalGeneration(P.PaliGemmaShape(vis, txt, txt.hidden_size))
-        for n, p in m.named_parameters():
-            with torch.no_grad():
-                p.copy_(T(recipe.param_value("pgl." + n, tuple(p.shape))))
-        return m.to(DEV).to(dt).eval()
+    m32 = P.PaliGemmaForConditionalGeneration(P.PaliGemmaShape(vis, txt, txt.hidden_size))
+    for n, p in m32.named_parameters():
+        with torch.no_grad():
+            p.copy_(T(recipe.param_value(prefix + n, tuple(p.shape))))
+    m16 = copy.deepcopy(m32).to(DEV).to(torch.bfloat16).eval()
+    m32 = m32.to(DEV).eval()
 
     def caches(dt):
         g = torch.Generator().manual_seed(3)
-        return [(torch.randn(1, 1, 64, 256, generator=g).to(dt).to(DEV), torch.randn(1, 1, 64, 256, generator=g).to(dt).to(DEV))
-                for _ in range(2)]
+        return [(torch.randn(B, hk, 64, dh, generator=g).to(dt).to(DEV), torch.randn(B, hk, 64, dh, generator=g).to(dt).to(DEV))
+                for _ in range(nl)]
 
-    x = (torch.randn(1, txt.hidden_size, generator=torch.Generator().manual_seed(4)) * 0.3)
+    x = (torch.randn(B, txt.hidden_size, generator=torch.Generator().manual_seed(4)) * 0.3)
     pos = 40
-    m16, m32 = model(torch.bfloat16), model(torch.float32)
     res = {}
     try:
         for name, lean, prescale in (("lean", 1, True), ("lean_noscale", 1, False), ("general", 0, False)):
             lib.vy_debug_set_gemma_lean(lean)
             cs = caches(torch.bfloat16)
-            plan = GemmaDecodePlan(m16, cs, 1, prescale=prescale)
-            res[name] = (plan.step(x.to(torch.bfloat16).to(DEV), pos).float().clone(),
-                         [c[0][:, :, pos].float().clone() for c in cs])
+            plan = GemmaDecodePlan(m16, cs, B, prescale=prescale)
+            out = plan.step(x.to(torch.bfloat16).to(DEV), pos).float().clone()
+            # which chain ran, before any number is compared: the fused matrix-vector chain, every layer (or none) on the
+            # B = 1 kernels, RMSNorm folded or not, rotary embedding inside the QKV product
+            assert gemma_last() == (1, lean_layers if lean else 0, int(prescale), 1), (name, gemma_last())
+            res[name] = (out, [c[0][:, :, pos].float().clone() for c in cs], [c[1][:, :, pos].float().clone() for c in cs])
             torch.cuda.synchronize()
     finally:
         lib.vy_debug_set_gemma_lean(1)
     cs32 = caches(torch.float32)
-    ref = GemmaDecodePlan(m32, cs32, 1).step(x.to(DEV), pos).float()
+    ref = GemmaDecodePlan(m32, cs32, B).step(x.to(DEV), pos).float()
+    assert gemma_last() == (0, 0, 0, 0), gemma_last()          # fp32: the MFMA chain
     e = {k: (v[0] - ref).abs().mean().item() for k, v in res.items()}
     scale = ref.abs().mean().item()
     assert e["general"] < 0.05 * scale + 1e-3, (e, scale)           # the bf16 error level of the general chain
@@ -255,3 +268,33 @@ def test_single_sequence_step_lean_kernels_vs_general_and_fp32():
     for name in ("lean", "lean_noscale"):   # rotated K rows written into the cache
         for a, b in zip(res[name][1], res["general"][1]):
             assert (a - b).abs().max().item() <= 0.05 * max(1.0, b.abs().max().item()), name
+        for a, b in zip(res[name][2], res["general"][2]):   # and the V rows
+            assert (a - b).abs().max().item() <= 0.05 * max(1.0, b.abs().max().item()), (name, "v")
+
+
+def test_single_sequence_step_lean_kernels_vs_general_and_fp32():
+    """B = 1 bf16 decode at the true Gemma-2B widths (d 2048, 8 x 256 query heads on one KV head, MLP 16384): the
+    straight-line matrix-vector kernels with the RMSNorms folded into pre-scaled weights and the rotary embedding
+    fused into the QKV product (vy_decode.hip) against the general chain (RMSNorm / QKV / RoPE launches), and both
+    against the fp32 step on the same weights and cache contents: same error level."""
+    _lean_general_fp32(dict(cases.GEMMA, num_hidden_layers=2, vocab_size=4096), "pgl.", 1, 2)
+
+
+def _one_layer(d, h, hk, dh, ffn, bias=False):
+    return dict(cases.GEMMA, num_hidden_layers=1, vocab_size=512, hidden_size=d, num_attention_heads=h,
+                num_key_value_heads=hk, head_dim=dh, intermediate_size=ffn, attention_bias=bias)
+
+
+@pytest.mark.parametrize("d,h,hk,dh,ffn,bias,B,lean_layers", [
+    (2048, 8, 1, 256, 16384, False, 1, 1),    # K = 2048 (QKV, gated, o_proj), 16384 (down): <4,1> and <GV_PLAIN,8,4>
+    (4096, 16, 2, 256, 4096, True, 1, 1),     # K = 4096 on all four links (<8,1>), hk = 2: real cache strides; biases
+    (2048, 32, 4, 256, 8192, False, 1, 1),    # o_proj and down at K = 8192 (<GV_PLAIN,8,2>)
+    (8192, 8, 1, 256, 2048, False, 1, 1),     # QKV and gated at K = 8192 (<GV_QKV / GV_GATED,8,2>)
+    (2048, 8, 1, 256, 16384, False, 2, 0),    # B = 2: gemv_bf16_kernel's PRESCALED / GATED / rope forms
+    (1536, 6, 1, 256, 4096, False, 1, 0),     # d = 1536: no lean K serves it, the fused gemv chain runs at B = 1
+], ids=lambda v: str(v))
+def test_gemma_step_chains_one_layer(d, h, hk, dh, ffn, bias, B, lean_layers):
+    """One-layer Gemma stacks that put every K instantiation of the B = 1 kernels (and, where none serves, the general
+    matrix-vector chain) under a whole step: which chain ran is asserted first, then the bars of the test above, on
+    the hidden state, the K rows and the V rows."""
+    _lean_general_fp32(_one_layer(d, h, hk, dh, ffn, bias), f"pg1.{d}.{h}.{ffn}.", B, lean_layers)

@@ -736,13 +736,13 @@ int vy_dec_linear_res_ln(const void* x, int ldx, const void* w, const void* bias
 static bool gemv1_ok(const void* x, const void* w, int N, int K) {
   return N % 4 == 0 && (K == 2048 || K == 4096 || K == 8192 || K == 16384) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0);
 }
-int vy_dec_gemv1(const void* x, const void* w, const void* bias, const void* residual, void* y, int N, int K, int prescaled,
-                 float eps, hipStream_t st) {
+// (the plain product has no NORM form: both of its call sites, o_proj and down_proj, take x as it is)
+int vy_dec_gemv1(const void* x, const void* w, const void* bias, const void* residual, void* y, int N, int K, hipStream_t st) {
   if (!gemv1_ok(x, w, N, K)) return VY_ERR_UNSUPPORTED;
   DecGemvArgs a{};
   a.x = (const bf16*)x; a.w = (const bf16*)w; a.bias = (const bf16*)bias; a.residual = (const bf16*)residual; a.y = (bf16*)y;
-  a.N = N; a.K = K; a.ldw = K; a.eps = eps;
-  if (prescaled ? dec_gemv1_go<GV_PLAIN, true>(a, st) : dec_gemv1_go<GV_PLAIN, false>(a, st)) return VY_ERR_UNSUPPORTED;
+  a.N = N; a.K = K; a.ldw = K;
+  if (dec_gemv1_go<GV_PLAIN, false>(a, st)) return VY_ERR_UNSUPPORTED;
   VY_CHECK_LAUNCH("vy_dec_gemv1");
   return VY_OK;
 }
@@ -766,6 +766,21 @@ int vy_dec_gemv1_qkv(const void* x, const void* w, const void* bias, void* q, vo
   if (prescaled ? dec_gemv1_go<GV_QKV, true>(a, st) : dec_gemv1_go<GV_QKV, false>(a, st)) return VY_ERR_UNSUPPORTED;
   VY_CHECK_LAUNCH("vy_dec_gemv1_qkv");
   return VY_OK;
+}
+// test aids, not part of include/vyom_hip.h: the three launchers above as they are (same arguments, same return code),
+// so that a test can drive one link at a time
+extern "C" int vy_debug_dec_gemv1(const void* x, const void* w, const void* bias, const void* residual, void* y, int N, int K,
+                                  void* stream) {
+  return vy_dec_gemv1(x, w, bias, residual, y, N, K, (hipStream_t)stream);
+}
+extern "C" int vy_debug_dec_gemv1_gated(const void* x, const void* wgu, void* y, int I, int K, int prescaled, float eps,
+                                        void* stream) {
+  return vy_dec_gemv1_gated(x, wgu, y, I, K, prescaled, eps, (hipStream_t)stream);
+}
+extern "C" int vy_debug_dec_gemv1_qkv(const void* x, const void* w, const void* bias, void* q, void* k, void* v, int64_t c_sh,
+                                      int h, int hk, int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K,
+                                      int prescaled, float eps, void* stream) {
+  return vy_dec_gemv1_qkv(x, w, bias, q, k, v, c_sh, h, hk, dh, cos_tab, sin_tab, pos, K, prescaled, eps, (hipStream_t)stream);
 }
 
 // single-query attention of the decode steps.  smax: an upper bound of the context length when it is read on the

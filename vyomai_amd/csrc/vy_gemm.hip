@@ -2131,6 +2131,24 @@ int vy_gemv_gated(const void* x, int64_t ldx, const void* w, int64_t ldw, int pr
   VY_CHECK_LAUNCH("vy_gemv_gated");
   return VY_OK;
 }
+// test aids, not part of include/vyom_hip.h: the three launchers above as they are (same arguments, same return code)
+extern "C" int vy_debug_gemv_norm(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, int prescaled,
+                                  float eps, const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t M, int64_t N,
+                                  int64_t K, void* stream) {
+  return vy_gemv_norm(x, ldx, w, ldw, bias, prescaled, eps, residual, ldr, y, ldy, M, N, K, stream);
+}
+extern "C" int vy_debug_gemv_qkv_norm(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, int prescaled,
+                                      float eps, void* q, int64_t q_sb, int64_t q_sh, void* k, int64_t k_sb, int64_t k_sh,
+                                      int64_t k_sl, void* v, int64_t v_sb, int64_t v_sh, int64_t v_sl, int64_t B, int64_t K,
+                                      int h, int hk, int dh, const float* cos_tab, const float* sin_tab, int64_t pos,
+                                      void* stream) {
+  return vy_gemv_qkv_norm(x, ldx, w, ldw, bias, prescaled, eps, q, q_sb, q_sh, k, k_sb, k_sh, k_sl, v, v_sb, v_sh, v_sl, B, K, h,
+                          hk, dh, cos_tab, sin_tab, pos, stream);
+}
+extern "C" int vy_debug_gemv_gated(const void* x, int64_t ldx, const void* w, int64_t ldw, int prescaled, float eps, void* y,
+                                   int64_t ldy, int64_t M, int64_t I, int64_t K, int act, void* stream) {
+  return vy_gemv_gated(x, ldx, w, ldw, prescaled, eps, y, ldy, M, I, K, act, stream);
+}
 
 int vy_qkv_rope_fwd_ex(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias,
                        const float* cos_tab, const float* sin_tab, int64_t pos0, const int* pos_dev, void* q,

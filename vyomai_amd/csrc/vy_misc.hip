@@ -959,6 +959,8 @@ extern "C" int vy_rmsnorm_fwd(const void* x, int64_t ldx, const void* w, void* y
   else if (nch <= 256) RMS_GO(T, 4);                     \
   else if (nch <= 512) RMS_GO(T, 8);                     \
   else if (nch <= 1024) RMS_GO(T, 16);                   \
+  /* fp32 rows up to the 8192 columns bf16 rows reach (the fp32 Gemma step at d = 8192) */ \
+  else if (nch <= 2048 && dtype == VY_F32) RMS_GO(float, 32); \
   else VY_FAIL(VY_ERR_UNSUPPORTED, "vy_rmsnorm_fwd: N=%ld too wide", (long)N)
   if (dtype == VY_BF16) { RMS_DISPATCH(bf16); }
   else if (dtype == VY_F32) { RMS_DISPATCH(float); }

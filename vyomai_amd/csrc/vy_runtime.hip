@@ -46,9 +46,14 @@ static int g_decode_lean = 1;
 static int g_gemma_lean = 1;
 extern "C" int vy_debug_set_decode_lean(int v) { g_decode_lean = v; return 0; }
 extern "C" int vy_debug_set_gemma_lean(int v) { g_gemma_lean = v; return 0; }
+// what the last vy_gemma_decoder_step ran: {chain (0 = MFMA chain, 1 = fused matrix-vector chain), layers whose four
+// products all ran the lean B = 1 kernels, prescaled, rope_fused}.  Host-side statics only.
+static int g_gemma_last[4];
+extern "C" void vy_debug_gemma_last(int out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = g_gemma_last[i];
+}
 
-int vy_dec_gemv1(const void* x, const void* w, const void* bias, const void* residual, void* y, int N, int K, int prescaled,
-                 float eps, hipStream_t st);
+int vy_dec_gemv1(const void* x, const void* w, const void* bias, const void* residual, void* y, int N, int K, hipStream_t st);
 int vy_dec_gemv1_gated(const void* x, const void* wgu, void* y, int I, int K, int prescaled, float eps, hipStream_t st);
 int vy_dec_gemv1_qkv(const void* x, const void* w, const void* bias, void* q, void* k, void* v, int64_t c_sh, int h, int hk,
                      int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K, int prescaled, float eps,
@@ -243,6 +248,7 @@ extern "C" int vy_gemma_decoder_step(const vy_gemma_plan* p, const void* x, int6
   const bool prescaled = fused && (p->flags & VY_GEMMA_PRESCALED);
   const bool rope_fused = fused && p->cos_tab && dh % 4 == 0 && (dh & (dh - 1)) == 0;
   const bool lean1 = fused && g_gemma_lean && B == 1;
+  g_gemma_last[0] = fused; g_gemma_last[1] = 0; g_gemma_last[2] = prescaled; g_gemma_last[3] = rope_fused;
   for (int l = 0; l < p->num_layers; ++l) {
     const vy_gemma_layer& L = p->layers[l];
     void* kdst = (char*)L.kcache + pos * L.c_sl * e;
@@ -274,7 +280,9 @@ extern "C" int vy_gemma_decoder_step(const vy_gemma_plan* p, const void* x, int6
       }
       if ((rc = vy_attn_decode_ex(q, (int64_t)h * dh, dh, L.kcache, L.c_sb, L.c_sh, L.c_sl, L.vcache, L.c_sb, L.c_sh, L.c_sl,
                                   ao, (int64_t)h * dh, B, h, hk, pos + 1, nullptr, dh, scale, p->dtype, stream))) return rc;
-      rc = lean_layer ? vy_dec_gemv1(ao, L.wo, L.bo, cur, x1, d, h * dh, 0, 0.f, hs) : VY_ERR_UNSUPPORTED;
+      int lean_links = lean_layer;
+      rc = lean_layer ? vy_dec_gemv1(ao, L.wo, L.bo, cur, x1, d, h * dh, hs) : VY_ERR_UNSUPPORTED;
+      lean_links += rc == VY_OK && lean_layer;
       if (rc == VY_ERR_UNSUPPORTED)
         rc = vy_gemv_norm(ao, (int64_t)h * dh, L.wo, (int64_t)h * dh, L.bo, 0, 0.f, cur, d, x1, d, B, d, (int64_t)h * dh, stream);
       if (rc) return rc;
@@ -284,12 +292,15 @@ extern "C" int vy_gemma_decoder_step(const vy_gemma_plan* p, const void* x, int6
         gin = n;
       }
       rc = lean_layer ? vy_dec_gemv1_gated(gin, L.wgu, act, ffn, d, prescaled, p->eps, hs) : VY_ERR_UNSUPPORTED;
+      lean_links += rc == VY_OK && lean_layer;
       if (rc == VY_ERR_UNSUPPORTED)
         rc = vy_gemv_gated(gin, d, L.wgu, d, prescaled, p->eps, act, ffn, B, ffn, d, VY_ACT_GELU_TANH, stream);
       if (rc) return rc;
-      rc = lean_layer ? vy_dec_gemv1(act, L.wdown, nullptr, x1, nxt, d, ffn, 0, 0.f, hs) : VY_ERR_UNSUPPORTED;
+      rc = lean_layer ? vy_dec_gemv1(act, L.wdown, nullptr, x1, nxt, d, ffn, hs) : VY_ERR_UNSUPPORTED;
+      lean_links += rc == VY_OK && lean_layer;
       if (rc == VY_ERR_UNSUPPORTED) rc = vy_gemv_norm(act, ffn, L.wdown, ffn, nullptr, 0, 0.f, x1, d, nxt, d, B, d, ffn, stream);
       if (rc) return rc;
+      g_gemma_last[1] += lean_links == 4;
       cur = nxt;
       continue;
     }
