@@ -635,6 +635,31 @@ int vy_spec_verify(const void* target_logits, int64_t ldt, int64_t t_rows, const
                    const float* top_p, const int64_t* seed, const int64_t* position0, int32_t* accept, int64_t* alt,
                    void* stream);
 
+/* vy_lora_shrink / vy_lora_expand: the per-request LoRA delta of a serving step (reference layers/adapters.py
+ *   LoraLinear.forward: linear(x) + scale * F.linear(F.linear(x, lora_a), lora_b); lora_dropout is the identity at
+ *   inference), added in place AFTER the projection's own GEMM, whatever its epilogue did (bias, residual):
+ *     u[t, 0:R]  = x[t, 0:K] @ A[slot].T                                              (shrink)
+ *     y[t, n]   += alpha[slot] * sum_{j < r_pad} u[t, part(n) * r_pad + j] * B[slot][n, j]     (expand)
+ *   for the rows t of the tiles.  tiles: device int32 (n_tiles, 3) = (row0, nrows, slot): nrows <= 16 consecutive rows
+ *   of the packed buffer that belong to one request.  A tile is skipped UNREAD -- no load, no store -- when slot lies
+ *   outside [0, slots), when nrows lies outside [1, 16] or when its rows leave [0, T).  Rows outside every tile, the
+ *   columns N .. ldy - 1 of y and everything behind row T are never written.  Two tiles must not share a row.
+ *   A: (slots, R, K) contiguous, R = parts * r_pad, the lora_a of a packed projection's parts stacked ([A_q; A_k; A_v],
+ *   [A_gate; A_up]), each part's rank padded with zero rows to r_pad.  B: (slots, N, r_pad) contiguous, the parts'
+ *   lora_b stacked along N, padded with zero columns.  part(n) = (n >= bound0) + (n >= bound1); a boundary that is not
+ *   used is passed as N.  alpha: fp32 (slots).  x, A, u, B, y share `dtype`.
+ *   Rounding: products accumulate in fp32 (bf16: mfma_f32_16x16x32_bf16; fp32: mfma_f32_16x16x4f32, a k-ordered fma
+ *   chain per quarter of K, the quarters added in order); u is stored in `dtype` -- in bf16 that is the reference's own
+ *   rounding of F.linear(x, lora_a) -- and y = round(fmaf(alpha, sum, y)), rounded once.
+ *   Shape limits: K % 32 == 0, r_pad % 32 == 0, N % 16 == 0, boundaries % 16 == 0 with 0 < bound0 <= bound1 <= N,
+ *   ldu >= R; rows of x, A, u (as expand reads it) and B 16-byte aligned, rows of u (as shrink writes it) and y aligned
+ *   to four elements.  n_tiles == 0 launches nothing.  VY_ERR_ARG otherwise, and for a null pointer or unknown dtype. */
+int vy_lora_shrink(const void* x, int64_t ldx, const void* A, const int32_t* tiles, int64_t n_tiles, void* u,
+                   int64_t ldu, int64_t T, int64_t K, int64_t R, int64_t slots, int dtype, void* stream);
+int vy_lora_expand(void* y, int64_t ldy, const void* u, int64_t ldu, const void* B, const float* alpha,
+                   const int32_t* tiles, int64_t n_tiles, int64_t T, int64_t N, int64_t r_pad, int64_t slots,
+                   int64_t bound0, int64_t bound1, int dtype, void* stream);
+
 /* y = x converted between fp32 and bf16 (n elements). src_dtype -> dst_dtype. */
 int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);
 

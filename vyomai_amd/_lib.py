@@ -89,6 +89,8 @@ PROTOTYPES = {
     "vy_sampling_probs": [_p, _i64, _i64, _i64, _i, _f, _i, _f, _p, _i64, _p],
     "vy_sample_rows": [_p, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p],
     "vy_spec_verify": [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "vy_lora_shrink": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p],
+    "vy_lora_expand": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "vy_decoder_step": [_p, _p, _i64, _p, _p, _p, _i64, _p],
     "vy_gemma_decoder_step": [_p, _p, _i64, _p, _i64, _p],
     "vy_cast": [_p, _p, _i64, _i, _i, _p],

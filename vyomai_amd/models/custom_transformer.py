@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import VyomHipError
+from ..adapters import layer_delta
 from ..autograd import _mask_args, _wants_grad
 from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
@@ -110,14 +111,21 @@ class MLP(nn.Module):
             hit = self._gu = (key, torch.cat([g, u], dim=0).contiguous())
         return hit[1]
 
-    def forward(self, x, residual: Optional[torch.Tensor] = None):
+    def forward(self, x, residual: Optional[torch.Tensor] = None, delta=None):
+        """delta (serving with adapters, adapters.layer_delta): f(group, y, x), called behind each of the two GEMMs."""
         _need_gpu(x, "MLP")
         if _wants_grad(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight):
             raise VyomHipError("the gated MLP trains inside its pre-norm block (DecoderLayer: RMSNorm, MLP and the "
                                "residual add are one autograd function); call it under torch.no_grad() on its own")
         dt = x.dtype
         gu = ops.linear(x, self._packed_gate_up(dt))
-        return ops.linear(ops.gated_act(gu, self.act), _shadow(self.down_proj.weight, dt), None, residual=residual)
+        if delta is not None:
+            delta("gate_up", gu, x)
+        h = ops.gated_act(gu, self.act)
+        y = ops.linear(h, _shadow(self.down_proj.weight, dt), None, residual=residual)
+        if delta is not None:
+            delta("down", y, h)
+        return y
 
 
 class Attention(_SelfAttentionBase):
@@ -487,12 +495,18 @@ class ModelForCausalLM(nn.Module):
             h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
             kc, vc = kv_mgr.k_cache[a.layer_idx], kv_mgr.v_cache[a.layer_idx]
             sw, sb = a._packed_shadow(dt)
-            qkv = ops.linear(layer.input_layernorm(x), sw, sb)
+            delta = layer_delta(metadata, a.layer_idx)      # a step with adapted rows: the LoRA delta behind each GEMM
+            n = layer.input_layernorm(x)
+            qkv = ops.linear(n, sw, sb)
+            if delta is not None:
+                delta("qkv", qkv, n)
             sc = page_scales(kv_mgr, a.layer_idx)      # fp8 pages: their scales; else nothing
             ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc, **sc)
             o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh, **sc)
             x = ops.linear(o, _shadow(a.o_proj.weight, dt), None, residual=x)
-            x = layer.mlp(layer.post_attention_layernorm(x), residual=x)
+            if delta is not None:
+                delta("o", x, o)
+            x = layer.mlp(layer.post_attention_layernorm(x), residual=x, delta=delta)
         return paged_step_logits(x, metadata["last_rows"], base.norm, self.lm_head.weight)
 
     @torch.no_grad()

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import ACT_SILU, VyomHipError
+from ..adapters import layer_delta
 from ..layers.attention import _shadow
 from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
 from .custom_transformer import _need_gpu
@@ -78,10 +79,17 @@ class FeedForward(nn.Module):
         self.fc1, self.fc2, self.fc3 = _linear(cfg, d, f), _linear(cfg, d, f), _linear(cfg, f, d)
 
     @torch.no_grad()
-    def forward(self, x, residual: Optional[torch.Tensor] = None):
+    def forward(self, x, residual: Optional[torch.Tensor] = None, delta=None):
+        """delta (serving with adapters, adapters.layer_delta): f(group, y, x), called behind each of the two GEMMs."""
         _need_gpu(x, "FeedForward")
         gu = ops.linear(x, _packed_rows(self, "_vy_gu", (self.fc1, self.fc2), x.dtype))
-        return ops.linear(ops.gated_act(gu, ACT_SILU), _shadow(self.fc3.weight, x.dtype), None, residual=residual)
+        if delta is not None:
+            delta("gate_up", gu, x)
+        h = ops.gated_act(gu, ACT_SILU)
+        y = ops.linear(h, _shadow(self.fc3.weight, x.dtype), None, residual=residual)
+        if delta is not None:
+            delta("down", y, h)
+        return y
 
 
 class GroupedQueryAttention(nn.Module):
@@ -194,7 +202,11 @@ class Qwen3Model(nn.Module):
             a = blk.att
             h, hk, dh = a.num_heads, a.num_kv_groups, a.head_dim
             kc, vc = kv_mgr.k_cache[a.layer_idx], kv_mgr.v_cache[a.layer_idx]
-            qkv = ops.linear(blk.norm1(x), a._packed_qkv(dt))
+            delta = layer_delta(metadata, a.layer_idx)      # a step with adapted rows: the LoRA delta behind each GEMM
+            n = blk.norm1(x)
+            qkv = ops.linear(n, a._packed_qkv(dt))
+            if delta is not None:
+                delta("qkv", qkv, n)
             sc = page_scales(kv_mgr, a.layer_idx)      # fp8 pages: their scales; else nothing
             if a.q_norm is not None:
                 if a.q_norm.eps != a.k_norm.eps:
@@ -206,7 +218,9 @@ class Qwen3Model(nn.Module):
                 ops.paged_rope_write_(qkv, positions, slots, cos, sin, h, kc, vc, **sc)
             o = paged_step_attention(qkv, kc, vc, metadata, h, hk, dh, **sc)
             x = ops.linear(o, _shadow(a.out_proj.weight, dt), None, residual=x)
-            x = blk.ff(blk.norm2(x), residual=x)
+            if delta is not None:
+                delta("o", x, o)
+            x = blk.ff(blk.norm2(x), residual=x, delta=delta)
         return paged_step_logits(x, metadata["last_rows"], self.final_norm, self.out_head.weight)
 
 

@@ -7,7 +7,7 @@ is no CPU or eager fallback.
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -835,6 +835,65 @@ def spec_verify(target_logits: Tensor, draft_logits: Tensor, draft_tokens: Tenso
          draft_tokens.data_ptr(), t_row0.data_ptr(), n_draft.data_ptr(), inv_temperature.data_ptr(), top_k.data_ptr(),
          top_p.data_ptr(), seed.data_ptr(), position0.data_ptr(), accept.data_ptr(), alt.data_ptr(), _stream())
     return accept, alt
+
+
+def lora_delta_(y: Tensor, x: Tensor, A: Tensor, B: Tensor, alpha: Tensor, tiles: Tensor, n_tiles: int,
+                boundaries: Sequence[int] = (), name: str = "projection") -> Tensor:
+    """y[t] += alpha[s] * (x[t] @ A[s].T) @ B[s].T in place for the rows of the tiles, s the tile's adapter slot
+    (vy_lora_shrink, then vy_lora_expand; the rule: include/vyom_hip.h) -> y.  y (T, N) is the output of the
+    projection's own GEMM over x (T, K) (its row stride may be padded), A (slots, parts * r_pad, K) and
+    B (slots, N, r_pad) the stacked adapters of the projection's parts, which start at column 0 and at `boundaries` (at
+    most two), alpha fp32 (slots,), tiles the int32 (n_tiles, 3) device view of (row0, nrows <= 16, slot).  n_tiles is
+    the host's count: it sizes the grid and 0 launches nothing.  `name`: the projection, for the messages."""
+    n_tiles = int(n_tiles)
+    if n_tiles == 0:
+        return y
+    for what, t in (("y", y), ("x", x), ("A", A), ("B", B), ("alpha", alpha), ("tiles", tiles)):
+        if not isinstance(t, Tensor):
+            raise ValueError(f"lora_delta_ ({name}): {what} must be a tensor")
+    if y.dtype not in (torch.float32, torch.bfloat16) or not (x.dtype == A.dtype == B.dtype == y.dtype):
+        raise ValueError(f"lora_delta_ ({name}): y, x, A and B must share float32 or bfloat16, got {y.dtype}, {x.dtype}, "
+                         f"{A.dtype}, {B.dtype}")
+    if y.dim() != 2 or x.dim() != 2 or x.shape[0] != y.shape[0] or y.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError(f"lora_delta_ ({name}): y (T, N) and x (T, K) must be 2-D over the same rows with unit column "
+                         f"stride, got {tuple(y.shape)} strides {y.stride()} and {tuple(x.shape)} strides {x.stride()}")
+    (T, N), K = y.shape, x.shape[1]
+    bounds = [int(b) for b in boundaries]
+    if len(bounds) > 2 or any(b % 16 for b in bounds) or bounds != sorted(set(bounds)) or (bounds and not 0 < bounds[0]) \
+            or (bounds and bounds[-1] >= N):
+        raise ValueError(f"lora_delta_ ({name}): boundaries {bounds} must be at most two increasing multiples of 16 "
+                         f"inside (0, {N})")
+    if T < 1 or K % 32 or N % 16 or K < 32 or N < 16:
+        raise ValueError(f"lora_delta_ ({name}): K = {K} must be a multiple of 32 and N = {N} (every part's width) a "
+                         "multiple of 16")
+    parts = 1 + len(bounds)
+    if A.dim() != 3 or B.dim() != 3 or not A.is_contiguous() or not B.is_contiguous() or A.shape[0] != B.shape[0] \
+            or A.shape[2] != K or B.shape[1] != N or B.shape[2] % 32 or A.shape[1] != parts * B.shape[2] or A.shape[0] < 1:
+        raise ValueError(f"lora_delta_ ({name}): A must be a contiguous (slots, {parts} * r_pad, {K}) and B a contiguous "
+                         f"(slots, {N}, r_pad) tensor with r_pad a multiple of 32, got {tuple(A.shape)} and {tuple(B.shape)}")
+    slots, _, r_pad = B.shape
+    if alpha.dtype != torch.float32 or alpha.dim() != 1 or alpha.numel() != slots or alpha.stride(0) != 1:
+        raise ValueError(f"lora_delta_ ({name}): alpha must be a contiguous float32 tensor of {slots} elements")
+    if tiles.dtype != torch.int32 or tiles.numel() != 3 * n_tiles or not tiles.is_contiguous() or n_tiles < 0:
+        raise ValueError(f"lora_delta_ ({name}): tiles must be a contiguous int32 tensor of {n_tiles} x 3 elements, got "
+                         f"{tiles.dtype} {tuple(tiles.shape)}")
+    es = y.element_size()
+    if y.stride(0) < N or y.stride(0) % 4 or y.data_ptr() % (4 * es) or x.stride(0) < K or (x.stride(0) * es) % 16 \
+            or x.data_ptr() % 16:
+        raise ValueError(f"lora_delta_ ({name}): rows of x must be 16-byte aligned and rows of y aligned to four "
+                         f"elements (row strides {x.stride(0)}, {y.stride(0)})")
+    for what, t in (("x", x), ("A", A), ("B", B), ("alpha", alpha), ("tiles", tiles)):
+        if t.device != y.device:
+            raise ValueError(f"lora_delta_ ({name}): {what} is on {t.device}, y on {y.device}")
+    _need_gpu(y)
+    R = parts * r_pad
+    u = torch.empty((T, R), dtype=y.dtype, device=y.device)
+    st, code = _stream(), dtype_code(y.dtype)
+    call("vy_lora_shrink", x.data_ptr(), x.stride(0), A.data_ptr(), tiles.data_ptr(), n_tiles, u.data_ptr(), R, T, K, R,
+         slots, code, st)
+    call("vy_lora_expand", y.data_ptr(), y.stride(0), u.data_ptr(), R, B.data_ptr(), alpha.data_ptr(), tiles.data_ptr(),
+         n_tiles, T, N, r_pad, slots, *(bounds + [N, N])[:2], code, st)
+    return y
 
 
 def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[int]) -> None:

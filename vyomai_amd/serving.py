@@ -91,7 +91,21 @@ free list and tree stay idle.  Invariant: both models write the same slots in th
 cache hands out holds valid rows of both models, and eviction and reuse overwrite both.  Speculative rows land only at
 positions >= prompt_len, in blocks that are never registered: a rejected draft never touches a shared block, its slot is
 simply overwritten later, and g_s keeps every write inside the blocks admission reserved.  The reference's
-skip_sample_adjustment is not carried over."""
+skip_sample_adjustment is not carried over.
+
+LoRA adapters (ContinuousBatchEngine(..., adapters=LoraAdapters(...)) and add_sequence(..., adapter="name"); needs
+varlen_prefill; off by default).  Requests with different adapters, or none, share the ONE packed forward over the ONE
+copy of the base weights: _PackedRows records, while it builds the segments, the tiles (row0, nrows <= 16, slot) of the
+adapted rows -- consecutive rows of one request, cut every 16: a decoding row is one tile, a verification segment of
+g + 1 rows one (or two), a prompt chunk of n rows ceil(n / 16) -- and puts them into the step's int32 upload;
+metadata["lora"] = {"tiles", "n_tiles", "adapters"} then makes forward_paged add the delta behind each of a layer's four
+GEMMs (vy_lora_shrink / vy_lora_expand, include/vyom_hip.h).  The tile count is known on the host and sizes the grid.
+A step WITHOUT an adapted row uploads and launches exactly what it does in an engine without a store.  The drafter of
+a speculative engine serves base weights (its forwards never carry tiles): the accept / reject rule is exact for any
+drafter.  K/V depend on the adapter, so the prefix cache keys the FIRST block of a chain by (uid,) + tokens, uid the
+id of that load of the adapter (a name loaded again with other weights is another adapter); requests without an adapter
+use today's keys.  A request holds its adapter from add_sequence until it retires (LoraAdapters.unload refuses
+meanwhile)."""
 from __future__ import annotations
 
 import itertools
@@ -165,8 +179,9 @@ class SequenceState:
     token (slot_mapping), all on the host.  `prefix_len` tokens were found in the prefix cache and are not computed."""
 
     def __init__(self, sid: int, prompt_ids: Sequence[int], max_gen_len: int, block_size: int, device="cpu",
-                 matched_blocks: Optional[Sequence[int]] = None):
+                 matched_blocks: Optional[Sequence[int]] = None, salt=None):
         self.id, self.device, self.block_size = sid, torch.device(device), block_size
+        self.salt = salt              # what keys the first block of its chain in the prefix cache (None: the tokens alone)
         matched_blocks = list(matched_blocks or [])
         self.prefix_len = len(matched_blocks) * block_size
         p_len = len(prompt_ids)
@@ -266,12 +281,14 @@ class PagedKVManager:
         return (num_tokens + self.block_size - 1) // self.block_size
 
     # ---- prefix cache ----------------------------------------------------------------------------------------
-    def match_prefix(self, token_ids: Sequence[int]) -> List[int]:
+    def match_prefix(self, token_ids: Sequence[int], salt=None) -> List[int]:
         """Block ids of the longest cached chain of whole blocks in front of token_ids, at most
-        (len - 1) // block_size of them (one token is always left to compute).  No side effects."""
+        (len - 1) // block_size of them (one token is always left to compute).  No side effects.  salt (not None): the
+        chains registered by sequences of that salt only -- the first block's key is (salt,) + tokens."""
         bs, node, out = self.block_size, self.radix_root, []
         for i in range((len(token_ids) - 1) // bs):
-            node = node.children.get(tuple(int(t) for t in token_ids[i * bs:(i + 1) * bs]))
+            key = tuple(int(t) for t in token_ids[i * bs:(i + 1) * bs])
+            node = node.children.get(key if i or salt is None else (salt,) + key)
             if node is None:
                 break
             out.append(node.block_id)
@@ -329,6 +346,8 @@ class PagedKVManager:
             return                       # the parent lost its registration: this block stays private
         parent = self.block_to_node[int(state.block_table[i - 1])] if i else self.radix_root
         key = tuple(state.tokens[i * self.block_size:(i + 1) * self.block_size].tolist())
+        if i == 0 and state.salt is not None:
+            key = (state.salt,) + key
         if key in parent.children:
             return                       # the same tokens were registered by a concurrent sequence: stays private
         node = RadixNode(block_id, parent, key)
@@ -438,10 +457,15 @@ class _PackedRows:
     one query row of a decoding sequence, for vy_attn_paged_decode.  varlen(s, a, b, n_last): tokens [a, b) as a segment
     of the ONE vy_attn_paged_prefill launch (cu_q counts rows of the packed buffer, ctx_len = a).  per_sequence(s, a, b,
     n_last): the default engine's prefill (first row, rows, prefix_len, its block table after a prefix hit).
-    put() appends all of it to the step's uploads under `prefix`, metadata() builds the dict from the views."""
+    put() appends all of it to the step's uploads under `prefix`, metadata() builds the dict from the views.
+    lora = (the LoraAdapters store, {sid: adapter slot}): the rows of those sequences are recorded as tiles
+    (row0, nrows <= 16, slot), cut every 16 rows; put() uploads them only if there are any, and only then has the
+    metadata a "lora" entry."""
 
-    def __init__(self, width: int, tables: Dict[int, List[int]], prefix: str = ""):
+    def __init__(self, width: int, tables: Dict[int, List[int]], prefix: str = "", lora=None):
         self.width, self.tables, self.prefix = width, tables, prefix
+        self.adapters, self.slot_of = lora if lora is not None else (None, {})
+        self.tiles: List[int] = []
         self.ids, self.pos, self.slots, self.last = [], [], [], []
         self.dec_rows, self.dec_lens, self.dec_tables, self.prefill = [], [], [], []
         self.seg_rows, self.ctx, self.seg_tables, self.max_q, self.max_kv = [], [], [], 0, 0
@@ -452,6 +476,10 @@ class _PackedRows:
         self.pos += range(a, b)
         self.slots += s.slot_mapping[a:b].tolist()
         self.last += range(row0 + b - a - n_last, row0 + b - a)
+        slot = self.slot_of.get(s.id)
+        if slot is not None:
+            for r in range(row0, row0 + b - a, 16):
+                self.tiles += (r, min(16, row0 + b - a - r), slot)
         return row0
 
     def decode(self, s: SequenceState) -> None:
@@ -483,6 +511,8 @@ class _PackedRows:
             up.put32(p + "cu", self.seg_rows + [len(self.ids)])      # the varlen segments end the forward
             up.put32(p + "ctx", self.ctx)
             up.put32(p + "tab", self.seg_tables)
+        if self.tiles:
+            up.put32(p + "tiles", self.tiles)
 
     def metadata(self, at: Dict[str, torch.Tensor], max_position: int) -> dict:
         """at: what upload() returned."""
@@ -495,7 +525,10 @@ class _PackedRows:
                       "block_table": at[p + "tab"].view(len(self.ctx), self.width)}
         prefill = [(row0, n, prefix_len, None if table is None else at[f"{p}prefill{k}"])
                    for k, (row0, n, prefix_len, table) in enumerate(self.prefill)]
-        return _metadata(at[p + "pos"], at[p + "slots"], at[p + "last"], max_position, prefill, decode, varlen)
+        md = _metadata(at[p + "pos"], at[p + "slots"], at[p + "last"], max_position, prefill, decode, varlen)
+        if self.tiles:
+            md["lora"] = {"tiles": at[p + "tiles"].view(-1, 3), "n_tiles": len(self.tiles) // 3, "adapters": self.adapters}
+        return md
 
 
 class ContinuousBatchEngine:
@@ -511,6 +544,9 @@ class ContinuousBatchEngine:
     draft_model / draft_kv_mgr / num_speculative_tokens: speculative decoding (module docstring).  drafts_proposed /
     drafts_accepted count over the engine's life.
 
+    adapters: a LoraAdapters store (module docstring); add_sequence(..., adapter="name") then serves that request with
+    the adapter's weights, `adapter[sid]` holds the name while the request lives.
+
     prompt_tokens_computed[sid]: prompt tokens that went through the model so far (the rest came from the prefix cache).
     record_logits=True keeps every step's last-row logits per sequence in `logits[sid]` (fp32, host): a debug aid.  In a
     speculative engine that is one row per emitted token, the target row that decided it, and `rounds[sid]` holds per
@@ -519,7 +555,7 @@ class ContinuousBatchEngine:
     def __init__(self, model, kv_mgr: PagedKVManager, max_batch_size: int = 8, eos_token_ids=None,
                  record_logits: bool = False, max_step_tokens: Optional[int] = None,
                  varlen_prefill: Optional[bool] = None, draft_model=None, draft_kv_mgr: Optional[PagedKVManager] = None,
-                 num_speculative_tokens: int = 0):
+                 num_speculative_tokens: int = 0, adapters=None):
         if varlen_prefill is None:
             varlen_prefill = max_step_tokens is not None
         if max_step_tokens is not None:
@@ -537,6 +573,11 @@ class ContinuousBatchEngine:
             if computes != torch.bfloat16 or kv_mgr.dtype != torch.bfloat16:
                 raise ValueError(f"fp8 KV pages serve a model that computes in bfloat16: the model computes in "
                                  f"{computes}, the manager was built for {kv_mgr.dtype}")
+        if adapters is not None and not varlen_prefill:
+            raise ValueError("adapters= needs varlen_prefill=True: the tiles of the adapted rows are recorded by the "
+                             "planner of the one varlen prefill launch, the per-sequence prefill loop stays as it is")
+        self.adapters = adapters
+        self.adapter: Dict[int, str] = {}            # the requests that carry an adapter -> its name
         self.speculative = draft_model is not None or draft_kv_mgr is not None or num_speculative_tokens != 0
         if self.speculative:
             self._check_drafter(model, kv_mgr, draft_model, draft_kv_mgr, num_speculative_tokens, max_batch_size)
@@ -594,15 +635,22 @@ class ContinuousBatchEngine:
                              "1 + g rows of the budget and a prefilling one must still progress")
 
     def add_sequence(self, prompt_ids: Sequence[int], max_gen_len: int = 128,
-                     sampling: Optional[SamplingParams] = None) -> int:
+                     sampling: Optional[SamplingParams] = None, adapter: Optional[str] = None) -> int:
         """sampling=None: greedy.  A sampled request without a seed gets one here from the package's random stream
-        (rng.next_offset(): torch.manual_seed / rng.manual_seed govern it, every call a different one)."""
+        (rng.next_offset(): torch.manual_seed / rng.manual_seed govern it, every call a different one).
+        adapter: the name of a loaded adapter of the engine's store (None: the base weights); the request holds it
+        until it retires."""
         prompt_ids = [int(t) for t in prompt_ids]
         if not prompt_ids or max_gen_len < 1:
             raise ValueError("a request needs a prompt and max_gen_len >= 1")
         if self.kv_mgr.blocks_for(len(prompt_ids) + max_gen_len) > self.kv_mgr.max_blocks:
             raise ValueError(f"{len(prompt_ids)} + {max_gen_len} tokens do not fit into {self.kv_mgr.max_blocks} blocks "
                              f"of {self.kv_mgr.block_size}")
+        if adapter is not None:
+            if self.adapters is None:
+                raise ValueError(f"adapter {adapter!r}: the engine was built without adapters=")
+            if adapter not in self.adapters.slots:
+                raise ValueError(f"adapter {adapter!r} is not loaded (loaded: {sorted(self.adapters.slots)})")
         if sampling is None:
             sampling = SamplingParams()
         elif not isinstance(sampling, SamplingParams):
@@ -615,7 +663,12 @@ class ContinuousBatchEngine:
                                       (base + 0x9E3779B97F4A7C15 * offset) & _MASK64)
         sid = next(self.id_gen)
         self.sampling[sid] = sampling
-        self.waiting_room.append({"sid": sid, "prompt_ids": prompt_ids, "max_gen_len": max_gen_len})
+        salt = None
+        if adapter is not None:
+            self.adapters.acquire(adapter)
+            self.adapter[sid] = adapter
+            salt = self.adapters.uid[adapter]        # K/V depend on the adapter: cached blocks are shared within one only
+        self.waiting_room.append({"sid": sid, "prompt_ids": prompt_ids, "max_gen_len": max_gen_len, "salt": salt})
         return sid
 
     def _try_schedule_waiting(self) -> None:
@@ -623,7 +676,7 @@ class ContinuousBatchEngine:
         mgr = self.kv_mgr
         while self.waiting_room and len(self.active) < self.max_batch:
             req = self.waiting_room[0]
-            matched = mgr.match_prefix(req["prompt_ids"])
+            matched = mgr.match_prefix(req["prompt_ids"], req["salt"])
             need = mgr.blocks_for(len(req["prompt_ids"]) + req["max_gen_len"]) - len(matched)
             claimed = sum(s.block_table.numel() - s.block_count for s in self.active.values())
             if need > mgr.available(matched) - claimed:
@@ -631,7 +684,7 @@ class ContinuousBatchEngine:
             self.waiting_room.popleft()
             mgr.acquire(matched)
             self.active[req["sid"]] = SequenceState(req["sid"], req["prompt_ids"], req["max_gen_len"], mgr.block_size,
-                                                    self.device, matched_blocks=matched)
+                                                    self.device, matched_blocks=matched, salt=req["salt"])
 
     def _schedule_prompts(self, decode_rows: int) -> List[SequenceState]:
         """The prefilling sequences that run in this step, in admission order, their chunk_end set.  Under
@@ -646,6 +699,12 @@ class ContinuousBatchEngine:
                 s.chunk_end = s.num_computed + n
                 run.append(s)
         return run
+
+    def _lora_rows(self, states: List[SequenceState]):
+        """What _PackedRows needs to record the tiles of the step's adapted rows; None in an engine without a store."""
+        if self.adapters is None:
+            return None
+        return self.adapters, {s.id: self.adapters.slots[self.adapter[s.id]] for s in states if s.id in self.adapter}
 
     def _allocate(self, s: SequenceState) -> None:
         """Blocks and slots of the tokens this step computes of its sequence."""
@@ -671,7 +730,7 @@ class ContinuousBatchEngine:
             states = dec + self._schedule_prompts(len(dec))
         for s in states:
             self._allocate(s)
-        rows = _PackedRows(*_padded_tables(states))
+        rows = _PackedRows(*_padded_tables(states), lora=self._lora_rows(states))
         for s in states:
             a, b = s.query_start, s.query_end
             if not s.is_prefill:
@@ -727,6 +786,8 @@ class ContinuousBatchEngine:
         self.kv_mgr.free(s)
         del self.active[s.id]
         del self.sampling[s.id]
+        if s.id in self.adapter:
+            self.adapters.release(self.adapter.pop(s.id))
         self.draft_computed.pop(s.id, None)
 
     def _finish_step(self, states: List[SequenceState], next_tokens: List[int]) -> Dict[int, List[int]]:
@@ -771,7 +832,8 @@ class ContinuousBatchEngine:
         # device), every row with logits; draft round 0: what the drafter has not computed yet of every sequence that
         # drafts, its last row with logits; both: the prompt chunks, the target's with a logits row where a prompt ends
         width, tables = _padded_tables(states)
-        v, r0 = _PackedRows(width, tables, "v_"), _PackedRows(width, tables, "r0_")
+        # (the drafter serves base weights: only the target's forward carries the tiles of adapted rows)
+        v, r0 = _PackedRows(width, tables, "v_", lora=self._lora_rows(states)), _PackedRows(width, tables, "r0_")
         for s in dec:
             v.varlen(s, s.num_tokens - 1, s.num_tokens + g_of[s.id], g_of[s.id] + 1)
             if g_of[s.id]:
