@@ -660,6 +660,28 @@ int vy_lora_expand(void* y, int64_t ldy, const void* u, int64_t ldu, const void*
                    const int32_t* tiles, int64_t n_tiles, int64_t T, int64_t N, int64_t r_pad, int64_t slots,
                    int64_t bound0, int64_t bound1, int dtype, void* stream);
 
+/* vy_lora_wgrad: both low-rank weight gradients of one GEMM group of LoRA fine-tuning (vyomai_amd/lora_train.py), for
+ *   the parts p of a packed projection (part(n) and bound0 / bound1 as in vy_lora_expand; a boundary that is not used
+ *   is N, so parts = 1 + (bound0 < N) + (bound1 < N) <= 3; col0_p is the part's first column):
+ *     dB_p[n, j] (+)= alpha * sum_m dY[m, col0_p + n] * u[m, p * r_pad + j]     fp32 (out_p, rank_p), row stride rank_p
+ *     dA_p[j, k] (+)= alpha * sum_m t[m, p * r_pad + j]  * x[m, k]              fp32 (rank_p, K),     row stride K
+ *   dY (M, N) is the gradient of the group's output, x (M, K) its input, u (M, R) what vy_lora_shrink left in the
+ *   forward and t (M, R) = dY @ B per part; R = parts * r_pad; dY, u, x, t share `dtype`.  A part whose dA_p and dB_p
+ *   are both null has no adapter and is neither written nor multiplied.  rank_p <= r_pad: the columns j >= rank_p of
+ *   u / t never reach an output.  accumulate = 1 adds to the outputs, 0 overwrites them.
+ *   Rounding: products are exact and accumulate in fp32 (bf16: mfma_f32_16x16x32_bf16, fp32: mfma_f32_16x16x4f32).
+ *   Determinism: M is cut into chunks of vy_lora_wgrad_chunk_rows(M, N, K) rows -- the shapes alone decide -- whose fp32
+ *   partial tiles go to the stream's workspace (vy_workspace_set; (N * r_pad + R * K) * chunks floats are needed) and
+ *   are added in chunk order by a second launch: no atomics, two runs give the same bits.
+ *   VY_ERR_ARG: a null operand, no part with outputs, one of dA_p / dB_p without the other, M <= 0, K % 32, N or a
+ *   boundary not a multiple of 16, r_pad other than 32 or 64, rank_p outside [1, r_pad], row strides below the widths,
+ *   rows of dY, u, x, t not 16-byte aligned, accumulate other than 0 / 1, an unknown dtype, no workspace of that size. */
+int vy_lora_wgrad(const void* dy, int64_t lddy, const void* u, int64_t ldu, const void* x, int64_t ldx, const void* t,
+                  int64_t ldt, float* dA0, float* dA1, float* dA2, float* dB0, float* dB1, float* dB2, int64_t rank0,
+                  int64_t rank1, int64_t rank2, int64_t M, int64_t N, int64_t K, int64_t r_pad, int64_t bound0,
+                  int64_t bound1, float alpha, int accumulate, int dtype, void* stream);
+int64_t vy_lora_wgrad_chunk_rows(int64_t M, int64_t N, int64_t K);
+
 /* y = x converted between fp32 and bf16 (n elements). src_dtype -> dst_dtype. */
 int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);
 

@@ -91,6 +91,8 @@ PROTOTYPES = {
     "vy_spec_verify": [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "vy_lora_shrink": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "vy_lora_expand": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _p],
+    "vy_lora_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64,
+                      _i64, _i64, _i64, _f, _i, _i, _p],
     "vy_decoder_step": [_p, _p, _i64, _p, _p, _p, _i64, _p],
     "vy_gemma_decoder_step": [_p, _p, _i64, _p, _i64, _p],
     "vy_cast": [_p, _p, _i64, _i, _i, _p],
@@ -103,7 +105,7 @@ PROTOTYPES = {
 }
 OTHER_SYMBOLS = ["vy_last_error", "vy_abi_version", "vy_layernorm_bwd_ws_rows", "vy_decode_ws_bytes",
                  "vy_gemma_ws_bytes", "vy_ddp_world", "vy_ddp_rank", "vy_attn_paged_decode_ws_bytes",
-                 "vy_attn_paged_decode_fp8_ws_bytes"]
+                 "vy_attn_paged_decode_fp8_ws_bytes", "vy_lora_wgrad_chunk_rows"]
 ALL_SYMBOLS = list(PROTOTYPES) + OTHER_SYMBOLS
 
 
@@ -151,6 +153,8 @@ def load() -> C.CDLL:
     lib.vy_attn_paged_decode_ws_bytes.argtypes = [_i64, _i, _i, _i, _i64, _i, _i]
     lib.vy_attn_paged_decode_fp8_ws_bytes.restype = C.c_int64
     lib.vy_attn_paged_decode_fp8_ws_bytes.argtypes = [_i64, _i, _i, _i, _i64, _i, _i]
+    lib.vy_lora_wgrad_chunk_rows.restype = C.c_int64
+    lib.vy_lora_wgrad_chunk_rows.argtypes = [_i64, _i64, _i64]
     _lib = lib
     return lib
 

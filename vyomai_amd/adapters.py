@@ -2,8 +2,9 @@
 (VyomAI/layers/adapters.py: linear(x) + alpha * F.linear(F.linear(x, lora_a), lora_b)) of many fine-tuned models, held
 next to ONE copy of the base weights and added per row of a serving step (vy_lora_shrink / vy_lora_expand, the rule:
 include/vyom_hip.h).  serving.ContinuousBatchEngine(..., adapters=store) and add_sequence(..., adapter="name") pick one
-per request.  Serving only: nothing here trains, and DoRA (which renormalises the whole weight, so it is no additive
-per-request delta) is refused.
+per request.  DoRA (which renormalises the whole weight, so it is no additive per-request delta) is refused.  The second
+half of this file is the training side: the reference's LoraLinear wrapper, add_lora / lora_state_dict / merge_lora /
+disable_lora for ModelForCausalLM (the forward and backward of a wrapped layer: lora_train.py).
 
 Layout.  Per layer and projection group -- qkv, o, gate_up, down: the four GEMMs of forward_paged -- the store keeps
 A (slots, parts * r_pad, K) and B (slots, N, r_pad) in the compute dtype, r_pad = max_rank rounded up to 32.  A packed
@@ -180,3 +181,143 @@ def layer_delta(metadata: dict, layer: int):
     if lora is None:
         return None
     return functools.partial(lora["adapters"].delta_, lora, layer)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Training through adapters: the reference's LoraLinear wrapper and what prepares a ModelForCausalLM for it.  The
+# forward and backward of a wrapped layer are lora_train.py's (DecoderLayer picks them up from the wrapped modules).
+# ------------------------------------------------------------------------------------------------------------------
+
+MAX_TRAIN_RANK = 64      # vy_lora_wgrad: r_pad is 32 or 64
+ALL_TARGETS = tuple(p for g in GROUPS for p in _CAUSAL_LM[g])
+
+
+class LoraLinear(torch.nn.Module):
+    """linear(x) + alpha * (x @ lora_a.T) @ lora_b.T around an nn.Linear, with the reference's constructor, attribute
+    and state_dict names (VyomAI/layers/adapters.py: `linear`, `lora_a` (rank, in) ~ N(0, 1 / rank), `lora_b`
+    (out, rank) zero, `dropout`).  `weight` / `bias` forward to the wrapped linear, so the packed-QKV and gate/up
+    machinery keeps reading the base weights; the low-rank term is added by the layer that owns the projection
+    (DecoderLayer: lora_train.py).  Called on its own it runs under torch.no_grad() only."""
+
+    def __init__(self, linear_layer, rank: int = 32, alpha=1, lora_dropout: float = 0.0) -> None:
+        super().__init__()
+        if not isinstance(linear_layer, torch.nn.Linear):
+            raise ValueError(f"LoraLinear wraps an nn.Linear, not a {type(linear_layer).__name__} (wrapping twice?)")
+        if lora_dropout:
+            raise ValueError(f"lora_dropout {lora_dropout}: dropout on the adapter's output has no kernel here; use 0.0")
+        if int(rank) != rank or not 1 <= rank <= MAX_TRAIN_RANK:
+            raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_TRAIN_RANK}")
+        self.linear = linear_layer
+        self.in_features, self.out_features = linear_layer.in_features, linear_layer.out_features
+        if self.in_features % 32 or self.out_features % 16:
+            raise ValueError(f"in_features {self.in_features} must be a multiple of 32 and out_features "
+                             f"{self.out_features} a multiple of 16 (vy_lora_shrink / vy_lora_expand)")
+        self.rank, self.alpha = int(rank), alpha
+        w = linear_layer.weight
+        self.lora_a = torch.nn.Parameter(torch.randn(self.rank, self.in_features, dtype=w.dtype, device=w.device)
+                                         * self.rank ** -0.5)
+        self.lora_b = torch.nn.Parameter(torch.zeros(self.out_features, self.rank, dtype=w.dtype, device=w.device))
+        self.dropout = torch.nn.Dropout(lora_dropout)
+        self._off = 0            # depth of disable_lora() contexts
+
+    weight = property(lambda self: self.linear.weight)
+    bias = property(lambda self: self.linear.bias)
+    enabled = property(lambda self: self._off == 0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from . import lora_train
+        return lora_train.lora_linear_forward(self, x)
+
+    def extra_repr(self) -> str:
+        return f"rank={self.rank}, alpha={self.alpha}"
+
+
+def _causal_lm(model, what: str):
+    from .models.custom_transformer import ModelForCausalLM
+    if not isinstance(model, ModelForCausalLM):
+        raise ValueError(f"{what} prepares a ModelForCausalLM, not a {type(model).__name__}: only its pre-norm blocks "
+                         "have a training path through adapters")
+    return list(model.model.layers[: model.config.num_hidden_layers])
+
+
+def _wrapped(model):
+    """-> [(owner module, attribute, key path, LoraLinear)] of every wrapped projection, in layer order."""
+    out = []
+    for l, layer in enumerate(_causal_lm(model, "LoRA")):
+        for path in ALL_TARGETS:
+            owner_name, attr = path.split(".")
+            owner = getattr(layer, owner_name)
+            m = getattr(owner, attr)
+            if isinstance(m, LoraLinear):
+                out.append((owner, attr, f"model.layers.{l}.{path}", m))
+    return out
+
+
+def add_lora(model, rank: int = 32, alpha=1.0, targets=ALL_TARGETS):
+    """Wrap the projections `targets` (paths of _CAUSAL_LM: "self_attn.q_proj", ..., "mlp.down_proj"; any subset) of
+    every layer of a ModelForCausalLM in a LoraLinear and freeze every other parameter, as Examples/adapters.ipynb does
+    -> the model.  ValueError: another model class, an unknown or empty target list, a model that is already wrapped."""
+    layers = _causal_lm(model, "add_lora")
+    targets = tuple(targets)
+    unknown = [t for t in targets if t not in ALL_TARGETS]
+    if unknown or not targets or len(set(targets)) != len(targets):
+        raise ValueError(f"targets {list(targets)} must be a non-empty subset of {list(ALL_TARGETS)} without repeats")
+    if _wrapped(model):
+        raise ValueError("the model already carries LoRA adapters: merge_lora(model) first")
+    if int(rank) != rank or not 1 <= rank <= MAX_TRAIN_RANK:
+        raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_TRAIN_RANK}")
+    for g in GROUPS:      # (everything is checked before anything is changed)
+        shapes = [functools.reduce(getattr, p.split("."), layers[0]).weight.shape for p in _CAUSAL_LM[g]]
+        if not any(p in targets for p in _CAUSAL_LM[g]):
+            continue
+        if sum(s[0] for s in shapes) % 32 or any(s[0] % 16 or s[1] % 32 for s in shapes):
+            raise ValueError(f"the packed {g} projection has parts {[tuple(s) for s in shapes]}: in_features must be a "
+                             "multiple of 32, every out_features of 16 and their sum of 32 (the adapter's backward "
+                             "contracts over the packed width: vy_lora_shrink)")
+    for p in model.parameters():
+        p.requires_grad_(False)
+    for layer in layers:
+        for path in targets:
+            owner_name, attr = path.split(".")
+            owner = getattr(layer, owner_name)
+            setattr(owner, attr, LoraLinear(getattr(owner, attr), rank=rank, alpha=alpha))
+    return model
+
+
+def lora_state_dict(model) -> Dict[str, torch.Tensor]:
+    """Exactly the lora_a / lora_b entries of the wrapped model's state_dict (detached copies): what
+    LoraAdapters.load(name, lora_state_dict(model), alpha) takes."""
+    out = {}
+    for _, _, key, m in _wrapped(model):
+        out[key + ".lora_a"] = m.lora_a.detach().clone()
+        out[key + ".lora_b"] = m.lora_b.detach().clone()
+    return out
+
+
+def merge_lora(model):
+    """W += alpha * lora_b @ lora_a in fp32 into every wrapped linear, and the plain nn.Linear back in its place -> the
+    model (the re-association of tests/golden/make_golden_lora.py's merged()).  requires_grad flags stay as they are."""
+    with torch.no_grad():
+        for owner, attr, _, m in _wrapped(model):
+            w = m.linear.weight
+            w += (float(m.alpha) * (m.lora_b.detach().float() @ m.lora_a.detach().float())).to(w.dtype)
+            setattr(owner, attr, m.linear)
+    return model
+
+
+class disable_lora:
+    """Context manager: inside it the wrapped model computes the base model (a DPO run scores its reference with the
+    same weights).  Nests; restores on exceptions."""
+
+    def __init__(self, model):
+        self.mods = [m for *_, m in _wrapped(model)]
+
+    def __enter__(self):
+        for m in self.mods:
+            m._off += 1
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.mods:
+            m._off -= 1
+        return False

@@ -871,6 +871,9 @@ def _wt_padded(param, dtype, ld):
 def _rms_bwd(dy, x, w, eps, add_to=None):
     """-> (dx + add_to, dw to return to autograd or None when accumulated in place): RMSNorm with w_offset = 0."""
     dt = x.dtype
+    if not w.requires_grad:   # a frozen weight (LoRA fine-tuning): no gradient is returned, nothing is written to .grad
+        scratch = torch.empty(w.shape, dtype=torch.float32, device=x.device)
+        return ops.rmsnorm_bwd(dy, x, _shadow(w, dt), eps, 0.0, scratch, False, add_to=add_to), None
     if _direct(w):
         dx = ops.rmsnorm_bwd(dy, x, _shadow(w, dt), eps, 0.0, w.grad, True, add_to=add_to)
         _notify(w)
@@ -1040,6 +1043,9 @@ def _tied_head_backward(buf, V, n, table, table_pending, alpha, row_scale=None):
     if row_scale is not None:
         rs = row_scale.view(-1, 1)
         dn = (dn * rs).to(dt)      # (the products are taken in fp32 and rounded once)
+    if not table.requires_grad:    # a frozen table (LoRA fine-tuning): the V x d weight gradient has no reader
+        return dn.view(n.shape), None
+    if row_scale is not None:
         n2 = (n2 * rs).to(dt)
     if _direct(table):
         ops.linear_wgrad(logits, n2, table.grad, None, accumulate=True, alpha=alpha)

@@ -2026,6 +2026,9 @@ extern "C" int vy_workspace_set(void* stream, void* ws, int64_t bytes) {
   g_ws[g_ws_n++] = WsEntry{st, ws, bytes};
   return VY_OK;
 }
+// internal: the stream's registered workspace for launchers in other files (vy_lora_train.hip), null when it has none
+// or fewer than `need` bytes
+float* vy_stream_ws(hipStream_t st, int64_t need) { return splitk_ws(st, need); }
 extern "C" int vy_set_concurrent_chains(int n) {
   if (n < 1 || n > 8) VY_FAIL(VY_ERR_ARG, "vy_set_concurrent_chains: n = %d (1..8)", n);
   g_chains = n;

@@ -91,6 +91,7 @@ class _SelfAttentionBase(nn.Module):
     num_attention_heads: int
     num_key_value_heads: int
     head_dim: int
+    _lora_aware = False      # True where the layer that owns the module applies a LoraLinear wrapper's term itself
 
     def _setup(self, config, layer_idx: int, kv_heads: Optional[int], fused_qkv: bool) -> None:
         if config.hidden_size % config.num_attention_heads != 0:
@@ -182,6 +183,8 @@ class _SelfAttentionBase(nn.Module):
         a missing attribute).  Adapters are outside SURVEY section 8; say so instead of computing without them."""
         for name in (("qkv",) if self._fused_qkv else ("query", "key", "value")):
             m = getattr(self, name)
+            if self._lora_aware and type(m).__name__ == "LoraLinear" and hasattr(m, "linear"):
+                continue      # (the owner adds the wrapper's term itself: lora_train.py; `weight` / `bias` forward)
             if not isinstance(m, nn.Linear):
                 raise VyomHipError(
                     f"attention.{name} is a {type(m).__name__}, not an nn.Linear: the MI355X attention path reads the "

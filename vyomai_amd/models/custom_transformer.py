@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import VyomHipError
-from ..adapters import layer_delta
+from ..adapters import LoraLinear, layer_delta
 from ..autograd import _mask_args, _wants_grad
 from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
@@ -114,6 +114,9 @@ class MLP(nn.Module):
     def forward(self, x, residual: Optional[torch.Tensor] = None, delta=None):
         """delta (serving with adapters, adapters.layer_delta): f(group, y, x), called behind each of the two GEMMs."""
         _need_gpu(x, "MLP")
+        if any(isinstance(p, LoraLinear) and p.enabled for p in (self.gate_proj, self.up_proj, self.down_proj)):
+            raise VyomHipError("the gated MLP applies LoRA adapters (LoraLinear) inside its pre-norm block (DecoderLayer) "
+                               "only; called on its own it would skip their term")
         if _wants_grad(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight):
             raise VyomHipError("the gated MLP trains inside its pre-norm block (DecoderLayer: RMSNorm, MLP and the "
                                "residual add are one autograd function); call it under torch.no_grad() on its own")
@@ -132,6 +135,8 @@ class Attention(_SelfAttentionBase):
     """q/k/v projections with bias, o_proj without (reference :164-223).  The forward lives in DecoderLayer: the
     RMSNorm in front and the residual add behind belong to the same fused group.  `query` / `key` / `value` alias the
     reference-named projections for the packed-QKV machinery shared with the other attention modules."""
+
+    _lora_aware = True       # DecoderLayer adds a wrapped projection's low-rank term (lora_train.py)
 
     def __init__(self, config: Config, layer_idx: int):
         super().__init__()
@@ -201,6 +206,10 @@ class DecoderLayer(nn.Module):
         a, m = self.self_attn, self.mlp
         x = hidden_states
         ln1, ln2 = self.input_layernorm, self.post_attention_layernorm
+        from .. import lora_train
+        if lora_train.layer_has_lora(self):
+            # (training, and validation under no_grad: the adapter's delta behind each of the four GEMMs)
+            return (lora_train.decoder_layer_forward(self, x, attention_mask, position_embeddings, past_key_value),)
         if _wants_grad(x, a.o_proj.weight, m.down_proj.weight, ln1.weight):
             if past_key_value is not None:
                 raise VyomHipError("KV caching is an inference feature; call under torch.no_grad()")
@@ -293,10 +302,15 @@ class BaseModel(nn.Module, PositionMixin):
         x = self._embed(self.embed_tokens, input_ids) if inputs_embeds is None else self._cast(inputs_embeds)
         B, L, _ = x.shape
         train = _wants_grad(x, self.norm.weight, self.embed_tokens.weight)
+        from .. import lora_train
+        layers = self.layers[: self.config.num_hidden_layers]
+        # (a cached step -- the decode loop -- does not ask: a wrapped layer refuses its past_key_value itself)
+        lora = past_key_values is None and any(lora_train.layer_has_lora(layer) for layer in layers)
+        train = train or (lora and _wants_grad(*(p for layer in layers for p in lora_train.layer_lora_params(layer))))
         if train and past_key_values is not None:
             raise VyomHipError("KV caching is an inference feature; call under torch.no_grad()")
         cache = None
-        if use_cache and not train:
+        if use_cache and not train and not lora:   # (adapters have no cached path: a wrapped model never starts a cache)
             cache = past_key_values if past_key_values is not None else DynamicCacheOne(self.config)
         if cache_position is not None:
             start = int(cache_position[0]) if torch.is_tensor(cache_position) else int(cache_position)
@@ -483,8 +497,11 @@ class ModelForCausalLM(nn.Module):
         residual, post_attention_layernorm and the MLP as in DecoderLayer.forward.  Every token attends to its
         sequence's whole cached context, also in a step that mixes the two phases.  The final norm and the tied head
         see one row per sequence (the notebook of Examples/simple_vllm.ipynb projects all T rows and then indexes)."""
-        _need_gpu(input_ids, "forward_paged()")
         base = self.model
+        from .. import lora_train
+        if any(lora_train.layer_has_lora(layer) for layer in base.layers[: self.config.num_hidden_layers]):
+            raise VyomHipError(lora_train.NO_CACHE.format(what="forward_paged() (the serving engine)"))
+        _need_gpu(input_ids, "forward_paged()")
         dev = input_ids.device
         x = base._embed(base.embed_tokens, input_ids.view(1, -1))[0]
         dt = x.dtype
@@ -516,6 +533,9 @@ class ModelForCausalLM(nn.Module):
         prefilled into a static KV cache, every further token is one single-token pass (vy_attn_decode when nothing is
         padded) and one vy_greedy_step.  Rows that have produced eos_token_id continue with pad_token_id.  (The
         reference inherits transformers' GenerationMixin; sampling, beams and stopping criteria are not reproduced.)"""
+        from .. import lora_train
+        if any(lora_train.layer_has_lora(layer) for layer in self.model.layers[: self.config.num_hidden_layers]):
+            raise VyomHipError(lora_train.NO_CACHE.format(what="generate() (it decodes through a KV cache)"))
         _need_gpu(input_ids, "generate()")
         dev = input_ids.device
         B, T = input_ids.shape

@@ -896,6 +896,162 @@ def lora_delta_(y: Tensor, x: Tensor, A: Tensor, B: Tensor, alpha: Tensor, tiles
     return y
 
 
+def _lora_rows(fn: str, name: str, dtype=None, **mats: Tensor):
+    """Shared host checks of the LoRA training entries: 2-D tensors of one float32 / bfloat16 dtype on one device over
+    the same rows, unit column stride, 16-byte aligned rows -> (rows, dtype)."""
+    first = next(iter(mats.values()))
+    for what, t in mats.items():
+        if not isinstance(t, Tensor):
+            raise ValueError(f"{fn} ({name}): {what} must be a tensor")
+    dtype = first.dtype if dtype is None else dtype
+    if dtype not in (torch.float32, torch.bfloat16) or any(t.dtype != dtype for t in mats.values()):
+        raise ValueError(f"{fn} ({name}): {', '.join(mats)} must share float32 or bfloat16, got "
+                         f"{[str(t.dtype) for t in mats.values()]}")
+    for what, t in mats.items():
+        if t.dim() != 2 or t.shape[0] != first.shape[0] or t.shape[0] < 1 or t.stride(1) != 1:
+            raise ValueError(f"{fn} ({name}): {what} must be 2-D over the same {first.shape[0]} rows with unit column "
+                             f"stride, got {tuple(t.shape)} strides {t.stride()}")
+        if (t.stride(0) * t.element_size()) % 16 or t.data_ptr() % 16 or t.stride(0) < t.shape[1]:
+            raise ValueError(f"{fn} ({name}): rows of {what} must be 16-byte aligned (row stride {t.stride(0)})")
+        if t.device != first.device:
+            raise ValueError(f"{fn} ({name}): {what} is on {t.device}, {next(iter(mats))} on {first.device}")
+    return first.shape[0], dtype
+
+
+def _lora_bounds(fn: str, name: str, boundaries: Sequence[int], N: int):
+    bounds = [int(b) for b in boundaries]
+    if len(bounds) > 2 or any(b % 16 for b in bounds) or bounds != sorted(set(bounds)) or (bounds and not 0 < bounds[0]) \
+            or (bounds and bounds[-1] >= N) or N % 16 or N < 16:
+        raise ValueError(f"{fn} ({name}): boundaries {bounds} must be at most two increasing multiples of 16 inside "
+                         f"(0, {N}), and N a multiple of 16: every part's width is a multiple of 16")
+    return bounds
+
+
+def _lora_tiles(fn: str, name: str, tiles: Tensor, n_tiles: int, like: Tensor) -> None:
+    if not isinstance(tiles, Tensor) or tiles.dtype != torch.int32 or tiles.numel() != 3 * n_tiles \
+            or not tiles.is_contiguous() or n_tiles < 1 or tiles.device != like.device:
+        raise ValueError(f"{fn} ({name}): tiles must be a contiguous int32 tensor of {n_tiles} x 3 elements on {like.device}")
+
+
+def lora_delta_keep_u_(y: Tensor, x: Tensor, A: Tensor, B: Tensor, alpha: Tensor, tiles: Tensor, n_tiles: int,
+                       boundaries: Sequence[int] = (), name: str = "projection") -> Tensor:
+    """lora_delta_ for training: y += alpha * (x @ A[0].T) @ B[0].T in place through the same launch pair and the same
+    operand layout (A (1, parts * r_pad, K), B (1, N, r_pad), alpha fp32 (1,), one slot) -> u (T, parts * r_pad), the
+    shrink's output in the storage dtype, which the backward keeps (vy_lora_wgrad's u).  The tiles must cover every
+    row: a row outside them would leave its u unwritten."""
+    fn = "lora_delta_keep_u_"
+    n_tiles = int(n_tiles)
+    T, dt = _lora_rows(fn, name, y=y, x=x)
+    (_, N), K = y.shape, x.shape[1]
+    bounds = _lora_bounds(fn, name, boundaries, N)
+    parts = 1 + len(bounds)
+    if K % 32 or K < 32:
+        raise ValueError(f"{fn} ({name}): K = {K} must be a multiple of 32")
+    for what, t in (("A", A), ("B", B)):
+        if not isinstance(t, Tensor) or t.dim() != 3 or t.shape[0] != 1 or not t.is_contiguous() or t.dtype != dt \
+                or t.device != y.device:
+            raise ValueError(f"{fn} ({name}): {what} must be a contiguous (1, rows, columns) {dt} tensor on {y.device}")
+    r_pad = B.shape[2]
+    if r_pad not in (32, 64) or tuple(B.shape) != (1, N, r_pad) or tuple(A.shape) != (1, parts * r_pad, K):
+        raise ValueError(f"{fn} ({name}): A must be (1, {parts} * r_pad, {K}) and B (1, {N}, r_pad) with r_pad 32 or 64, "
+                         f"got {tuple(A.shape)} and {tuple(B.shape)}")
+    if not isinstance(alpha, Tensor) or alpha.dtype != torch.float32 or alpha.numel() != 1 or alpha.device != y.device:
+        raise ValueError(f"{fn} ({name}): alpha must be a float32 tensor of one element on {y.device}")
+    _lora_tiles(fn, name, tiles, n_tiles, y)
+    _need_gpu(y)
+    R = parts * r_pad
+    u = torch.empty((T, R), dtype=dt, device=y.device)
+    st, code = _stream(), dtype_code(dt)
+    call("vy_lora_shrink", x.data_ptr(), x.stride(0), A.data_ptr(), tiles.data_ptr(), n_tiles, u.data_ptr(), R, T, K, R,
+         1, code, st)
+    call("vy_lora_expand", y.data_ptr(), y.stride(0), u.data_ptr(), R, B.data_ptr(), alpha.data_ptr(), tiles.data_ptr(),
+         n_tiles, T, N, r_pad, 1, *(bounds + [N, N])[:2], code, st)
+    return u
+
+
+def lora_dgrad_(dx: Optional[Tensor], dy: Tensor, Bt: Tensor, At: Tensor, alpha: Tensor, tiles: Tensor, n_tiles: int,
+                name: str = "projection") -> Tensor:
+    """The adapter's two data-gradient products of one GEMM group -> t (M, R) = dy @ B per part, and, when dx is given,
+    dx += alpha * t @ A in place (what dx held -- the base dgrad, an add_to -- is kept).  dy (M, N); Bt (R, N) the
+    block-diagonal transposed B (row p * r_pad + j holds column j of B_p in part p's columns, zeros elsewhere), so ONE
+    vy_lora_shrink over dy serves every part; At (K, R) the transposed stacked A, vy_lora_expand's `B` with
+    r_pad := R and no boundaries.  N and R multiples of 32 (the shrink contracts over N), K of 16."""
+    fn = "lora_dgrad_"
+    n_tiles = int(n_tiles)
+    M, dt = _lora_rows(fn, name, dy=dy) if dx is None else _lora_rows(fn, name, dy=dy, dx=dx)
+    N = dy.shape[1]
+    for what, t in (("Bt", Bt), ("At", At)):
+        if not isinstance(t, Tensor) or t.dim() != 2 or not t.is_contiguous() or t.dtype != dt or t.device != dy.device:
+            raise ValueError(f"{fn} ({name}): {what} must be a contiguous 2-D {dt} tensor on {dy.device}")
+    R, K = Bt.shape[0], At.shape[0]
+    if N % 32 or R % 32 or not 32 <= R <= 192 or K % 16 or Bt.shape[1] != N or At.shape[1] != R \
+            or (dx is not None and dx.shape[1] != K):
+        raise ValueError(f"{fn} ({name}): dy (M, N = {N}) needs Bt (R, N) and At (K, R) with N and R multiples of 32, "
+                         f"R <= 192, K of 16 and dx (M, K); got Bt {tuple(Bt.shape)}, At {tuple(At.shape)}, dx "
+                         f"{None if dx is None else tuple(dx.shape)}")
+    if not isinstance(alpha, Tensor) or alpha.dtype != torch.float32 or alpha.numel() != 1 or alpha.device != dy.device:
+        raise ValueError(f"{fn} ({name}): alpha must be a float32 tensor of one element on {dy.device}")
+    _lora_tiles(fn, name, tiles, n_tiles, dy)
+    _need_gpu(dy)
+    t = torch.empty((M, R), dtype=dt, device=dy.device)
+    st, code = _stream(), dtype_code(dt)
+    call("vy_lora_shrink", dy.data_ptr(), dy.stride(0), Bt.data_ptr(), tiles.data_ptr(), n_tiles, t.data_ptr(), R, M, N, R,
+         1, code, st)
+    if dx is not None:
+        call("vy_lora_expand", dx.data_ptr(), dx.stride(0), t.data_ptr(), R, At.data_ptr(), alpha.data_ptr(),
+             tiles.data_ptr(), n_tiles, M, K, R, 1, K, K, code, st)
+    return t
+
+
+def lora_wgrad_chunk_rows(M: int, N: int, K: int) -> int:
+    """Rows of M per chunk of vy_lora_wgrad (the shapes alone decide; cdiv(M, rows) chunks, the last one ragged)."""
+    return int(_lib.load().vy_lora_wgrad_chunk_rows(int(M), int(N), int(K)))
+
+
+def lora_wgrad(dy: Tensor, u: Tensor, x: Tensor, t: Tensor, dA: Sequence[Optional[Tensor]],
+               dB: Sequence[Optional[Tensor]], boundaries: Sequence[int], r_pad: int, alpha: float, accumulate: bool,
+               name: str = "projection") -> None:
+    """Both low-rank weight gradients of one GEMM group in one launch pair (vy_lora_wgrad; the rule: include/vyom_hip.h):
+    dB[p] (out_p, rank_p) (+)= alpha * dy[:, part p].T @ u[:, p * r_pad : + rank_p] and
+    dA[p] (rank_p, K) (+)= alpha * t[:, p * r_pad : + rank_p].T @ x, fp32 contiguous, one pair per part of the packed
+    projection; a part without an adapter has None for both.  Deterministic: two calls give the same bits."""
+    fn = "lora_wgrad"
+    M, dt = _lora_rows(fn, name, dy=dy, u=u, x=x, t=t)
+    N, K = dy.shape[1], x.shape[1]
+    bounds = _lora_bounds(fn, name, boundaries, N)
+    parts = 1 + len(bounds)
+    if K % 32 or K < 32:
+        raise ValueError(f"{fn} ({name}): K = {K} must be a multiple of 32")
+    if r_pad not in (32, 64) or u.shape[1] != parts * r_pad or t.shape[1] != parts * r_pad:
+        raise ValueError(f"{fn} ({name}): r_pad {r_pad} must be 32 or 64 and u, t (M, {parts} * r_pad), got "
+                         f"{tuple(u.shape)} and {tuple(t.shape)}")
+    if len(dA) != parts or len(dB) != parts or all(a is None for a in dA):
+        raise ValueError(f"{fn} ({name}): dA and dB need one entry per part ({parts}), at least one of them a tensor")
+    cols = [0] + bounds + [N]
+    ptrs_a, ptrs_b, ranks = [None] * 3, [None] * 3, [0] * 3
+    for p, (a, b) in enumerate(zip(dA, dB)):
+        if (a is None) != (b is None):
+            raise ValueError(f"{fn} ({name}): part {p} has one of dA / dB only")
+        if a is None:
+            continue
+        out_p = cols[p + 1] - cols[p]
+        rank = a.shape[0] if isinstance(a, Tensor) and a.dim() == 2 else -1
+        if not 1 <= rank <= r_pad:
+            raise ValueError(f"{fn} ({name}): rank {rank} of part {p} is outside [1, r_pad = {r_pad}]")
+        for what, g, shape in (("dA", a, (rank, K)), ("dB", b, (out_p, rank))):
+            if not isinstance(g, Tensor) or g.dtype != torch.float32 or tuple(g.shape) != shape or not g.is_contiguous() \
+                    or g.device != dy.device:
+                raise ValueError(f"{fn} ({name}): {what}[{p}] must be a contiguous float32 {shape} tensor on {dy.device}, "
+                                 f"got {getattr(g, 'dtype', None)} {tuple(getattr(g, 'shape', ()))}")
+        ptrs_a[p], ptrs_b[p], ranks[p] = a.data_ptr(), b.data_ptr(), rank
+    _need_gpu(dy)
+    st = _stream()
+    _stream_ws()
+    call("vy_lora_wgrad", dy.data_ptr(), dy.stride(0), u.data_ptr(), u.stride(0), x.data_ptr(), x.stride(0), t.data_ptr(),
+         t.stride(0), *ptrs_a, *ptrs_b, *ranks, M, N, K, int(r_pad), *(bounds + [N, N])[:2], float(alpha),
+         1 if accumulate else 0, dtype_code(dt), st)
+
+
 def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[int]) -> None:
     """dw[ids[m], :] += dout[m, :] in fp32, skipping padding_idx  (vy_embedding_bwd)."""
     _need_gpu(dout, ids, dw)
