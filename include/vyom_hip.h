@@ -300,6 +300,40 @@ int vy_rmsnorm_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, con
 int vy_gated_act_bwd(const void* d_act, int64_t lddo, const void* gate_up, int64_t ldg, void* d_gate_up,
                      int64_t lddg, int64_t M, int64_t I, int act, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Qwen3's qk_norm on the training side (Examples/simple_vllm.ipynb cell 2, GroupedQueryAttention.forward).
+ * qkv[T][ld] are the packed rows of the plain bias-free QKV GEMM, T = B * L, columns [q heads | k heads | v heads] of dh
+ * each, W = (h + 2 hk) * dh <= ld; q_scale / k_scale are fp32 [dh], shared by all heads of their kind.  bf16 and fp32;
+ * dh a multiple of 8 up to 256; h a multiple of hk; ld / ldd (and the q / k strides) multiples of 8 (bf16) or 4 (fp32)
+ * elements; every pointer 16-byte aligned; eps >= 0.  Anything else is VY_ERR_ARG before a launch.  Neither allocates.
+ *
+ * vy_qknorm_rope_fwd: for every q and k head of every row, in fp32 from the load to the ONE rounding at the store:
+ *   n = x * rsqrt(mean_d(x^2) + eps) * scale, rotated (rotate_half pairing d, d + dh/2) with row pos0 + l of the fp32
+ *   cos / sin tables [table_rows][dh/2] (table_rows >= pos0 + L), written to q (B,h,L,dh) / k (B,hk,L,dh) through
+ *   element strides {batch, head, token} as vy_qkv_rope_fwd writes them.  The rows of qkv are NOT modified: they are the
+ *   saved activation of vy_qknorm_bwd.  The v heads are not touched (vy_attn_fwd / vy_attn_bwd read them in place:
+ *   v_sb = L * ld, v_sh = dh, v_sl = ld).  An all-zero head gives zeros.
+ *   replaces: `queries = self.q_norm(queries)`, `keys = self.k_norm(keys)` and the two apply_rope calls of
+ *   GroupedQueryAttention.forward (prefill branch).  The notebook's bf16 model rounds after each of them.
+ *
+ * vy_qknorm_bwd: dqkv[T][ldd], layout [dq | dk | dv], holds in its q and k columns the gradient dy of the NORMALISED
+ *   heads (vy_attn_bwd leaves it there, un-rotated through its cos / sin arguments).  They are overwritten IN PLACE by
+ *   the gradient of the raw projection, dx = r g dy - x r^3 / dh * sum_d(x g dy) with r = rsqrt(mean_d(x^2) + eps)
+ *   recomputed from qkv (no saved statistics); the dv columns and any pad columns past W keep their bits.
+ *   dq_scale / dk_scale (fp32 [dh]) = beta * themselves + sum over (token, head) of dy * x * r, beta 0 or 1.  The sums
+ *   are deterministic: per-workgroup partials go to ws (vy_qknorm_bwd_ws_floats(T, h, hk, dh) floats, 16-byte aligned)
+ *   and a second small launch adds them in a fixed order -- no atomics.
+ *   replaces: the autograd of the two RMSNorm.forward calls above.
+ * ------------------------------------------------------------------------------------------ */
+int vy_qknorm_rope_fwd(const void* qkv, int64_t ld, const float* cos_tab, const float* sin_tab, int64_t table_rows,
+                       int64_t pos0, const float* q_scale, const float* k_scale, float eps,
+                       void* q, int64_t q_sb, int64_t q_sh, int64_t q_sl, void* k, int64_t k_sb, int64_t k_sh,
+                       int64_t k_sl, int64_t B, int64_t L, int h, int hk, int dh, int dtype, void* stream);
+int64_t vy_qknorm_bwd_ws_floats(int64_t T, int h, int hk, int dh);
+int vy_qknorm_bwd(void* dqkv, int64_t ldd, const void* qkv, int64_t ld, const float* q_scale, const float* k_scale,
+                  float eps, float* dq_scale, float* dk_scale, float beta, float* ws, int64_t T, int h, int hk,
+                  int dh, int dtype, void* stream);
+
 /* vy_rope_fwd: in-place rotary embedding on a (B,heads,L,dh) tensor (strides as above);
  * used when the fused epilogue does not apply.  `inverse` != 0 applies the transpose rotation
  * (the backward of RoPE).  replaces: VyomAI/layers/positional_embeddings.py:155-182. */

@@ -52,6 +52,9 @@ PROTOTYPES = {
     "vy_gated_act_fwd": [_p, _i64, _p, _i64, _i64, _i64, _i, _i, _p],
     "vy_rmsnorm_bwd": [_p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _f, _f, _i, _p],
     "vy_gated_act_bwd": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i, _i, _p],
+    "vy_qknorm_rope_fwd": [_p, _i64, _p, _p, _i64, _i64, _p, _p, _f, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64,
+                           _i64, _i64, _i, _i, _i, _i, _p],
+    "vy_qknorm_bwd": [_p, _i64, _p, _i64, _p, _p, _f, _p, _p, _f, _p, _i64, _i, _i, _i, _i, _p],
     "vy_rope_fwd": [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i, _i64, _i, _i, _i, _p],
     "vy_linear_dgrad": [_p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _p],
     "vy_linear_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _i64, _i, _p],
@@ -105,7 +108,7 @@ PROTOTYPES = {
 }
 OTHER_SYMBOLS = ["vy_last_error", "vy_abi_version", "vy_layernorm_bwd_ws_rows", "vy_decode_ws_bytes",
                  "vy_gemma_ws_bytes", "vy_ddp_world", "vy_ddp_rank", "vy_attn_paged_decode_ws_bytes",
-                 "vy_attn_paged_decode_fp8_ws_bytes", "vy_lora_wgrad_chunk_rows"]
+                 "vy_attn_paged_decode_fp8_ws_bytes", "vy_lora_wgrad_chunk_rows", "vy_qknorm_bwd_ws_floats"]
 ALL_SYMBOLS = list(PROTOTYPES) + OTHER_SYMBOLS
 
 
@@ -155,6 +158,8 @@ def load() -> C.CDLL:
     lib.vy_attn_paged_decode_fp8_ws_bytes.argtypes = [_i64, _i, _i, _i, _i64, _i, _i]
     lib.vy_lora_wgrad_chunk_rows.restype = C.c_int64
     lib.vy_lora_wgrad_chunk_rows.argtypes = [_i64, _i64, _i64]
+    lib.vy_qknorm_bwd_ws_floats.restype = C.c_int64
+    lib.vy_qknorm_bwd_ws_floats.argtypes = [_i64, _i, _i, _i]
     _lib = lib
     return lib
 

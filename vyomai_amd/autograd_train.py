@@ -941,6 +941,95 @@ class PreNormAttentionFn(torch.autograd.Function):
         return (dx, None, None, None, dlnw, None, dwo, *grads)
 
 
+def _qk_scale_bwd(packed, qkv, h, hk, dh, q_scale, k_scale, eps):
+    """vy_qknorm_bwd on the packed [dq | dk | dv] buffer, in place -> the two scale gradients to return to autograd.  The
+    three ways of _rms_bwd, per scale: accumulated into the arena gradient and reported (None), returned as a tensor, or
+    -- a frozen scale -- neither written nor returned."""
+    qs, ks = _shadow(q_scale, torch.float32), _shadow(k_scale, torch.float32)
+    if _direct(q_scale) and _direct(k_scale) and q_scale.requires_grad and k_scale.requires_grad:
+        ops.qknorm_bwd_(packed, qkv, h, hk, dh, qs, ks, eps, q_scale.grad, k_scale.grad, True)
+        _notify(q_scale, k_scale)
+        return None, None
+    dq = torch.empty((dh,), dtype=torch.float32, device=qkv.device)
+    dk = torch.empty((dh,), dtype=torch.float32, device=qkv.device)
+    ops.qknorm_bwd_(packed, qkv, h, hk, dh, qs, ks, eps, dq, dk, False)
+    out = []
+    for p, g in ((q_scale, dq), (k_scale, dk)):
+        if not p.requires_grad:
+            out.append(None)
+        elif _direct(p):
+            p.grad.add_(g)
+            _notify(p)
+            out.append(None)
+        else:
+            out.append(g.to(p.dtype))
+    return out[0], out[1]
+
+
+class PreNormQkNormAttentionFn(torch.autograd.Function):
+    """PreNormAttentionFn for a block whose q and k heads pass a per-head RMSNorm between the projection and the rotation
+    (Qwen3's qk_norm; Examples/simple_vllm.ipynb, GroupedQueryAttention.forward): the plain bias-free packed GEMM keeps
+    the RAW qkv rows, vy_qknorm_rope_fwd writes the normalised, rotated q and k beside them, and attention reads v in
+    place as a strided view of those rows.  The backward is PreNormAttentionFn's with one launch added: vy_qknorm_bwd
+    turns the dq | dk columns of the packed gradient into the gradient of the raw projection, in place, before the dgrad
+    and the weight gradient of the packed projection read it.  Inputs after `k_scale` are the projection weights in
+    _params() order."""
+
+    @staticmethod
+    def forward(ctx, x, mod, attention_mask, freqs, ln_w, eps, wo, q_scale, k_scale, qk_eps, *params):
+        _require_bf16(x)
+        B, L, _ = x.shape
+        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+        dt, dev = x.dtype, x.device
+        if attention_mask is not None and not isinstance(attention_mask, AttnMask):
+            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
+                               "backward kernel")
+        cos, sin, pos0 = resolve_freqs(freqs, dev)
+        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
+        qkv = ops.linear(n, mod._packed_shadow(dt)[0])       # (B, L, W): W is a multiple of 8, so the rows are dense
+        q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
+        k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
+        ops.qknorm_rope(qkv, h, hk, dh, _shadow(q_scale, torch.float32), _shadow(k_scale, torch.float32), qk_eps, cos, sin,
+                        pos0, q, k)
+        v = _heads(qkv[:, :, (h + hk) * dh:(h + 2 * hk) * dh], hk, dh)
+        lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
+        causal, kp, sp = False, None, 0
+        if attention_mask is not None:
+            causal, kp, sp = attention_mask.causal, attention_mask.keypad, attention_mask.start_pos
+            if kp is not None:
+                kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
+        o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
+        y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+        ctx.save_for_backward(x, n, qkv, q, k, o, lse)
+        ctx.meta = (mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, q_scale, k_scale, qk_eps, params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, n, qkv, q, k, o, lse = ctx.saved_tensors
+        mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, q_scale, k_scale, qk_eps, params = ctx.meta
+        B, L, _ = x.shape
+        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+        dt = x.dtype
+        dy = dy.contiguous()
+        do = ops.linear_dgrad(dy, _wt(wo, dt))
+        dwo, _ = _wgrad(dy, o, wo, None)
+        W = (h + 2 * hk) * dh
+        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
+        dq = _heads(packed[:, :, : h * dh], h, dh)
+        dk = _heads(packed[:, :, h * dh:(h + hk) * dh], hk, dh)
+        dv = _heads(packed[:, :, (h + hk) * dh:], hk, dh)
+        v = _heads(qkv[:, :, (h + hk) * dh:W], hk, dh)
+        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
+                          cos=cos, sin=sin, rope_pos0=pos0)
+        dqs, dks = _qk_scale_bwd(packed, qkv, h, hk, dh, q_scale, k_scale, qk_eps)
+        w, b = mod._packed()
+        dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt))
+        grads = _packed_wgrad(mod, packed, n, w, b, params)
+        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        return (dx, None, None, None, dlnw, None, dwo, dqs, dks, None, *grads)
+
+
 def _wt_gate_up(mlp, dtype):
     """W^T of the packed [gate; up] projection of a gated MLP module (gate_proj / up_proj / _packed_gate_up)."""
     return _wt_cached(mlp, lambda m: (m.gate_proj.weight._version, m.up_proj.weight._version, WEIGHT_EPOCH[0], dtype),

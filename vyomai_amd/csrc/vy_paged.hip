@@ -10,6 +10,7 @@
 // group sum), and a long context is split over workgroups whose fp32 (m, l, o) partials a second small launch combines.
 #include "vy_attn_gen.h"
 #include "vy_common.h"
+#include "vy_qknorm.h"
 #include "vy_wave.h"
 #include <float.h>
 
@@ -251,62 +252,26 @@ __global__ __launch_bounds__(64) void paged_combine_kernel(const float* __restri
   }
 }
 
-// four consecutive elements (8 bytes of bf16, 16 of fp32): half a head is a multiple of 4 elements, not of 8
-template <typename T> struct Quad;
-template <> struct Quad<float> {
-  static __device__ __forceinline__ void load(const float* p, float* v) { Chunk<float>::load(p, v); }
-  static __device__ __forceinline__ void store(float* p, const float* v) { Chunk<float>::store(p, v); }
-};
-template <> struct Quad<bf16> {
-  static __device__ __forceinline__ void load(const bf16* p, float* v) {
-    const bf16x4 t = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (float)t[e];
-  }
-  static __device__ __forceinline__ void store(bf16* p, const float* v) {
-    bf16x4 t;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) t[e] = (bf16)v[e];
-    *reinterpret_cast<bf16x4*>(p) = t;
-  }
-};
-
-// What follows the loads in both rope-write kernels.  The lane holds columns i4 .. i4 + 3 of the lower half (lo) and the
-// same 4 of the upper half (hi) of head hd of token t's packed row: q and k heads are rotated with row positions[t] of
-// the tables (the pairing d, d + dh/2 and the formula of rope2_kernel, vy_misc.hip, evaluated in fp32 and rounded once)
-// and stored in place, k and v heads are then stored into slot slots[t] of the pages.  pre(lo, hi) is what the caller
-// does to a q / k head in front of the rotation (the qk-norm factors, or nothing): called inside the q / k branch, so
-// its loads and the table loads are requested together.
-template <typename T, typename Pre>
-__device__ __forceinline__ void rope_store_quads(T* __restrict__ row, float (&lo)[4], float (&hi)[4], int i4, int hd,
-                                                 long long t, const int* __restrict__ positions,
-                                                 const long long* __restrict__ slots, const float* __restrict__ cos_tab,
-                                                 const float* __restrict__ sin_tab, long long table_rows,
-                                                 T* __restrict__ kc, T* __restrict__ vc, long long n_slots, int h, int hk,
-                                                 int dh, Pre pre) {
-  const int half = dh >> 1;
-  if (hd < h + hk) {
-    pre(lo, hi);
-    long long pos = positions[t];
-    pos = pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;   // memory safety only
-    const f32x4 c = *reinterpret_cast<const f32x4*>(cos_tab + pos * half + i4);
-    const f32x4 s = *reinterpret_cast<const f32x4*>(sin_tab + pos * half + i4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float a = lo[e], bb = hi[e];
-      lo[e] = a * c[e] - bb * s[e];
-      hi[e] = bb * c[e] + a * s[e];
-    }
-    Quad<T>::store(row + i4, lo);
-    Quad<T>::store(row + half + i4, hi);
-  }
+// What follows the rotation in both rope-write kernels: the lane holds columns i4 .. i4 + 3 of the lower half (lo) and
+// the same 4 of the upper half (hi) of head hd of token t's packed row; k and v heads go into slot slots[t] of the pages
+// (k: rounded exactly as the in-place store rounds them; v: the loaded bits).
+template <typename T>
+__device__ __forceinline__ void page_store_quads(const float (&lo)[4], const float (&hi)[4], int i4, int hd, long long t,
+                                                 const long long* __restrict__ slots, T* __restrict__ kc,
+                                                 T* __restrict__ vc, long long n_slots, int h, int hk, int dh) {
   if (hd < h) return;
   const long long slot = slots[t];
   if (slot < 0 || slot >= n_slots) return;
   const bool isk = hd < h + hk;
   T* dst = (isk ? kc : vc) + (slot * hk + (isk ? hd - h : hd - h - hk)) * dh;
-  Quad<T>::store(dst + i4, lo);   // (k: rounded exactly as the in-place store rounds them; v: the loaded bits)
-  Quad<T>::store(dst + half + i4, hi);
+  Quad<T>::store(dst + i4, lo);
+  Quad<T>::store(dst + (dh >> 1) + i4, hi);
+}
+
+// row positions[t] of the tables, clamped into them (memory safety only)
+__device__ __forceinline__ long long table_pos(const int* __restrict__ positions, long long t, long long table_rows) {
+  const long long pos = positions[t];
+  return pos < 0 ? 0 : pos < table_rows ? pos : table_rows - 1;
 }
 
 // thread = (token, head of the packed row, 4 columns of the lower half and the same 4 of the upper half)
@@ -329,38 +294,12 @@ __global__ __launch_bounds__(256) void paged_rope_write_kernel(T* __restrict__ q
   float lo[4], hi[4];
   Quad<T>::load(row + i4, lo);
   Quad<T>::load(row + half + i4, hi);
-  rope_store_quads(row, lo, hi, i4, hd, t, positions, slots, cos_tab, sin_tab, table_rows, kc, vc, n_slots, h, hk, dh,
-                   [](float (&)[4], float (&)[4]) {});
-}
-
-// sum over the 1 << lg lanes of a lane group (aligned to its size inside the wave, at most 32 lanes), in every lane of
-// it.  lg is wave-uniform, so the steps are scalar branches; the DPP steps and the row swap read neighbouring lanes,
-// so EVERY lane of the wave must arrive here (no early return, no divergent branch around the call).
-__device__ __forceinline__ float pow2_group_sum(float v, int lg) {
-  if (lg >= 1) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  if (lg >= 2) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  if (lg >= 3) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false));  // row_half_mirror
-  if (lg >= 4) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
-  if (lg >= 5) {   // the neighbouring row of 16
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = __builtin_bit_cast(float, (unsigned)s16[0]) + __builtin_bit_cast(float, (unsigned)s16[1]);
+  if (hd < h + hk) {   // q and k heads: the pairing d, d + dh/2 and the formula of rope2_kernel (vy_misc.hip), in fp32, one rounding
+    rope_rotate_quads(lo, hi, cos_tab, sin_tab, table_pos(positions, t, table_rows), half, i4);
+    Quad<T>::store(row + i4, lo);
+    Quad<T>::store(row + half + i4, hi);
   }
-  return v;
-}
-
-// the maximum over the same lane group, under the same rule: every lane of the wave arrives
-__device__ __forceinline__ float pow2_group_max(float v, int lg) {
-  if (lg >= 1) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false)));
-  if (lg >= 2) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false)));
-  if (lg >= 3) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, false)));
-  if (lg >= 4) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false)));
-  if (lg >= 5) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
-  }
-  return v;
+  page_store_quads(lo, hi, i4, hd, t, slots, kc, vc, n_slots, h, hk, dh);
 }
 
 // paged_rope_write_kernel with the per-head RMSNorm of q and k in front of the rotation (Qwen3's qk_norm).  A (token,
@@ -396,25 +335,15 @@ __global__ __launch_bounds__(256) void paged_qknorm_rope_write_kernel(T* __restr
     Quad<T>::load(row + i4, lo);
     Quad<T>::load(row + half + i4, hi);
   }
-  float ss = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ss = fmaf(lo[e], lo[e], ss);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ss = fmaf(hi[e], hi[e], ss);
-  ss = pow2_group_sum(ss, lg);                        // every lane of the wave, also the idle ones
+  const float ss = qk_group_sumsq(lo, hi, lg);        // every lane of the wave, also the idle ones
   if (!on) return;
-  rope_store_quads(row, lo, hi, i4, hd, t, positions, slots, cos_tab, sin_tab, table_rows, kc, vc, n_slots, h, hk, dh,
-                   [&](float (&a)[4], float (&b)[4]) {
-                     const float r = rsqrtf(fmaf(ss, inv_dh, eps));
-                     const float* sc = hd < h ? q_scale : k_scale;
-                     const f32x4 wl = *reinterpret_cast<const f32x4*>(sc + i4);
-                     const f32x4 wh = *reinterpret_cast<const f32x4*>(sc + half + i4);
-#pragma unroll
-                     for (int e = 0; e < 4; ++e) {
-                       a[e] = a[e] * r * wl[e];
-                       b[e] = b[e] * r * wh[e];
-                     }
-                   });
+  if (hd < h + hk) {
+    qknorm_rope_quads(lo, hi, ss, inv_dh, eps, hd < h ? q_scale : k_scale, cos_tab, sin_tab,
+                      table_pos(positions, t, table_rows), half, i4);
+    Quad<T>::store(row + i4, lo);
+    Quad<T>::store(row + half + i4, hi);
+  }
+  page_store_quads(lo, hi, i4, hd, t, slots, kc, vc, n_slots, h, hk, dh);
 }
 
 // The second launch of vy_paged_rope_write_fp8 (bf16 rows).  The first is the bf16 kernel above -- the plain one or the

@@ -25,7 +25,7 @@ from ..layers.kv_cache import DynamicCacheOne, StaticCacheOne
 from ..layers.mask import AttnMask
 from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
 from ..layers.positional_embeddings import RopeSlice, RopeTable, resolve_freqs
-from .common import PositionMixin
+from .common import PositionMixin, SequenceScoreMixin
 
 
 class Config:
@@ -342,7 +342,7 @@ class BaseModel(nn.Module, PositionMixin):
         return CausalLMOutput(last_hidden_state=self.norm(x), past_key_values=cache)
 
 
-class ModelForCausalLM(nn.Module):
+class ModelForCausalLM(nn.Module, SequenceScoreMixin):
     """BaseModel + the tied LM head.  Reference :606-747.
 
     The reference class inherits BaseModel and therefore also allocates a second trunk at the top level
@@ -421,65 +421,14 @@ class ModelForCausalLM(nn.Module):
         return TiedLMHeadLossFn.apply(hidden, labels, ignore_index, norm.weight, norm.variance_epsilon,
                                       self.lm_head.weight, self._table_pending(input_ids), self._label_flag(hidden.device))
 
-    def _label_flag(self, dev) -> torch.Tensor:
-        flag = getattr(self, "label_error", None)
-        if flag is None or flag.device != dev:
-            flag = self.label_error = torch.zeros(1, dtype=torch.int32, device=dev)
-        return flag
-
-    def sequence_logprobs(self, input_ids: torch.Tensor, selection_mask: torch.Tensor,
-                          attention_mask: Optional[torch.Tensor] = None,
-                          inputs_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Masked average log-probability of each sequence -> fp32 (B,): the notebook's
-        compute_logprobs(model(input_ids).logits, input_ids, selection_mask)
-        (Examples/vyom-ai-llm-sft-dpo-training.ipynb), with the final RMSNorm, the tied vocabulary GEMM and the
-        log-softmax fused.  With grad the logits are overwritten in place by their unit gradient (TiedLMHeadLogprobFn);
-        under torch.no_grad() they are only read (vy_logprob_fwd) and freed on return.  A sequence whose mask selects
-        nothing scores 0.  `inputs_embeds` replaces the embedding lookup (input_ids still supply the labels)."""
-        from ..autograd_train import TiedLMHeadLogprobFn, logprob_rows, tied_head_logprobs
-        if selection_mask.shape != input_ids.shape:
-            raise ValueError(f"selection_mask {tuple(selection_mask.shape)} must match input_ids {tuple(input_ids.shape)}")
-        _need_gpu(input_ids, "sequence_logprobs()")
+    # sequence_logprobs / dpo_loss / _label_flag: common.SequenceScoreMixin over these two
+    def _score_trunk(self, input_ids, attention_mask, inputs_embeds=None):
         if inputs_embeds is None:
-            hidden, _ = self.model.forward_hidden(input_ids, attention_mask)
-        else:
-            hidden, _ = self.model.forward_hidden(None, attention_mask, inputs_embeds=inputs_embeds)
-        labels, w = logprob_rows(input_ids, selection_mask)
-        norm, table = self.model.norm, self.lm_head.weight
-        flag = self._label_flag(hidden.device)
-        if _wants_grad(hidden, norm.weight, table):
-            return TiedLMHeadLogprobFn.apply(hidden, labels, w, norm.weight, norm.variance_epsilon, table,
-                                             self._table_pending(None if inputs_embeds is not None else input_ids), flag)
-        return tied_head_logprobs(hidden, labels, w, norm.weight, norm.variance_epsilon, table, flag)[0]
+            return self.model.forward_hidden(input_ids, attention_mask)[0]
+        return self.model.forward_hidden(None, attention_mask, inputs_embeds=inputs_embeds)[0]
 
-    def dpo_loss(self, batch, ref_model: Optional["ModelForCausalLM"] = None, beta: float = 0.1, ref_logprobs=None):
-        """Direct preference optimisation on one collated batch -> (loss, chosen_rewards, rejected_rewards): the
-        notebook's compute_dpo_loss_batch (Examples/vyom-ai-llm-sft-dpo-training.ipynb).  `batch` is its dict: chosen,
-        rejected (ids) and chosen_mask, rejected_mask, all (B, L) -- dpo_collate pads both sides to one length, so the
-        two are scored as ONE 2B-row batch and this module runs once per graph.  The frozen model is `ref_model`,
-        scored the same way under torch.no_grad(), or its precomputed scores `ref_logprobs = (chosen, rejected)`.
-        loss = mean -logsigmoid(beta * ((pi_c - pi_r) - (ref_c - ref_r))); the rewards are detached means."""
-        chosen, rejected = batch["chosen"], batch["rejected"]
-        cmask, rmask = batch["chosen_mask"], batch["rejected_mask"]
-        if chosen.shape != rejected.shape or cmask.shape != chosen.shape or rmask.shape != rejected.shape:
-            raise ValueError(f"dpo_loss needs chosen {tuple(chosen.shape)}, rejected {tuple(rejected.shape)} and their "
-                             f"masks {tuple(cmask.shape)}, {tuple(rmask.shape)} padded to one common length, as the "
-                             "notebook's dpo_collate does")
-        if (ref_model is None) == (ref_logprobs is None):
-            raise ValueError("dpo_loss needs exactly one of ref_model and ref_logprobs=(chosen, rejected)")
-        B = chosen.shape[0]
-        ids = torch.cat([chosen, rejected], dim=0)
-        mask = torch.cat([cmask, rmask], dim=0)
-        if ref_logprobs is None:
-            with torch.no_grad():   # scored first: its logits are gone before the policy's are allocated
-                ref = ref_model.sequence_logprobs(ids, mask)
-            ref_c, ref_r = ref[:B], ref[B:]
-        else:
-            ref_c, ref_r = (t.detach().to(device=ids.device, dtype=torch.float32) for t in ref_logprobs)
-        pi = self.sequence_logprobs(ids, mask)
-        pi_c, pi_r = pi[:B], pi[B:]
-        losses = -torch.nn.functional.logsigmoid(beta * ((pi_c - pi_r) - (ref_c - ref_r)))
-        return losses.mean(), (pi_c - ref_c).detach().mean(), (pi_r - ref_r).detach().mean()
+    def _score_head(self):
+        return self.model.norm.weight, self.model.norm.variance_epsilon, self.lm_head.weight
 
     @torch.no_grad()
     def forward_paged(self, input_ids: torch.Tensor, positions: torch.Tensor, metadata: dict, kv_mgr) -> torch.Tensor:

@@ -18,7 +18,14 @@ What differs from the notebook:
 * The block norms run through vy_rmsnorm_fwd, which takes the scale in the activations' dtype: in a bf16 model the fp32
   scale is rounded to bf16 once (a cached copy), where the notebook multiplies by the fp32 scale before its rounding.
 * The notebook-signature forward(input_ids, k_caches, v_caches, metadata) is not reproduced (its mixed-step semantics
-  are the engine's departure 1, serving.py); inference only, greedy decoding only."""
+  are the engine's departure 1, serving.py).
+
+Training (a model built with cfg["dtype"] = torch.float32: the parameters are the trainer's masters): forward_hidden,
+clm_loss, sequence_logprobs and dpo_loss run each half of a block as ONE autograd function, as ModelForCausalLM does --
+autograd_train.PreNormQkNormAttentionFn (vy_qknorm_rope_fwd / vy_qknorm_bwd around the plain packed QKV GEMM; a block
+without qk_norm takes PreNormAttentionFn) and PreNormGatedMlpFn -- and the head through TiedLMHeadLossFn /
+TiedLMHeadLogprobFn, tied or not.  GroupedQueryAttention and FeedForward carry the attribute names those functions ask
+of a module as aliases over their own parameters.  LoRA on this model is not wired."""
 from __future__ import annotations
 
 from typing import Optional
@@ -30,18 +37,33 @@ from .. import ops
 from .._lib import ACT_SILU, VyomHipError
 from ..adapters import layer_delta
 from ..layers.attention import _shadow
+from ..layers.mask import AttnMask
 from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
+from ..layers.positional_embeddings import RopeSlice, RopeTable
+from .common import SequenceScoreMixin
 from .custom_transformer import _need_gpu
 
 
 def _packed_rows(owner: nn.Module, slot: str, linears, dtype: torch.dtype) -> torch.Tensor:
-    """[W0; W1; ...] of bias-free linears in `dtype` for one packed GEMM: a concatenation cached on `owner`, rebuilt
-    when a member is written (its version counter), replaced (`lin.weight = ...`) or moved (its data pointer)."""
+    """[W0; W1; ...] of bias-free linears in `dtype` for one packed GEMM.  A view when the copies sit back to back in one
+    buffer (the trainer's arenas lay them out so); else a concatenation cached on `owner`, rebuilt when a member is
+    written (its version counter), replaced (`lin.weight = ...`) or moved (its data pointer), or when the trainer's
+    AdamW kernel has rewritten the arena copies (the weight epoch: it does not touch tensor versions)."""
+    from ..autograd_train import WEIGHT_EPOCH
     ws = [lin.weight for lin in linears]
-    key = tuple((w._version, w.data_ptr()) for w in ws) + (dtype,)
+    cs = [_shadow(w, dtype).detach() for w in ws]
+    c0, end = cs[0], cs[0].data_ptr()
+    for c in cs:
+        if not c.is_contiguous() or c.data_ptr() != end or \
+                c.untyped_storage().data_ptr() != c0.untyped_storage().data_ptr():   # one buffer, not two neighbours
+            break
+        end += c.numel() * c.element_size()
+    else:
+        return torch.as_strided(c0, (sum(c.shape[0] for c in cs), c0.shape[1]), (c0.shape[1], 1))
+    key = tuple((w._version, w.data_ptr()) for w in ws) + (WEIGHT_EPOCH[0], dtype)
     hit = getattr(owner, slot, None)
     if hit is None or hit[0] != key:
-        hit = (key, torch.cat([_shadow(w, dtype).detach() for w in ws], dim=0).contiguous())
+        hit = (key, torch.cat(cs, dim=0).contiguous())
         setattr(owner, slot, hit)
     return hit[1]
 
@@ -78,11 +100,20 @@ class FeedForward(nn.Module):
         d, f = cfg["emb_dim"], cfg["hidden_dim"]
         self.fc1, self.fc2, self.fc3 = _linear(cfg, d, f), _linear(cfg, d, f), _linear(cfg, f, d)
 
+    # what autograd_train.PreNormGatedMlpFn asks of a gated MLP, over the same three linears (no state_dict key)
+    act = ACT_SILU
+    gate_proj = property(lambda self: self.fc1)
+    up_proj = property(lambda self: self.fc2)
+    down_proj = property(lambda self: self.fc3)
+
+    def _packed_gate_up(self, dtype: torch.dtype) -> torch.Tensor:
+        return _packed_rows(self, "_vy_gu", (self.fc1, self.fc2), dtype)
+
     @torch.no_grad()
     def forward(self, x, residual: Optional[torch.Tensor] = None, delta=None):
         """delta (serving with adapters, adapters.layer_delta): f(group, y, x), called behind each of the two GEMMs."""
         _need_gpu(x, "FeedForward")
-        gu = ops.linear(x, _packed_rows(self, "_vy_gu", (self.fc1, self.fc2), x.dtype))
+        gu = ops.linear(x, self._packed_gate_up(x.dtype))
         if delta is not None:
             delta("gate_up", gu, x)
         h = ops.gated_act(gu, ACT_SILU)
@@ -114,6 +145,22 @@ class GroupedQueryAttention(nn.Module):
     def _packed_qkv(self, dtype: torch.dtype) -> torch.Tensor:
         return _packed_rows(self, "_vy_qkv", (self.W_query, self.W_key, self.W_value), dtype)
 
+    # what autograd_train's packed-QKV functions (_packed_wgrad, _wt_packed, PreNorm*AttentionFn) ask of an attention
+    # module, over the same three bias-free linears (no state_dict key, no second copy of a weight)
+    _fused_qkv = False
+    attention_bias = False
+    num_attention_heads = property(lambda self: self.num_heads)
+    num_key_value_heads = property(lambda self: self.num_kv_groups)
+
+    def _params(self):
+        return [self.W_query.weight, self.W_key.weight, self.W_value.weight]
+
+    def _packed(self):
+        return self._packed_qkv(self.W_query.weight.dtype), None
+
+    def _packed_shadow(self, dtype: torch.dtype):
+        return self._packed_qkv(dtype), None
+
     def forward(self, *args, **kwargs):
         raise VyomHipError("GroupedQueryAttention runs inside Qwen3Model.forward_paged")
 
@@ -144,9 +191,12 @@ class _ConfigView:
         self.rope_theta = cfg["rope_base"]
 
 
-class Qwen3Model(nn.Module):
+class Qwen3Model(nn.Module, SequenceScoreMixin):
     """tok_emb, trf_blocks, final_norm, out_head and the cos_buf / sin_buf buffers of the notebook's model;
-    `forward_paged` is the engine's protocol, `.config` the view PagedKVManager(model.config, ...) needs."""
+    `forward_paged` is the engine's protocol, `.config` the view PagedKVManager(model.config, ...) needs;
+    forward_hidden / clm_loss / sequence_logprobs / dpo_loss are the training side (fp32 parameters)."""
+
+    compute_dtype = None   # set by FlatTrainer (None = the parameters' dtype)
 
     def __init__(self, cfg):
         super().__init__()
@@ -162,24 +212,91 @@ class Qwen3Model(nn.Module):
         cos, sin = freqs.cos().contiguous(), freqs.sin().contiguous()
         self.register_buffer("cos_buf", cos.to(cfg["dtype"]))
         self.register_buffer("sin_buf", sin.to(cfg["dtype"]))
-        # the tables the kernels read: fp32, host (not buffers: they are neither saved nor cast by .to(dtype))
-        self._rope_host = (cos, sin)
-        self._rope_dev = {}
+        # the tables the kernels read: fp32, evaluated on the host by the same two calls and uploaded once per device
+        # (not buffers: they are neither saved nor cast by .to(dtype))
+        self._rope = RopeTable(freqs)
 
     def tie_head(self) -> None:
         """out_head shares tok_emb's matrix from now on (state_dict() keeps both names)."""
         self.out_head.weight = self.tok_emb.weight
 
     def _rope_tables(self, dev: torch.device):
-        if dev not in self._rope_dev:
-            self._rope_dev[dev] = tuple(t.to(dev) for t in self._rope_host)
-        return self._rope_dev[dev]
+        return self._rope.on(dev)
 
     def forward(self, *args, **kwargs):
         raise VyomHipError("Qwen3Model is served through forward_paged(input_ids, positions, metadata, kv_mgr) "
                            "(serving.ContinuousBatchEngine); the notebook's forward(input_ids, k_caches, v_caches, "
                            "metadata) is not reproduced")
 
+    # ---- training ---------------------------------------------------------------------------------
+    def _table_pending(self, input_ids) -> bool:
+        """Does this graph's backward also scatter embedding gradients into the head's table?  Only a tied head: an
+        untied one is a table that embedded nothing."""
+        w = self.tok_emb.weight
+        return input_ids is not None and self.out_head.weight is w and torch.is_grad_enabled() and w.requires_grad
+
+    def forward_hidden(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The trunk without the final norm over whole sequences: input_ids (B, L), positions 0 .. L-1 in every row;
+        attention_mask: a 2-D padding mask (1 = token), which becomes the causal + key-padding descriptor.  With grad
+        each half of a block is one autograd function; under torch.no_grad() the same launches run and nothing is
+        kept."""
+        from ..autograd_train import (EmbeddingFn, PreNormAttentionFn, PreNormGatedMlpFn, PreNormQkNormAttentionFn)
+        _need_gpu(input_ids, "forward_hidden()")
+        B, L = input_ids.shape
+        if L > self.cfg["context_length"]:
+            raise ValueError(f"sequence length {L} exceeds context_length {self.cfg['context_length']}")
+        w = self.tok_emb.weight
+        if torch.is_grad_enabled() and w.dtype != torch.float32 and any(p.requires_grad for p in self.parameters()):
+            raise VyomHipError(f"Qwen3Model trains on fp32 parameters (the trainer's masters), these are {w.dtype}: build "
+                               "the model with cfg['dtype'] = torch.float32 and load_state_dict() into it; bf16 compute "
+                               "comes from FlatTrainer(model)")
+        dt = self.compute_dtype or w.dtype
+        if torch.is_grad_enabled() and w.requires_grad:
+            x = EmbeddingFn.apply(input_ids, w, None, dt)
+        else:
+            x = ops.embedding(_shadow(w, dt), input_ids)
+        if attention_mask is not None:
+            if attention_mask.dim() != 2:
+                raise VyomHipError("training needs a mask descriptor (pass the 2-D padding mask): dense additive masks "
+                                   "have no backward kernel")
+            mask = AttnMask.from_padding(attention_mask, causal=True, start_pos=0, query_len=L)
+        else:
+            mask = AttnMask(causal=True, start_pos=0, query_len=L, key_len=L) if L > 1 else None
+        freqs = RopeSlice(self._rope, 0, L)
+        for blk in self.trf_blocks:
+            a, ff = blk.att, blk.ff
+            if a.q_norm is not None:
+                if a.q_norm.eps != a.k_norm.eps:
+                    raise ValueError("q_norm and k_norm share one eps in vy_qknorm_rope_fwd")
+                x = PreNormQkNormAttentionFn.apply(x, a, mask, freqs, blk.norm1.scale, blk.norm1.eps, a.out_proj.weight,
+                                                   a.q_norm.scale, a.k_norm.scale, a.q_norm.eps, *a._params())
+            else:
+                x = PreNormAttentionFn.apply(x, a, mask, freqs, blk.norm1.scale, blk.norm1.eps, a.out_proj.weight,
+                                             *a._params())
+            x = PreNormGatedMlpFn.apply(x, ff, blk.norm2.scale, blk.norm2.eps, ff.act, ff.fc1.weight, ff.fc2.weight,
+                                        ff.fc3.weight)
+        return x
+
+    def clm_loss(self, input_ids: torch.Tensor, labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                 ignore_index: int = -100) -> torch.Tensor:
+        """Shifted next-token loss with the final RMSNorm, the vocabulary GEMM (out_head, tied or not) and the
+        cross-entropy fused: the logits are reduced and overwritten by their gradient in place, never kept."""
+        from ..autograd_train import TiedLMHeadLossFn
+        hidden = self.forward_hidden(input_ids, attention_mask)
+        return TiedLMHeadLossFn.apply(hidden, labels, ignore_index, self.final_norm.scale, self.final_norm.eps,
+                                      self.out_head.weight, self._table_pending(input_ids),
+                                      self._label_flag(hidden.device))
+
+    # sequence_logprobs / dpo_loss: common.SequenceScoreMixin over these two
+    def _score_trunk(self, input_ids, attention_mask, inputs_embeds=None):
+        if inputs_embeds is not None:
+            raise VyomHipError("Qwen3Model scores token ids (inputs_embeds is not wired)")
+        return self.forward_hidden(input_ids, attention_mask)
+
+    def _score_head(self):
+        return self.final_norm.scale, self.final_norm.eps, self.out_head.weight
+
+    # ---- serving ----------------------------------------------------------------------------------
     @torch.no_grad()
     def forward_paged(self, input_ids: torch.Tensor, positions: torch.Tensor, metadata: dict, kv_mgr) -> torch.Tensor:
         """One step of serving.ContinuousBatchEngine -> logits (sequences, vocab) of the last row of each sequence whose

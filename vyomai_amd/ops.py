@@ -1146,6 +1146,47 @@ def gated_act_bwd(d_act: Tensor, gate_up: Tensor, act: int) -> Tensor:
     return out.view(gate_up.shape)
 
 
+def _qk_scales(dh: int, *scales: Tensor) -> None:
+    for s in scales:
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.shape == (dh,)
+
+
+def qknorm_rope(qkv: Tensor, h: int, hk: int, dh: int, q_scale: Tensor, k_scale: Tensor, eps: float, cos: Tensor,
+                sin: Tensor, pos0: int, q: Tensor, k: Tensor) -> None:
+    """qkv (B, L, >= (h + 2 hk) dh), the packed rows of the bias-free QKV GEMM, left as they are: every q head becomes
+    rope(x * rsqrt(mean x^2 + eps) * q_scale) in q (B, h, L, dh), every k head the same with k_scale in k (B, hk, L, dh)
+    -- views written in place; scales fp32 (dh,), fp32 cos / sin tables, row pos0 + l; fp32 from the load to the one
+    store.  (vy_qknorm_rope_fwd)"""
+    _need_gpu(qkv, q_scale, k_scale, cos, sin, q, k)
+    B, L = qkv.shape[0], qkv.shape[1]
+    assert qkv.dim() == 3 and qkv.stride(2) == 1 and qkv.stride(0) == L * qkv.stride(1) and qkv.shape[2] >= (h + 2 * hk) * dh
+    assert q.shape == (B, h, L, dh) and k.shape == (B, hk, L, dh) and q.stride(3) == 1 and k.stride(3) == 1
+    assert q.dtype == qkv.dtype and k.dtype == qkv.dtype
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape[1] == dh // 2 and sin.shape == cos.shape
+    _qk_scales(dh, q_scale, k_scale)
+    call("vy_qknorm_rope_fwd", qkv.data_ptr(), qkv.stride(1), cos.data_ptr(), sin.data_ptr(), cos.shape[0], int(pos0),
+         q_scale.data_ptr(), k_scale.data_ptr(), float(eps), q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+         k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), B, L, h, hk, dh, dtype_code(qkv.dtype), _stream())
+
+
+def qknorm_bwd_(dqkv: Tensor, qkv: Tensor, h: int, hk: int, dh: int, q_scale: Tensor, k_scale: Tensor, eps: float,
+                dq_scale: Tensor, dk_scale: Tensor, accumulate: bool) -> Tensor:
+    """dqkv (..., >= (h + 2 hk) dh), layout [dq | dk | dv] with dq / dk the gradients of the NORMALISED heads: its q and k
+    columns are overwritten in place by the gradient of the raw projection qkv (the saved rows qknorm_rope read); the dv
+    columns keep their bits.  dq_scale / dk_scale (fp32 (dh,)) (+)= the scale gradients, deterministic.
+    (vy_qknorm_bwd: no saved statistics)"""
+    _need_gpu(dqkv, qkv, q_scale, k_scale, dq_scale, dk_scale)
+    d2, x2 = dqkv.view(-1, dqkv.shape[-1]), qkv.view(-1, qkv.shape[-1])
+    T = x2.shape[0]
+    assert d2.shape[0] == T and d2.stride(1) == 1 and x2.stride(1) == 1 and d2.dtype == x2.dtype
+    _qk_scales(dh, q_scale, k_scale, dq_scale, dk_scale)
+    ws = torch.empty((_lib.load().vy_qknorm_bwd_ws_floats(T, h, hk, dh),), dtype=torch.float32, device=qkv.device)
+    call("vy_qknorm_bwd", d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0), q_scale.data_ptr(), k_scale.data_ptr(),
+         float(eps), dq_scale.data_ptr(), dk_scale.data_ptr(), 1.0 if accumulate else 0.0, ws.data_ptr(), T, h, hk, dh,
+         dtype_code(qkv.dtype), _stream())
+    return dqkv
+
+
 # ------------------------------------------------------------------------------------------
 # paged KV cache (vy_paged.hip)
 # ------------------------------------------------------------------------------------------
