@@ -4,6 +4,8 @@
   linear_residual_layernorm AttentionSelfOutput on its own
   ffn_block                 GEMM+GELU -> GEMM + residual -> LayerNorm
 
+and the gated MLP of the pre-norm decoders (gated_mlp: packed gate/up GEMM -> gated activation -> GEMM + residual).
+
 The grouping follows the reference author's own fused ops (Examples/vyom-ai-decoder-fused.ipynb
 cells 2-7: LinearRms, FFNGeLU, ScaledDotProductAttention, RotaryEmbeddingFunction).  Inference
 calls go straight to the forward kernels; when gradients are required the same kernels run inside
@@ -68,6 +70,21 @@ def ffn_block(x, residual, w1, b1, w2, b2, ln_w, ln_b, eps, act, p_drop: float =
     s = ops.linear(hmid, _shadow(w2, dt), _shadow(b2, dt), residual=residual, dropout=drop)
     y, _, _ = ops.layernorm(s, _shadow(ln_w, dt), _shadow(ln_b, dt), eps)
     return y
+
+
+def gated_mlp(x, mlp, act, wd, residual=None, delta=None):
+    """(act(x Wg^T) * x Wu^T) Wd^T + residual -> (y, gate_up): one packed [gate; up] GEMM (mlp._packed_gate_up),
+    vy_gated_act_fwd, the down GEMM (wd: its weight in x's dtype) with the residual in its epilogue.  delta =
+    f(group, y, x) is called behind each of the two GEMMs and adds a LoRA delta to y in place: adapters.layer_delta in
+    serving, lora_train.py in fine-tuning."""
+    gu = ops.linear(x, mlp._packed_gate_up(x.dtype))
+    if delta is not None:
+        delta("gate_up", gu, x)
+    h = ops.gated_act(gu, act)
+    y = ops.linear(h, wd, None, residual=residual)
+    if delta is not None:
+        delta("down", y, h)
+    return y, gu
 
 
 def _mask_args(mask, B, L, S, device):

@@ -15,12 +15,13 @@ from __future__ import annotations
 import os
 
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib, ops
 from ._lib import ACT_GELU_ERF, ACT_NONE, VyomHipError
+from .autograd import gated_mlp
 from .layers.attention import _shadow
 from .layers.mask import AttnMask
 from .layers.positional_embeddings import resolve_freqs
@@ -419,6 +420,93 @@ class FfnBlockFn(torch.autograd.Function):
         return dx, ds, dw1, db1, dw2, db2, dg, dbt, None, None, None
 
 
+class _AttnArgs(NamedTuple):
+    """What the attention kernels take from the mask descriptor and the RoPE slice."""
+    causal: bool
+    keypad: Optional[torch.Tensor]
+    start_pos: int
+    cos: Optional[torch.Tensor]
+    sin: Optional[torch.Tensor]
+    pos0: int
+
+
+def _attn_args(attention_mask, freqs, S: int, device) -> _AttnArgs:
+    """S: the number of keys the kernels see; a wider key-padding row is trimmed to it."""
+    if attention_mask is not None and not isinstance(attention_mask, AttnMask):
+        raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
+                           "backward kernel")
+    cos, sin, pos0 = resolve_freqs(freqs, device)
+    if attention_mask is None:
+        return _AttnArgs(False, None, 0, cos, sin, pos0)
+    kp = attention_mask.keypad
+    if kp is not None and kp.shape[1] != S:
+        kp = kp[:, :S].contiguous()
+    return _AttnArgs(attention_mask.causal, kp, attention_mask.start_pos, cos, sin, pos0)
+
+
+def _heads(x2: torch.Tensor, heads: int, dh: int) -> torch.Tensor:
+    B, L, _ = x2.shape
+    return x2.view(B, L, heads, dh).permute(0, 2, 1, 3)
+
+
+def _qkv_heads(packed: torch.Tensor, h: int, hk: int, dh: int):
+    """The q / k / v head views (B, heads, L, dh) of packed (B, L, >= (h + 2 hk) dh) rows laid out [q | k | v], 'b l (h d)'."""
+    return (_heads(packed[:, :, : h * dh], h, dh), _heads(packed[:, :, h * dh:(h + hk) * dh], hk, dh),
+            _heads(packed[:, :, (h + hk) * dh:(h + 2 * hk) * dh], hk, dh))
+
+
+def _project_qkv(n, mod, am: _AttnArgs, qk=None, delta=None):
+    """The packed q / k / v projection of n (B, L, d) with RoPE -> (q, k, v as (B, heads, L, dh), qkv).  `mod` packs
+    q/k/v as the _SelfAttentionBase modules do.  Three ways, each with its own launches and rounding:
+      * neither: vy_qkv_rope_fwd writes the rotated q, k and v into three buffers; qkv is None;
+      * qk = (q_scale, k_scale, eps), Qwen3's qk_norm: the plain bias-free GEMM keeps the RAW rows in qkv,
+        vy_qknorm_rope_fwd writes the normalised, rotated q and k beside them, and v is a strided view of those rows;
+      * delta = f(group, y, x), LoRA: the plain GEMM, the adapter's delta behind it -- before RoPE -- and ops.rope_ on the
+        q and k views of qkv; all three are views."""
+    B, L, _ = n.shape
+    h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+    dt, dev = n.dtype, n.device
+    sw, sb = mod._packed_shadow(dt)
+    if delta is not None:
+        qkv = torch.empty((B, L, (h + 2 * hk) * dh), dtype=dt, device=dev)
+        ops.linear(n, sw, sb, out=qkv)
+        delta("qkv", qkv, n)
+        q, k, v = _qkv_heads(qkv, h, hk, dh)
+        ops.rope_(q, am.cos, am.sin, am.pos0)
+        ops.rope_(k, am.cos, am.sin, am.pos0)
+        return q, k, v, qkv
+    q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
+    k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
+    if qk is not None:
+        q_scale, k_scale, qk_eps = qk
+        qkv = ops.linear(n, sw)       # (B, L, W): W is a multiple of 8, so the rows are dense
+        ops.qknorm_rope(qkv, h, hk, dh, _shadow(q_scale, torch.float32), _shadow(k_scale, torch.float32), qk_eps, am.cos,
+                        am.sin, am.pos0, q, k)
+        return q, k, _qkv_heads(qkv, h, hk, dh)[2], qkv
+    v = torch.empty_like(k)
+    ops.qkv_rope(n, sw, sb, h, hk, dh, am.cos, am.sin, am.pos0, q, k, v)
+    return q, k, v, None
+
+
+def _attend(q, k, v, am: _AttnArgs):
+    """-> (o (B, L, h dh), lse)."""
+    B, h, L, _ = q.shape
+    lse = torch.empty((B, h, L), dtype=torch.float32, device=q.device)
+    return ops.attention(q, k, v, causal=am.causal, start_pos=am.start_pos, keypad=am.keypad, lse=lse), lse
+
+
+def _attention_bwd(q, k, v, o, do, lse, am: _AttnArgs) -> torch.Tensor:
+    """-> the packed gradient (B, L, (h + 2 hk) dh), [dq | dk | dv] as the packed projection lays its columns out.
+    RoPE is orthogonal: its backward (the inverse rotation of dq, dk) runs in the epilogues."""
+    B, h, L, dh = q.shape
+    hk = k.shape[1]
+    packed = torch.empty((B, L, (h + 2 * hk) * dh), dtype=o.dtype, device=o.device)
+    dq, dk, dv = _qkv_heads(packed, h, hk, dh)
+    ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=am.causal, start_pos=am.start_pos, keypad=am.keypad,
+                      cos=am.cos, sin=am.sin, rope_pos0=am.pos0)
+    return packed
+
+
 class SelfAttentionFn(torch.autograd.Function):
     """o = merge_heads(softmax(rope(q) rope(k)^T / sqrt(dh) + mask) v) with q,k,v = x W^T + b.
     Inputs after `mod` are the projection parameters in module order (q,k,v weights then biases,
@@ -427,47 +515,20 @@ class SelfAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, attention_mask, freqs, start_pos, *params):
         _require_bf16(x)
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
-        dt, dev = x.dtype, x.device
-        w, b = mod._packed()
-        if attention_mask is not None and not isinstance(attention_mask, AttnMask):
-            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
-                               "backward kernel")
-        cos, sin, pos0 = resolve_freqs(freqs, dev)
-        q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
-        k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
-        v = torch.empty_like(k)
-        sw, sb = mod._packed_shadow(dt)
-        ops.qkv_rope(x, sw, sb, h, hk, dh, cos, sin, pos0, q, k, v)
-        lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
-        causal, kp, sp = False, None, 0
-        if attention_mask is not None:
-            causal, kp, sp = attention_mask.causal, attention_mask.keypad, attention_mask.start_pos
-            if kp is not None:
-                kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
-        o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
+        am = _attn_args(attention_mask, freqs, x.shape[1], x.device)
+        q, k, v, _ = _project_qkv(x, mod, am)
+        o, lse = _attend(q, k, v, am)
         ctx.save_for_backward(x, q, k, v, o, lse)
-        ctx.meta = (mod, causal, kp, sp, cos, sin, pos0, params)
+        ctx.meta = (mod, am, params)
         ctx.defer = _defer_list(x)
         return o
 
     @staticmethod
     def backward(ctx, do):
         x, q, k, v, o, lse = ctx.saved_tensors
-        mod, causal, kp, sp, cos, sin, pos0, params = ctx.meta
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+        mod, am, params = ctx.meta
         dt = x.dtype
-        do = do.contiguous()
-        W = (h + 2 * hk) * dh
-        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
-        dq = packed[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
-        dk = packed[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        dv = packed[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        # RoPE is orthogonal: its backward (the inverse rotation of dq, dk) runs in the epilogues
-        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
-                          cos=cos, sin=sin, rope_pos0=pos0)
+        packed = _attention_bwd(q, k, v, o, do.contiguous(), lse, am)
         w, b = mod._packed()
         # the layer input's other gradient contributions (residual paths of this layer's out-projection
         # and feed-forward, deferred by their backward) are added in this GEMM's epilogue
@@ -496,26 +557,19 @@ class CrossAttentionFn(torch.autograd.Function):
     def forward(ctx, x, enc, mod, enc_mask, wq, bq, wk, bk, wv, bv):
         _require_bf16(x)
         B, L, _ = x.shape
-        S = enc.shape[1]
         h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
         dt, dev = x.dtype, x.device
-        if enc_mask is not None and not isinstance(enc_mask, AttnMask):
-            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
-                               "backward kernel")
+        am = _attn_args(enc_mask, None, enc.shape[1], dev)
+        if am.causal:
+            raise VyomHipError("cross-attention takes a key-padding mask, not a causal one")
         q2 = ops.linear(x, _shadow(wq, dt), _shadow(bq, dt))
         k2 = ops.linear(enc, _shadow(wk, dt), _shadow(bk, dt))
         v2 = ops.linear(enc, _shadow(wv, dt), _shadow(bv, dt))
-        kp = None
-        if enc_mask is not None:
-            if enc_mask.causal:
-                raise VyomHipError("cross-attention takes a key-padding mask, not a causal one")
-            kp = enc_mask.keypad
-            if kp is not None:
-                kp = kp[:, :S].contiguous() if kp.shape[1] != S else kp
         lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
-        o = ops.attention(_heads(q2, h, dh), _heads(k2, hk, dh), _heads(v2, hk, dh), causal=False, keypad=kp, lse=lse)
+        o = ops.attention(_heads(q2, h, dh), _heads(k2, hk, dh), _heads(v2, hk, dh), causal=False, keypad=am.keypad,
+                          lse=lse)
         ctx.save_for_backward(x, enc, q2, k2, v2, o, lse)
-        ctx.meta = (mod, kp, (wq, bq, wk, bk, wv, bv))
+        ctx.meta = (mod, am.keypad, (wq, bq, wk, bk, wv, bv))
         return o
 
     @staticmethod
@@ -535,11 +589,6 @@ class CrossAttentionFn(torch.autograd.Function):
         dwk, dbk = _wgrad(dk2, enc, wk, bk)
         dwv, dbv = _wgrad(dv2, enc, wv, bv)
         return dx, denc, None, None, dwq, dbq, dwk, dbk, dwv, dbv
-
-
-def _heads(x2: torch.Tensor, heads: int, dh: int) -> torch.Tensor:
-    B, L, _ = x2.shape
-    return x2.view(B, L, heads, dh).permute(0, 2, 1, 3)
 
 
 def _wt_packed(mod, w, dtype):
@@ -883,61 +932,77 @@ def _rms_bwd(dy, x, w, eps, add_to=None):
     return dx, dw.to(w.dtype)
 
 
+def prenorm_attention_forward(x, mod, attention_mask, freqs, ln_w, eps, wo, qk=None, delta=None):
+    """y = x + attn(project(RMSNorm(x))) Wo^T: the attention half of a pre-norm block (the reference's DecoderLayer,
+    models/custom_transformer.py:268-282) -> (y, (n, q, k, v, qkv, o, lse), am).  `mod`, qk and delta: see _project_qkv,
+    the only step that differs between the plain, the qk_norm and the LoRA block; delta is also called behind the
+    out-projection, as delta("o", y, o)."""
+    dt = x.dtype
+    am = _attn_args(attention_mask, freqs, x.shape[1], x.device)
+    n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
+    q, k, v, qkv = _project_qkv(n, mod, am, qk, delta)
+    o, lse = _attend(q, k, v, am)
+    y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+    if delta is not None:
+        delta("o", y, o)
+    return y, (n, q, k, v, qkv, o, lse), am
+
+
+def prenorm_attention_backward(dy, x, n, o, lse, am, mod, ln_w, eps, wo, params=(), q=None, k=None, v=None, qkv=None,
+                               qk=None, adapters=None, need_dx=True):
+    """Backward of prenorm_attention_forward -> (dx, dln_w, dwo, dq_scale, dk_scale, the gradients of `params`, the
+    projection's parameters in _params() order), each None where nothing is returned to autograd.  q / k / v that the
+    forward left as views of qkv are passed as None and read there.  adapters: None trains the base weights (_wgrad,
+    _packed_wgrad); a dict group -> f(dy, x, dx) freezes them and runs the adapter backward of the groups it names
+    (lora_train.py), and then need_dx=False skips the packed dgrad and the RMSNorm backward nobody reads.  The residual
+    branch's gradient is added in the RMSNorm backward's store (vy_rmsnorm_bwd add_to)."""
+    h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
+    dt = x.dtype
+    dy = dy.contiguous()
+    do = ops.linear_dgrad(dy, _wt(wo, dt))
+    dwo = None
+    if adapters is None:
+        dwo, _ = _wgrad(dy, o, wo, None)
+    elif "o" in adapters:
+        adapters["o"](dy, o, do)
+    if qkv is not None:
+        views = _qkv_heads(qkv, h, hk, dh)
+        q, k, v = (t if t is not None else view for t, view in zip((q, k, v), views))
+    packed = _attention_bwd(q, k, v, o, do, lse, am)
+    dqs = dks = None
+    if qk is not None:    # the dq | dk columns become the gradient of the raw projection, in place, before both readers
+        dqs, dks = _qk_scale_bwd(packed, qkv, h, hk, dh, *qk)
+    w, b = mod._packed()
+    dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt)) if need_dx else None
+    grads = ()
+    if adapters is None:
+        grads = _packed_wgrad(mod, packed, n, w, b, params)
+    elif "qkv" in adapters:
+        adapters["qkv"](packed, n, dn)
+    dx = dlnw = None
+    if need_dx:
+        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+    return dx, dlnw, dwo, dqs, dks, grads
+
+
 class PreNormAttentionFn(torch.autograd.Function):
-    """y = x + attn(qkv_rope(RMSNorm(x))) Wo^T: the attention half of the reference's DecoderLayer
-    (models/custom_transformer.py:268-282; biased q/k/v, bias-free o_proj).  `mod` packs q/k/v as the
-    _SelfAttentionBase modules do and carries `o_proj`; inputs after `wo` are its q/k/v parameters in _params() order.
-    The residual branch's gradient is added in the RMSNorm backward's store (vy_rmsnorm_bwd add_to)."""
+    """prenorm_attention_forward / _backward with the fused QKV + RoPE projection (biased q/k/v or bias-free, bias-free
+    o_proj).  `mod` carries `o_proj`; inputs after `wo` are its q/k/v parameters in _params() order."""
 
     @staticmethod
     def forward(ctx, x, mod, attention_mask, freqs, ln_w, eps, wo, *params):
         _require_bf16(x)
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
-        dt, dev = x.dtype, x.device
-        if attention_mask is not None and not isinstance(attention_mask, AttnMask):
-            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
-                               "backward kernel")
-        cos, sin, pos0 = resolve_freqs(freqs, dev)
-        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-        q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
-        k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
-        v = torch.empty_like(k)
-        sw, sb = mod._packed_shadow(dt)
-        ops.qkv_rope(n, sw, sb, h, hk, dh, cos, sin, pos0, q, k, v)
-        lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
-        causal, kp, sp = False, None, 0
-        if attention_mask is not None:
-            causal, kp, sp = attention_mask.causal, attention_mask.keypad, attention_mask.start_pos
-            if kp is not None:
-                kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
-        o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
-        y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+        y, (n, q, k, v, _, o, lse), am = prenorm_attention_forward(x, mod, attention_mask, freqs, ln_w, eps, wo)
         ctx.save_for_backward(x, n, q, k, v, o, lse)
-        ctx.meta = (mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, params)
+        ctx.meta = (mod, am, ln_w, eps, wo, params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, n, q, k, v, o, lse = ctx.saved_tensors
-        mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, params = ctx.meta
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
-        dt = x.dtype
-        dy = dy.contiguous()
-        do = ops.linear_dgrad(dy, _wt(wo, dt))
-        dwo, _ = _wgrad(dy, o, wo, None)
-        W = (h + 2 * hk) * dh
-        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
-        dq = packed[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
-        dk = packed[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        dv = packed[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
-                          cos=cos, sin=sin, rope_pos0=pos0)
-        w, b = mod._packed()
-        dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt))
-        grads = _packed_wgrad(mod, packed, n, w, b, params)
-        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        mod, am, ln_w, eps, wo, params = ctx.meta
+        dx, dlnw, dwo, _, _, grads = prenorm_attention_backward(dy, x, n, o, lse, am, mod, ln_w, eps, wo, params,
+                                                                q=q, k=k, v=v)
         return (dx, None, None, None, dlnw, None, dwo, *grads)
 
 
@@ -968,65 +1033,24 @@ def _qk_scale_bwd(packed, qkv, h, hk, dh, q_scale, k_scale, eps):
 
 class PreNormQkNormAttentionFn(torch.autograd.Function):
     """PreNormAttentionFn for a block whose q and k heads pass a per-head RMSNorm between the projection and the rotation
-    (Qwen3's qk_norm; Examples/simple_vllm.ipynb, GroupedQueryAttention.forward): the plain bias-free packed GEMM keeps
-    the RAW qkv rows, vy_qknorm_rope_fwd writes the normalised, rotated q and k beside them, and attention reads v in
-    place as a strided view of those rows.  The backward is PreNormAttentionFn's with one launch added: vy_qknorm_bwd
-    turns the dq | dk columns of the packed gradient into the gradient of the raw projection, in place, before the dgrad
-    and the weight gradient of the packed projection read it.  Inputs after `k_scale` are the projection weights in
-    _params() order."""
+    (Qwen3's qk_norm; Examples/simple_vllm.ipynb, GroupedQueryAttention.forward).  The backward is PreNormAttentionFn's
+    with one launch added, vy_qknorm_bwd.  Inputs after `k_scale` are the projection weights in _params() order."""
 
     @staticmethod
     def forward(ctx, x, mod, attention_mask, freqs, ln_w, eps, wo, q_scale, k_scale, qk_eps, *params):
         _require_bf16(x)
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
-        dt, dev = x.dtype, x.device
-        if attention_mask is not None and not isinstance(attention_mask, AttnMask):
-            raise VyomHipError("training needs a mask descriptor (AttnMask): dense additive masks have no "
-                               "backward kernel")
-        cos, sin, pos0 = resolve_freqs(freqs, dev)
-        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-        qkv = ops.linear(n, mod._packed_shadow(dt)[0])       # (B, L, W): W is a multiple of 8, so the rows are dense
-        q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
-        k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
-        ops.qknorm_rope(qkv, h, hk, dh, _shadow(q_scale, torch.float32), _shadow(k_scale, torch.float32), qk_eps, cos, sin,
-                        pos0, q, k)
-        v = _heads(qkv[:, :, (h + hk) * dh:(h + 2 * hk) * dh], hk, dh)
-        lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
-        causal, kp, sp = False, None, 0
-        if attention_mask is not None:
-            causal, kp, sp = attention_mask.causal, attention_mask.keypad, attention_mask.start_pos
-            if kp is not None:
-                kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
-        o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
-        y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+        qk = (q_scale, k_scale, qk_eps)
+        y, (n, q, k, _, qkv, o, lse), am = prenorm_attention_forward(x, mod, attention_mask, freqs, ln_w, eps, wo, qk=qk)
         ctx.save_for_backward(x, n, qkv, q, k, o, lse)
-        ctx.meta = (mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, q_scale, k_scale, qk_eps, params)
+        ctx.meta = (mod, am, ln_w, eps, wo, qk, params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, n, qkv, q, k, o, lse = ctx.saved_tensors
-        mod, causal, kp, sp, cos, sin, pos0, ln_w, eps, wo, q_scale, k_scale, qk_eps, params = ctx.meta
-        B, L, _ = x.shape
-        h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
-        dt = x.dtype
-        dy = dy.contiguous()
-        do = ops.linear_dgrad(dy, _wt(wo, dt))
-        dwo, _ = _wgrad(dy, o, wo, None)
-        W = (h + 2 * hk) * dh
-        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
-        dq = _heads(packed[:, :, : h * dh], h, dh)
-        dk = _heads(packed[:, :, h * dh:(h + hk) * dh], hk, dh)
-        dv = _heads(packed[:, :, (h + hk) * dh:], hk, dh)
-        v = _heads(qkv[:, :, (h + hk) * dh:W], hk, dh)
-        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
-                          cos=cos, sin=sin, rope_pos0=pos0)
-        dqs, dks = _qk_scale_bwd(packed, qkv, h, hk, dh, q_scale, k_scale, qk_eps)
-        w, b = mod._packed()
-        dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt))
-        grads = _packed_wgrad(mod, packed, n, w, b, params)
-        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        mod, am, ln_w, eps, wo, qk, params = ctx.meta
+        dx, dlnw, dwo, dqs, dks, grads = prenorm_attention_backward(dy, x, n, o, lse, am, mod, ln_w, eps, wo, params,
+                                                                    q=q, k=k, qkv=qkv, qk=qk)
         return (dx, None, None, None, dlnw, None, dwo, dqs, dks, None, *grads)
 
 
@@ -1063,19 +1087,44 @@ def _gate_up_wgrad(dgu, n, wg, wu):
     return outs[0], outs[1]
 
 
+def prenorm_gated_mlp_forward(x, mlp, ln_w, eps, act, wd, delta=None):
+    """y = x + (act(n Wg^T) * n Wu^T) Wd^T with n = RMSNorm(x): the MLP half of a pre-norm block (the reference's
+    DecoderLayer, models/custom_transformer.py:76-89, 285-288) -> (y, n, gate_up).  delta: see autograd.gated_mlp."""
+    n = ops.rmsnorm(x, _shadow(ln_w, x.dtype), eps, 0.0)
+    y, gu = gated_mlp(n, mlp, act, _shadow(wd, x.dtype), residual=x, delta=delta)
+    return y, n, gu
+
+
+def prenorm_gated_mlp_backward(dy, x, n, gu, mlp, ln_w, eps, act, wg, wu, wd, adapters=None):
+    """Backward of prenorm_gated_mlp_forward -> (dx, dln_w, dwg, dwu, dwd).  The gated product is recomputed from gate_up
+    (one streaming pass) for whoever reads it: the down projection's weight gradient or its adapter's.  adapters: as in
+    prenorm_attention_backward, groups "gate_up" and "down"."""
+    dt = x.dtype
+    dy = dy.contiguous()
+    da = ops.linear_dgrad(dy, _wt(wd, dt))
+    dwg = dwu = dwd = None
+    if adapters is None:
+        dwd, _ = _wgrad(dy, ops.gated_act(gu, act), wd, None)
+    elif "down" in adapters:
+        adapters["down"](dy, ops.gated_act(gu, act), da)
+    dgu = ops.gated_act_bwd(da, gu, act)
+    dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt))
+    if adapters is None:
+        dwg, dwu = _gate_up_wgrad(dgu, n, wg, wu)
+    elif "gate_up" in adapters:
+        adapters["gate_up"](dgu, n, dn)
+    dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+    return dx, dlnw, dwg, dwu, dwd
+
+
 class PreNormGatedMlpFn(torch.autograd.Function):
-    """y = x + (act(n Wg^T) * n Wu^T) Wd^T with n = RMSNorm(x): the MLP half of the reference's DecoderLayer
-    (models/custom_transformer.py:76-89, 285-288).  One packed [gate; up] GEMM; gate_up and n are saved, the gated
-    product is recomputed in the backward (one streaming pass) instead of being kept."""
+    """prenorm_gated_mlp_forward / _backward over the three base weights: one packed [gate; up] GEMM; gate_up and n are
+    saved, the gated product is not."""
 
     @staticmethod
     def forward(ctx, x, mlp, ln_w, eps, act, wg, wu, wd):
         _require_bf16(x)
-        dt = x.dtype
-        n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-        gu = ops.linear(n, mlp._packed_gate_up(dt))
-        a = ops.gated_act(gu, act)
-        y = ops.linear(a, _shadow(wd, dt), None, residual=x)
+        y, n, gu = prenorm_gated_mlp_forward(x, mlp, ln_w, eps, act, wd)
         ctx.save_for_backward(x, n, gu)
         ctx.meta = (mlp, ln_w, eps, act, wg, wu, wd)
         return y
@@ -1083,15 +1132,7 @@ class PreNormGatedMlpFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, n, gu = ctx.saved_tensors
-        mlp, ln_w, eps, act, wg, wu, wd = ctx.meta
-        dt = x.dtype
-        dy = dy.contiguous()
-        da = ops.linear_dgrad(dy, _wt(wd, dt))
-        dwd, _ = _wgrad(dy, ops.gated_act(gu, act), wd, None)
-        dgu = ops.gated_act_bwd(da, gu, act)
-        dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt))
-        dwg, dwu = _gate_up_wgrad(dgu, n, wg, wu)
-        dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        dx, dlnw, dwg, dwu, dwd = prenorm_gated_mlp_backward(dy, x, n, gu, *ctx.meta)
         return dx, None, dlnw, None, None, dwg, dwu, dwd
 
 

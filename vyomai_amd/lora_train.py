@@ -1,6 +1,7 @@
 """LoRA fine-tuning inside the fused pre-norm blocks of ModelForCausalLM: the forward of a DecoderLayer whose
 projections are wrapped in adapters.LoraLinear, and the LoRA counterparts of autograd_train.PreNormAttentionFn /
-PreNormGatedMlpFn, which they mirror launch for launch except that
+PreNormGatedMlpFn.  Both run the bodies those functions run (autograd_train.prenorm_attention_forward / _backward,
+prenorm_gated_mlp_forward / _backward) and give them the two hooks defined here, so that
 
   * the adapter's delta lands behind each of the four GEMMs (vy_lora_shrink / vy_lora_expand over an identity tile
     table, one slot, the serving store's operand layout: a trained adapter is served with the arithmetic it was
@@ -21,10 +22,9 @@ import torch
 from . import ops
 from ._lib import VyomHipError
 from .adapters import _CAUSAL_LM, GROUPS, LoraLinear
-from .autograd_train import (WEIGHT_EPOCH, _direct, _notify, _require_bf16, _rms_bwd, _wt, _wt_gate_up, _wt_packed)
+from .autograd_train import (WEIGHT_EPOCH, _direct, _notify, _require_bf16, prenorm_attention_backward,
+                             prenorm_attention_forward, prenorm_gated_mlp_backward, prenorm_gated_mlp_forward)
 from .layers.attention import _shadow
-from .layers.mask import AttnMask
-from .layers.positional_embeddings import resolve_freqs
 
 NO_CACHE = ("a model whose projections carry LoRA adapters (LoraLinear) cannot run {what}: that path would skip the "
             "adapter's term.  Either fold the adapters into the weights with vyomai_amd.merge_lora(model), or serve the "
@@ -167,65 +167,36 @@ def lora_linear_forward(mod: LoraLinear, x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-# ------------------------------------------------------------------------------------------
-# forward of the two blocks (shared by the autograd functions and the no-grad path)
-# ------------------------------------------------------------------------------------------
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    return t.view(-1, t.shape[-1])
 
 
-def _attention_block(x, a, mask, freqs, ln_w, eps, wo, G):
-    """y = x + (attn(rope(RMSNorm(x) Wqkv^T + b + delta_qkv)) Wo^T + delta_o) -> (y, what the backward keeps)."""
-    B, L, d = x.shape
-    h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
-    dt, dev = x.dtype, x.device
-    if mask is not None and not isinstance(mask, AttnMask):
-        raise VyomHipError("the LoRA path needs a mask descriptor (AttnMask): pass the 2-D padding mask")
-    cos, sin, pos0 = resolve_freqs(freqs, dev)
-    n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-    n2 = n.view(B * L, d)
-    sw, sb = a._packed_shadow(dt)
-    W = (h + 2 * hk) * dh
-    qkv = torch.empty((B * L, W), dtype=dt, device=dev)
-    ops.linear(n2, sw, sb, out=qkv)
-    u_qkv = _delta(G["qkv"], qkv, n2)
-    p3 = qkv.view(B, L, W)
-    q = p3[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
-    k = p3[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
-    v = p3[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
-    ops.rope_(q, cos, sin, pos0)
-    ops.rope_(k, cos, sin, pos0)
-    lse = torch.empty((B, h, L), dtype=torch.float32, device=dev)
-    causal, kp, sp = False, None, 0
-    if mask is not None:
-        causal, kp, sp = mask.causal, mask.keypad, mask.start_pos
-        if kp is not None:
-            kp = kp[:, :L].contiguous() if kp.shape[1] != L else kp
-    o = ops.attention(q, k, v, causal=causal, start_pos=sp, keypad=kp, lse=lse)
-    y = torch.empty_like(x)
-    ops.linear(o, _shadow(wo, dt), None, residual=x, out=y)
-    u_o = _delta(G["o"], y.view(B * L, d), o.view(B * L, h * dh))
-    return y, (n, qkv, o, lse, u_qkv, u_o), (causal, kp, sp, cos, sin, pos0)
+def _deltas(G, us: dict):
+    """The forward hook of the shared block bodies, f(group, y, x) behind each of the four GEMMs (the serving hook's
+    signature, adapters.layer_delta): adds the group's delta to y in place and leaves its u in us[group]."""
+    def f(g, y, x):
+        us[g] = _delta(G[g], _rows(y), _rows(x))
+    return f
 
 
-def _mlp_block(x, mlp, ln_w, eps, G):
-    """y = x + (gated_act(RMSNorm(x) Wgu^T + delta_gu) Wd^T + delta_down) -> (y, what the backward keeps)."""
-    dt = x.dtype
-    d = x.shape[-1]
-    n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-    n2 = n.view(-1, d)
-    wgu = mlp._packed_gate_up(dt)
-    gu = torch.empty((n2.shape[0], wgu.shape[0]), dtype=dt, device=x.device)
-    ops.linear(n2, wgu, None, out=gu)
-    u_gu = _delta(G["gate_up"], gu, n2)
-    act = ops.gated_act(gu, mlp.act)
-    y = torch.empty_like(x)
-    ops.linear(act, _shadow(mlp.down_proj.weight, dt), None, residual=x.view(-1, d), out=y.view(-1, d))
-    u_down = _delta(G["down"], y.view(-1, d), act)
-    return y, (n, gu, u_gu, u_down)
+def _adapter_backwards(G, us: dict, grads: dict):
+    """The backward hooks of the shared block bodies: group -> f(dy, x, dx), for the groups that carry adapters."""
+    def hook(g):
+        return lambda dy, x, dx: _adapter_backward(G[g], _rows(dy), _rows(x), us[g], None if dx is None else _rows(dx),
+                                                   grads)
+    return {g: hook(g) for g in G if G[g] is not None}
 
 
-# ------------------------------------------------------------------------------------------
-# backward pieces
-# ------------------------------------------------------------------------------------------
+def _save(ctx, tensors, us: dict) -> None:
+    """save_for_backward: the block's tensors, then the u of every group that has one."""
+    ctx.groups = tuple(g for g, u in us.items() if u is not None)
+    ctx.save_for_backward(*tensors, *(us[g] for g in ctx.groups))
+
+
+def _saved(ctx, n: int):
+    """-> (the block's n tensors, group -> u)."""
+    ts = ctx.saved_tensors
+    return ts[:n], dict(zip(ctx.groups, ts[n:]))
 
 
 def _adapter_backward(G: Optional[GroupOperands], dy2, x2, u, dx2, grads: dict) -> None:
@@ -273,50 +244,22 @@ class LoraPreNormAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, layer, mask, freqs, G, ln_w, *lora_params):
         _require_bf16(x)
-        a, ln = layer.self_attn, layer.input_layernorm
-        y, saved, meta = _attention_block(x, a, mask, freqs, ln_w, ln.variance_epsilon, a.o_proj.weight, G)
-        ctx.save_for_backward(x, *[t for t in saved if t is not None])
-        ctx.has = tuple(t is not None for t in saved)
-        ctx.meta = (layer, G, meta, ln_w, lora_params)
+        a, us = layer.self_attn, {}
+        y, (n, _, _, _, qkv, o, lse), am = prenorm_attention_forward(
+            x, a, mask, freqs, ln_w, layer.input_layernorm.variance_epsilon, a.o_proj.weight, delta=_deltas(G, us))
+        _save(ctx, (x, n, qkv, o, lse), us)
+        ctx.meta = (layer, G, am, ln_w, lora_params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, *rest = ctx.saved_tensors
-        it = iter(rest)
-        n, qkv, o, lse, u_qkv, u_o = (next(it) if h_ else None for h_ in ctx.has)
-        layer, G, (causal, kp, sp, cos, sin, pos0), ln_w, lora_params = ctx.meta
-        a, eps = layer.self_attn, layer.input_layernorm.variance_epsilon
-        B, L, d = x.shape
-        h, hk, dh = a.num_attention_heads, a.num_key_value_heads, a.head_dim
-        dt = x.dtype
-        dy = dy.contiguous()
-        grads: dict = {}
-        dy2 = dy.view(B * L, d)
-        do = ops.linear_dgrad(dy, _wt(a.o_proj.weight, dt))
-        _adapter_backward(G["o"], dy2, o.view(B * L, h * dh), u_o, do.view(B * L, h * dh), grads)
-        W = (h + 2 * hk) * dh
-        packed = torch.empty((B, L, W), dtype=dt, device=x.device)  # [dq | dk | dv], 'b l (h d)'
-        dq = packed[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
-        dk = packed[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        dv = packed[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        p3 = qkv.view(B, L, W)
-        q = p3[:, :, : h * dh].view(B, L, h, dh).permute(0, 2, 1, 3)
-        k = p3[:, :, h * dh:(h + hk) * dh].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        v = p3[:, :, (h + hk) * dh:].view(B, L, hk, dh).permute(0, 2, 1, 3)
-        # RoPE is orthogonal: its backward (the inverse rotation of dq, dk) runs in the epilogues
-        ops.attention_bwd(q, k, v, o, do, lse, dq, dk, dv, causal=causal, start_pos=sp, keypad=kp,
-                          cos=cos, sin=sin, rope_pos0=pos0)
-        p2, n2 = packed.view(B * L, W), n.view(B * L, d)
-        need_dx = ctx.needs_input_grad[0] or ln_w.requires_grad
-        dn = None
-        if need_dx:      # (layer 0 over a frozen embedding: nobody reads this dgrad)
-            w, _ = a._packed()
-            dn = ops.linear_dgrad(packed, _wt_packed(a, w, dt))
-        _adapter_backward(G["qkv"], p2, n2, u_qkv, None if dn is None else dn.view(B * L, d), grads)
-        dx = dlnw = None
-        if need_dx:
-            dx, dlnw = _rms_bwd(dn, x, ln_w, eps, add_to=dy)
+        (x, n, qkv, o, lse), us = _saved(ctx, 5)
+        layer, G, am, ln_w, lora_params = ctx.meta
+        a, grads = layer.self_attn, {}
+        # (layer 0 over a frozen embedding and a frozen norm: nobody reads dx)
+        dx, dlnw, *_ = prenorm_attention_backward(
+            dy, x, n, o, lse, am, a, ln_w, layer.input_layernorm.variance_epsilon, a.o_proj.weight, qkv=qkv,
+            adapters=_adapter_backwards(G, us, grads), need_dx=ctx.needs_input_grad[0] or ln_w.requires_grad)
         return (dx, None, None, None, None, dlnw, *_param_grads(lora_params, grads))
 
 
@@ -326,31 +269,21 @@ class LoraPreNormGatedMlpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, layer, G, ln_w, *lora_params):
         _require_bf16(x)
-        y, saved = _mlp_block(x, layer.mlp, ln_w, layer.post_attention_layernorm.variance_epsilon, G)
-        ctx.save_for_backward(x, *[t for t in saved if t is not None])
-        ctx.has = tuple(t is not None for t in saved)
+        mlp, us = layer.mlp, {}
+        y, n, gu = prenorm_gated_mlp_forward(x, mlp, ln_w, layer.post_attention_layernorm.variance_epsilon, mlp.act,
+                                             mlp.down_proj.weight, delta=_deltas(G, us))
+        _save(ctx, (x, n, gu), us)
         ctx.meta = (layer, G, ln_w, lora_params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, *rest = ctx.saved_tensors
-        it = iter(rest)
-        n, gu, u_gu, u_down = (next(it) if h_ else None for h_ in ctx.has)
+        (x, n, gu), us = _saved(ctx, 3)
         layer, G, ln_w, lora_params = ctx.meta
-        mlp, eps = layer.mlp, layer.post_attention_layernorm.variance_epsilon
-        dt = x.dtype
-        d = x.shape[-1]
-        dy = dy.contiguous()
-        grads: dict = {}
-        dy2 = dy.view(-1, d)
-        da = ops.linear_dgrad(dy2, _wt(mlp.down_proj.weight, dt))
-        if G["down"] is not None:
-            _adapter_backward(G["down"], dy2, ops.gated_act(gu, mlp.act), u_down, da, grads)
-        dgu = ops.gated_act_bwd(da, gu, mlp.act)
-        dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt))
-        _adapter_backward(G["gate_up"], dgu, n.view(-1, d), u_gu, dn, grads)
-        dx, dlnw = _rms_bwd(dn.view(x.shape), x, ln_w, eps, add_to=dy)
+        mlp, grads = layer.mlp, {}
+        dx, dlnw, *_ = prenorm_gated_mlp_backward(
+            dy, x, n, gu, mlp, ln_w, layer.post_attention_layernorm.variance_epsilon, mlp.act, mlp.gate_proj.weight,
+            mlp.up_proj.weight, mlp.down_proj.weight, adapters=_adapter_backwards(G, us, grads))
         return (dx, None, None, dlnw, *_param_grads(lora_params, grads))
 
 
@@ -371,5 +304,6 @@ def decoder_layer_forward(layer, x, mask, freqs, past_key_value):
         x = LoraPreNormAttentionFn.apply(x, layer, mask, freqs, G, ln1.weight, *attn_p)
         return LoraPreNormGatedMlpFn.apply(x, layer, G, ln2.weight, *mlp_p)
     _require_bf16(x)
-    x, _, _ = _attention_block(x, a, mask, freqs, ln1.weight, ln1.variance_epsilon, a.o_proj.weight, G)
-    return _mlp_block(x, m, ln2.weight, ln2.variance_epsilon, G)[0]
+    delta = _deltas(G, {})
+    x = prenorm_attention_forward(x, a, mask, freqs, ln1.weight, ln1.variance_epsilon, a.o_proj.weight, delta=delta)[0]
+    return prenorm_gated_mlp_forward(x, m, ln2.weight, ln2.variance_epsilon, m.act, m.down_proj.weight, delta=delta)[0]

@@ -18,7 +18,7 @@ import torch.nn as nn
 from .. import ops
 from .._lib import VyomHipError
 from ..adapters import LoraLinear, layer_delta
-from ..autograd import _mask_args, _wants_grad
+from ..autograd import _mask_args, _wants_grad, gated_mlp
 from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
 from ..layers.kv_cache import DynamicCacheOne, StaticCacheOne
@@ -120,15 +120,7 @@ class MLP(nn.Module):
         if _wants_grad(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight):
             raise VyomHipError("the gated MLP trains inside its pre-norm block (DecoderLayer: RMSNorm, MLP and the "
                                "residual add are one autograd function); call it under torch.no_grad() on its own")
-        dt = x.dtype
-        gu = ops.linear(x, self._packed_gate_up(dt))
-        if delta is not None:
-            delta("gate_up", gu, x)
-        h = ops.gated_act(gu, self.act)
-        y = ops.linear(h, _shadow(self.down_proj.weight, dt), None, residual=residual)
-        if delta is not None:
-            delta("down", y, h)
-        return y
+        return gated_mlp(x, self, self.act, _shadow(self.down_proj.weight, x.dtype), residual, delta)[0]
 
 
 class Attention(_SelfAttentionBase):

@@ -36,6 +36,7 @@ import torch.nn as nn
 from .. import ops
 from .._lib import ACT_SILU, VyomHipError
 from ..adapters import layer_delta
+from ..autograd import gated_mlp
 from ..layers.attention import _shadow
 from ..layers.mask import AttnMask
 from ..layers.paged import page_scales, paged_step_attention, paged_step_logits
@@ -113,14 +114,7 @@ class FeedForward(nn.Module):
     def forward(self, x, residual: Optional[torch.Tensor] = None, delta=None):
         """delta (serving with adapters, adapters.layer_delta): f(group, y, x), called behind each of the two GEMMs."""
         _need_gpu(x, "FeedForward")
-        gu = ops.linear(x, self._packed_gate_up(x.dtype))
-        if delta is not None:
-            delta("gate_up", gu, x)
-        h = ops.gated_act(gu, ACT_SILU)
-        y = ops.linear(h, _shadow(self.fc3.weight, x.dtype), None, residual=residual)
-        if delta is not None:
-            delta("down", y, h)
-        return y
+        return gated_mlp(x, self, ACT_SILU, _shadow(self.fc3.weight, x.dtype), residual, delta)[0]
 
 
 class GroupedQueryAttention(nn.Module):
