@@ -393,6 +393,33 @@ typedef struct vy_colsum_desc {
 int vy_linear_wgrad_grouped_cs(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs, int dtype,
                                void* stream);
 
+/* The same launch with AdamW riding in it: up to 8 ranges of a flat arena are stepped -- the update of vy_adamw_step
+ * (below), bit for bit, without its device scale and gate -- by workgroups dispatched behind the weight-gradient and
+ * column-sum ones, on the CUs the tiles leave idle.  The optimizer is an HBM stream and the tiles are not HBM-bound.
+ * The ranges must have no data dependence on the launch: a range's g, p and p_bf16 may not intersect any dw, db,
+ * out0 / out1 or slab of it (VY_ERR_ARG), and the caller orders the launch behind the kernels that wrote g.
+ * How much rides is the launcher's decision: (256 - weight-gradient workgroups) idle CUs x a measured per-CU streaming
+ * rate x the estimated duration of the longest weight-gradient workgroup, none when fewer than 8 CUs are idle; the
+ * ranges are taken in order and `taken` (out) says how many leading elements of each were stepped -- n, 0, or a whole
+ * number of chunks of the last range that fit.  The caller keeps the rest for a later launch or vy_adamw_step.  A launch
+ * without weight gradients (n = 0; ncs may be 0 too) takes every range whole.  Range starts: 16-byte aligned in the
+ * four fp32 arrays, 8-byte in p_bf16 (nullable).  fp32: the riders run as plain vy_adamw_step launches, all taken.
+ * vy_linear_wgrad_grouped and _cs are this entry point with nopt = 0. */
+typedef struct vy_adamw_ride_desc {
+  float* p; const float* g; float* m; float* v;
+  void* p_bf16;
+  int64_t n;
+  int64_t taken;
+} vy_adamw_ride_desc;
+typedef struct vy_adamw_hyper {
+  float lr, beta1, beta2, eps, weight_decay;
+  float grad_scale;
+  int64_t step;
+} vy_adamw_hyper;
+int vy_linear_wgrad_grouped_opt(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
+                                vy_adamw_ride_desc* opt, int32_t nopt, const vy_adamw_hyper* hyper, int dtype,
+                                void* stream);
+
 /* LayerNorm backward: dx = rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma;
  * dgamma/dbeta fp32 [N] accumulated (beta) from per-block partials in `ws`
  * (ws: fp32, at least 2 * ws_rows * N elements; ws_rows = vy_layernorm_bwd_ws_rows(M)). */

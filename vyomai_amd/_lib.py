@@ -60,6 +60,7 @@ PROTOTYPES = {
     "vy_linear_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _i64, _i, _p],
     "vy_linear_wgrad_grouped": [_p, _i, _i, _p],
     "vy_linear_wgrad_grouped_cs": [_p, _i, _p, _i, _i, _p],
+    "vy_linear_wgrad_grouped_opt": [_p, _i, _p, _i, _p, _i, _p, _i, _p],
     "vy_layernorm_bwd_partial": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i, _p],
     "vy_layernorm_bwd": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _f, _p, _i64, _i64, _i, _p],
     "vy_attn_bwd": [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64,
@@ -121,6 +122,17 @@ class VyWgradDesc(C.Structure):
 class VyColsumDesc(C.Structure):
     """vy_colsum_desc of include/vyom_hip.h."""
     _fields_ = [("ws", _p), ("W", C.c_int32), ("N", C.c_int32), ("out0", _p), ("out1", _p), ("acc", C.c_int32)]
+
+
+class VyAdamwRideDesc(C.Structure):
+    """vy_adamw_ride_desc of include/vyom_hip.h (taken: written by the launcher)."""
+    _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("p_bf16", _p), ("n", _i64), ("taken", _i64)]
+
+
+class VyAdamwHyper(C.Structure):
+    """vy_adamw_hyper of include/vyom_hip.h."""
+    _fields_ = [("lr", _f), ("beta1", _f), ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("grad_scale", _f),
+                ("step", _i64)]
 
 
 class VyomHipError(RuntimeError):

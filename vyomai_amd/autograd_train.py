@@ -144,6 +144,21 @@ class _WgradGroup:
 
     def __init__(self):
         self.items, self.colsums, self.tiles, self.armed = [], [], 0, False
+        # AdamW ranges waiting for a seat in a launch (add_ride): [ops.AdamWRide, owner]
+        self.rides = []
+
+    def add_ride(self, ride, owner) -> None:
+        """ride: an ops.AdamWRide whose gradients are final and were written by launches already enqueued.  It is stepped
+        by spare workgroups of the next grouped launches that hold a weight gradient, as far as the launcher's budget
+        goes -- never by the launch that is being flushed when it is queued: a rider's only ordering against the kernels
+        that write its gradients is the stream's kernel boundary.  owner.rode(ranges, bytes) hears what went; whatever is
+        still here when backward returns is the owner's to step (take_rides)."""
+        self.rides.append([ride, owner])
+
+    def take_rides(self, owner) -> list:
+        mine = [r for r, o in self.rides if o is owner]
+        self.rides = [e for e in self.rides if e[1] is not owner]
+        return mine
 
     def wants(self, dy, w, alpha) -> bool:
         if alpha is not None or not _GROUP_WGRADS:
@@ -185,8 +200,23 @@ class _WgradGroup:
         items, colsums, self.items, self.colsums, self.tiles = self.items, self.colsums, [], [], 0
         if not items and not colsums:
             return
-        ops.linear_wgrad_grouped([(dy, x, dw, db) for dy, x, dw, db, _ in items] +
-                                 [ops.ColSum(ws, dg, db, True, torch.bfloat16) for ws, dg, db, _ in colsums])
+        # the AdamW ranges queued before this flush ride along (what the notifications below queue waits for the next one)
+        k = 0   # (the leading ones that share their hyper-parameters: one launch carries one set)
+        while items and k < min(8, len(self.rides)) and self.rides[k][0][5:] == self.rides[0][0][5:]:
+            k += 1
+        rides, self.rides = self.rides[:k], self.rides[k:]
+        taken = ops.linear_wgrad_grouped([(dy, x, dw, db) for dy, x, dw, db, _ in items] +
+                                         [ops.ColSum(ws, dg, db, True, torch.bfloat16) for ws, dg, db, _ in colsums] +
+                                         [r for r, _ in rides])
+        if rides:
+            left = []
+            for (r, owner), got in zip(rides, taken):
+                if got:
+                    owner.rode(1, got * (30 if r.p_bf16 is not None else 28))
+                if got < r.p.numel():   # over budget: the rest keeps its place in the queue
+                    left.append([r._replace(p=r.p[got:], g=r.g[got:], m=r.m[got:], v=r.v[got:],
+                                            p_bf16=None if r.p_bf16 is None else r.p_bf16[got:]), owner])
+            self.rides = left + self.rides
         for *_, members in items + colsums:
             for p in members:
                 p._vy_deferred = False
@@ -201,6 +231,7 @@ class _WgradGroup:
             for p in members:
                 p._vy_deferred = False
         self.items, self.colsums, self.tiles, self.armed = [], [], 0, False
+        self.rides = []
 
 
 _GROUP_WGRADS = os.environ.get("VY_WGRAD_GROUP", "1") != "0"

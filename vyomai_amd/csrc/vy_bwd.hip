@@ -456,9 +456,70 @@ __device__ __forceinline__ void colsum_slab_block(const ColsumItem& it, int blk)
   }
 }
 
+// AdamW riding in the same launch (vy_linear_wgrad_grouped_opt): the optimizer is the one large HBM-only stream of the
+// training step without a data dependence on this launch, and the weight-gradient tiles are MFMA / LDS-ingest bound.
+// The workgroups behind the column-sum ones each step one chunk of ADAMW_RIDE_CHUNK elements of one range with the
+// body of adamw_kernel (VyAdamw4, vy_common.h).  No device gate, no device scale: those stay on the plain launch.
+struct AdamwRange { float* p; const float* g; float* m; float* v; bf16* pb; int64_t n; int blk0; };   // blk0: first chunk of this range
+struct AdamwGroup { AdamwRange r[8]; VyAdamwScalars s; int n; int blk0; };                            // blk0: first AdamW workgroup of the launch
+
+// A workgroup is alone on its CU (the kernel's registers and LDS allow one), so the loads in flight are what its 8 waves
+// issue before their first use: ADAMW_RIDE_UNROLL independent groups of four 16-byte loads per thread, 128 KiB per CU.
+constexpr int ADAMW_RIDE_UNROLL = 4;
+constexpr int ADAMW_RIDE_PASS = 512 * 4 * ADAMW_RIDE_UNROLL;   // elements the workgroup steps per pass
+constexpr int ADAMW_RIDE_CHUNK = 2 * ADAMW_RIDE_PASS;          // elements per workgroup (16384: 480 KiB of traffic)
+
+__device__ __forceinline__ void adamw_ride_chunk(const AdamwRange& r, const VyAdamwScalars& s, int chunk) {
+  const int64_t c0 = (int64_t)chunk * ADAMW_RIDE_CHUNK;
+  const int64_t c1 = c0 + ADAMW_RIDE_CHUNK < r.n ? c0 + ADAMW_RIDE_CHUNK : r.n;
+  const int tid = threadIdx.x;
+  for (int64_t i0 = c0; i0 < c1; i0 += ADAMW_RIDE_PASS) {
+    if (i0 + ADAMW_RIDE_PASS <= c1) {
+      VyAdamw4 a[ADAMW_RIDE_UNROLL];
+#pragma unroll
+      for (int u = 0; u < ADAMW_RIDE_UNROLL; ++u) {
+        const int64_t i = i0 + (int64_t)(u * 512 + tid) * 4;
+        a[u].load(r.p + i, r.g + i, r.m + i, r.v + i);
+      }
+#pragma unroll
+      for (int u = 0; u < ADAMW_RIDE_UNROLL; ++u) {
+        const int64_t i = i0 + (int64_t)(u * 512 + tid) * 4;
+        a[u].step(s);
+        a[u].store(r.p + i, r.m + i, r.v + i, r.pb ? r.pb + i : nullptr);
+      }
+    } else {   // the last, partial pass of a range: whole groups of four, then adamw_kernel's element-wise tail
+#pragma unroll 1
+      for (int u = 0; u < ADAMW_RIDE_UNROLL; ++u) {
+        const int64_t i = i0 + (int64_t)(u * 512 + tid) * 4;
+        if (i + 3 < c1) {
+          VyAdamw4 a;
+          a.load(r.p + i, r.g + i, r.m + i, r.v + i);
+          a.step(s);
+          a.store(r.p + i, r.m + i, r.v + i, r.pb ? r.pb + i : nullptr);
+        } else if (i < c1) {
+          vy_adamw_tail(r.p + i, r.g + i, r.m + i, r.v + i, r.pb ? r.pb + i : nullptr, (int)(c1 - i), s);
+        }
+      }
+    }
+  }
+}
+
 template <int BN, int BKW, int MS, int NS>
-__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, ColsumGroup cs) {
-  if ((int)blockIdx.x >= cs.items) {   // (workgroup-uniform) the column-sum workgroups: dispatched last, onto the idle CUs
+__global__ __launch_bounds__(BN * 2, 1) void wgrad_tn_bf16_grouped_kernel(WgradGroup grp, ColsumGroup cs, AdamwGroup opt) {
+  if ((int)blockIdx.x >= opt.blk0) {   // (workgroup-uniform) the AdamW workgroups: dispatched last of all
+    const int blk = (int)blockIdx.x - opt.blk0;
+    int d = 0;
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+      if (i < opt.n && blk >= opt.r[i].blk0) d = i;
+    AdamwRange r = opt.r[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+      if (d == i) r = opt.r[i];
+    adamw_ride_chunk(r, opt.s, blk - r.blk0);
+    return;
+  }
+  if ((int)blockIdx.x >= cs.items) {   // (workgroup-uniform) the column-sum workgroups: dispatched behind the tiles, onto the idle CUs
     const int blk = (int)blockIdx.x - cs.items;
     int d = 0;
 #pragma unroll
@@ -965,15 +1026,79 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
   return VY_OK;
 }
 
+// ---- how much AdamW rides in a grouped launch (the one statement of the rule) --------------------------------
+// budget = idle CUs x what one CU streams x how long the longest weight-gradient workgroup runs.
+// ADAMW_RIDE_CU_BYTES_PER_US: one rider workgroup per CU, 40 workgroups on an otherwise idle chip stream 18.6 GB/s each
+// (tools/bench_adamw_ride.py, DESIGN section 3 "AdamW in the grouped launch"); beside the tiles they share L2 and HBM with
+// the tiles' loads, and the grouped kernel already grows at 16, so 16 it is.  ADAMW_RIDE_ITEM_US: wgrad_tn_bf16_grouped_kernel<256,256,32,4> at the
+// benchmark layer (108 tiles x 2 M-splits, 8192 rows per workgroup) takes 276 us (profiles/r04_train_step_kernel_stats.csv);
+// every workgroup is a 256 x 256 tile, so its time scales with its rows.
+constexpr double ADAMW_RIDE_CU_BYTES_PER_US = 16000.0;
+constexpr double ADAMW_RIDE_ITEM_US = 276.0;
+constexpr int64_t ADAMW_RIDE_ITEM_ROWS = 8192;
+constexpr int ADAMW_RIDE_MIN_IDLE_CUS = 8;
+constexpr int VY_CUS = 256;
+
+// bytes a launch of `items` weight-gradient workgroups of at most `rows` rows may carry (items = 0: no limit, nothing to slow down)
+static int64_t adamw_ride_budget(int64_t items, int64_t rows) {
+  if (items == 0) return INT64_MAX;
+  const int64_t idle = VY_CUS - items;
+  if (idle < ADAMW_RIDE_MIN_IDLE_CUS) return 0;
+  return (int64_t)((double)idle * ADAMW_RIDE_CU_BYTES_PER_US * ADAMW_RIDE_ITEM_US * (double)rows / (double)ADAMW_RIDE_ITEM_ROWS);
+}
+
+static bool ranges_meet(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+  if (!a || !b || abytes <= 0 || bbytes <= 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
 static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
-                        int dtype, void* stream) {
+                        vy_adamw_ride_desc* opt, int32_t nopt, const vy_adamw_hyper* hy, int dtype, void* stream) {
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "%s: bad dtype %d", who, dtype);
-  if (n < 0 || n > 8 || (n > 0 && !descs) || ncs < 0 || ncs > 8 || (ncs > 0 && !cs) || n + ncs == 0)
+  if (nopt < 0 || nopt > 8 || (nopt > 0 && (!opt || !hy))) VY_FAIL(VY_ERR_ARG, "%s: 0..8 AdamW ranges (with their hyper-parameters)", who);
+  if (n < 0 || n > 8 || (n > 0 && !descs) || ncs < 0 || ncs > 8 || (ncs > 0 && !cs) || n + ncs + nopt == 0)
     VY_FAIL(VY_ERR_ARG, "%s: 1..8 descriptors", who);
   for (int i = 0; i < ncs; ++i)
     if (!cs[i].ws || cs[i].W <= 0 || cs[i].N <= 0 || (cs[i].acc != 0 && cs[i].acc != 1))
       VY_FAIL(VY_ERR_ARG, "%s: column-sum descriptor %d: bad arguments", who, i);
+  for (int i = 0; i < n; ++i) {
+    const vy_wgrad_desc& d = descs[i];
+    if (!d.dy || !d.x || !d.dw || d.M <= 0 || d.N <= 0 || d.K <= 0) VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: bad arguments", who, i);
+  }
+  if (nopt > 0 && hy->step <= 0) VY_FAIL(VY_ERR_ARG, "%s: AdamW step must be >= 1", who);
+  for (int i = 0; i < nopt; ++i) {
+    const vy_adamw_ride_desc& o = opt[i];
+    if (!o.p || !o.g || !o.m || !o.v || o.n <= 0) VY_FAIL(VY_ERR_ARG, "%s: AdamW range %d: bad arguments", who, i);
+    if ((uintptr_t)o.p % 16 || (uintptr_t)o.g % 16 || (uintptr_t)o.m % 16 || (uintptr_t)o.v % 16 || (uintptr_t)o.p_bf16 % 8)
+      VY_FAIL(VY_ERR_ARG, "%s: AdamW range %d: p, g, m, v must be 16-byte aligned (p_bf16: 8-byte)", who, i);
+    // no data dependence on this launch: what a rider reads or the next forward reads from it is not written here
+    const void* mine[3] = {o.g, o.p, o.p_bf16};
+    const int64_t mine_bytes[3] = {o.n * 4, o.n * 4, o.n * 2};
+    for (int k = 0; k < 3; ++k) {
+      bool hit = false;
+      for (int j = 0; j < n; ++j) {
+        const vy_wgrad_desc& d = descs[j];
+        hit = hit || ranges_meet(mine[k], mine_bytes[k], d.dw, ((d.N - 1) * d.lddw + d.K) * 4) ||
+              ranges_meet(mine[k], mine_bytes[k], d.db, d.N * 4);
+      }
+      for (int j = 0; j < ncs; ++j) {
+        const vy_colsum_desc& c = cs[j];
+        hit = hit || ranges_meet(mine[k], mine_bytes[k], c.out0, (int64_t)c.N * 4) ||
+              ranges_meet(mine[k], mine_bytes[k], c.out1, (int64_t)c.N * 4) ||
+              ranges_meet(mine[k], mine_bytes[k], c.ws, 2 * (int64_t)c.W * c.N * 4);
+      }
+      if (hit) VY_FAIL(VY_ERR_ARG, "%s: AdamW range %d intersects a gradient or slab of the same launch", who, i);
+    }
+  }
+  for (int i = 0; i < nopt; ++i) opt[i].taken = 0;
   if (dtype == VY_F32) {   // the parity path: one plain launch per descriptor
+    for (int i = 0; i < nopt; ++i) {
+      vy_adamw_ride_desc& o = opt[i];
+      if (int rc = vy_adamw_step(o.p, o.g, o.m, o.v, o.p_bf16, o.n, hy->lr, hy->beta1, hy->beta2, hy->eps, hy->weight_decay,
+                                 hy->step, hy->grad_scale, nullptr, stream)) return rc;
+      o.taken = o.n;
+    }
     for (int i = 0; i < ncs; ++i)
       if (int rc = vy_ln_colsum(cs[i].ws, cs[i].W, cs[i].N, cs[i].out0, cs[i].out1, cs[i].acc, (hipStream_t)stream)) return rc;
     for (int i = 0; i < n; ++i) {
@@ -994,11 +1119,12 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
   WgradGroup grp;
   memset(&grp, 0, sizeof(grp));   // (n == 0: column sums only)
   grp.n = n;
-  int64_t items = 0;
+  int64_t items = 0, rows_max = 0;
   for (int i = 0; i < n; ++i) {
     const vy_wgrad_desc& d = descs[i];
     const int64_t tiles_k = vy_cdiv(d.K, 256), tiles = vy_cdiv(d.N, 256) * tiles_k;
     const WgradSplit sp = wgrad_split(d.M, 256 / tiles_total);   // at most one round of workgroups (the column sums do not count: they are short)
+    rows_max = sp.m_chunk > rows_max ? sp.m_chunk : rows_max;
     WgradItem& it = grp.g[i];
     it.dY = (const bf16*)d.dy; it.X = (const bf16*)d.x; it.dW = d.dw; it.db = d.db;
     it.lddy = d.lddy; it.ldx = d.ldx; it.lddw = d.lddw;
@@ -1019,20 +1145,53 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
     c.blk0 = (int)blocks;
     blocks += vy_cdiv(c.N, 64);
   }
-  hipLaunchKernelGGL((wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4>), dim3((unsigned)(items + blocks)), dim3(512), 0,
-                     (hipStream_t)stream, grp, cg);
+  // the AdamW ranges, in order, as far as the budget goes: a range that does not fit whole gives its leading chunks
+  AdamwGroup og;
+  memset(&og, 0, sizeof(og));
+  int64_t chunks = 0;
+  if (nopt > 0) {
+    const float bc1 = 1.0f - powf(hy->beta1, (float)hy->step);   // (as vy_adamw_step computes them)
+    const float bc2s = sqrtf(1.0f - powf(hy->beta2, (float)hy->step));
+    og.s = {hy->lr, hy->beta1, hy->beta2, hy->eps, hy->weight_decay, bc1, bc2s, hy->grad_scale};
+    int64_t left = adamw_ride_budget(items, rows_max);
+    for (int i = 0; i < nopt && og.n < 8; ++i) {
+      const vy_adamw_ride_desc& o = opt[i];
+      const int64_t per = o.p_bf16 ? 30 : 28;   // bytes of traffic per element
+      int64_t take = o.n;
+      if (left / per < take) take = left / per / ADAMW_RIDE_CHUNK * ADAMW_RIDE_CHUNK;
+      if (take <= 0) break;
+      AdamwRange& r = og.r[og.n++];
+      r.p = o.p; r.g = o.g; r.m = o.m; r.v = o.v; r.pb = (bf16*)o.p_bf16; r.n = take; r.blk0 = (int)chunks;
+      chunks += vy_cdiv(take, ADAMW_RIDE_CHUNK);
+      opt[i].taken = take;
+      left -= take * per;
+      if (take < o.n) break;
+    }
+    for (int i = og.n; i < 8; ++i) og.r[i] = og.r[0];
+  }
+  og.blk0 = (int)(items + blocks);
+  if (items + blocks + chunks > INT32_MAX) VY_FAIL(VY_ERR_ARG, "%s: too many workgroups", who);
+  if (items + blocks + chunks == 0) return VY_OK;   // (riders only and a budget of none cannot happen: n = 0 has no limit)
+  hipLaunchKernelGGL((wgrad_tn_bf16_grouped_kernel<256, 256, 32, 4>), dim3((unsigned)(items + blocks + chunks)), dim3(512), 0,
+                     (hipStream_t)stream, grp, cg, og);
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }
 
 extern "C" int vy_linear_wgrad_grouped(const vy_wgrad_desc* descs, int32_t n, int dtype, void* stream) {
   if (!descs || n <= 0 || n > 8) VY_FAIL(VY_ERR_ARG, "vy_linear_wgrad_grouped: 1..8 descriptors");
-  return wgrad_grouped("vy_linear_wgrad_grouped", descs, n, nullptr, 0, dtype, stream);
+  return wgrad_grouped("vy_linear_wgrad_grouped", descs, n, nullptr, 0, nullptr, 0, nullptr, dtype, stream);
 }
 
 extern "C" int vy_linear_wgrad_grouped_cs(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
                                           int dtype, void* stream) {
-  return wgrad_grouped("vy_linear_wgrad_grouped_cs", descs, n, cs, ncs, dtype, stream);
+  return wgrad_grouped("vy_linear_wgrad_grouped_cs", descs, n, cs, ncs, nullptr, 0, nullptr, dtype, stream);
+}
+
+extern "C" int vy_linear_wgrad_grouped_opt(const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
+                                           vy_adamw_ride_desc* opt, int32_t nopt, const vy_adamw_hyper* hyper, int dtype,
+                                           void* stream) {
+  return wgrad_grouped("vy_linear_wgrad_grouped_opt", descs, n, cs, ncs, opt, nopt, hyper, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------

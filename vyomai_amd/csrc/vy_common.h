@@ -113,6 +113,74 @@ int vy_ln_colsum(float* ws, int WB, int N, float* dgamma, float* dbeta, int acc,
 // the library is built without relocatable device code).
 static __device__ __attribute__((aligned(16))) uint32_t vy_zero16[4] = {0, 0, 0, 0};
 
+// ---- AdamW, one element group ----------------------------------------------------------------
+// The per-element update of vy_adamw_step, shared by adamw_kernel (vy_misc.hip) and the AdamW workgroups that ride in
+// the grouped weight-gradient launch (vy_bwd.hip): one body, so both give the same bits.  The launch-uniform scalars:
+struct VyAdamwScalars { float lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale; };
+
+// One element:  g' = g gscale;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g' g';
+//               p = p (1 - lr wd) - (lr / bc1) (m / (sqrt(v) / bc2_sqrt + eps)).
+// Which products are fused into an fma is spelled out and contraction is off: left to the compiler it depends on the
+// code around the call (the riders' copy differed from adamw_kernel's by an ulp of v).  The spelling is the one the
+// compiler had chosen for adamw_kernel when the update lived there, so its results are what they were -- including
+// that the groups of four and the element-wise tail fuse the second moment differently (VEC).
+template <bool VEC>
+__device__ __forceinline__ void vy_adamw_element(float& p, float g, float& m, float& v, const VyAdamwScalars& s) {
+#pragma clang fp contract(off)
+  const float keep = __builtin_fmaf(-s.lr, s.wd, 1.0f);
+  const float rate = s.lr / s.bc1;
+  const float gg = g * s.gscale;
+  const float t = (1.0f - s.b2) * gg;
+  m = __builtin_fmaf(1.0f - s.b1, gg, s.b1 * m);
+  v = VEC ? __builtin_fmaf(s.b2, v, t * gg) : __builtin_fmaf(t, gg, s.b2 * v);
+  const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;
+  p = __builtin_fmaf(keep, p, -(rate * (m / denom)));
+}
+
+// Four consecutive elements.  The optimizer state is touched once per step: streamed both ways (nt), so that it does
+// not take the Infinity Cache away from the backward kernels' hand-offs.  The bf16 working copy keeps the default
+// policy: the next forward reads it.  load / step / store are separate so that a caller can have several groups'
+// loads in flight before the first use.
+struct VyAdamw4 {
+  f32x4 p, g, m, v;
+  __device__ __forceinline__ void load(const float* pp, const float* gp, const float* mp, const float* vp) {
+    p = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pp));
+    g = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gp));
+    m = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mp));
+    v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vp));
+  }
+  __device__ __forceinline__ void step(const VyAdamwScalars& s) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p[e], me = m[e], ve = v[e];
+      vy_adamw_element<true>(pe, g[e], me, ve, s);
+      p[e] = pe; m[e] = me; v[e] = ve;
+    }
+  }
+  __device__ __forceinline__ void store(float* pp, float* mp, float* vp, bf16* pb) const {
+    __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(pp));
+    __builtin_nontemporal_store(m, reinterpret_cast<f32x4*>(mp));
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(vp));
+    if (pb) {
+      bf16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (bf16)p[e];
+      *reinterpret_cast<bf16x4*>(pb) = o;
+    }
+  }
+};
+
+// the last n < 4 elements of a range, one at a time (pb: nullable)
+__device__ __forceinline__ void vy_adamw_tail(float* p, const float* g, float* m, float* v, bf16* pb, int n,
+                                              const VyAdamwScalars& s) {
+  for (int e = 0; e < 4 && e < n; ++e) {
+    float pv = p[e], mv = m[e], vv = v[e];
+    vy_adamw_element<false>(pv, g[e], mv, vv, s);
+    p[e] = pv; m[e] = mv; v[e] = vv;
+    if (pb) pb[e] = (bf16)pv;
+  }
+}
+
 // device helpers ------------------------------------------------------------------------
 __device__ __forceinline__ float vy_gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

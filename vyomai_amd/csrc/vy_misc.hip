@@ -468,45 +468,17 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                              const float* __restrict__ gscale_dev, const float* __restrict__ gate) {
   if (gate && *gate == 0.0f) return;       // a parameter no rank had a gradient for: left alone (vy_adamw_step_gated)
   if (gscale_dev) gscale *= *gscale_dev;   // e.g. the gradient-clipping coefficient, computed on the device
+  const VyAdamwScalars sc = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale};
   int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
   for (; i < n; i += stride) {
-    if (i + 3 < n) {
-      // the optimizer state is touched once per step (3.7 GB per step for 124 M parameters, under the backward pass on a side
-      // stream): streamed both ways (nt), so that it does not take the Infinity Cache away from the backward kernels'
-      // hand-offs.  The bf16 working copy keeps the default policy: the next forward reads it.
-      f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p + i));
-      const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i));
-      f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m + i));
-      f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v + i));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float gg = gv[e] * gscale;
-        pv[e] *= (1.0f - lr * wd);
-        mv[e] = b1 * mv[e] + (1.0f - b1) * gg;
-        vv[e] = b2 * vv[e] + (1.0f - b2) * gg * gg;
-        const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-        pv[e] -= (lr / bc1) * (mv[e] / denom);
-      }
-      __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p + i));
-      __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m + i));
-      __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + i));
-      if (pb) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bf16)pv[e];
-        *reinterpret_cast<bf16x4*>(pb + i) = o;
-      }
+    if (i + 3 < n) {   // (the update itself: VyAdamw4, vy_common.h -- shared with the grouped weight-gradient launch's riders)
+      VyAdamw4 a;
+      a.load(p + i, g + i, m + i, v + i);
+      a.step(sc);
+      a.store(p + i, m + i, v + i, pb ? pb + i : nullptr);
     } else {
-      for (int e = 0; e < 4 && i + e < n; ++e) {
-        const float gg = g[i + e] * gscale;
-        float pv = p[i + e] * (1.0f - lr * wd);
-        const float mv = b1 * m[i + e] + (1.0f - b1) * gg;
-        const float vv = b2 * v[i + e] + (1.0f - b2) * gg * gg;
-        pv -= (lr / bc1) * (mv / (sqrtf(vv) / bc2_sqrt + eps));
-        p[i + e] = pv; m[i + e] = mv; v[i + e] = vv;
-        if (pb) pb[i + e] = (bf16)pv;
-      }
+      vy_adamw_tail(p + i, g + i, m + i, v + i, pb ? pb + i : nullptr, (int)(n - i), sc);
     }
   }
 }

@@ -378,17 +378,39 @@ class ColSum(NamedTuple):
     dtype: torch.dtype
 
 
-def linear_wgrad_grouped(items) -> None:
+class AdamWRide(NamedTuple):
+    """An entry of linear_wgrad_grouped's list that is an optimizer update: adamw_step(p, g, m, v, p_bf16, ...) over a
+    flat range, done by spare workgroups of the same launch as far as the launcher's budget goes.  The range must not
+    depend on the launch (its gradients were written by earlier launches).  Every AdamWRide of a list carries the same
+    hyper-parameters."""
+    p: Tensor
+    g: Tensor
+    m: Tensor
+    v: Tensor
+    p_bf16: Optional[Tensor]
+    lr: float
+    beta1: float
+    beta2: float
+    eps: float
+    weight_decay: float
+    step: int
+    grad_scale: float = 1.0
+
+
+def linear_wgrad_grouped(items):
     """items: up to 8 tuples (dy, x, dw, db|None): dw += dy^T @ x, db += colsum(dy), ONE launch
     (vy_linear_wgrad_grouped).  The tensors must stay alive until the launch has been enqueued (they do:
     the caller holds them).
     The list may also hold up to 8 ColSum entries, summed in the same launch (vy_linear_wgrad_grouped_cs), and
-    then need not hold a weight gradient at all."""
+    then need not hold a weight gradient at all.
+    It may also hold up to 8 AdamWRide entries (vy_linear_wgrad_grouped_opt); then the return value is the list of how
+    many leading elements of each the launch stepped (the launcher's budget decides), otherwise None."""
     import ctypes as C
+    rides = [it for it in items if isinstance(it, AdamWRide)]
     colsums = [it for it in items if isinstance(it, ColSum)]
-    items = [it for it in items if not isinstance(it, ColSum)]
-    n, ncs = len(items), len(colsums)
-    assert n <= 8 and ncs <= 8 and n + ncs >= 1
+    items = [it for it in items if not isinstance(it, (ColSum, AdamWRide))]
+    n, ncs, nopt = len(items), len(colsums), len(rides)
+    assert n <= 8 and ncs <= 8 and nopt <= 8 and n + ncs + nopt >= 1
     arr = (_lib.VyWgradDesc * max(n, 1))()
     dt = None
     for i, (dy, x, dw, db) in enumerate(items):
@@ -404,10 +426,10 @@ def linear_wgrad_grouped(items) -> None:
         a.dy, a.lddy, a.x, a.ldx = d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0)
         a.dw, a.lddw, a.db = dw.data_ptr(), dw.stride(0), _ptr(db)
         a.M, a.N, a.K = M, N, K
-    if not ncs:
+    if not ncs and not nopt:
         call("vy_linear_wgrad_grouped", C.cast(arr, C.c_void_p), n, dtype_code(dt), _stream())
-        return
-    cs = (_lib.VyColsumDesc * ncs)()
+        return None
+    cs = (_lib.VyColsumDesc * max(ncs, 1))()
     for i, (ws, dgamma, dbeta, accumulate, cdt) in enumerate(colsums):
         _need_gpu(ws, dgamma, dbeta)
         dt = cdt if dt is None else dt
@@ -418,8 +440,26 @@ def linear_wgrad_grouped(items) -> None:
         c = cs[i]
         c.ws, c.W, c.N = ws.data_ptr(), ws.numel() // (2 * N), N
         c.out0, c.out1, c.acc = dgamma.data_ptr(), dbeta.data_ptr(), 1 if accumulate else 0
-    call("vy_linear_wgrad_grouped_cs", C.cast(arr, C.c_void_p) if n else None, n, C.cast(cs, C.c_void_p), ncs,
-         dtype_code(dt), _stream())
+    if not nopt:
+        call("vy_linear_wgrad_grouped_cs", C.cast(arr, C.c_void_p) if n else None, n, C.cast(cs, C.c_void_p), ncs,
+             dtype_code(dt), _stream())
+        return None
+    opt = (_lib.VyAdamwRideDesc * nopt)()
+    hyper = None
+    for i, r in enumerate(rides):
+        _need_gpu(r.p, r.g, r.m, r.v, r.p_bf16)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == r.p.numel() for t in (r.p, r.g, r.m, r.v))
+        assert r.p_bf16 is None or (r.p_bf16.dtype == torch.bfloat16 and r.p_bf16.is_contiguous() and r.p_bf16.numel() == r.p.numel())
+        assert hyper is None or hyper == tuple(r[5:]), "the AdamWRide entries of one launch share their hyper-parameters"
+        hyper = tuple(r[5:])
+        o = opt[i]
+        o.p, o.g, o.m, o.v, o.p_bf16, o.n = r.p.data_ptr(), r.g.data_ptr(), r.m.data_ptr(), r.v.data_ptr(), _ptr(r.p_bf16), r.p.numel()
+    lr, beta1, beta2, eps, weight_decay, step, grad_scale = hyper
+    hy = _lib.VyAdamwHyper(lr, beta1, beta2, eps, weight_decay, grad_scale, step)
+    # (a launch of riders alone runs on the bf16 path: the one with spare workgroups)
+    call("vy_linear_wgrad_grouped_opt", C.cast(arr, C.c_void_p) if n else None, n, C.cast(cs, C.c_void_p) if ncs else None, ncs,
+         C.cast(opt, C.c_void_p), nopt, C.byref(hy), dtype_code(torch.bfloat16 if dt is None else dt), _stream())
+    return [int(o.taken) for o in opt]
 
 
 def layernorm_bwd_partial(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tensor):

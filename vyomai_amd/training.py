@@ -408,7 +408,8 @@ class FlatTrainer:
                  eps: float = 1e-8, weight_decay: float = 0.01, compute_dtype: torch.dtype = torch.bfloat16,
                  process_group=None, bucket_bytes: int = 64 << 20, overlap_optimizer: bool = True,
                  accumulate_steps: int = 1, max_grad_norm: Optional[float] = None,
-                 grad_comm_dtype: Optional[torch.dtype] = None, native_rccl: Optional[bool] = None):
+                 grad_comm_dtype: Optional[torch.dtype] = None, native_rccl: Optional[bool] = None,
+                 adamw_ride: bool = True):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         for m in model.modules():
@@ -445,6 +446,22 @@ class FlatTrainer:
         if self._side is not None:
             self.reducer.on_bucket = self._bucket_final
         self._needs_zero = False   # an optimizer step has consumed the arena: zero_grad() must come next
+        # One rank alone: the side stream hides little -- the backward GEMM and weight-gradient kernels fill their CUs
+        # (one 512-thread workgroup each), so no AdamW wave becomes resident beside them -- but the grouped weight-gradient
+        # launches leave 40 of 256 CUs idle.  A final bucket's ranges wait on autograd_train._wgrad_group instead and are
+        # stepped by spare workgroups of the following grouped launches (ops.AdamWRide); backward() steps the rest when it returns.
+        if os.environ.get("VY_ADAMW_RIDE") == "0":   # A/B knob
+            adamw_ride = False
+        # (gradient accumulation and fp32 compute keep the side stream)
+        self._ride = bool(adamw_ride and self._side is not None and self.reducer.world == 1 and not self.reducer.force
+                          and self.accumulate_steps == 1 and self.arena.shadow is not None)
+        # per step (reset by zero_grad): AdamW ranges / bytes of optimizer traffic that rode in grouped launches, and that
+        # found no seat and were stepped with launches of their own (_drain_rides)
+        self.ride_stats = {"rode_ranges": 0, "rode_bytes": 0, "drained_ranges": 0, "drained_bytes": 0}
+
+    def rode(self, ranges: int, nbytes: int) -> None:
+        self.ride_stats["rode_ranges"] += ranges
+        self.ride_stats["rode_bytes"] += nbytes
 
     # ---- arena ranges that an update may touch ---------------------------------------------------
     def _ranges(self, lo: int, hi: int, touched_only: bool) -> List[Tuple[int, int]]:
@@ -477,6 +494,7 @@ class FlatTrainer:
         self.reducer.reset()
         self._stepped = set()
         self._needs_zero = False
+        self.ride_stats = dict.fromkeys(self.ride_stats, 0)
 
     def backward(self, loss: torch.Tensor) -> None:
         if self._needs_zero:
@@ -502,6 +520,10 @@ class FlatTrainer:
         self._micro += 1
         (loss / k if k > 1 else loss).backward()
         self.reducer.enabled = True
+        # what found no seat in a grouped launch: the last buckets, anything over the launches' budget.  Stepped here and
+        # not in optimizer_step(), so that a backward pass leaves the buckets it has finished stepped whichever way they
+        # went -- as the side stream does (tests/test_training_gpu.py compares grouped and ungrouped runs of exactly that)
+        self._drain_rides()
 
     def _adamw(self, lo: int, hi: int, step: int, scale_dev: Optional[torch.Tensor] = None,
                gate: Optional[torch.Tensor] = None) -> None:
@@ -534,6 +556,16 @@ class FlatTrainer:
     def _bucket_final(self, b: int, work) -> None:
         """Reducer callback (during backward): step bucket b on the side stream."""
         lo, hi = self.reducer.buckets[b]
+        if self._ride:
+            from . import ops
+            from .autograd_train import _wgrad_group
+            a = self.arena
+            for s, e in self._ranges(lo, hi, touched_only=True):
+                _wgrad_group.add_ride(ops.AdamWRide(a.master[s:e], a.grad[s:e], self.m[s:e], self.v[s:e], a.shadow[s:e],
+                                                    self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                                    self.step_count + 1, self._scale), self)
+            self._stepped.add(b)
+            return
         ev = torch.cuda.current_stream().record_event()   # after the kernels that wrote its gradients
         self._side.wait_event(ev)
         with torch.cuda.stream(self._side):
@@ -542,6 +574,17 @@ class FlatTrainer:
                 self.reducer.writeback(b)
             self._step_range(lo, hi, self.step_count + 1)
         self._stepped.add(b)
+
+    def _drain_rides(self) -> None:
+        """AdamW ranges still waiting on autograd_train._wgrad_group: plain launches on the current stream."""
+        if not self._ride:
+            return
+        from . import ops
+        from .autograd_train import _wgrad_group
+        for r in _wgrad_group.take_rides(self):
+            ops.adamw_step(r.p, r.g, r.m, r.v, r.p_bf16, r.lr, r.beta1, r.beta2, r.eps, r.weight_decay, r.step, r.grad_scale)
+            self.ride_stats["drained_ranges"] += 1
+            self.ride_stats["drained_bytes"] += r.p.numel() * 30
 
     def _sumsq(self) -> torch.Tensor:
         from . import ops
@@ -573,6 +616,7 @@ class FlatTrainer:
             for b, (lo, hi) in enumerate(self.reducer.buckets):
                 if b not in self._stepped:
                     self._step_range(lo, hi, self.step_count)
+            self._drain_rides()   # (buckets that finish() has just flushed)
             torch.cuda.current_stream().wait_stream(self._side)
         WEIGHT_EPOCH[0] += 1
         self._needs_zero = True
