@@ -743,6 +743,39 @@ int vy_lora_wgrad(const void* dy, int64_t lddy, const void* u, int64_t ldu, cons
                   int64_t bound1, float alpha, int accumulate, int dtype, void* stream);
 int64_t vy_lora_wgrad_chunk_rows(int64_t M, int64_t N, int64_t K);
 
+/* DoRA fine-tuning (vyomai_amd/dora_train.py): the reference's DoraLinear (VyomAI/layers/adapters.py:50-75) is a
+ *   re-parameterisation of the weight,
+ *     D = W + dora_a @ dora_b   (out, in)      c[k] = ||D[:, k]||_2, no epsilon      W'[n, k] = dora_m[k] * D[n, k] / c[k]
+ *   with dora_a (out, r), dora_b (r, in), dora_m (in).  Both entry points take a table of 1..8 problems, so that the
+ *   seven projections of a decoder layer are one call.  w: (out, in) in w_dtype (VY_F32 | VY_BF16), row stride ldw;
+ *   a, b, m, c and every gradient: fp32, contiguous.  D = W + an fma chain over j = 0..r-1 in that order; it is never
+ *   written to memory.
+ *   vy_dora_compose: D and the sum of its squares over the rows accumulate in fp64 (a bf16 W' is held to 2^-8 |W'| per
+ *     element, which an fp32 chain misses where W and a b cancel; fp32 products are exact in fp64), c (written) is the
+ *     square root rounded to fp32; wp (out, in) in out_dtype, row stride ldwp -- a part of a packed projection points
+ *     into its row block of the packed buffer -- = fp32(D) * (m / c) in fp32, rounded once more at a bf16 store.  Rows and columns outside (out, in) are never written.  g, dm, da, db are ignored.
+ *   vy_dora_bwd: with g = dL/dW' (out, in) fp32, row stride ldg, p[k] = sum_n g[n, k] D[n, k] and s[k] = m[k] / c[k]:
+ *       dm[k] (+)= p[k] / c[k]        dD[n, k] = s[k] * (g[n, k] - (p[k] / c[k]^2) * D[n, k])
+ *       da (out, r) (+)= dD @ b^T     db (r, in) (+)= a^T @ dD
+ *     D is recomputed in fp32; c is read (what vy_dora_compose left); wp is ignored.  accumulate = 1 adds to dm / da /
+ *     db, 0 overwrites them.
+ *     Two launches: a column-stripe pass owns p, dm and db (p goes to the stream's workspace, vy_workspace_set: the sum
+ *     of the problems' `in` floats), a row-block pass owns da.  Every output element has one owner that sums in a fixed
+ *     order: no atomics, two runs give the same bits.
+ *   VY_ERR_ARG: n outside 1..8, a null operand, in or out not a positive multiple of 8, r outside 1..64, a row stride
+ *   below `in`, an unknown dtype, accumulate other than 0 / 1, vy_dora_bwd on a stream without that workspace. */
+typedef struct vy_dora_desc {
+  const void* w; int64_t ldw; int32_t w_dtype;
+  const float* a; const float* b; const float* m;
+  float* c;
+  void* wp; int64_t ldwp;
+  const float* g; int64_t ldg;
+  float* dm; float* da; float* db;
+  int64_t out, in, r;
+} vy_dora_desc;
+int vy_dora_compose(const vy_dora_desc* descs, int32_t n, int out_dtype, void* stream);
+int vy_dora_bwd(const vy_dora_desc* descs, int32_t n, int accumulate, void* stream);
+
 /* y = x converted between fp32 and bf16 (n elements). src_dtype -> dst_dtype. */
 int vy_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);
 

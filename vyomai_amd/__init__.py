@@ -18,6 +18,7 @@ from .models import qwen3  # noqa: F401
 from .models.qwen3 import Qwen3Model, load_weights_into_qwen  # noqa: F401
 from .serving import RadixNode, SequenceState, PagedKVManager, ContinuousBatchEngine, SamplingParams  # noqa: F401
 from .adapters import LoraAdapters, LoraLinear, add_lora, disable_lora, lora_state_dict, merge_lora  # noqa: F401
+from .adapters import DoraLinear, add_dora, disable_dora, dora_state_dict, merge_dora  # noqa: F401
 from .generation_utils import generate, generate_multimodel, generate_seq2seq  # noqa: F401
 from .logits_processors import (LogitsProcessor, GreedyProcessor, MultinomialProcessor, TopKProcessor,  # noqa: F401
                                 NucleusProcessor, TopKNucleusProcessor)

@@ -97,6 +97,8 @@ PROTOTYPES = {
     "vy_lora_expand": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "vy_lora_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64,
                       _i64, _i64, _i64, _f, _i, _i, _p],
+    "vy_dora_compose": [_p, _i, _i, _p],
+    "vy_dora_bwd": [_p, _i, _i, _p],
     "vy_decoder_step": [_p, _p, _i64, _p, _p, _p, _i64, _p],
     "vy_gemma_decoder_step": [_p, _p, _i64, _p, _i64, _p],
     "vy_cast": [_p, _p, _i64, _i, _i, _p],
@@ -133,6 +135,13 @@ class VyAdamwHyper(C.Structure):
     """vy_adamw_hyper of include/vyom_hip.h."""
     _fields_ = [("lr", _f), ("beta1", _f), ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("grad_scale", _f),
                 ("step", _i64)]
+
+
+class VyDoraDesc(C.Structure):
+    """vy_dora_desc of include/vyom_hip.h."""
+    _fields_ = [("w", _p), ("ldw", _i64), ("w_dtype", C.c_int32), ("a", _p), ("b", _p), ("m", _p), ("c", _p),
+                ("wp", _p), ("ldwp", _i64), ("g", _p), ("ldg", _i64), ("dm", _p), ("da", _p), ("db", _p),
+                ("out", _i64), ("in_", _i64), ("r", _i64)]
 
 
 class VyomHipError(RuntimeError):

@@ -2,9 +2,10 @@
 (VyomAI/layers/adapters.py: linear(x) + alpha * F.linear(F.linear(x, lora_a), lora_b)) of many fine-tuned models, held
 next to ONE copy of the base weights and added per row of a serving step (vy_lora_shrink / vy_lora_expand, the rule:
 include/vyom_hip.h).  serving.ContinuousBatchEngine(..., adapters=store) and add_sequence(..., adapter="name") pick one
-per request.  DoRA (which renormalises the whole weight, so it is no additive per-request delta) is refused.  The second
-half of this file is the training side: the reference's LoraLinear wrapper, add_lora / lora_state_dict / merge_lora /
-disable_lora for ModelForCausalLM (the forward and backward of a wrapped layer: lora_train.py).
+per request.  DoRA (which renormalises the whole weight, so it is no additive per-request delta) is refused there: a
+DoRA model is served merged.  The second half of this file is the training side: the reference's LoraLinear and
+DoraLinear wrappers, add_lora / lora_state_dict / merge_lora / disable_lora and their DoRA counterparts for
+ModelForCausalLM (the forward and backward of a wrapped layer: lora_train.py, dora_train.py).
 
 Layout.  Per layer and projection group -- qkv, o, gate_up, down: the four GEMMs of forward_paged -- the store keeps
 A (slots, parts * r_pad, K) and B (slots, N, r_pad) in the compute dtype, r_pad = max_rank rounded up to 32.  A packed
@@ -240,15 +241,17 @@ def _causal_lm(model, what: str):
     return list(model.model.layers[: model.config.num_hidden_layers])
 
 
-def _wrapped(model):
-    """-> [(owner module, attribute, key path, LoraLinear)] of every wrapped projection, in layer order."""
+def _wrapped(model, cls=None, what: str = "LoRA"):
+    """-> [(owner module, attribute, key path, wrapper)] of every projection wrapped in a `cls` (LoraLinear), in layer
+    order."""
+    cls = LoraLinear if cls is None else cls
     out = []
-    for l, layer in enumerate(_causal_lm(model, "LoRA")):
+    for l, layer in enumerate(_causal_lm(model, what)):
         for path in ALL_TARGETS:
             owner_name, attr = path.split(".")
             owner = getattr(layer, owner_name)
             m = getattr(owner, attr)
-            if isinstance(m, LoraLinear):
+            if isinstance(m, cls):
                 out.append((owner, attr, f"model.layers.{l}.{path}", m))
     return out
 
@@ -264,6 +267,8 @@ def add_lora(model, rank: int = 32, alpha=1.0, targets=ALL_TARGETS):
         raise ValueError(f"targets {list(targets)} must be a non-empty subset of {list(ALL_TARGETS)} without repeats")
     if _wrapped(model):
         raise ValueError("the model already carries LoRA adapters: merge_lora(model) first")
+    if _wrapped(model, DoraLinear):
+        raise ValueError("the model carries DoRA adapters, and a layer runs one kind: merge_dora(model) first")
     if int(rank) != rank or not 1 <= rank <= MAX_TRAIN_RANK:
         raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_TRAIN_RANK}")
     for g in GROUPS:      # (everything is checked before anything is changed)
@@ -311,6 +316,134 @@ class disable_lora:
 
     def __init__(self, model):
         self.mods = [m for *_, m in _wrapped(model)]
+
+    def __enter__(self):
+        for m in self.mods:
+            m._off += 1
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.mods:
+            m._off -= 1
+        return False
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# DoRA: the reference's DoraLinear re-parameterises the weight, W' = dora_m * D / ||D||_col with D = W + dora_a @ dora_b.
+# All of its arithmetic is weight-sized: dora_train.py composes W' once per optimizer step (vy_dora_compose), runs the
+# plain fused block on it and turns dL/dW' into the three small gradients (vy_dora_bwd).
+# ------------------------------------------------------------------------------------------------------------------
+
+MAX_DORA_RANK = 64       # vy_dora_compose / vy_dora_bwd
+
+
+def _dora_shape_error(in_f: int, out_f: int) -> Optional[str]:
+    if in_f % 8 or out_f % 8:
+        return (f"in_features {in_f} and out_features {out_f} must be multiples of 8 (vy_dora_compose / vy_dora_bwd)")
+    return None
+
+
+class DoraLinear(torch.nn.Module):
+    """F.linear(x, dora_m * D / ||D||_2 over dim 0, bias) with D = linear.weight + dora_a @ dora_b around an nn.Linear,
+    with the reference's constructor, attribute and state_dict names (VyomAI/layers/adapters.py:50-75: `linear`,
+    `dora_m` (1, in) = the column norms of the weight, `dora_a` (out, rank) ~ N(0, 1 / rank), `dora_b` (rank, in) zero).
+    `weight` / `bias` forward to the wrapped linear; the layer that owns the projection composes the weight
+    (DecoderLayer: dora_train.py).  Called on its own it runs under torch.no_grad() only."""
+
+    def __init__(self, linear_layer, rank: int = 32) -> None:
+        super().__init__()
+        if not isinstance(linear_layer, torch.nn.Linear):
+            raise ValueError(f"DoraLinear wraps an nn.Linear, not a {type(linear_layer).__name__} (wrapping twice?)")
+        if int(rank) != rank or not 1 <= rank <= MAX_DORA_RANK:
+            raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_DORA_RANK}")
+        self.linear = linear_layer
+        self.in_features, self.out_features = linear_layer.in_features, linear_layer.out_features
+        bad = _dora_shape_error(self.in_features, self.out_features)
+        if bad:
+            raise ValueError(bad)
+        self.rank = int(rank)
+        w = linear_layer.weight
+        with torch.no_grad():
+            self.dora_m = torch.nn.Parameter(w.detach().norm(p=2, dim=0, keepdim=True))
+        self.dora_a = torch.nn.Parameter(torch.randn(self.out_features, self.rank, dtype=w.dtype, device=w.device)
+                                         * self.rank ** -0.5)
+        self.dora_b = torch.nn.Parameter(torch.zeros(self.rank, self.in_features, dtype=w.dtype, device=w.device))
+        self._off = 0            # depth of disable_dora() contexts
+
+    weight = property(lambda self: self.linear.weight)
+    bias = property(lambda self: self.linear.bias)
+    enabled = property(lambda self: self._off == 0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from . import dora_train
+        return dora_train.dora_linear_forward(self, x)
+
+    def extra_repr(self) -> str:
+        return f"rank={self.rank}"
+
+
+def add_dora(model, rank: int = 32, targets=ALL_TARGETS):
+    """Wrap the projections `targets` (paths of _CAUSAL_LM, any non-empty subset of the seven) of every layer of a
+    ModelForCausalLM in a DoraLinear and freeze every other parameter, as Examples/adapters.ipynb does -> the model.
+    ValueError, before anything is changed: another model class, an unknown or empty target list, a bad rank or
+    shape, a model that already carries LoRA or DoRA wrappers."""
+    layers = _causal_lm(model, "add_dora")
+    targets = tuple(targets)
+    unknown = [t for t in targets if t not in ALL_TARGETS]
+    if unknown or not targets or len(set(targets)) != len(targets):
+        raise ValueError(f"targets {list(targets)} must be a non-empty subset of {list(ALL_TARGETS)} without repeats")
+    if _wrapped(model):
+        raise ValueError("the model carries LoRA adapters, and a layer runs one kind: merge_lora(model) first")
+    if _wrapped(model, DoraLinear):
+        raise ValueError("the model already carries DoRA adapters: merge_dora(model) first")
+    if int(rank) != rank or not 1 <= rank <= MAX_DORA_RANK:
+        raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_DORA_RANK}")
+    for layer in layers:
+        for path in targets:
+            lin = functools.reduce(getattr, path.split("."), layer)
+            if not isinstance(lin, torch.nn.Linear):
+                raise ValueError(f"{path} is a {type(lin).__name__}, not an nn.Linear")
+            bad = _dora_shape_error(lin.in_features, lin.out_features)
+            if bad:
+                raise ValueError(f"{path}: {bad}")
+    for p in model.parameters():
+        p.requires_grad_(False)
+    for layer in layers:
+        for path in targets:
+            owner_name, attr = path.split(".")
+            owner = getattr(layer, owner_name)
+            setattr(owner, attr, DoraLinear(getattr(owner, attr), rank=rank))
+    return model
+
+
+def dora_state_dict(model) -> Dict[str, torch.Tensor]:
+    """Exactly the dora_m / dora_a / dora_b entries of the wrapped model's state_dict (detached copies)."""
+    out = {}
+    for _, _, key, m in _wrapped(model, DoraLinear, "DoRA"):
+        for leaf in ("dora_m", "dora_a", "dora_b"):
+            out[f"{key}.{leaf}"] = getattr(m, leaf).detach().clone()
+    return out
+
+
+def merge_dora(model):
+    """W <- dora_m * D / ||D||_col with D = W + dora_a @ dora_b, in fp32, into every wrapped linear, and the plain
+    nn.Linear back in its place -> the model: what generate() and the serving engine run.  requires_grad flags stay as
+    they are."""
+    with torch.no_grad():
+        for owner, attr, _, m in _wrapped(model, DoraLinear, "DoRA"):
+            w = m.linear.weight
+            d = w.detach().float() + m.dora_a.detach().float() @ m.dora_b.detach().float()
+            w.copy_((m.dora_m.detach().float() * (d / d.norm(p=2, dim=0, keepdim=True))).to(w.dtype))
+            setattr(owner, attr, m.linear)
+    return model
+
+
+class disable_dora:
+    """Context manager: inside it the wrapped model computes the base model and nothing is composed (a DPO run scores
+    its reference with the same weights).  Nests; restores on exceptions."""
+
+    def __init__(self, model):
+        self.mods = [m for *_, m in _wrapped(model, DoraLinear, "DoRA")]
 
     def __enter__(self):
         for m in self.mods:

@@ -72,12 +72,13 @@ def ffn_block(x, residual, w1, b1, w2, b2, ln_w, ln_b, eps, act, p_drop: float =
     return y
 
 
-def gated_mlp(x, mlp, act, wd, residual=None, delta=None):
+def gated_mlp(x, mlp, act, wd, residual=None, delta=None, gate_up=None):
     """(act(x Wg^T) * x Wu^T) Wd^T + residual -> (y, gate_up): one packed [gate; up] GEMM (mlp._packed_gate_up),
     vy_gated_act_fwd, the down GEMM (wd: its weight in x's dtype) with the residual in its epilogue.  delta =
     f(group, y, x) is called behind each of the two GEMMs and adds a LoRA delta to y in place: adapters.layer_delta in
-    serving, lora_train.py in fine-tuning."""
-    gu = ops.linear(x, mlp._packed_gate_up(x.dtype))
+    serving, lora_train.py in fine-tuning.  gate_up: a packed [gate; up] weight to use in place of the module's own
+    (DoRA's composed one: dora_train.py)."""
+    gu = ops.linear(x, mlp._packed_gate_up(x.dtype) if gate_up is None else gate_up)
     if delta is not None:
         delta("gate_up", gu, x)
     h = ops.gated_act(gu, act)

@@ -486,18 +486,21 @@ def _qkv_heads(packed: torch.Tensor, h: int, hk: int, dh: int):
             _heads(packed[:, :, (h + hk) * dh:(h + 2 * hk) * dh], hk, dh))
 
 
-def _project_qkv(n, mod, am: _AttnArgs, qk=None, delta=None):
+def _project_qkv(n, mod, am: _AttnArgs, qk=None, delta=None, w=None):
     """The packed q / k / v projection of n (B, L, d) with RoPE -> (q, k, v as (B, heads, L, dh), qkv).  `mod` packs
     q/k/v as the _SelfAttentionBase modules do.  Three ways, each with its own launches and rounding:
       * neither: vy_qkv_rope_fwd writes the rotated q, k and v into three buffers; qkv is None;
       * qk = (q_scale, k_scale, eps), Qwen3's qk_norm: the plain bias-free GEMM keeps the RAW rows in qkv,
         vy_qknorm_rope_fwd writes the normalised, rotated q and k beside them, and v is a strided view of those rows;
       * delta = f(group, y, x), LoRA: the plain GEMM, the adapter's delta behind it -- before RoPE -- and ops.rope_ on the
-        q and k views of qkv; all three are views."""
+        q and k views of qkv; all three are views.
+    w: a packed weight to use in place of the module's own shadow (DoRA's composed one: dora_train.py)."""
     B, L, _ = n.shape
     h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
     dt, dev = n.dtype, n.device
     sw, sb = mod._packed_shadow(dt)
+    if w is not None:
+        sw = w
     if delta is not None:
         qkv = torch.empty((B, L, (h + 2 * hk) * dh), dtype=dt, device=dev)
         ops.linear(n, sw, sb, out=qkv)
@@ -963,34 +966,45 @@ def _rms_bwd(dy, x, w, eps, add_to=None):
     return dx, dw.to(w.dtype)
 
 
-def prenorm_attention_forward(x, mod, attention_mask, freqs, ln_w, eps, wo, qk=None, delta=None):
+def _override(weights, group: str, transposed: bool = False):
+    """The matrix a block body reads for `group` in place of the module's own shadow (or of its transposed copy), or None.
+    weights: None, or an object with w (group -> matrix in the compute dtype) and wt(group) (dora_train.py)."""
+    if weights is None or group not in weights.w:
+        return None
+    return weights.wt(group) if transposed else weights.w[group]
+
+
+def prenorm_attention_forward(x, mod, attention_mask, freqs, ln_w, eps, wo, qk=None, delta=None, weights=None):
     """y = x + attn(project(RMSNorm(x))) Wo^T: the attention half of a pre-norm block (the reference's DecoderLayer,
     models/custom_transformer.py:268-282) -> (y, (n, q, k, v, qkv, o, lse), am).  `mod`, qk and delta: see _project_qkv,
     the only step that differs between the plain, the qk_norm and the LoRA block; delta is also called behind the
-    out-projection, as delta("o", y, o)."""
+    out-projection, as delta("o", y, o).  weights: see _override (groups "qkv" and "o"); absent, nothing changes."""
     dt = x.dtype
     am = _attn_args(attention_mask, freqs, x.shape[1], x.device)
     n = ops.rmsnorm(x, _shadow(ln_w, dt), eps, 0.0)
-    q, k, v, qkv = _project_qkv(n, mod, am, qk, delta)
+    q, k, v, qkv = _project_qkv(n, mod, am, qk, delta, _override(weights, "qkv"))
     o, lse = _attend(q, k, v, am)
-    y = ops.linear(o, _shadow(wo, dt), None, residual=x)
+    wo_c = _override(weights, "o")
+    y = ops.linear(o, _shadow(wo, dt) if wo_c is None else wo_c, None, residual=x)
     if delta is not None:
         delta("o", y, o)
     return y, (n, q, k, v, qkv, o, lse), am
 
 
 def prenorm_attention_backward(dy, x, n, o, lse, am, mod, ln_w, eps, wo, params=(), q=None, k=None, v=None, qkv=None,
-                               qk=None, adapters=None, need_dx=True):
+                               qk=None, adapters=None, need_dx=True, weights=None):
     """Backward of prenorm_attention_forward -> (dx, dln_w, dwo, dq_scale, dk_scale, the gradients of `params`, the
     projection's parameters in _params() order), each None where nothing is returned to autograd.  q / k / v that the
     forward left as views of qkv are passed as None and read there.  adapters: None trains the base weights (_wgrad,
     _packed_wgrad); a dict group -> f(dy, x, dx) freezes them and runs the adapter backward of the groups it names
     (lora_train.py), and then need_dx=False skips the packed dgrad and the RMSNorm backward nobody reads.  The residual
-    branch's gradient is added in the RMSNorm backward's store (vy_rmsnorm_bwd add_to)."""
+    branch's gradient is added in the RMSNorm backward's store (vy_rmsnorm_bwd add_to).  weights: as in the forward; the
+    dgrads read its transposed copies."""
     h, hk, dh = mod.num_attention_heads, mod.num_key_value_heads, mod.head_dim
     dt = x.dtype
     dy = dy.contiguous()
-    do = ops.linear_dgrad(dy, _wt(wo, dt))
+    wot = _override(weights, "o", True)
+    do = ops.linear_dgrad(dy, _wt(wo, dt) if wot is None else wot)
     dwo = None
     if adapters is None:
         dwo, _ = _wgrad(dy, o, wo, None)
@@ -1004,7 +1018,8 @@ def prenorm_attention_backward(dy, x, n, o, lse, am, mod, ln_w, eps, wo, params=
     if qk is not None:    # the dq | dk columns become the gradient of the raw projection, in place, before both readers
         dqs, dks = _qk_scale_bwd(packed, qkv, h, hk, dh, *qk)
     w, b = mod._packed()
-    dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt)) if need_dx else None
+    wt = _override(weights, "qkv", True) if need_dx else None
+    dn = ops.linear_dgrad(packed, _wt_packed(mod, w, dt) if wt is None else wt) if need_dx else None
     grads = ()
     if adapters is None:
         grads = _packed_wgrad(mod, packed, n, w, b, params)
@@ -1118,28 +1133,33 @@ def _gate_up_wgrad(dgu, n, wg, wu):
     return outs[0], outs[1]
 
 
-def prenorm_gated_mlp_forward(x, mlp, ln_w, eps, act, wd, delta=None):
+def prenorm_gated_mlp_forward(x, mlp, ln_w, eps, act, wd, delta=None, weights=None):
     """y = x + (act(n Wg^T) * n Wu^T) Wd^T with n = RMSNorm(x): the MLP half of a pre-norm block (the reference's
-    DecoderLayer, models/custom_transformer.py:76-89, 285-288) -> (y, n, gate_up).  delta: see autograd.gated_mlp."""
+    DecoderLayer, models/custom_transformer.py:76-89, 285-288) -> (y, n, gate_up).  delta: see autograd.gated_mlp.
+    weights: see _override (groups "gate_up" and "down")."""
     n = ops.rmsnorm(x, _shadow(ln_w, x.dtype), eps, 0.0)
-    y, gu = gated_mlp(n, mlp, act, _shadow(wd, x.dtype), residual=x, delta=delta)
+    wd_c = _override(weights, "down")
+    y, gu = gated_mlp(n, mlp, act, _shadow(wd, x.dtype) if wd_c is None else wd_c, residual=x, delta=delta,
+                      gate_up=_override(weights, "gate_up"))
     return y, n, gu
 
 
-def prenorm_gated_mlp_backward(dy, x, n, gu, mlp, ln_w, eps, act, wg, wu, wd, adapters=None):
+def prenorm_gated_mlp_backward(dy, x, n, gu, mlp, ln_w, eps, act, wg, wu, wd, adapters=None, weights=None):
     """Backward of prenorm_gated_mlp_forward -> (dx, dln_w, dwg, dwu, dwd).  The gated product is recomputed from gate_up
     (one streaming pass) for whoever reads it: the down projection's weight gradient or its adapter's.  adapters: as in
-    prenorm_attention_backward, groups "gate_up" and "down"."""
+    prenorm_attention_backward, groups "gate_up" and "down"; weights: as in the forward."""
     dt = x.dtype
     dy = dy.contiguous()
-    da = ops.linear_dgrad(dy, _wt(wd, dt))
+    wdt = _override(weights, "down", True)
+    da = ops.linear_dgrad(dy, _wt(wd, dt) if wdt is None else wdt)
     dwg = dwu = dwd = None
     if adapters is None:
         dwd, _ = _wgrad(dy, ops.gated_act(gu, act), wd, None)
     elif "down" in adapters:
         adapters["down"](dy, ops.gated_act(gu, act), da)
     dgu = ops.gated_act_bwd(da, gu, act)
-    dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt))
+    wgut = _override(weights, "gate_up", True)
+    dn = ops.linear_dgrad(dgu, _wt_gate_up(mlp, dt) if wgut is None else wgut)
     if adapters is None:
         dwg, dwu = _gate_up_wgrad(dgu, n, wg, wu)
     elif "gate_up" in adapters:

@@ -183,8 +183,10 @@ class _SelfAttentionBase(nn.Module):
         a missing attribute).  Adapters are outside SURVEY section 8; say so instead of computing without them."""
         for name in (("qkv",) if self._fused_qkv else ("query", "key", "value")):
             m = getattr(self, name)
-            if self._lora_aware and type(m).__name__ == "LoraLinear" and hasattr(m, "linear"):
-                continue      # (the owner adds the wrapper's term itself: lora_train.py; `weight` / `bias` forward)
+            if self._lora_aware and type(m).__name__ in ("LoraLinear", "DoraLinear") and hasattr(m, "linear"):
+                # (the owner adds a LoraLinear's term and composes a DoraLinear's weight itself: lora_train.py,
+                # dora_train.py; `weight` / `bias` forward)
+                continue
             if not isinstance(m, nn.Linear):
                 raise VyomHipError(
                     f"attention.{name} is a {type(m).__name__}, not an nn.Linear: the MI355X attention path reads the "

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import VyomHipError
-from ..adapters import LoraLinear, layer_delta
+from ..adapters import DoraLinear, LoraLinear, layer_delta
 from ..autograd import _mask_args, _wants_grad, gated_mlp
 from ..layers.attention import _SelfAttentionBase, _shadow
 from ..layers.ffn import _FUSED_ACT
@@ -117,6 +117,9 @@ class MLP(nn.Module):
         if any(isinstance(p, LoraLinear) and p.enabled for p in (self.gate_proj, self.up_proj, self.down_proj)):
             raise VyomHipError("the gated MLP applies LoRA adapters (LoraLinear) inside its pre-norm block (DecoderLayer) "
                                "only; called on its own it would skip their term")
+        if any(isinstance(p, DoraLinear) and p.enabled for p in (self.gate_proj, self.up_proj, self.down_proj)):
+            raise VyomHipError("the gated MLP runs on DoRA's composed weights (DoraLinear) inside its pre-norm block "
+                               "(DecoderLayer) only; called on its own it would compute the base model")
         if _wants_grad(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight):
             raise VyomHipError("the gated MLP trains inside its pre-norm block (DecoderLayer: RMSNorm, MLP and the "
                                "residual add are one autograd function); call it under torch.no_grad() on its own")
@@ -202,6 +205,10 @@ class DecoderLayer(nn.Module):
         if lora_train.layer_has_lora(self):
             # (training, and validation under no_grad: the adapter's delta behind each of the four GEMMs)
             return (lora_train.decoder_layer_forward(self, x, attention_mask, position_embeddings, past_key_value),)
+        from .. import dora_train
+        if dora_train.layer_has_dora(self):
+            # (the plain block bodies on the composed weights; the adapter's own arithmetic is weight-sized)
+            return (dora_train.decoder_layer_forward(self, x, attention_mask, position_embeddings, past_key_value),)
         if _wants_grad(x, a.o_proj.weight, m.down_proj.weight, ln1.weight):
             if past_key_value is not None:
                 raise VyomHipError("KV caching is an inference feature; call under torch.no_grad()")
@@ -297,8 +304,11 @@ class BaseModel(nn.Module, PositionMixin):
         from .. import lora_train
         layers = self.layers[: self.config.num_hidden_layers]
         # (a cached step -- the decode loop -- does not ask: a wrapped layer refuses its past_key_value itself)
-        lora = past_key_values is None and any(lora_train.layer_has_lora(layer) for layer in layers)
-        train = train or (lora and _wants_grad(*(p for layer in layers for p in lora_train.layer_lora_params(layer))))
+        from .. import dora_train
+        lora = past_key_values is None and any(lora_train.layer_has_lora(layer) or dora_train.layer_has_dora(layer)
+                                               for layer in layers)
+        train = train or (lora and _wants_grad(*(p for layer in layers for p in lora_train.layer_lora_params(layer)
+                                                 + dora_train.layer_dora_params(layer))))
         if train and past_key_values is not None:
             raise VyomHipError("KV caching is an inference feature; call under torch.no_grad()")
         cache = None
@@ -442,6 +452,9 @@ class ModelForCausalLM(nn.Module, SequenceScoreMixin):
         from .. import lora_train
         if any(lora_train.layer_has_lora(layer) for layer in base.layers[: self.config.num_hidden_layers]):
             raise VyomHipError(lora_train.NO_CACHE.format(what="forward_paged() (the serving engine)"))
+        from .. import dora_train
+        if any(dora_train.layer_has_dora(layer) for layer in base.layers[: self.config.num_hidden_layers]):
+            raise VyomHipError(dora_train.NO_CACHE.format(what="forward_paged() (the serving engine)"))
         _need_gpu(input_ids, "forward_paged()")
         dev = input_ids.device
         x = base._embed(base.embed_tokens, input_ids.view(1, -1))[0]
@@ -477,6 +490,9 @@ class ModelForCausalLM(nn.Module, SequenceScoreMixin):
         from .. import lora_train
         if any(lora_train.layer_has_lora(layer) for layer in self.model.layers[: self.config.num_hidden_layers]):
             raise VyomHipError(lora_train.NO_CACHE.format(what="generate() (it decodes through a KV cache)"))
+        from .. import dora_train
+        if any(dora_train.layer_has_dora(layer) for layer in self.model.layers[: self.config.num_hidden_layers]):
+            raise VyomHipError(dora_train.NO_CACHE.format(what="generate() (it decodes through a KV cache)"))
         _need_gpu(input_ids, "generate()")
         dev = input_ids.device
         B, T = input_ids.shape

@@ -1092,6 +1092,88 @@ def lora_wgrad(dy: Tensor, u: Tensor, x: Tensor, t: Tensor, dA: Sequence[Optiona
          1 if accumulate else 0, dtype_code(dt), st)
 
 
+class DoraProblem(NamedTuple):
+    """One projection of dora_compose / dora_bwd's table (vy_dora_desc; the rule: include/vyom_hip.h).  w: (out, in)
+    float32 or bfloat16 with unit column stride; a (out, r), b (r, in), m (in) and c (in): contiguous float32.
+    dora_compose writes c and wp -- (out, in) in the compute dtype, any row stride: a part of a packed projection passes
+    its row block of the packed buffer.  dora_bwd reads c and g (out, in) float32 and writes dm, da, db, contiguous
+    float32 of m's, a's and b's shapes."""
+    w: Tensor
+    a: Tensor
+    b: Tensor
+    m: Tensor
+    c: Tensor
+    wp: Optional[Tensor] = None
+    g: Optional[Tensor] = None
+    dm: Optional[Tensor] = None
+    da: Optional[Tensor] = None
+    db: Optional[Tensor] = None
+
+
+def _dora_table(fn: str, problems: Sequence[DoraProblem], bwd: bool):
+    import ctypes as C
+    problems = list(problems)
+    if not 1 <= len(problems) <= 8:
+        raise ValueError(f"{fn}: a table holds 1 to 8 problems, got {len(problems)}")
+    arr = (_lib.VyDoraDesc * len(problems))()
+    dev = problems[0].w.device if isinstance(problems[0].w, Tensor) else None
+    for i, p in enumerate(problems):
+        w = p.w
+        if not isinstance(w, Tensor) or w.dim() != 2 or w.dtype not in (torch.float32, torch.bfloat16) or w.stride(1) != 1:
+            raise ValueError(f"{fn}: problem {i}: w must be a float32 or bfloat16 (out, in) matrix with unit column stride")
+        _need_gpu(w)
+        out_f, in_f = w.shape
+        r = p.a.shape[1] if isinstance(p.a, Tensor) and p.a.dim() == 2 else -1
+        if in_f % 8 or out_f % 8 or not 1 <= r <= 64:
+            raise ValueError(f"{fn}: problem {i}: in {in_f} and out {out_f} must be multiples of 8 and the rank {r} lie in "
+                             "1..64")
+        small = [("a", p.a, (out_f, r)), ("b", p.b, (r, in_f)), ("m", p.m, (in_f,)), ("c", p.c, (in_f,))]
+        if bwd:
+            small += [("dm", p.dm, (in_f,)), ("da", p.da, (out_f, r)), ("db", p.db, (r, in_f))]
+        for what, t, shape in small:
+            # (a vector may come as the reference's (1, in) parameter)
+            if not isinstance(t, Tensor) or t.dtype != torch.float32 or t.numel() != math.prod(shape) \
+                    or (len(shape) > 1 and tuple(t.shape) != shape) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{fn}: problem {i}: {what} must be a contiguous float32 {shape} tensor on {dev}, got "
+                                 f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+        big, what = (p.g, "g") if bwd else (p.wp, "wp")
+        if not isinstance(big, Tensor) or tuple(big.shape) != (out_f, in_f) or big.stride(1) != 1 or big.stride(0) < in_f \
+                or big.device != dev or (bwd and big.dtype != torch.float32):
+            raise ValueError(f"{fn}: problem {i}: {what} must be an (out, in) = {(out_f, in_f)} matrix on {dev} with unit "
+                             f"column stride{' in float32' if bwd else ''}")
+        d = arr[i]
+        d.w, d.ldw, d.w_dtype = w.data_ptr(), w.stride(0), dtype_code(w.dtype)
+        d.a, d.b, d.m, d.c = p.a.data_ptr(), p.b.data_ptr(), p.m.data_ptr(), p.c.data_ptr()
+        d.out, d.in_, d.r = out_f, in_f, r
+        if bwd:
+            d.g, d.ldg = big.data_ptr(), big.stride(0)
+            d.dm, d.da, d.db = p.dm.data_ptr(), p.da.data_ptr(), p.db.data_ptr()
+        else:
+            d.wp, d.ldwp = big.data_ptr(), big.stride(0)
+    return C.cast(arr, C.c_void_p), len(problems), arr
+
+
+def dora_compose(problems: Sequence[DoraProblem]) -> None:
+    """W' = dora_m * D / c with D = w + a @ b and c = the column norms of D (written too), for up to 8 projections in one
+    launch (vy_dora_compose).  Every wp of a table has the same dtype, float32 or bfloat16."""
+    fn = "dora_compose"
+    table, n, keep = _dora_table(fn, problems, False)
+    dts = {p.wp.dtype for p in problems}
+    if len(dts) != 1:
+        raise ValueError(f"{fn}: the wp of one table share a dtype, got {sorted(map(str, dts))}")
+    call("vy_dora_compose", table, n, dtype_code(dts.pop()), _stream())
+
+
+def dora_bwd(problems: Sequence[DoraProblem], accumulate: bool) -> None:
+    """dm, da, db (+)= the gradients of dora_m, dora_a, dora_b given g = dL/dW' in float32, for up to 8 projections in
+    one launch pair (vy_dora_bwd); D is recomputed, c is what dora_compose left.  Deterministic: two calls give the same
+    bits."""
+    table, n, keep = _dora_table("dora_bwd", problems, True)
+    st = _stream()
+    _stream_ws()
+    call("vy_dora_bwd", table, n, 1 if accumulate else 0, st)
+
+
 def embedding_bwd_(dout: Tensor, ids: Tensor, dw: Tensor, padding_idx: Optional[int]) -> None:
     """dw[ids[m], :] += dout[m, :] in fp32, skipping padding_idx  (vy_embedding_bwd)."""
     _need_gpu(dout, ids, dw)
