@@ -274,8 +274,11 @@ def test_vy_lora_wgrad_argument_checks_and_chunk_rule():
     for kw in bad:
         assert rc(**kw) == -1, kw          # VY_ERR_ARG
         assert b"vy_lora_wgrad" in lib.vy_last_error(), kw
-    # valid arguments get as far as the workspace check: this stream has none registered in a process without a GPU
-    assert rc() == -1 and b"workspace" in lib.vy_last_error()
+    # valid arguments get as far as the workspace check: this stream has none registered in a process without a GPU.
+    # Where there is a GPU an earlier test of the same process may have registered one, and the call would launch on
+    # these host pointers: it is made only where there is none.
+    if not torch.cuda.is_available():
+        assert rc() == -1 and b"workspace" in lib.vy_last_error()
     # the cut of M: chunks of at least 128 rows, whole stages of 32, about 1024 workgroups over the column tiles
     assert ops.lora_wgrad_chunk_rows(256, 48, 64) == 128 and ops.lora_wgrad_chunk_rows(257, 1024, 512) == 128
     assert ops.lora_wgrad_chunk_rows(16384, 1152, 896) == 512 and ops.lora_wgrad_chunk_rows(16384, 9728, 896) == 2368

@@ -4,7 +4,7 @@ special regimes were built for switched in.  No kernel runs here.
 Forward: the two-pass form of layernorm_fwd_kernel (per-lane partial sums over the lane's chunks, a butterfly over the 64
 lanes, the variance about the mean) and a one-pass variant (E[x^2] - mean^2).  Backward: layernorm_bwd_kernel's wave walk
 (wave w takes rows w, w + W, ...), the four-wave sum of a workgroup, the slab and the sliced column sums of
-vy_ln_colsum, with two faults: the last row of a walk of more than one row is skipped; row r uses the statistics of row
+vy_colsum, with two faults: the last row of a walk of more than one row is skipped; row r uses the statistics of row
 r + W.  Asserted: the faithful restatements sit at no more than half of every bar on every case of the tables, the
 one-pass variant breaks the rstd bar on every offset case and none on the plain ones, each backward fault breaks the exact
 twin wherever a wave walks more than one row, and the twin's expected values are the same in fp64 and fp32."""
@@ -58,7 +58,7 @@ BWD_FAULTS = ("skip_last", "stats_ahead")
 
 
 def colsum_restated(slab, out, acc):
-    """vy_ln_colsum on a [WB, N] slab: slices of rows, four row groups a slice summed in row order, ((p0 + p1) + p2) + p3,
+    """vy_colsum on a [WB, N] slab: slices of rows, four row groups a slice summed in row order, ((p0 + p1) + p2) + p3,
     the slices in slice order."""
     WB, N = slab.shape
     slices = S.ln_colsum_slices(WB)

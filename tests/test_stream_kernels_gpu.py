@@ -163,7 +163,7 @@ def bwd_pads(dtype, M, N):
 
 @pytest.mark.parametrize("dtype,M,N", ln_bwd_params())
 def test_layernorm_bwd_vs_fp64(dtype, M, N):
-    """layernorm_bwd_kernel<T, CH> + vy_ln_colsum with statistics computed in fp64 (not by the forward kernel): dx, dgamma
+    """layernorm_bwd_kernel<T, CH> + vy_colsum with statistics computed in fp64 (not by the forward kernel): dx, dgamma
     and dbeta against fp64; a second run gives the same bits; accumulate adds onto them."""
     case = S.ln_bwd_inputs(dtype, M, N)
     want_dx, want_dg, want_db = S.ln_bwd_reference(*case)

@@ -17,6 +17,7 @@
 // one is spelled out by the reference author in Examples/vyom-ai-decoder-fused.ipynb cell 7
 // (dS = P o (dP - rowsum(dO o O))).
 #include "vy_attn_tile.h"
+#include "vy_colsum.h"
 #include <float.h>
 #include <string.h>
 
@@ -403,49 +404,30 @@ struct WgradGroup { WgradItem g[8]; int n; };
 // Column sums of LayerNorm-backward slabs riding in the same launch (vy_linear_wgrad_grouped_cs): a layer's grouped
 // launch fills 216 of 256 CUs, and its two LayerNorms' dgamma / dbeta -- 2 x 512 x 768 floats each -- were two launches of
 // their own per LayerNorm.  The workgroups behind the `items` weight-gradient ones each take a 64-column block of one
-// slab pair, all slices of it, in the summation order of vy_ln_colsum_slices (vy_common.h).
+// slab pair, all slices of it, in the summation order of vy_colsum.h.
 struct ColsumItem { const float* ws; float* out0; float* out1; int W, N, rps, acc, blk0; };   // blk0: first block of this slab
 struct ColsumGroup { ColsumItem c[8]; int n; int items; };
 
-// 512 threads: column c = tid & 63, row group g = (tid >> 6) & 3, and the two halves of the workgroup take the even and
-// the odd slices, so two slices' rows are in flight at once
+// 512 threads: the two halves of the workgroup take the even and the odd slices, so two slices' rows are in flight at
+// once; each half is the 4 row groups x 64 columns of vy_colsum_slice_groups.  A single slice is added to 0.f like any
+// other: its sum is never -0.f (vy_colsum.h), so the bits are its own.
 __device__ __forceinline__ void colsum_slab_block(const ColsumItem& it, int blk) {
   __shared__ float red[2][2][4][64];
   const int tid = threadIdx.x;
-  const int c = tid & 63, g = (tid >> 6) & 3, h = tid >> 8;
+  const int c = tid & 63, h = tid >> 8;
   const int n = blk * 64 + c;
   const int W = it.W, N = it.N, rps = it.rps;
-  const float* __restrict__ ws = it.ws;
-  const bool one = rps >= W;   // one slice: its sum is the result (no 0 + sum)
   float ta = 0.f, tb = 0.f;
   for (int s0 = 0; s0 * rps < W; s0 += 2) {
     const int w0 = (s0 + h) * rps, w1 = min(W, w0 + rps);
-    float a = 0.f, b = 0.f;
-    if (n < N) {
-      for (int wb = w0 + g; wb < w1; wb += 32) {
-        float av[8], bv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int w = wb + 4 * i;
-          const int wc = w < w1 ? w : wb;
-          av[i] = ws[(int64_t)wc * N + n];
-          bv[i] = ws[(int64_t)(W + wc) * N + n];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (wb + 4 * i < w1) { a += av[i]; b += bv[i]; }
-      }
-    }
-    red[h][0][g][c] = a; red[h][1][g][c] = b;
+    vy_colsum_slice_groups<2>(it.ws, (int64_t)W * N, N, n, n < N, w0, w1, red[h]);
     __syncthreads();
     if (tid < 64) {
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
         if ((s0 + hh) * rps < W) {
-          const float sa = red[hh][0][0][c] + red[hh][0][1][c] + red[hh][0][2][c] + red[hh][0][3][c];
-          const float sb = red[hh][1][0][c] + red[hh][1][1][c] + red[hh][1][2][c] + red[hh][1][3][c];
-          ta = one ? sa : ta + sa;
-          tb = one ? sb : tb + sb;
+          ta += vy_colsum_slice_sum(red[hh], 0, c);
+          tb += vy_colsum_slice_sum(red[hh], 1, c);
         }
     }
     __syncthreads();
@@ -1100,7 +1082,8 @@ static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n,
       o.taken = o.n;
     }
     for (int i = 0; i < ncs; ++i)
-      if (int rc = vy_ln_colsum(cs[i].ws, cs[i].W, cs[i].N, cs[i].out0, cs[i].out1, cs[i].acc, (hipStream_t)stream)) return rc;
+      if (int rc = vy_colsum("vy_layernorm_bwd", cs[i].ws, 2, (int64_t)cs[i].W * cs[i].N, cs[i].N, cs[i].W, cs[i].N,
+                             vy_ln_colsum_slices(cs[i].W), cs[i].out0, cs[i].out1, cs[i].acc, (hipStream_t)stream)) return rc;
     for (int i = 0; i < n; ++i) {
       const vy_wgrad_desc& d = descs[i];
       if (!d.dy || !d.x || !d.dw || d.M <= 0 || d.N <= 0 || d.K <= 0) VY_FAIL(VY_ERR_ARG, "%s: descriptor %d: bad arguments", who, i);

@@ -102,12 +102,13 @@ void vy_set_error(const char* fmt, ...);
 
 static inline int64_t vy_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// The column sums of a LayerNorm-backward slab of WB rows (dgamma, dbeta): WB is cut into this many row slices, a slice
-// is summed per row group g = 0..3 over rows w0 + g, w0 + g + 4, ..., the groups as ((p0 + p1) + p2) + p3, the slices
-// in slice order.  vy_ln_colsum (vy_misc.hip) does it in launches of its own, the grouped weight-gradient launch
-// (vy_bwd.hip) in spare workgroups -- in the same order, so both give the same bits.
+// Row slices of a LayerNorm- or RMSNorm-backward slab of WB rows; the order of the sum itself is stated in vy_colsum.h.
 static inline int vy_ln_colsum_slices(int WB) { return WB >= 64 ? 16 : 1; }
-int vy_ln_colsum(float* ws, int WB, int N, float* dgamma, float* dbeta, int acc, hipStream_t st);
+// internal (vy_misc.hip): the ordered column sums of S = 1 or 2 slabs, W rows in `slices` slices, as launches of their
+// own; out0 / out1 may be null.  With several slices the first row of each slice is overwritten with the slice's sum.
+// `who` names the caller in a launch error.
+int vy_colsum(const char* who, float* ws, int S, int64_t slab_stride, int ld, int W, int N, int slices, float* out0,
+              float* out1, int acc, hipStream_t st);
 
 // 16 zero bytes: source for out-of-range chunks of LDS-DMA loads (one copy per translation unit:
 // the library is built without relocatable device code).

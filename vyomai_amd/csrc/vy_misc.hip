@@ -2,6 +2,7 @@
 // transposes and the fused AdamW step.  All are one pass over their operands with 16-byte
 // accesses per lane; LayerNorm keeps the whole row in registers (one wave per row).
 #include "vy_common.h"
+#include "vy_colsum.h"
 #include <stdarg.h>
 #include <string.h>
 
@@ -258,64 +259,48 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
   }
 }
 
-// column sums of the [W, N] partial slabs: grid = (column blocks of 64) x (row slices), 4 row groups
-// per block reduced through LDS.  No atomics, so dgamma / dbeta are the same from run to run: with one
-// slice the block writes out0/out1 itself (added to them when acc); with several, each block leaves its
-// sums in the first slab row of its slice (rows only this block reads) and colsum_finish_kernel adds
-// the slices up in slice order.
-__global__ __launch_bounds__(256) void colsum_partials_kernel(float* __restrict__ ws, int W, int N,
-                                                              float* __restrict__ out0, float* __restrict__ out1,
-                                                              int rows_per_slice, int acc) {
-  __shared__ float red[2][4][64];
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+// The ordered column sums of vy_colsum.h as launches of their own: grid = (column blocks of 64) x (row slices).  With one
+// slice the block writes out0 / out1 itself; with several, each block leaves its sums in the first slab row of its slice
+// (rows only this block reads) and colsum_finish_kernel adds the slices up in slice order.
+template <int S>
+__global__ __launch_bounds__(256) void colsum_partials_kernel(float* __restrict__ ws, int64_t slab_stride, int ld, int W, int N,
+                                                            float* __restrict__ out0, float* __restrict__ out1,
+                                                            int rows_per_slice, int acc) {
+  __shared__ float red[S][4][64];
+  const int c = threadIdx.x & 63;
   const int n = blockIdx.x * 64 + c;
   const int w0 = blockIdx.y * rows_per_slice, w1 = min(W, w0 + rows_per_slice);
-  float a = 0.f, b = 0.f;
-  if (n < N) {
-    // eight rows of both slabs requested at once (one round trip for the usual 32-row slice; a loop of dependent
-    // 4-byte loads made this 3 MB reduction an 11.8 us launch, 25 times per step), summed in row order as before
-    for (int wb = w0 + g; wb < w1; wb += 32) {
-      float av[8], bv[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int w = wb + 4 * i;
-        const int wc = w < w1 ? w : wb;
-        av[i] = ws[(int64_t)wc * N + n];
-        bv[i] = ws[(int64_t)(W + wc) * N + n];
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (wb + 4 * i < w1) { a += av[i]; b += bv[i]; }
-    }
-  }
-  red[0][g][c] = a; red[1][g][c] = b;
+  vy_colsum_slice_groups<S>(ws, slab_stride, ld, n, n < N, w0, w1, red);
   __syncthreads();
-  if (g == 0 && n < N && w0 < w1) {
-    a = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
-    b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
-    if (gridDim.y == 1) {
-      if (out0) out0[n] = (acc ? out0[n] : 0.f) + a;
-      if (out1) out1[n] = (acc ? out1[n] : 0.f) + b;
-    } else {
-      ws[(int64_t)w0 * N + n] = a;
-      ws[(int64_t)(W + w0) * N + n] = b;
+  if (threadIdx.x < 64 && n < N && w0 < w1) {
+    float* const out[2] = {out0, out1};
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const float a = vy_colsum_slice_sum(red, s, c);
+      if (gridDim.y > 1) ws[s * slab_stride + (int64_t)w0 * ld + n] = a;
+      else if (out[s]) out[s][n] = (acc ? out[s][n] : 0.f) + a;
     }
   }
 }
 
 // out0/out1[n] (+)= the slice sums colsum_partials_kernel left in slab rows 0, rps, 2 rps, ... < W, in that order
-__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ ws, int W, int N,
-                                                            float* __restrict__ out0, float* __restrict__ out1,
+template <int S>
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ ws, int64_t slab_stride, int ld, int W,
+                                                            int N, float* __restrict__ out0, float* __restrict__ out1,
                                                             int rows_per_slice, int acc) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  float a = 0.f, b = 0.f;
+  float a[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) a[s] = 0.f;
   for (int w = 0; w < W; w += rows_per_slice) {
-    a += ws[(int64_t)w * N + n];
-    b += ws[(int64_t)(W + w) * N + n];
+#pragma unroll
+    for (int s = 0; s < S; ++s) a[s] += ws[s * slab_stride + (int64_t)w * ld + n];
   }
-  if (out0) out0[n] = (acc ? out0[n] : 0.f) + a;
-  if (out1) out1[n] = (acc ? out1[n] : 0.f) + b;
+  float* const out[2] = {out0, out1};
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+    if (out[s]) out[s][n] = (acc ? out[s][n] : 0.f) + a[s];
 }
 
 // ---- RoPE (standalone, in place) ------------------------------------------------------------
@@ -883,24 +868,21 @@ int ln_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, co
   VY_CHECK_LAUNCH("vy_layernorm_bwd");
   if (partial) return VY_OK;
   if (beta != 0.f && beta != 1.f) VY_FAIL(VY_ERR_ARG, "vy_layernorm_bwd: beta must be 0 or 1");
-  return vy_ln_colsum(ws, WB, (int)N, dgamma, dbeta, beta == 1.f, st);
+  return vy_colsum("vy_layernorm_bwd", ws, 2, (int64_t)WB * N, (int)N, WB, (int)N, vy_ln_colsum_slices(WB), dgamma, dbeta,
+                   beta == 1.f, st);
 }
 
 }  // namespace
 
-// internal: the column sums of a LayerNorm-backward slab as launches of their own (vy_layernorm_bwd, and the fp32 path
-// of vy_linear_wgrad_grouped_cs); the summation order is vy_ln_colsum_slices' (vy_common.h)
-int vy_ln_colsum(float* ws, int WB, int N, float* dgamma, float* dbeta, int acc, hipStream_t st) {
-  const int slices = vy_ln_colsum_slices(WB);
-  const int rps = (int)vy_cdiv(WB, slices);
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3((unsigned)vy_cdiv(N, 64), (unsigned)slices), dim3(256), 0, st, ws, WB,
-                     N, dgamma, dbeta, rps, acc);
-  VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum)");
-  if (slices > 1) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)vy_cdiv(N, 256)), dim3(256), 0, st, ws, WB, N, dgamma,
-                       dbeta, rps, acc);
-    VY_CHECK_LAUNCH("vy_layernorm_bwd(colsum finish)");
-  }
+int vy_colsum(const char* who, float* ws, int S, int64_t slab_stride, int ld, int W, int N, int slices, float* out0,
+              float* out1, int acc, hipStream_t st) {
+  const int rps = (int)vy_cdiv(W, slices);
+  auto go = [&](auto* kernel, dim3 grid) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ws, slab_stride, ld, W, N, out0, out1, rps, acc); };
+  go(S == 1 ? colsum_partials_kernel<1> : colsum_partials_kernel<2>, dim3((unsigned)vy_cdiv(N, 64), (unsigned)slices));
+  if (hipError_t e = hipGetLastError()) VY_FAIL(VY_ERR_LAUNCH, "%s(colsum): %s", who, hipGetErrorString(e));
+  if (slices == 1) return VY_OK;
+  go(S == 1 ? colsum_finish_kernel<1> : colsum_finish_kernel<2>, dim3((unsigned)vy_cdiv(N, 256)));
+  if (hipError_t e = hipGetLastError()) VY_FAIL(VY_ERR_LAUNCH, "%s(colsum finish): %s", who, hipGetErrorString(e));
   return VY_OK;
 }
 

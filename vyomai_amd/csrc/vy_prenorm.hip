@@ -137,48 +137,6 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(
   }
 }
 
-// column sums of the [W, N] slab, no atomics (dw is the same from run to run): grid = (column blocks of 64) x
-// (row slices); a block adds the rows of its slice in a fixed order (4 row groups through LDS).  With one slice it
-// writes dw itself (added to it when acc); with several it leaves its sum in the first slab row of its slice and
-// rms_colsum_finish_kernel adds the slices up in slice order (the scheme of the LayerNorm backward).
-__global__ __launch_bounds__(256) void rms_colsum_kernel(float* __restrict__ ws, int W, int N, float* __restrict__ out,
-                                                         int rows_per_slice, int acc) {
-  __shared__ float red[4][64];
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + c;
-  const int w0 = blockIdx.y * rows_per_slice, w1 = min(W, w0 + rows_per_slice);
-  float a = 0.f;
-  if (n < N) {
-    for (int wb = w0 + g; wb < w1; wb += 32) {
-      float av[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int w = wb + 4 * i;
-        av[i] = ws[(int64_t)(w < w1 ? w : wb) * N + n];
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (wb + 4 * i < w1) a += av[i];
-    }
-  }
-  red[g][c] = a;
-  __syncthreads();
-  if (g == 0 && n < N && w0 < w1) {
-    a = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-    if (gridDim.y == 1) out[n] = (acc ? out[n] : 0.f) + a;
-    else ws[(int64_t)w0 * N + n] = a;
-  }
-}
-
-__global__ __launch_bounds__(256) void rms_colsum_finish_kernel(const float* __restrict__ ws, int W, int N,
-                                                                float* __restrict__ out, int rows_per_slice, int acc) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  float a = 0.f;
-  for (int w = 0; w < W; w += rows_per_slice) a += ws[(int64_t)w * N + n];
-  out[n] = (acc ? out[n] : 0.f) + a;
-}
-
 template <typename T>
 int rms_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, const void* w, const void* add_to,
                      int64_t ldadd, void* dx, int64_t lddx, float* dw, float beta, float* ws, int64_t M, int64_t N,
@@ -198,18 +156,8 @@ int rms_bwd_dispatch(const void* dy, int64_t lddy, const void* x, int64_t ldx, c
   else RMS_GO(16, false);
 #undef RMS_GO
   VY_CHECK_LAUNCH("vy_rmsnorm_bwd");
-  const int acc = beta == 1.f;
-  const int slices = WB >= 64 ? 16 : 1;
-  const int rps = (int)vy_cdiv(WB, slices);
-  hipLaunchKernelGGL(rms_colsum_kernel, dim3((unsigned)vy_cdiv(N, 64), (unsigned)slices), dim3(256), 0, st, ws, WB, (int)N,
-                     dw, rps, acc);
-  VY_CHECK_LAUNCH("vy_rmsnorm_bwd(colsum)");
-  if (slices > 1) {
-    hipLaunchKernelGGL(rms_colsum_finish_kernel, dim3((unsigned)vy_cdiv(N, 256)), dim3(256), 0, st, ws, WB, (int)N, dw, rps,
-                       acc);
-    VY_CHECK_LAUNCH("vy_rmsnorm_bwd(colsum finish)");
-  }
-  return VY_OK;
+  // dw: the ordered column sum of the one [WB][N] slab (vy_colsum.h), sliced as the LayerNorm backward's
+  return vy_colsum("vy_rmsnorm_bwd", ws, 1, 0, (int)N, WB, (int)N, vy_ln_colsum_slices(WB), dw, nullptr, beta == 1.f, st);
 }
 
 // ---- gated activation backward ---------------------------------------------------------------

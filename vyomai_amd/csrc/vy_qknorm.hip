@@ -155,28 +155,6 @@ __global__ __launch_bounds__(256) void qknorm_bwd_kernel(T* __restrict__ dqkv, l
   }
 }
 
-// out[j] (+)= the sum of column j over the `rows` slab rows, in a fixed order: 4 row groups of a workgroup take every
-// fourth row, then the four are added in group order.  Columns [0, dh) are dq_scale, [dh, 2 dh) dk_scale.
-__global__ __launch_bounds__(256) void qknorm_colsum_kernel(const float* __restrict__ ws, int rows, int dh,
-                                                            float* __restrict__ dq_scale, float* __restrict__ dk_scale,
-                                                            int acc) {
-  __shared__ float red[4][64];
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + c, N = 2 * dh;
-  float a = 0.f;
-  if (j < N) {
-#pragma unroll 8
-    for (int w = g; w < rows; w += 4) a += ws[(long long)w * N + j];
-  }
-  red[g][c] = a;
-  __syncthreads();
-  if (g == 0 && j < N) {
-    a = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    float* out = j < dh ? dq_scale + j : dk_scale + (j - dh);
-    *out = (acc ? *out : 0.f) + a;
-  }
-}
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int lane_log2(int dh) {                               // lanes per (token, head): dh / 8 rounded up to a power of two
@@ -281,8 +259,7 @@ extern "C" int vy_qknorm_bwd(void* dqkv, int64_t ldd, const void* qkv, int64_t l
     hipLaunchKernelGGL(qknorm_bwd_kernel<float>, grid, block, 0, st, (float*)dqkv, ldd, (const float*)qkv, ld, q_scale,
                        k_scale, eps, inv_dh, ws, units, iters, lg, h, hk, dh);
   VY_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(qknorm_colsum_kernel, dim3((unsigned)vy_cdiv(2 * dh, 64)), dim3(256), 0, st, ws, (int)blocks, dh, dq_scale,
-                     dk_scale, (int)(beta == 1.f));
-  VY_CHECK_LAUNCH("vy_qknorm_bwd(colsum)");
-  return VY_OK;
+  // the slab's columns [0, dh) are dq_scale's partials, [dh, 2 dh) dk_scale's: two slabs of row length 2 dh, dh apart,
+  // summed in the order of vy_colsum.h -- in ONE slice whatever the row count
+  return vy_colsum(who, ws, 2, dh, 2 * dh, (int)blocks, dh, 1, dq_scale, dk_scale, beta == 1.f, st);
 }
