@@ -721,6 +721,52 @@ int vy_lora_expand(void* y, int64_t ldy, const void* u, int64_t ldu, const void*
                    const int32_t* tiles, int64_t n_tiles, int64_t T, int64_t N, int64_t r_pad, int64_t slots,
                    int64_t bound0, int64_t bound1, int dtype, void* stream);
 
+/* vy_lora_expand_epi: vy_lora_expand with the epilogue of the GEMM it follows, for LoRA fine-tuning of the post-LN
+ *   encoder block (vyomai_amd/encoder_lora_train.py).  The reference wraps the nn.Linear itself (layers/adapters.py:21-47,
+ *   LoraLinear.forward; Examples/adapters.ipynb wraps query / value / attention.output.dense / intermediate.dense /
+ *   output.dense), so the adapter's term sits INSIDE whatever follows the linear: the activation of FeedForward
+ *   (layers/ffn.py:34-36) and the dropout of AttentionSelfOutput and FeedForward (layers/attention.py:69-72,
+ *   layers/ffn.py:37-40).  z (T, N) is the base GEMM's output with its bias and nothing else, in `dtype`; per element
+ *     v = fmaf(alpha[slot], sum_{j < r_pad} u[t, part(n) * r_pad + j] * B[slot][n, j], (float)z[t, n])      fp32, not rounded
+ *   VY_LORA_EPI_ACT:      out = act(v), pre = act'(v) -- every vy_act but VY_ACT_NONE, the exact (not the reduced-cost)
+ *     functions of the GEMM epilogue, so pre is what vy_linear_dgrad takes with pre= and act | 0x100.
+ *   VY_LORA_EPI_DROP_RES: out = keep(t, n) ? v * scale + res[t, n] : res[t, n], the mask of vy_dropout for the same
+ *     (p_drop, seed, offset) with t the row of the (T, N) matrix; p_drop == 0 is out = v + res.  0 <= p_drop < 1.
+ *   VY_LORA_EPI_MUL:      out = v * pre[t, n], pre read-only: the backward's twin of ACT.  With z the base dgrad of the
+ *     GEMM behind the activation, u = dY @ B and B := the transposed stacked A (r_pad := R, no boundaries), out is the
+ *     gradient of the pre-activation, (dY W + alpha (dY B) A) * act'(v): the adapter's term has to be inside the product.
+ *   out may be z (every element is read and written by one lane); pre and res may not overlap out.  Each result is
+ *   rounded to `dtype` once.  Tiles, boundaries, skipped tiles, shape limits and alignment: vy_lora_expand's, with z, out,
+ *   pre and res in the place of y.  pre is null in DROP_RES mode, res in the others.  VY_ERR_ARG: an unknown mode or act, a
+ *   missing pre / res, p_drop outside [0, 1), and everything vy_lora_expand refuses. */
+enum { VY_LORA_EPI_ACT = 0, VY_LORA_EPI_DROP_RES = 1, VY_LORA_EPI_MUL = 2 };
+int vy_lora_expand_epi(const void* z, int64_t ldz, void* out, int64_t ldo, void* pre, int64_t ldp, const void* res,
+                       int64_t ldr, const void* u, int64_t ldu, const void* B, const float* alpha, const int32_t* tiles,
+                       int64_t n_tiles, int64_t T, int64_t N, int64_t r_pad, int64_t slots, int64_t bound0,
+                       int64_t bound1, int mode, int act, float p_drop, uint64_t seed, uint64_t offset, int dtype,
+                       void* stream);
+
+/* vy_cls_head_fwd / vy_cls_head_bwd: the sequence-classification head of Examples/adapters.ipynb and
+ *   vyom-ai-classification.ipynb (ClinicModel: hidden[:, 0, :] -> nn.Linear(hidden, n_classes) -> CrossEntropyLoss).
+ *   h: the encoder's hidden state (B, L, d) in `dtype`, ldb = the stride between sequences (L * d); only row 0 of each
+ *   sequence is read.  w (C, d) contiguous and bias (C, nullable) in `dtype`.
+ * fwd: logits[b, c] (fp32, (B, C) contiguous) = h[b, 0, :] . w[c] + bias[c], fp32 accumulation.  With labels (int64,
+ *      B): lse[b] (fp32), *loss = sum_b (lse[b] - logits[b, label_b]) / count and, IN PLACE, logits <- dlogits =
+ *      (softmax - onehot) / count, count = the rows whose label lies in [0, C) (at least 1).  A label outside [0, C) is
+ *      never dereferenced and never clamped: its row adds no loss, gets a zero gradient and sets *err_flag = 1 (nullable;
+ *      the flag of the vy_xent entry points).
+ * bwd: dw[c, :] = g * sum_b dlogits[b, c] h[b, 0, :], db[c] = g * sum_b dlogits[b, c] (fp32, contiguous, db nullable;
+ *      added to what is there when accumulate == 1), dh (B, L, d) contiguous in `dtype`: dh[b, 0, :] = g * dlogits[b] @ w
+ *      and every other row zero, written by the same launch.  g = *gscale (device fp32, null = 1).
+ * Determinism: sums over b and over c run in ascending order, the d-sum of a logit in one wave's shuffle tree; no
+ *      atomics: two calls give the same bits.  1 <= B <= 8192, C >= 1, d % 8 == 0, ldb % 8 == 0, h / w / dh 16-byte
+ *      aligned.  VY_ERR_ARG otherwise, for a null operand and an unknown dtype. */
+int vy_cls_head_fwd(const void* h, int64_t ldb, const void* w, const void* bias, float* logits, const int64_t* labels,
+                    float* lse, float* loss, int32_t* err_flag, int64_t B, int64_t C, int64_t d, int dtype, void* stream);
+int vy_cls_head_bwd(const void* h, int64_t ldb, const void* w, const float* dlogits, const float* gscale, void* dh,
+                    float* dw, float* db, int accumulate, int64_t B, int64_t L, int64_t C, int64_t d, int dtype,
+                    void* stream);
+
 /* vy_lora_wgrad: both low-rank weight gradients of one GEMM group of LoRA fine-tuning (vyomai_amd/lora_train.py), for
  *   the parts p of a packed projection (part(n) and bound0 / bound1 as in vy_lora_expand; a boundary that is not used
  *   is N, so parts = 1 + (bound0 < N) + (bound1 < N) <= 3; col0_p is the part's first column):

@@ -5,7 +5,7 @@ path; the math runs in hand-written gfx950 HIP kernels behind the C ABI in inclu
 """
 from .utils import EncoderConfig  # noqa: F401
 from .layers.kv_cache import DynamicCache, StaticCache, StaticCacheOne, DynamicCacheOne  # noqa: F401
-from .models.encoder import EncoderModel, EncoderForMaskedLM  # noqa: F401
+from .models.encoder import EncoderModel, EncoderForMaskedLM, EncoderForSequenceClassification  # noqa: F401
 from .models.decoder import DecoderModel  # noqa: F401
 from .models.electra import Discriminator, ElectraModel, ElectraLoss  # noqa: F401
 from . import pretraining  # noqa: F401

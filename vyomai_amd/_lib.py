@@ -18,6 +18,7 @@ ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH = 0, 1, 2
 # the reference's other hidden_act choices (vy_act in include/vyom_hip.h; leaky_relu: slope 0.01)
 ACT_SILU, ACT_TANH, ACT_SIGMOID, ACT_RELU6, ACT_LEAKY_RELU = 3, 4, 5, 6, 7
 ACT_SAVE_DERIV = 0x100   # saved tensor = act'(pre) instead of pre (include/vyom_hip.h)
+LORA_EPI_ACT, LORA_EPI_DROP_RES, LORA_EPI_MUL = 0, 1, 2   # vy_lora_expand_epi's modes
 MASK_NONE, MASK_CAUSAL, MASK_KEYPAD, MASK_ADDITIVE = 0, 1, 2, 4
 
 _p, _i64, _i, _f, _u64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64
@@ -95,6 +96,10 @@ PROTOTYPES = {
     "vy_spec_verify": [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "vy_lora_shrink": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "vy_lora_expand": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _p],
+    "vy_lora_expand_epi": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                           _i64, _i64, _i, _i, _f, _u64, _u64, _i, _p],
+    "vy_cls_head_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _p],
+    "vy_cls_head_bwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _i, _p],
     "vy_lora_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64,
                       _i64, _i64, _i64, _f, _i, _i, _p],
     "vy_dora_compose": [_p, _i, _i, _p],

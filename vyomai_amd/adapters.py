@@ -5,7 +5,8 @@ include/vyom_hip.h).  serving.ContinuousBatchEngine(..., adapters=store) and add
 per request.  DoRA (which renormalises the whole weight, so it is no additive per-request delta) is refused there: a
 DoRA model is served merged.  The second half of this file is the training side: the reference's LoraLinear and
 DoraLinear wrappers, add_lora / lora_state_dict / merge_lora / disable_lora and their DoRA counterparts for
-ModelForCausalLM (the forward and backward of a wrapped layer: lora_train.py, dora_train.py).
+ModelForCausalLM (the forward and backward of a wrapped layer: lora_train.py, dora_train.py); the LoRA functions also
+take an EncoderModel or a module holding one (encoder_lora_train.py).
 
 Layout.  Per layer and projection group -- qkv, o, gate_up, down: the four GEMMs of forward_paged -- the store keeps
 A (slots, parts * r_pad, K) and B (slots, N, r_pad) in the compute dtype, r_pad = max_rank rounded up to 32.  A packed
@@ -27,6 +28,12 @@ _CAUSAL_LM = {"qkv": ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"
 _QWEN3 = {"qkv": ("att.W_query", "att.W_key", "att.W_value"), "o": ("att.out_proj",), "gate_up": ("ff.fc1", "ff.fc2"),
           "down": ("ff.fc3",)}
 GROUPS = ("qkv", "o", "gate_up", "down")
+# the post-LN encoder block (EncoderModel.all_layer[l]; training only: encoder_lora_train.py).  The reference's names
+# are BERT's -- attention.output.dense, intermediate.dense, output.dense -- and these are this package's for the same
+# linears.
+_ENCODER = {"qkv": ("attention.query", "attention.key", "attention.value"), "o": ("attention.out.dense",),
+            "ffn1": ("feed_forward.intermediate",), "ffn2": ("feed_forward.out",)}
+ENCODER_GROUPS = ("qkv", "o", "ffn1", "ffn2")
 
 
 def _layers_of(model) -> Tuple[str, list, dict]:
@@ -191,6 +198,9 @@ def layer_delta(metadata: dict, layer: int):
 
 MAX_TRAIN_RANK = 64      # vy_lora_wgrad: r_pad is 32 or 64
 ALL_TARGETS = tuple(p for g in GROUPS for p in _CAUSAL_LM[g])
+ENCODER_TARGETS = tuple(p for g in ENCODER_GROUPS for p in _ENCODER[g])
+# Examples/adapters.ipynb wraps query, value, attention.output.dense, intermediate.dense and output.dense: key is off
+NOTEBOOK_ENCODER_TARGETS = tuple(p for p in ENCODER_TARGETS if p != "attention.key")
 
 
 class LoraLinear(torch.nn.Module):
@@ -241,39 +251,77 @@ def _causal_lm(model, what: str):
     return list(model.model.layers[: model.config.num_hidden_layers])
 
 
+class _Family:
+    """What add_lora and its companions need to know about a model: the key prefix of layer l ({} for l), the layers,
+    group -> part paths, the groups in order and every target path."""
+
+    def __init__(self, prefix, layers, table, groups):
+        self.prefix, self.layers, self.table, self.groups = prefix, layers, table, groups
+        self.targets = tuple(p for g in groups for p in table[g])
+        self.encoder = table is _ENCODER
+        self.default = NOTEBOOK_ENCODER_TARGETS if self.encoder else self.targets
+
+
+def _family(model, what: str) -> _Family:
+    """ModelForCausalLM; an EncoderModel, or a module that holds one as a direct child (EncoderForSequenceClassification
+    .model, EncoderForMaskedLM.encoder).  Everything else is refused."""
+    from .models.custom_transformer import ModelForCausalLM
+    from .models.encoder import EncoderModel
+    if isinstance(model, ModelForCausalLM):
+        return _Family("model.layers.{}.", _causal_lm(model, what), _CAUSAL_LM, GROUPS)
+    if isinstance(model, EncoderModel):
+        return _Family("all_layer.{}.", list(model.all_layer), _ENCODER, ENCODER_GROUPS)
+    if isinstance(model, torch.nn.Module):
+        held = [(n, c) for n, c in model.named_children() if isinstance(c, EncoderModel)]
+        if len(held) == 1:
+            return _Family(held[0][0] + ".all_layer.{}.", list(held[0][1].all_layer), _ENCODER, ENCODER_GROUPS)
+    raise ValueError(f"{what} prepares a ModelForCausalLM, not a {type(model).__name__}: only its pre-norm blocks and the "
+                     "post-LN blocks of an EncoderModel (alone, or held by EncoderForSequenceClassification / "
+                     "EncoderForMaskedLM) have a training path through adapters.  For a DecoderModel, a vision encoder or "
+                     "an encoder-decoder, fold a trained update into the weights (W + alpha * lora_b @ lora_a) and run "
+                     "the plain model")
+
+
 def _wrapped(model, cls=None, what: str = "LoRA"):
     """-> [(owner module, attribute, key path, wrapper)] of every projection wrapped in a `cls` (LoraLinear), in layer
     order."""
     cls = LoraLinear if cls is None else cls
+    fam = _family(model, what)
     out = []
-    for l, layer in enumerate(_causal_lm(model, what)):
-        for path in ALL_TARGETS:
-            owner_name, attr = path.split(".")
-            owner = getattr(layer, owner_name)
+    for l, layer in enumerate(fam.layers):
+        for path in fam.targets:
+            owner_path, _, attr = path.rpartition(".")
+            owner = functools.reduce(getattr, owner_path.split("."), layer)
             m = getattr(owner, attr)
             if isinstance(m, cls):
-                out.append((owner, attr, f"model.layers.{l}.{path}", m))
+                out.append((owner, attr, fam.prefix.format(l) + path, m))
     return out
 
 
-def add_lora(model, rank: int = 32, alpha=1.0, targets=ALL_TARGETS):
-    """Wrap the projections `targets` (paths of _CAUSAL_LM: "self_attn.q_proj", ..., "mlp.down_proj"; any subset) of
-    every layer of a ModelForCausalLM in a LoraLinear and freeze every other parameter, as Examples/adapters.ipynb does
-    -> the model.  ValueError: another model class, an unknown or empty target list, a model that is already wrapped."""
-    layers = _causal_lm(model, "add_lora")
-    targets = tuple(targets)
-    unknown = [t for t in targets if t not in ALL_TARGETS]
+def add_lora(model, rank: int = 32, alpha=1.0, targets=None):
+    """Wrap the projections `targets` of every layer in a LoraLinear and freeze every parameter the model has at that
+    moment, as Examples/adapters.ipynb does -> the model.  A ModelForCausalLM takes the paths of _CAUSAL_LM
+    ("self_attn.q_proj", ..., "mlp.down_proj"; default: all seven); an EncoderModel -- or a module holding one:
+    EncoderForSequenceClassification, EncoderForMaskedLM -- those of _ENCODER ("attention.query", "attention.key",
+    "attention.value", "attention.out.dense", "feed_forward.intermediate", "feed_forward.out"; default: the notebook's
+    five, key off).  Any non-empty subset.  What is created afterwards -- the notebook's classification head -- stays
+    trainable; add_lora(classifier.model) keeps an existing head trainable.  ValueError: another model class, an unknown
+    or empty target list, a model that is already wrapped."""
+    fam = _family(model, "add_lora")
+    layers = fam.layers
+    targets = fam.default if targets is None else tuple(targets)
+    unknown = [t for t in targets if t not in fam.targets]
     if unknown or not targets or len(set(targets)) != len(targets):
-        raise ValueError(f"targets {list(targets)} must be a non-empty subset of {list(ALL_TARGETS)} without repeats")
+        raise ValueError(f"targets {list(targets)} must be a non-empty subset of {list(fam.targets)} without repeats")
     if _wrapped(model):
         raise ValueError("the model already carries LoRA adapters: merge_lora(model) first")
     if _wrapped(model, DoraLinear):
         raise ValueError("the model carries DoRA adapters, and a layer runs one kind: merge_dora(model) first")
     if int(rank) != rank or not 1 <= rank <= MAX_TRAIN_RANK:
         raise ValueError(f"rank {rank} must be an integer from 1 to {MAX_TRAIN_RANK}")
-    for g in GROUPS:      # (everything is checked before anything is changed)
-        shapes = [functools.reduce(getattr, p.split("."), layers[0]).weight.shape for p in _CAUSAL_LM[g]]
-        if not any(p in targets for p in _CAUSAL_LM[g]):
+    for g in fam.groups:      # (everything is checked before anything is changed)
+        shapes = [functools.reduce(getattr, p.split("."), layers[0]).weight.shape for p in fam.table[g]]
+        if not any(p in targets for p in fam.table[g]):
             continue
         if sum(s[0] for s in shapes) % 32 or any(s[0] % 16 or s[1] % 32 for s in shapes):
             raise ValueError(f"the packed {g} projection has parts {[tuple(s) for s in shapes]}: in_features must be a "
@@ -283,8 +331,8 @@ def add_lora(model, rank: int = 32, alpha=1.0, targets=ALL_TARGETS):
         p.requires_grad_(False)
     for layer in layers:
         for path in targets:
-            owner_name, attr = path.split(".")
-            owner = getattr(layer, owner_name)
+            owner_path, _, attr = path.rpartition(".")
+            owner = functools.reduce(getattr, owner_path.split("."), layer)
             setattr(owner, attr, LoraLinear(getattr(owner, attr), rank=rank, alpha=alpha))
     return model
 

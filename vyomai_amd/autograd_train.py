@@ -506,8 +506,9 @@ def _project_qkv(n, mod, am: _AttnArgs, qk=None, delta=None, w=None):
         ops.linear(n, sw, sb, out=qkv)
         delta("qkv", qkv, n)
         q, k, v = _qkv_heads(qkv, h, hk, dh)
-        ops.rope_(q, am.cos, am.sin, am.pos0)
-        ops.rope_(k, am.cos, am.sin, am.pos0)
+        if am.cos is not None:       # (an encoder with absolute or sinusoidal positions has no rotation)
+            ops.rope_(q, am.cos, am.sin, am.pos0)
+            ops.rope_(k, am.cos, am.sin, am.pos0)
         return q, k, v, qkv
     q = torch.empty((B, h, L, dh), dtype=dt, device=dev)
     k = torch.empty((B, hk, L, dh), dtype=dt, device=dev)
@@ -926,6 +927,66 @@ class BceHeadLogitsFn(torch.autograd.Function):
         db = torch.empty(b.shape, dtype=torch.float32, device=dev)
         dh = ops.bce_head_bwd(hidden, ws, z, y, live8, _one(dev), _one(dev), dw.view(-1), db, False)
         return dh, dw.to(w.dtype), db.to(b.dtype)
+
+
+def _cls_head_backward(hidden, w, b, dlogits, gs):
+    """-> (dh, dw, db) of the classification head to return to autograd (None where accumulated in place)."""
+    ws = _shadow(w, hidden.dtype)
+    if not w.requires_grad and (b is None or not b.requires_grad):     # a frozen head: only dh is read
+        scratch = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        return ops.cls_head_bwd(hidden, ws, dlogits, gs, scratch, None, False), None, None
+    if _direct(w) and (b is None or _direct(b)):
+        dh = ops.cls_head_bwd(hidden, ws, dlogits, gs, w.grad, None if b is None else b.grad, True)
+        _notify(w, b)
+        return dh, None, None
+    dw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+    db = None if b is None else torch.empty(b.shape, dtype=torch.float32, device=w.device)
+    dh = ops.cls_head_bwd(hidden, ws, dlogits, gs, dw, db, False)
+    return dh, dw.to(w.dtype), None if b is None else db.to(b.dtype)
+
+
+class ClsHeadLossFn(torch.autograd.Function):
+    """The sequence-classification head and its loss: mean CrossEntropyLoss of hidden[:, 0, :] @ W^T + b against the
+    labels (Examples/adapters.ipynb and vyom-ai-classification.ipynb, ClinicModel) in vy_cls_head_fwd / vy_cls_head_bwd:
+    no gather of the first rows, no (B, L, d) zero-fill pass, no atomics.  -> the loss (fp32 scalar)."""
+
+    @staticmethod
+    def forward(ctx, hidden, labels, w, b, err_flag):
+        _require_bf16(hidden)
+        dt = hidden.dtype
+        hidden = hidden.contiguous()
+        dlogits, _, loss = ops.cls_head_fwd(hidden, _shadow(w, dt), _shadow(b, dt), labels.reshape(-1).contiguous(),
+                                            err_flag)
+        ctx.save_for_backward(hidden, dlogits)
+        ctx.params = (w, b)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        hidden, dlogits = ctx.saved_tensors
+        w, b = ctx.params
+        gs = gout.detach().to(torch.float32).reshape(1).contiguous()
+        dh, dw, db = _cls_head_backward(hidden, w, b, dlogits, gs)
+        return dh, None, dw, db, None
+
+
+class ClsHeadLogitsFn(torch.autograd.Function):
+    """logits (B, C) fp32 alone (ClinicModel.forward; the notebook's loop takes its own loss of them)."""
+
+    @staticmethod
+    def forward(ctx, hidden, w, b):
+        _require_bf16(hidden)
+        hidden = hidden.contiguous()
+        ctx.save_for_backward(hidden)
+        ctx.params = (w, b)
+        return ops.cls_head_fwd(hidden, _shadow(w, hidden.dtype), _shadow(b, hidden.dtype))
+
+    @staticmethod
+    def backward(ctx, gz):
+        (hidden,) = ctx.saved_tensors
+        w, b = ctx.params
+        dh, dw, db = _cls_head_backward(hidden, w, b, gz.to(torch.float32).contiguous(), None)
+        return dh, dw, db
 
 
 _ONES = {}

@@ -3,6 +3,8 @@
 // (reference layers/adapters.py LoraLinear.forward: linear(x) + scale * F.linear(F.linear(x, lora_a), lora_b)).
 //   vy_lora_shrink   u[t, 0:R] = x[t, 0:K] @ A[slot].T          one workgroup per (tile, 16 columns of R)
 //   vy_lora_expand   y[t, n] += alpha[slot] * u[t, part(n)] . B[slot][n]   one wave per (tile, 16 columns of N)
+//   vy_lora_expand_epi   the same tile, then the activation or the dropout + residual of the GEMM it follows
+//                        (encoder LoRA fine-tuning: the reference applies the adapter before either)
 // The rule (tiles, the rounding of u, what is skipped): include/vyom_hip.h.
 //
 // Both are 16 x 16 MFMA tiles whose operands come straight from global memory: the weight rows (A[slot] / B[slot]) are
@@ -110,25 +112,25 @@ __global__ __launch_bounds__(64 * LW) void lora_shrink_kernel(const T* __restric
   }
 }
 
-// grid (n_tiles, ceil(N / 16 / LW)); wave w of a workgroup owns columns 16 (LW blockIdx.y + w) .. + 15
+// The expand tile both expand kernels share: wave w of a workgroup owns columns 16 (LW blockIdx.y + w) .. + 15 of the
+// tile's rows.  false: nothing to do (a skipped tile, columns past N); otherwise acc holds the four sums of row
+// tl.row0 + (lane & 15), columns n0 + 4 (lane >> 4) + reg -- zeros in a dead lane (live false), which stores nothing.
 template <typename T>
-__global__ __launch_bounds__(64 * LW) void lora_expand_kernel(T* __restrict__ y, int64_t ldy, const T* __restrict__ u,
-                                                              int64_t ldu, const T* __restrict__ B,
-                                                              const float* __restrict__ alpha,
-                                                              const int32_t* __restrict__ tiles, int64_t rows, int N,
-                                                              int r_pad, int slots, int bound0, int bound1) {
+__device__ __forceinline__ bool lora_expand_tile(const T* __restrict__ u, int64_t ldu, const T* __restrict__ B,
+                                                 const int32_t* __restrict__ tiles, int64_t rows, int N, int r_pad,
+                                                 int slots, int bound0, int bound1, LoraTile& tl, int& n0, bool& live,
+                                                 f32x4& acc) {
   using F = LoraFrag<T>;
-  LoraTile tl;
-  if (!lora_tile(tiles, blockIdx.x, rows, slots, tl)) return;
+  if (!lora_tile(tiles, blockIdx.x, rows, slots, tl)) return false;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = (blockIdx.y * LW + wave) * 16;
-  if (n0 >= N) return;                                               // (no barrier in this kernel)
+  n0 = (blockIdx.y * LW + wave) * 16;
+  if (n0 >= N) return false;                                         // (no barrier in these kernels)
   const int r = lane & 15, kq = (lane >> 4) * F::VEC;
-  const bool live = r < tl.nrows;
+  live = r < tl.nrows;
   const int part = (n0 >= bound0) + (n0 >= bound1);                  // (boundaries are multiples of 16: one part a wave)
   const T* wrow = B + ((int64_t)tl.slot * N + n0 + r) * r_pad + kq;
   const T* urow = u + (int64_t)(tl.row0 + (live ? r : 0)) * ldu + (int64_t)part * r_pad + kq;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  acc = f32x4{0.f, 0.f, 0.f, 0.f};
   typename F::V zero;
 #pragma unroll
   for (int e = 0; e < F::VEC; ++e) zero[e] = (T)0.f;
@@ -138,13 +140,92 @@ __global__ __launch_bounds__(64 * LW) void lora_expand_kernel(T* __restrict__ y,
     if (!live) a = zero;
     acc = F::mma(w, a, acc);
   }
+  return true;
+}
+
+// grid (n_tiles, ceil(N / 16 / LW))
+template <typename T>
+__global__ __launch_bounds__(64 * LW) void lora_expand_kernel(T* __restrict__ y, int64_t ldy, const T* __restrict__ u,
+                                                              int64_t ldu, const T* __restrict__ B,
+                                                              const float* __restrict__ alpha,
+                                                              const int32_t* __restrict__ tiles, int64_t rows, int N,
+                                                              int r_pad, int slots, int bound0, int bound1) {
+  using F = LoraFrag<T>;
+  LoraTile tl;
+  int n0;
+  bool live;
+  f32x4 acc;
+  if (!lora_expand_tile(u, ldu, B, tiles, rows, N, r_pad, slots, bound0, bound1, tl, n0, live, acc)) return;
   if (live) {
+    const int lane = threadIdx.x & 63, r = lane & 15;
     const float al = alpha[tl.slot];
     typename F::Out* dst = reinterpret_cast<typename F::Out*>(y + (int64_t)(tl.row0 + r) * ldy + n0 + (lane >> 4) * 4);
     f32x4 v = F::unpack(*dst);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaf(al, acc[e], v[e]);
     *dst = F::pack(v);
+  }
+}
+
+// vy_lora_expand_epi: the expand tile with the epilogue of the GEMM it follows.  v = fmaf(alpha, acc, z) in fp32 is
+// never rounded before the epilogue.  z and out may be the same buffer (every element is read and written by one
+// lane), so neither is __restrict__.
+//   MODE VY_LORA_EPI_ACT       out = act(v), pre = act'(v)            (ACT: a vy_act or VY_ACT_RUNTIME with `code`)
+//   MODE VY_LORA_EPI_DROP_RES  out = keep(row, col) ? v * scale + res : res; thr == 0: v + res
+//   MODE VY_LORA_EPI_MUL       out = v * pre                          (the backward's twin of ACT: pre is read)
+// A lane's four columns are one half of an 8-column Philox chunk: the lot of column c is lot c & 7 of chunk c >> 3.
+template <typename T, int MODE, int ACT>
+__global__ __launch_bounds__(64 * LW) void lora_expand_epi_kernel(const T* z, int64_t ldz, T* out, int64_t ldo, T* pre,
+                                                                  int64_t ldp, const T* res, int64_t ldr,
+                                                                  const T* __restrict__ u, int64_t ldu,
+                                                                  const T* __restrict__ B, const float* __restrict__ alpha,
+                                                                  const int32_t* __restrict__ tiles, int64_t rows, int N,
+                                                                  int r_pad, int slots, int bound0, int bound1, int code,
+                                                                  VyDrop d) {
+  using F = LoraFrag<T>;
+  LoraTile tl;
+  int n0;
+  bool live;
+  f32x4 acc;
+  if (!lora_expand_tile(u, ldu, B, tiles, rows, N, r_pad, slots, bound0, bound1, tl, n0, live, acc)) return;
+  if (!live) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = tl.row0 + (lane & 15);
+  const int col = n0 + (lane >> 4) * 4;
+  const float al = alpha[tl.slot];
+  f32x4 v = F::unpack(*reinterpret_cast<const typename F::Out*>(z + row * ldz + col));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = fmaf(al, acc[e], v[e]);
+  if constexpr (MODE == VY_LORA_EPI_ACT) {
+    f32x4 h, g;
+    vy_act_dispatch<ACT>(code, [&](auto a) {
+      constexpr int A = decltype(a)::value;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        h[e] = vy_act_fwd<A>(v[e]);
+        g[e] = vy_act_grad<A>(v[e]);
+      }
+    });
+    *reinterpret_cast<typename F::Out*>(out + row * ldo + col) = F::pack(h);
+    *reinterpret_cast<typename F::Out*>(pre + row * ldp + col) = F::pack(g);
+  } else if constexpr (MODE == VY_LORA_EPI_MUL) {
+    const f32x4 g = F::unpack(*reinterpret_cast<const typename F::Out*>(pre + row * ldp + col));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] *= g[e];
+    *reinterpret_cast<typename F::Out*>(out + row * ldo + col) = F::pack(v);
+  } else {
+    const f32x4 rs = F::unpack(*reinterpret_cast<const typename F::Out*>(res + row * ldr + col));
+    f32x4 s;
+    if (d.thr == 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = v[e] + rs[e];
+    } else {
+      uint32_t lots[4];
+      vy_drop_lots(d, row, col >> 3, lots);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = vy_drop_keep(d, lots, (col + e) & 7) ? v[e] * d.scale + rs[e] : rs[e];
+    }
+    *reinterpret_cast<typename F::Out*>(out + row * ldo + col) = F::pack(s);
   }
 }
 
@@ -215,4 +296,77 @@ extern "C" int vy_lora_expand(void* y, int64_t ldy, const void* u, int64_t ldu, 
                        (const float*)B, alpha, tiles, T, (int)N, (int)r_pad, (int)slots, (int)bound0, (int)bound1);
   VY_CHECK_LAUNCH("vy_lora_expand");
   return VY_OK;
+}
+
+namespace {
+
+template <typename T>
+int lora_expand_epi_launch(const void* z, int64_t ldz, void* out, int64_t ldo, void* pre, int64_t ldp, const void* res,
+                           int64_t ldr, const void* u, int64_t ldu, const void* B, const float* alpha,
+                           const int32_t* tiles, dim3 grid, int64_t T_, int N, int r_pad, int slots, int bound0, int bound1,
+                           int mode, int act, const VyDrop& d, hipStream_t st) {
+#define EPI_GO(MODE, ACT)                                                                                              \
+  hipLaunchKernelGGL((lora_expand_epi_kernel<T, MODE, ACT>), grid, dim3(64 * LW), 0, st, (const T*)z, ldz, (T*)out, ldo, \
+                     (T*)pre, ldp, (const T*)res, ldr, (const T*)u, ldu, (const T*)B, alpha, tiles, T_, N, r_pad, slots,  \
+                     bound0, bound1, act, d)
+  if (mode == VY_LORA_EPI_DROP_RES) EPI_GO(VY_LORA_EPI_DROP_RES, VY_ACT_NONE);
+  else if (mode == VY_LORA_EPI_MUL) EPI_GO(VY_LORA_EPI_MUL, VY_ACT_NONE);
+  else if (act == VY_ACT_GELU_ERF) EPI_GO(VY_LORA_EPI_ACT, VY_ACT_GELU_ERF);
+  else if (act == VY_ACT_GELU_TANH) EPI_GO(VY_LORA_EPI_ACT, VY_ACT_GELU_TANH);
+  else EPI_GO(VY_LORA_EPI_ACT, VY_ACT_RUNTIME);
+#undef EPI_GO
+  VY_CHECK_LAUNCH("vy_lora_expand_epi");
+  return VY_OK;
+}
+
+}  // namespace
+
+extern "C" int vy_lora_expand_epi(const void* z, int64_t ldz, void* out, int64_t ldo, void* pre, int64_t ldp,
+                                  const void* res, int64_t ldr, const void* u, int64_t ldu, const void* B,
+                                  const float* alpha, const int32_t* tiles, int64_t n_tiles, int64_t T, int64_t N,
+                                  int64_t r_pad, int64_t slots, int64_t bound0, int64_t bound1, int mode, int act,
+                                  float p_drop, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  if (n_tiles == 0) return VY_OK;
+  if (!z || !out || !u || !B || !alpha || !tiles) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: null operand");
+  if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: bad dtype %d", dtype);
+  if (mode == VY_LORA_EPI_ACT) {
+    if (act != VY_ACT_GELU_ERF && act != VY_ACT_GELU_TANH && !vy_act_is_runtime(act))
+      VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: ACT mode takes every vy_act but VY_ACT_NONE, got %d", act);
+    if (!pre || ldp < N) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: ACT mode writes pre (ldp %lld)", (long long)ldp);
+  } else if (mode == VY_LORA_EPI_DROP_RES) {
+    if (!res || ldr < N) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: DROP_RES mode reads res (ldr %lld)", (long long)ldr);
+    if (!(p_drop >= 0.f && p_drop < 1.f)) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: p_drop=%g outside [0, 1)", (double)p_drop);
+  } else if (mode == VY_LORA_EPI_MUL) {
+    if (!pre || ldp < N) VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: MUL mode reads pre (ldp %lld)", (long long)ldp);
+  } else {
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: bad mode %d", mode);
+  }
+  if (n_tiles < 0 || n_tiles > INT32_MAX || T <= 0 || T > INT32_MAX || slots <= 0 || slots > INT32_MAX)
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: bad shape (tiles %lld, T %lld, slots %lld)", (long long)n_tiles, (long long)T,
+            (long long)slots);
+  if (N <= 0 || N % 16 || N > INT32_MAX || vy_cdiv(N, 16 * LW) > 65535 || r_pad <= 0 || r_pad % 32 || r_pad > INT32_MAX ||
+      ldz < N || ldo < N)
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: bad shape (N %lld must be a multiple of 16, r_pad %lld of 32, ldz %lld, ldo %lld)",
+            (long long)N, (long long)r_pad, (long long)ldz, (long long)ldo);
+  if (bound0 <= 0 || bound0 > N || bound1 < bound0 || bound1 > N || bound0 % 16 || bound1 % 16)
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: boundaries %lld, %lld must be multiples of 16 with 0 < b0 <= b1 <= N = %lld",
+            (long long)bound0, (long long)bound1, (long long)N);
+  const int64_t parts = 1 + (bound0 < N) + (bound1 < N);
+  if (ldu < parts * r_pad)
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: ldu %lld is below %lld parts of r_pad %lld", (long long)ldu, (long long)parts,
+            (long long)r_pad);
+  const int out_bytes = dtype == VY_BF16 ? 8 : 16;
+  if (!lora_aligned(u, ldu, dtype, 16) || !lora_aligned(B, r_pad, dtype, 16) || !lora_aligned(z, ldz, dtype, out_bytes) ||
+      !lora_aligned(out, ldo, dtype, out_bytes) || (pre && !lora_aligned(pre, ldp, dtype, out_bytes)) ||
+      (res && !lora_aligned(res, ldr, dtype, out_bytes)))
+    VY_FAIL(VY_ERR_ARG, "vy_lora_expand_epi: u and B rows must be 16-byte aligned, z / out / pre / res rows %d-byte aligned",
+            out_bytes);
+  const VyDrop d = vy_make_drop(mode == VY_LORA_EPI_DROP_RES ? p_drop : 0.f, seed, offset);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)n_tiles, (unsigned)vy_cdiv(N, 16 * LW));
+  if (dtype == VY_BF16)
+    return lora_expand_epi_launch<bf16>(z, ldz, out, ldo, pre, ldp, res, ldr, u, ldu, B, alpha, tiles, grid, T, (int)N,
+                                        (int)r_pad, (int)slots, (int)bound0, (int)bound1, mode, act, d, st);
+  return lora_expand_epi_launch<float>(z, ldz, out, ldo, pre, ldp, res, ldr, u, ldu, B, alpha, tiles, grid, T, (int)N,
+                                       (int)r_pad, (int)slots, (int)bound0, (int)bound1, mode, act, d, st);
 }

@@ -80,6 +80,9 @@ class AttentionSelfOutput(nn.Module):
 
     def forward(self, hidden_states: torch.Tensor, input_tensor: torch.Tensor) -> torch.Tensor:
         from ..autograd import linear_residual_layernorm
+        if type(self.dense) is not nn.Linear:
+            from ..encoder_lora_train import refuse_direct_call
+            refuse_direct_call("AttentionSelfOutput.dense", self.dense)
         return linear_residual_layernorm(hidden_states, input_tensor, self.dense.weight, self.dense.bias,
                                          self.layernorm.weight, self.layernorm.bias, self.layernorm.eps,
                                          self.dropout.p, self.training)
@@ -234,6 +237,12 @@ class _SelfAttentionBase(nn.Module):
     def _attend(self, hidden_state: torch.Tensor, attention_mask, freqs, cache=None,
                 cache_index: Optional[int] = None, start_pos: int = 0) -> torch.Tensor:
         from ..autograd import self_attention_block
+        if self._lora_aware and not self._fused_qkv and any(type(m) is not nn.Linear for m in (self.query, self.key, self.value)):
+            # (an encoder layer applies its wrappers' terms itself and never comes through here with one enabled)
+            from ..encoder_lora_train import NO_CACHE, refuse_direct_call
+            if cache is not None and any(getattr(m, "enabled", False) for m in (self.query, self.key, self.value)):
+                raise VyomHipError(NO_CACHE.format(what="with a KV cache"))
+            refuse_direct_call(f"{type(self).__name__}.query / key / value", self.query, self.key, self.value)
         if not hidden_state.is_cuda:
             raise VyomHipError("vyomai_amd attention runs on MI355X only (got a CPU tensor; there is "
                                "no CPU fallback -- the CPU restatement lives in oracle/ for tests)")
@@ -242,6 +251,8 @@ class _SelfAttentionBase(nn.Module):
 
 class EncoderAttention(_SelfAttentionBase):
     """forward(hidden_state, attention_mask, freqs=None) -> Tensor.  Reference :75-133."""
+
+    _lora_aware = True       # EncoderLayer adds a wrapped projection's low-rank term (encoder_lora_train.py)
 
     def __init__(self, config, layer_idx: int) -> None:
         super().__init__()
@@ -253,6 +264,8 @@ class EncoderAttention(_SelfAttentionBase):
 
 class EncoderAttentionGqa(_SelfAttentionBase):
     """Grouped-query encoder attention (num_key_value_heads default 4).  Reference :136-215."""
+
+    _lora_aware = True       # as EncoderAttention
 
     def __init__(self, config, layer_idx: int) -> None:
         super().__init__()
@@ -318,6 +331,11 @@ class _CrossAttentionBase(_SelfAttentionBase):
         AttentionSelfOutput with `hidden_state` as residual.  `encoder_attention_mask` is a key-padding
         descriptor (AttnMask) or the reference's additive (B,1,1,S) tensor."""
         from ..autograd import cross_attention_block
+        for name in ("query", "key", "value"):
+            if type(getattr(self, name)).__name__ in ("LoraLinear", "DoraLinear"):
+                raise VyomHipError(f"cross-attention's {name} is a {type(getattr(self, name)).__name__}: adapters have no "
+                                   "path through the encoder-decoder attention.  Fold the update into the weight "
+                                   "(W + alpha * lora_b @ lora_a) and restore the nn.Linear")
         if not hidden_state.is_cuda:
             raise VyomHipError("vyomai_amd attention runs on MI355X only (got a CPU tensor; there is "
                                "no CPU fallback -- the CPU restatement lives in oracle/ for tests)")

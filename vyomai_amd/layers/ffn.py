@@ -35,6 +35,9 @@ class FeedForward(nn.Module):
 
     def forward(self, hidden_state: torch.Tensor, input_tensor: torch.Tensor) -> torch.Tensor:
         from ..autograd import ffn_block
+        if type(self.intermediate) is not nn.Linear or type(self.out) is not nn.Linear:
+            from ..encoder_lora_train import refuse_direct_call
+            refuse_direct_call("FeedForward.intermediate / out", self.intermediate, self.out)
         return ffn_block(hidden_state, input_tensor, self.intermediate.weight, self.intermediate.bias,
                          self.out.weight, self.out.bias, self.layernorm.weight, self.layernorm.bias,
                          self.layernorm.eps, self.act, self.dropout.p, self.training)

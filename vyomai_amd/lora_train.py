@@ -199,17 +199,18 @@ def _saved(ctx, n: int):
     return ts[:n], dict(zip(ctx.groups, ts[n:]))
 
 
-def _adapter_backward(G: Optional[GroupOperands], dy2, x2, u, dx2, grads: dict) -> None:
-    """The adapter's part of one group's backward: t = dY @ B, dx2 += alpha * t @ A (dx2 None: nobody reads dX) and
-    both low-rank weight gradients, delivered as autograd_train._wgrad delivers them: accumulated into a trainer's
-    arena gradient in place (and reported ready), or as fresh tensors in `grads` (id(parameter) -> gradient)."""
+def _adapter_backward(G: Optional[GroupOperands], dy2, x2, u, dx2, grads: dict):
+    """The adapter's part of one group's backward: t = dY @ B, dx2 += alpha * t @ A (dx2 None: nobody reads dX, or the
+    caller adds the term itself from the t returned here) and both low-rank weight gradients, delivered as
+    autograd_train._wgrad delivers them: accumulated into a trainer's arena gradient in place (and reported ready), or
+    as fresh tensors in `grads` (id(parameter) -> gradient).  -> t (None without adapters)."""
     if G is None:
-        return
+        return None
     tiles, n = _tiles(dy2.shape[0], dy2.device)
     t = ops.lora_dgrad_(dx2, dy2, G.Bt, G.At, G.alpha, tiles, n, name=G.name)
     live = [m for m in G.loras if m is not None and (m.lora_a.requires_grad or m.lora_b.requires_grad)]
     if not live:
-        return
+        return t
     direct = all(_direct(m.lora_a) and _direct(m.lora_b) for m in live)
     dA: List[Optional[torch.Tensor]] = []
     dB: List[Optional[torch.Tensor]] = []
@@ -231,6 +232,7 @@ def _adapter_backward(G: Optional[GroupOperands], dy2, x2, u, dx2, grads: dict) 
             _notify(m.lora_a, m.lora_b)
         else:
             grads[id(m.lora_a)], grads[id(m.lora_b)] = ga.to(m.lora_a.dtype), gb.to(m.lora_b.dtype)
+    return t
 
 
 def _param_grads(params, grads: dict):

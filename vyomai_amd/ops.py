@@ -1009,6 +1009,144 @@ def lora_delta_keep_u_(y: Tensor, x: Tensor, A: Tensor, B: Tensor, alpha: Tensor
     return u
 
 
+def lora_shrink(x: Tensor, A: Tensor, tiles: Tensor, n_tiles: int, name: str = "projection") -> Tensor:
+    """u (T, R) = x @ A[0].T over the tiles (vy_lora_shrink, one slot): the first half of lora_delta_keep_u_, for a
+    caller that hands u to lora_expand_epi_.  x (T, K), A (1, R, K) contiguous, K and R multiples of 32."""
+    fn = "lora_shrink"
+    n_tiles = int(n_tiles)
+    T, dt = _lora_rows(fn, name, x=x)
+    K = x.shape[1]
+    if not isinstance(A, Tensor) or A.dim() != 3 or A.shape[0] != 1 or not A.is_contiguous() or A.dtype != dt \
+            or A.device != x.device or A.shape[2] != K or A.shape[1] % 32 or A.shape[1] < 32 or K % 32 or K < 32:
+        raise ValueError(f"{fn} ({name}): A must be a contiguous (1, R, {K}) {dt} tensor on {x.device} with R and K "
+                         f"multiples of 32, got {tuple(getattr(A, 'shape', ()))}")
+    _lora_tiles(fn, name, tiles, n_tiles, x)
+    _need_gpu(x)
+    R = A.shape[1]
+    u = torch.empty((T, R), dtype=dt, device=x.device)
+    call("vy_lora_shrink", x.data_ptr(), x.stride(0), A.data_ptr(), tiles.data_ptr(), n_tiles, u.data_ptr(), R, T, K, R,
+         1, dtype_code(dt), _stream())
+    return u
+
+
+def lora_expand_epi_(z: Tensor, u: Tensor, B: Tensor, alpha: Tensor, tiles: Tensor, n_tiles: int,
+                     boundaries: Sequence[int] = (), *, act: Optional[int] = None, pre: Optional[Tensor] = None,
+                     residual: Optional[Tensor] = None, dropout=None, mul: Optional[Tensor] = None,
+                     out: Optional[Tensor] = None, name: str = "projection") -> Tensor:
+    """The expand half of the adapter's delta with the epilogue of the GEMM it follows (vy_lora_expand_epi; the rule:
+    include/vyom_hip.h) -> out.  z (T, N): the base GEMM's output with its bias; u (T, parts * r_pad): lora_shrink's
+    output; B (1, N, r_pad), alpha fp32 (1,), one slot; v = z + alpha * u @ B.T in fp32, never rounded, then one of
+      act=<a vy_act but ACT_NONE>, pre=(T, N):  out = act(v), pre <- act'(v)      (what linear_dgrad(pre=) takes)
+      residual=(T, N), dropout=None | (p, seed, offset):  out = dropout(v) + residual, the mask of ops.dropout
+      mul=(T, N):  out = v * mul   (the backward behind an adapted GEMM: z the base dgrad, u = lora_dgrad_'s t, B the
+                                    transposed stacked A as (1, K, R), mul the saved act')
+    r_pad is 32 or 64 (mul=: any multiple of 32 up to 192, no boundaries).  out defaults to z (in place); given, it must
+    not overlap pre, residual or mul.  The tiles must cover every row."""
+    fn = "lora_expand_epi_"
+    n_tiles = int(n_tiles)
+    if (act is not None) + (residual is not None) + (mul is not None) != 1:
+        raise ValueError(f"{fn} ({name}): give exactly one of act= (with pre=), residual= (with dropout=) and mul=")
+    out = z if out is None else out
+    mats = dict(z=z, u=u, out=out)
+    if act is not None:
+        if int(act) not in range(_lib.ACT_GELU_ERF, _lib.ACT_LEAKY_RELU + 1):
+            raise ValueError(f"{fn} ({name}): act = {act} must be an activation code other than ACT_NONE (without flags)")
+        if pre is None or dropout is not None:
+            raise ValueError(f"{fn} ({name}): act= writes act'(v) to pre= and takes no dropout")
+        mats["pre"] = pre
+        mode = _lib.LORA_EPI_ACT
+    else:
+        if pre is not None or (mul is not None and dropout is not None):
+            raise ValueError(f"{fn} ({name}): pre= belongs to act=, dropout= to residual=")
+        if mul is not None:
+            mats["mul"], mode = mul, _lib.LORA_EPI_MUL
+        else:
+            mats["residual"], mode = residual, _lib.LORA_EPI_DROP_RES
+    T, dt = _lora_rows(fn, name, **mats)
+    N = z.shape[1]
+    bounds = _lora_bounds(fn, name, boundaries, N)
+    parts = 1 + len(bounds)
+    for what, t in mats.items():
+        if what != "u" and t.shape[1] != N:
+            raise ValueError(f"{fn} ({name}): {what} must be (T, {N}), got {tuple(t.shape)}")
+    ranks = range(32, 193, 32) if mul is not None else (32, 64)
+    if not isinstance(B, Tensor) or B.dim() != 3 or B.shape[0] != 1 or not B.is_contiguous() or B.dtype != dt \
+            or B.device != z.device or B.shape[1] != N or B.shape[2] not in ranks or (mul is not None and bounds):
+        raise ValueError(f"{fn} ({name}): B must be a contiguous (1, {N}, r_pad) {dt} tensor on {z.device} with r_pad in "
+                         f"{list(ranks)} (mul=: no boundaries), got {tuple(getattr(B, 'shape', ()))}")
+    r_pad = B.shape[2]
+    if u.shape[1] != parts * r_pad:
+        raise ValueError(f"{fn} ({name}): u must be (T, {parts} * {r_pad}), got {tuple(u.shape)}")
+    if not isinstance(alpha, Tensor) or alpha.dtype != torch.float32 or alpha.numel() != 1 or alpha.device != z.device:
+        raise ValueError(f"{fn} ({name}): alpha must be a float32 tensor of one element on {z.device}")
+    _lora_tiles(fn, name, tiles, n_tiles, z)
+    for what in ("pre", "residual", "mul"):
+        t = mats.get(what)
+        if t is not None and t.data_ptr() == out.data_ptr():
+            raise ValueError(f"{fn} ({name}): {what} must not be the output buffer")
+    p, seed, offset = (0.0, 0, 0) if dropout is None else dropout
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"{fn} ({name}): dropout p = {p} must lie in [0, 1)")
+    _need_gpu(z)
+    side = pre if act is not None else mul
+    call("vy_lora_expand_epi", z.data_ptr(), z.stride(0), out.data_ptr(), out.stride(0), _ptr(side),
+         0 if side is None else side.stride(0), _ptr(residual), 0 if residual is None else residual.stride(0),
+         u.data_ptr(), u.stride(0), B.data_ptr(), alpha.data_ptr(), tiles.data_ptr(), n_tiles, T, N, r_pad, 1,
+         *(bounds + [N, N])[:2], mode, int(act or 0), float(p), int(seed), int(offset), dtype_code(dt), _stream())
+    return out
+
+
+def cls_head_fwd(hidden: Tensor, w: Tensor, bias: Optional[Tensor], labels: Optional[Tensor] = None,
+                 err_flag: Optional[Tensor] = None):
+    """The classification head over row 0 of every sequence (vy_cls_head_fwd): hidden (B, L, d) contiguous, w (C, d),
+    bias (C) in hidden's dtype -> logits fp32 (B, C); with labels (int64, B) -> (dlogits fp32 (B, C) = (softmax -
+    onehot) / count in the logits' place, lse fp32 (B), loss fp32 scalar tensor)."""
+    _need_gpu(hidden, w, bias, labels, err_flag)
+    if hidden.dim() != 3 or not hidden.is_contiguous() or w.dim() != 2 or not w.is_contiguous() \
+            or w.shape[1] != hidden.shape[2] or w.dtype != hidden.dtype or hidden.shape[2] % 8:
+        raise ValueError(f"cls_head_fwd: hidden must be a contiguous (B, L, d) tensor with d a multiple of 8 and w a "
+                         f"contiguous (C, d) tensor of its dtype, got {tuple(hidden.shape)} {hidden.dtype} and "
+                         f"{tuple(w.shape)} {w.dtype}")
+    B, L, d = hidden.shape
+    C = w.shape[0]
+    if bias is not None and (bias.dtype != w.dtype or bias.numel() != C or not bias.is_contiguous()):
+        raise ValueError(f"cls_head_fwd: bias must be a contiguous ({C},) tensor of w's dtype")
+    logits = torch.empty((B, C), dtype=torch.float32, device=hidden.device)
+    lse = loss = None
+    if labels is not None:
+        if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+            raise ValueError(f"cls_head_fwd: labels must be a contiguous int64 tensor of {B} elements")
+        if err_flag is not None and (err_flag.dtype != torch.int32 or err_flag.numel() != 1):
+            raise ValueError("cls_head_fwd: err_flag must be an int32 tensor of one element")
+        lse = torch.empty(B, dtype=torch.float32, device=hidden.device)
+        loss = torch.empty((), dtype=torch.float32, device=hidden.device)
+    call("vy_cls_head_fwd", hidden.data_ptr(), L * d, w.data_ptr(), _ptr(bias), logits.data_ptr(), _ptr(labels), _ptr(lse),
+         _ptr(loss), _ptr(err_flag), B, C, d, dtype_code(hidden.dtype), _stream())
+    return logits if labels is None else (logits, lse, loss)
+
+
+def cls_head_bwd(hidden: Tensor, w: Tensor, dlogits: Tensor, gscale: Optional[Tensor], dw: Tensor,
+                 db: Optional[Tensor], accumulate: bool) -> Tensor:
+    """-> dh (hidden's shape and dtype): row 0 of every sequence = gscale * dlogits @ w, every other row zero; dw (C, d) /
+    db (C) fp32 written or (accumulate) added to (vy_cls_head_bwd).  Deterministic."""
+    _need_gpu(hidden, w, dlogits, gscale, dw, db)
+    B, L, d = hidden.shape
+    C = w.shape[0]
+    if not hidden.is_contiguous() or not w.is_contiguous() or w.dtype != hidden.dtype or tuple(w.shape) != (C, d):
+        raise ValueError("cls_head_bwd: hidden (B, L, d) and w (C, d) must be contiguous and share a dtype")
+    if dlogits.dtype != torch.float32 or tuple(dlogits.shape) != (B, C) or not dlogits.is_contiguous():
+        raise ValueError(f"cls_head_bwd: dlogits must be a contiguous float32 ({B}, {C}) tensor")
+    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1):
+        raise ValueError("cls_head_bwd: gscale must be a float32 tensor of one element")
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (C, d) or not dw.is_contiguous() \
+            or (db is not None and (db.dtype != torch.float32 or db.numel() != C or not db.is_contiguous())):
+        raise ValueError(f"cls_head_bwd: dw must be a contiguous float32 ({C}, {d}) tensor and db one of {C} elements")
+    dh = torch.empty_like(hidden)
+    call("vy_cls_head_bwd", hidden.data_ptr(), L * d, w.data_ptr(), dlogits.data_ptr(), _ptr(gscale), dh.data_ptr(),
+         dw.data_ptr(), _ptr(db), 1 if accumulate else 0, B, L, C, d, dtype_code(hidden.dtype), _stream())
+    return dh
+
+
 def lora_dgrad_(dx: Optional[Tensor], dy: Tensor, Bt: Tensor, At: Tensor, alpha: Tensor, tiles: Tensor, n_tiles: int,
                 name: str = "projection") -> Tensor:
     """The adapter's two data-gradient products of one GEMM group -> t (M, R) = dy @ B per part, and, when dx is given,
