@@ -896,6 +896,33 @@ int64_t vy_gemma_ws_bytes(int32_t B, int32_t d, int32_t h, int32_t dh, int32_t f
 int vy_gemma_decoder_step(const vy_gemma_plan* plan, const void* x, int64_t pos, void* logits, int64_t ldv,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weight-only fp8 for the single-sequence step (B = 1 is a weight stream: half the bytes per token).
+ *
+ * vy_quant_rows_fp8: w (N, K) bf16 or fp32, leading dimension ldw -> codes (N, K) OCP e4m3fn bytes, leading
+ * dimension ldc, and one fp32 scale per row.  The rule of the fp8 KV pages, per output row:
+ *   s = amax > 0 ? amax / 448 : 1 ;  code = e4m3fn(clamp(w / s, -448, 448))   IEEE fp32 division, nearest even
+ * so that w ~ code * s with |code * s - w| <= max(2^-4 |w|, 2^-10 s).  K, ldc multiples of 4.  Once per plan.
+ *
+ * vy_gemma_decoder_step_w8: vy_gemma_decoder_step on a plan whose wqkv / wo / wgu / wdown point at such codes
+ * (leading dimension K bytes); `w8` carries their row scales (s_gu: 2 ffn of them, gate rows then up rows) and a
+ * quantised copy of the vocabulary matrix.  Biases, norm weights, caches, tables and workspace as in the bf16
+ * plan; VY_GEMMA_PRESCALED as there (the codes then quantise the fp32 product W (1 + ln)).  Each product
+ * accumulates code * x in fp32 and multiplies the sum by the row's scale once; everything after that is the bf16
+ * step's arithmetic.  One chain only: bf16 activations, B = 1, d, h * dh and ffn each one of 2048 / 4096 / 8192 /
+ * 16384, dh a power of two with the rotary tables given, vocab a multiple of 4.  Anything else returns
+ * VY_ERR_UNSUPPORTED with a message before the first launch: no kernel that expects bf16 weights reads codes.
+ * -------------------------------------------------------------------------------------------- */
+int vy_quant_rows_fp8(const void* w, int64_t ldw, void* codes, int64_t ldc, float* scales, int64_t N, int64_t K,
+                      int dtype, void* stream);
+typedef struct vy_gemma_w8_layer { const float *s_qkv, *s_o, *s_gu, *s_down; } vy_gemma_w8_layer;
+typedef struct vy_gemma_w8 {
+  const vy_gemma_w8_layer* layers;
+  const void* head_codes; const float* head_scale;   /* [vocab, d] codes, [vocab] scales */
+} vy_gemma_w8;
+int vy_gemma_decoder_step_w8(const vy_gemma_plan* plan, const vy_gemma_w8* w8, const void* x, int64_t pos,
+                             void* logits, int64_t ldv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

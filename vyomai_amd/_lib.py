@@ -106,6 +106,8 @@ PROTOTYPES = {
     "vy_dora_bwd": [_p, _i, _i, _p],
     "vy_decoder_step": [_p, _p, _i64, _p, _p, _p, _i64, _p],
     "vy_gemma_decoder_step": [_p, _p, _i64, _p, _i64, _p],
+    "vy_quant_rows_fp8": [_p, _i64, _p, _i64, _p, _i64, _i64, _i, _p],
+    "vy_gemma_decoder_step_w8": [_p, _p, _p, _i64, _p, _i64, _p],
     "vy_cast": [_p, _p, _i64, _i, _i, _p],
     "vy_ddp_unique_id": [_p],
     "vy_ddp_init": [_p, _i, _i],

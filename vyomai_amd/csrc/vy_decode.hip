@@ -530,53 +530,22 @@ struct DecGemvArgs {
   const float* cos_tab; const float* sin_tab; int pos, nq, nkv, dh;
 };
 
-template <int EPI, int CH, int NB, bool NORM>
-__global__ __launch_bounds__(256) void dec_gemv1_kernel(const DecGemvArgs p) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-  __shared__ float rope_x[4];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+// the column of wave `wv`: four consecutive ones per workgroup, or with the rotary embedding the two pairs of one head
+__device__ __forceinline__ int dec_gemv1_column(const DecGemvArgs& p, int wv, bool rope_on) {
   int n = (int)blockIdx.x * 4 + wv;
-  const bool rope_on = EPI == GV_QKV && p.cos_tab != nullptr;
   if (rope_on) {
     const int per_head = p.dh >> 2;
     const int hd = (int)blockIdx.x / per_head, pi = (int)blockIdx.x - hd * per_head;
     n = hd * p.dh + 2 * pi + (wv & 1) + (p.dh >> 1) * (wv >> 1);
   }
-  const bf16* wp = p.w + (long long)n * p.ldw + lane * 8;
-  const bf16* wp2 = p.w + (long long)(p.N + n) * p.ldw + lane * 8;   // GV_GATED: the "up" row
-  const bf16* xp = p.x + lane * 8;
-  float acc = 0.f, acc2 = 0.f, sq = 0.f;
-  bf16x8 wa[2][CH], wb[2][CH], xa[2][CH];
-  auto issue = [&](int b, int buf) {
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      const int off = (b * CH + u) * 512;
-      wa[buf][u] = dec_load_stream(wp + off);   // 5.8 GB of weights per token, each byte once: streamed
-      if constexpr (EPI == GV_GATED) wb[buf][u] = dec_load_stream(wp2 + off);
-      xa[buf][u] = *reinterpret_cast<const bf16x8*>(xp + off);
-    }
-  };
-  issue(0, 0);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    if (b + 1 < NB) issue(b + 1, (b + 1) & 1);
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-      union { bf16x8 v; bf16x2_t h[4]; } a, a2, x;
-      a.v = wa[b & 1][u];
-      x.v = xa[b & 1][u];
-      if constexpr (EPI == GV_GATED) a2.v = wb[b & 1][u];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc = __builtin_amdgcn_fdot2_f32_bf16(a.h[e], x.h[e], acc, false);
-        if constexpr (EPI == GV_GATED) acc2 = __builtin_amdgcn_fdot2_f32_bf16(a2.h[e], x.h[e], acc2, false);
-        if constexpr (NORM) sq = __builtin_amdgcn_fdot2_f32_bf16(x.h[e], x.h[e], sq, false);
-      }
-    }
-  }
-  acc = dec_wave_sum(acc);
-  if constexpr (EPI == GV_GATED) acc2 = dec_wave_sum(acc2);
+  return n;
+}
+
+// Everything after the wave sums, shared by the bf16 and the fp8-weight kernels: the NORM factor, bias, residual, the
+// bf16 roundings, gelu_tanh, the rotary swap through LDS, the store.  acc / acc2: wave sums; sq: this lane's sum x^2.
+template <int EPI, bool NORM>
+__device__ __forceinline__ void dec_gemv1_tail(const DecGemvArgs& p, int n, int wv, int lane, bool rope_on, float acc, float acc2,
+                                               float sq, float* rope_x) {
   if constexpr (NORM) {
     const float ms = dec_wave_sum(sq) / (float)p.K + p.eps;
     const float r = rsqrtf(ms);
@@ -624,6 +593,136 @@ __global__ __launch_bounds__(256) void dec_gemv1_kernel(const DecGemvArgs p) {
   }
 }
 
+template <int EPI, int CH, int NB, bool NORM>
+__global__ __launch_bounds__(256) void dec_gemv1_kernel(const DecGemvArgs p) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+  __shared__ float rope_x[4];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool rope_on = EPI == GV_QKV && p.cos_tab != nullptr;
+  const int n = dec_gemv1_column(p, wv, rope_on);
+  const bf16* wp = p.w + (long long)n * p.ldw + lane * 8;
+  const bf16* wp2 = p.w + (long long)(p.N + n) * p.ldw + lane * 8;   // GV_GATED: the "up" row
+  const bf16* xp = p.x + lane * 8;
+  float acc = 0.f, acc2 = 0.f, sq = 0.f;
+  bf16x8 wa[2][CH], wb[2][CH], xa[2][CH];
+  auto issue = [&](int b, int buf) {
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const int off = (b * CH + u) * 512;
+      wa[buf][u] = dec_load_stream(wp + off);   // 5.8 GB of weights per token, each byte once: streamed
+      if constexpr (EPI == GV_GATED) wb[buf][u] = dec_load_stream(wp2 + off);
+      xa[buf][u] = *reinterpret_cast<const bf16x8*>(xp + off);
+    }
+  };
+  issue(0, 0);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (b + 1 < NB) issue(b + 1, (b + 1) & 1);
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      union { bf16x8 v; bf16x2_t h[4]; } a, a2, x;
+      a.v = wa[b & 1][u];
+      x.v = xa[b & 1][u];
+      if constexpr (EPI == GV_GATED) a2.v = wb[b & 1][u];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc = __builtin_amdgcn_fdot2_f32_bf16(a.h[e], x.h[e], acc, false);
+        if constexpr (EPI == GV_GATED) acc2 = __builtin_amdgcn_fdot2_f32_bf16(a2.h[e], x.h[e], acc2, false);
+        if constexpr (NORM) sq = __builtin_amdgcn_fdot2_f32_bf16(x.h[e], x.h[e], sq, false);
+      }
+    }
+  }
+  acc = dec_wave_sum(acc);
+  if constexpr (EPI == GV_GATED) acc2 = dec_wave_sum(acc2);
+  dec_gemv1_tail<EPI, NORM>(p, n, wv, lane, rope_on, acc, acc2, sq, rope_x);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same three products on fp8 weights: W is (N, K) OCP e4m3fn codes with one fp32 scale per output row
+// (vy_quant_rows_fp8), x stays bf16.  The step is a weight stream, so half the bytes is the whole point.  A lane's load
+// stays 16 bytes, now 16 codes: a wave instruction covers 1024 columns, and the lane takes the matching 16 bf16 of x in
+// two 16-byte loads.  Codes go to fp32 with v_cvt_pk_f32_fp8 (exact), the products are accumulated in fp32, and the row
+// scale multiplies the WAVE SUM, never an element: acc * scale[n] comes first, then everything dec_gemv1_tail does, with
+// its roundings where they are.  At most 4 chunks in flight twice over (16 + 16 + 32 registers a chunk in the gated
+// form): K = 2048 / 4096 / 8192 / 16384 are <2,1>, <4,1>, <4,2>, <4,4>.
+// ------------------------------------------------------------------------------------------
+struct DecGemvW8Args {
+  DecGemvArgs a;                     // a.w is unused: the weights are `codes`, leading dimension a.ldw BYTES
+  const unsigned char* codes;
+  const float* scales;               // [N]; GV_GATED: [2 N], gate rows then up rows
+};
+
+__device__ __forceinline__ u32x4 dec_load_stream(const unsigned char* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+}
+
+template <int EPI, int CH, int NB, bool NORM>
+__global__ __launch_bounds__(256) void dec_gemv1_w8_kernel(const DecGemvW8Args q) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+  const DecGemvArgs& p = q.a;
+  __shared__ float rope_x[4];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool rope_on = EPI == GV_QKV && p.cos_tab != nullptr;
+  const int n = dec_gemv1_column(p, wv, rope_on);
+  const unsigned char* wp = q.codes + (long long)n * p.ldw + lane * 16;
+  const unsigned char* wp2 = q.codes + (long long)(p.N + n) * p.ldw + lane * 16;   // GV_GATED: the "up" row
+  const bf16* xp = p.x + lane * 16;
+  const float sc = q.scales[n];
+  float sc2 = 0.f;
+  if constexpr (EPI == GV_GATED) sc2 = q.scales[p.N + n];
+  float acc = 0.f, acc2 = 0.f, sq = 0.f;
+  u32x4 wa[2][CH], wb[2][CH];
+  bf16x8 xa[2][CH][2];
+  auto issue = [&](int b, int buf) {
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const int off = (b * CH + u) * 1024;
+      wa[buf][u] = dec_load_stream(wp + off);
+      if constexpr (EPI == GV_GATED) wb[buf][u] = dec_load_stream(wp2 + off);
+      xa[buf][u][0] = *reinterpret_cast<const bf16x8*>(xp + off);
+      xa[buf][u][1] = *reinterpret_cast<const bf16x8*>(xp + off + 8);
+    }
+  };
+  issue(0, 0);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (b + 1 < NB) issue(b + 1, (b + 1) & 1);
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {   // dword j: codes 4 j .. 4 j + 3, the lowest byte first
+        union { bf16x4 v; bf16x2_t h[2]; } x;
+        const bf16x8 xv = xa[b & 1][u][j >> 1];
+        x.v = (j & 1) ? __builtin_shufflevector(xv, xv, 4, 5, 6, 7) : __builtin_shufflevector(xv, xv, 0, 1, 2, 3);
+        const float x0 = (float)x.v[0], x1 = (float)x.v[1], x2 = (float)x.v[2], x3 = (float)x.v[3];
+        const int c = (int)wa[b & 1][u][j];
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(c, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(c, true);
+        acc = fmaf(lo[0], x0, acc);
+        acc = fmaf(lo[1], x1, acc);
+        acc = fmaf(hi[0], x2, acc);
+        acc = fmaf(hi[1], x3, acc);
+        if constexpr (EPI == GV_GATED) {
+          const int c2 = (int)wb[b & 1][u][j];
+          const f32x2 lo2 = __builtin_amdgcn_cvt_pk_f32_fp8(c2, false), hi2 = __builtin_amdgcn_cvt_pk_f32_fp8(c2, true);
+          acc2 = fmaf(lo2[0], x0, acc2);
+          acc2 = fmaf(lo2[1], x1, acc2);
+          acc2 = fmaf(hi2[0], x2, acc2);
+          acc2 = fmaf(hi2[1], x3, acc2);
+        }
+        if constexpr (NORM) {
+          sq = __builtin_amdgcn_fdot2_f32_bf16(x.h[0], x.h[0], sq, false);
+          sq = __builtin_amdgcn_fdot2_f32_bf16(x.h[1], x.h[1], sq, false);
+        }
+      }
+    }
+  }
+  acc = dec_wave_sum(acc) * sc;
+  if constexpr (EPI == GV_GATED) acc2 = dec_wave_sum(acc2) * sc2;
+  dec_gemv1_tail<EPI, NORM>(p, n, wv, lane, rope_on, acc, acc2, sq, rope_x);
+}
+
 template <int EPI, bool NORM>
 int dec_gemv1_go(const DecGemvArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)(a.N / 4)), block(256);
@@ -631,6 +730,17 @@ int dec_gemv1_go(const DecGemvArgs& a, hipStream_t st) {
   else if (a.K == 4096) hipLaunchKernelGGL((dec_gemv1_kernel<EPI, 8, 1, NORM>), grid, block, 0, st, a);
   else if (a.K == 8192) hipLaunchKernelGGL((dec_gemv1_kernel<EPI, 8, 2, NORM>), grid, block, 0, st, a);
   else if (a.K == 16384) hipLaunchKernelGGL((dec_gemv1_kernel<EPI, 8, 4, NORM>), grid, block, 0, st, a);
+  else return 1;
+  return 0;
+}
+
+template <int EPI, bool NORM>
+int dec_gemv1_w8_go(const DecGemvW8Args& q, hipStream_t st) {
+  const dim3 grid((unsigned)(q.a.N / 4)), block(256);
+  if (q.a.K == 2048) hipLaunchKernelGGL((dec_gemv1_w8_kernel<EPI, 2, 1, NORM>), grid, block, 0, st, q);
+  else if (q.a.K == 4096) hipLaunchKernelGGL((dec_gemv1_w8_kernel<EPI, 4, 1, NORM>), grid, block, 0, st, q);
+  else if (q.a.K == 8192) hipLaunchKernelGGL((dec_gemv1_w8_kernel<EPI, 4, 2, NORM>), grid, block, 0, st, q);
+  else if (q.a.K == 16384) hipLaunchKernelGGL((dec_gemv1_w8_kernel<EPI, 4, 4, NORM>), grid, block, 0, st, q);
   else return 1;
   return 0;
 }
@@ -781,6 +891,58 @@ extern "C" int vy_debug_dec_gemv1_qkv(const void* x, const void* w, const void* 
                                       int h, int hk, int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K,
                                       int prescaled, float eps, void* stream) {
   return vy_dec_gemv1_qkv(x, w, bias, q, k, v, c_sh, h, hk, dh, cos_tab, sin_tab, pos, K, prescaled, eps, (hipStream_t)stream);
+}
+
+// ---- the same three products on e4m3fn codes with one fp32 scale per output row (gated: 2 I scales, gate rows then up
+// rows).  Same contract as above: N % 4 == 0, K one of the four, x and codes 16-byte aligned, VY_ERR_UNSUPPORTED with
+// nothing launched otherwise
+int vy_dec_gemv1_w8(const void* x, const void* codes, const float* scales, const void* bias, const void* residual, void* y, int N,
+                    int K, hipStream_t st) {
+  if (!gemv1_ok(x, codes, N, K) || !scales) return VY_ERR_UNSUPPORTED;
+  DecGemvW8Args q{};
+  q.a.x = (const bf16*)x; q.a.bias = (const bf16*)bias; q.a.residual = (const bf16*)residual; q.a.y = (bf16*)y;
+  q.a.N = N; q.a.K = K; q.a.ldw = K; q.codes = (const unsigned char*)codes; q.scales = scales;
+  if (dec_gemv1_w8_go<GV_PLAIN, false>(q, st)) return VY_ERR_UNSUPPORTED;
+  VY_CHECK_LAUNCH("vy_dec_gemv1_w8");
+  return VY_OK;
+}
+int vy_dec_gemv1_gated_w8(const void* x, const void* codes, const float* scales, void* y, int I, int K, int prescaled, float eps,
+                          hipStream_t st) {
+  if (!gemv1_ok(x, codes, I, K) || !scales) return VY_ERR_UNSUPPORTED;
+  DecGemvW8Args q{};
+  q.a.x = (const bf16*)x; q.a.y = (bf16*)y; q.a.N = I; q.a.K = K; q.a.ldw = K; q.a.eps = eps;
+  q.codes = (const unsigned char*)codes; q.scales = scales;
+  if (prescaled ? dec_gemv1_w8_go<GV_GATED, true>(q, st) : dec_gemv1_w8_go<GV_GATED, false>(q, st)) return VY_ERR_UNSUPPORTED;
+  VY_CHECK_LAUNCH("vy_dec_gemv1_gated_w8");
+  return VY_OK;
+}
+int vy_dec_gemv1_qkv_w8(const void* x, const void* codes, const float* scales, const void* bias, void* q_out, void* k, void* v,
+                        int64_t c_sh, int h, int hk, int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K,
+                        int prescaled, float eps, hipStream_t st) {
+  const int N = (h + 2 * hk) * dh;
+  if (!gemv1_ok(x, codes, N, K) || !scales || dh % 4 || (dh & (dh - 1))) return VY_ERR_UNSUPPORTED;
+  DecGemvW8Args q{};
+  q.a.x = (const bf16*)x; q.a.bias = (const bf16*)bias; q.a.N = N; q.a.K = K; q.a.ldw = K; q.a.eps = eps;
+  q.a.q = (bf16*)q_out; q.a.k = (bf16*)k; q.a.v = (bf16*)v; q.a.c_sh = c_sh; q.a.cos_tab = cos_tab; q.a.sin_tab = sin_tab;
+  q.a.pos = (int)pos; q.a.nq = h * dh; q.a.nkv = hk * dh; q.a.dh = dh;
+  q.codes = (const unsigned char*)codes; q.scales = scales;
+  if (prescaled ? dec_gemv1_w8_go<GV_QKV, true>(q, st) : dec_gemv1_w8_go<GV_QKV, false>(q, st)) return VY_ERR_UNSUPPORTED;
+  VY_CHECK_LAUNCH("vy_dec_gemv1_qkv_w8");
+  return VY_OK;
+}
+extern "C" int vy_debug_dec_gemv1_w8(const void* x, const void* codes, const float* scales, const void* bias, const void* residual,
+                                     void* y, int N, int K, void* stream) {
+  return vy_dec_gemv1_w8(x, codes, scales, bias, residual, y, N, K, (hipStream_t)stream);
+}
+extern "C" int vy_debug_dec_gemv1_gated_w8(const void* x, const void* codes, const float* scales, void* y, int I, int K,
+                                           int prescaled, float eps, void* stream) {
+  return vy_dec_gemv1_gated_w8(x, codes, scales, y, I, K, prescaled, eps, (hipStream_t)stream);
+}
+extern "C" int vy_debug_dec_gemv1_qkv_w8(const void* x, const void* codes, const float* scales, const void* bias, void* q, void* k,
+                                         void* v, int64_t c_sh, int h, int hk, int dh, const float* cos_tab, const float* sin_tab,
+                                         int64_t pos, int K, int prescaled, float eps, void* stream) {
+  return vy_dec_gemv1_qkv_w8(x, codes, scales, bias, q, k, v, c_sh, h, hk, dh, cos_tab, sin_tab, pos, K, prescaled, eps,
+                             (hipStream_t)stream);
 }
 
 // single-query attention of the decode steps.  smax: an upper bound of the context length when it is read on the

@@ -58,6 +58,13 @@ int vy_dec_gemv1_gated(const void* x, const void* wgu, void* y, int I, int K, in
 int vy_dec_gemv1_qkv(const void* x, const void* w, const void* bias, void* q, void* k, void* v, int64_t c_sh, int h, int hk,
                      int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K, int prescaled, float eps,
                      hipStream_t st);
+int vy_dec_gemv1_w8(const void* x, const void* codes, const float* scales, const void* bias, const void* residual, void* y, int N,
+                    int K, hipStream_t st);
+int vy_dec_gemv1_gated_w8(const void* x, const void* codes, const float* scales, void* y, int I, int K, int prescaled, float eps,
+                          hipStream_t st);
+int vy_dec_gemv1_qkv_w8(const void* x, const void* codes, const float* scales, const void* bias, void* q_out, void* k, void* v,
+                        int64_t c_sh, int h, int hk, int dh, const float* cos_tab, const float* sin_tab, int64_t pos, int K,
+                        int prescaled, float eps, hipStream_t st);
 
 namespace {
 inline int64_t esize(int dtype) { return dtype == VY_BF16 ? 2 : 4; }
@@ -323,4 +330,100 @@ extern "C" int vy_gemma_decoder_step(const vy_gemma_plan* p, const void* x, int6
   if ((rc = vy_rmsnorm_fwd(cur, d, p->norm_w, n, d, B, d, p->eps, 1.0f, p->dtype, stream))) return rc;
   return vy_linear_fwd(n, d, p->head_w, d, nullptr, nullptr, 0, logits, ldv, nullptr, B, p->vocab, d, VY_ACT_NONE,
                        p->dtype, stream);
+}
+
+// what the last vy_gemma_decoder_step_w8 ran: {layers whose four links ran the fp8-weight kernels, the head ran one}
+static int g_gemma_w8_last[2];
+extern "C" void vy_debug_gemma_w8_last(int out[2]) {
+  out[0] = g_gemma_w8_last[0];
+  out[1] = g_gemma_w8_last[1];
+}
+// and its launches in order, for the test of the chain: 1 = RMSNorm, 2 = qkv (w8), 3 = attention, 4 = plain product (w8),
+// 5 = gated product (w8); at most 64 are kept.  -> how many the step made.  Host-side statics only.
+static int g_gemma_w8_trace[64], g_gemma_w8_trace_n;
+extern "C" int vy_debug_gemma_w8_trace(int* out, int cap) {
+  for (int i = 0; i < g_gemma_w8_trace_n && i < 64 && i < cap; ++i) out[i] = g_gemma_w8_trace[i];
+  return g_gemma_w8_trace_n;
+}
+static void w8_note(int code) {
+  if (g_gemma_w8_trace_n < 64) g_gemma_w8_trace[g_gemma_w8_trace_n] = code;
+  ++g_gemma_w8_trace_n;
+}
+
+// The single-sequence step on fp8 weights: the plan's wqkv / wo / wgu / wdown are e4m3fn codes, `w8` holds their row
+// scales and a quantised copy of the vocabulary matrix.  ONE chain, the lean bf16 one launch for launch (qkv, attention,
+// o_proj, gated, down; RMSNorm launches in front of qkv and gated unless the plan is pre-scaled), then the final RMSNorm
+// and the vocabulary product as one more matrix-vector launch.  Every shape is checked before the first launch: no
+// kernel that takes bf16 weights may ever see the codes.
+extern "C" int vy_gemma_decoder_step_w8(const vy_gemma_plan* p, const vy_gemma_w8* w8, const void* x, int64_t pos,
+                                        void* logits, int64_t ldv, void* stream) {
+  const char* who = "vy_gemma_decoder_step_w8";
+  if (!p || !w8 || !x || !p->layers || !p->ws || !logits || !w8->layers || !w8->head_codes || !w8->head_scale)
+    VY_FAIL(VY_ERR_ARG, "%s: null plan/scales/input/workspace/output", who);
+  if (pos < 0) VY_FAIL(VY_ERR_ARG, "%s: negative position", who);
+  const GemmaWs ws(p->B, p->d, p->h, p->dh, p->ffn, p->dtype);
+  if (p->ws_bytes < ws.bytes) VY_FAIL(VY_ERR_ARG, "%s: workspace too small", who);
+  const int d = p->d, h = p->h, hk = p->hk, dh = p->dh, ffn = p->ffn;
+  auto k_ok = [](int64_t K) { return K == 2048 || K == 4096 || K == 8192 || K == 16384; };
+  g_gemma_w8_last[0] = g_gemma_w8_last[1] = g_gemma_w8_trace_n = 0;
+  if (p->dtype != VY_BF16 || p->B != 1)
+    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: fp8 weights serve bf16 activations at B = 1 only (dtype %d, B = %d)", who, p->dtype, p->B);
+  if (!k_ok(d) || !k_ok((int64_t)h * dh) || !k_ok(ffn))
+    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: d = %d, h * dh = %d, ffn = %d: every K must be 2048, 4096, 8192 or 16384", who, d, h * dh, ffn);
+  if (!p->cos_tab || !p->sin_tab || dh % 4 || (dh & (dh - 1)))
+    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: the rotary embedding is fused: tables and a power-of-two head width (dh = %d)", who, dh);
+  if (p->vocab % 4 || ldv < p->vocab || ffn % 4)
+    VY_FAIL(VY_ERR_UNSUPPORTED, "%s: vocab = %d (ldv %lld), ffn = %d: multiples of 4", who, p->vocab, (long long)ldv, ffn);
+  char* w = (char*)p->ws;
+  void *n = w + ws.n, *q = w + ws.q, *ao = w + ws.ao, *x1 = w + ws.x1, *act = w + ws.act;
+  void* hb[2] = {w + ws.hb[0], w + ws.hb[1]};
+  const bool prescaled = p->flags & VY_GEMMA_PRESCALED;
+  const float scale = 1.0f / sqrtf((float)dh);
+  hipStream_t hs = (hipStream_t)stream;
+  // the launchers' own refusal (an operand off its 16-byte alignment) ends the step: there is no other kernel for codes
+#define W8_LINK(code, call)                                                                              \
+  do {                                                                                                   \
+    rc = (call);                                                                                         \
+    if (rc == VY_ERR_UNSUPPORTED) VY_FAIL(rc, "%s: layer %d: x and the codes must be 16-byte aligned", who, l); \
+    if (rc) return rc;                                                                                   \
+    w8_note(code);                                                                                       \
+  } while (0)
+  const void* cur = x;
+  int rc, l;
+  for (l = 0; l < p->num_layers; ++l) {
+    const vy_gemma_layer& L = p->layers[l];
+    const vy_gemma_w8_layer& S = w8->layers[l];
+    if (!S.s_qkv || !S.s_o || !S.s_gu || !S.s_down) VY_FAIL(VY_ERR_ARG, "%s: layer %d: null scales", who, l);
+    void* kdst = (char*)L.kcache + pos * L.c_sl * 2;
+    void* vdst = (char*)L.vcache + pos * L.c_sl * 2;
+    void* nxt = hb[l & 1];
+    const void* qin = cur;
+    if (!prescaled) {
+      if ((rc = vy_rmsnorm_fwd(cur, d, L.ln_in, n, d, 1, d, p->eps, 1.0f, p->dtype, stream))) return rc;
+      w8_note(1);
+      qin = n;
+    }
+    W8_LINK(2, vy_dec_gemv1_qkv_w8(qin, L.wqkv, S.s_qkv, L.bqkv, q, kdst, vdst, L.c_sh, h, hk, dh, p->cos_tab, p->sin_tab, pos, d,
+                                prescaled, p->eps, hs));
+    if ((rc = vy_attn_decode_ex(q, (int64_t)h * dh, dh, L.kcache, L.c_sb, L.c_sh, L.c_sl, L.vcache, L.c_sb, L.c_sh, L.c_sl, ao,
+                                (int64_t)h * dh, 1, h, hk, pos + 1, nullptr, dh, scale, p->dtype, stream))) return rc;
+    w8_note(3);
+    W8_LINK(4, vy_dec_gemv1_w8(ao, L.wo, S.s_o, L.bo, cur, x1, d, h * dh, hs));
+    const void* gin = x1;
+    if (!prescaled) {
+      if ((rc = vy_rmsnorm_fwd(x1, d, L.ln_post, n, d, 1, d, p->eps, 1.0f, p->dtype, stream))) return rc;
+      w8_note(1);
+      gin = n;
+    }
+    W8_LINK(5, vy_dec_gemv1_gated_w8(gin, L.wgu, S.s_gu, act, ffn, d, prescaled, p->eps, hs));
+    W8_LINK(4, vy_dec_gemv1_w8(act, L.wdown, S.s_down, nullptr, x1, nxt, d, ffn, hs));
+    g_gemma_w8_last[0] += 1;
+    cur = nxt;
+  }
+  if ((rc = vy_rmsnorm_fwd(cur, d, p->norm_w, n, d, 1, d, p->eps, 1.0f, p->dtype, stream))) return rc;
+  w8_note(1);
+  W8_LINK(4, vy_dec_gemv1_w8(n, w8->head_codes, w8->head_scale, nullptr, nullptr, logits, p->vocab, d, hs));
+#undef W8_LINK
+  g_gemma_w8_last[1] = 1;
+  return VY_OK;
 }

@@ -167,6 +167,28 @@ class VyGemmaPlan(C.Structure):
 GEMMA_PRESCALED = 1
 
 
+class VyGemmaW8Layer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("s_qkv", "s_o", "s_gu", "s_down")]
+
+
+class VyGemmaW8(C.Structure):
+    _fields_ = [("layers", C.POINTER(VyGemmaW8Layer)), ("head_codes", C.c_void_p), ("head_scale", C.c_void_p)]
+
+
+W8_K = (2048, 4096, 8192, 16384)   # the K the fp8-weight matrix-vector kernels exist for
+
+
+def quant_rows_fp8(w: torch.Tensor):
+    """(N, K) bf16 / fp32 on the GPU -> (codes (N, K) uint8 e4m3fn, scales (N,) fp32): vy_quant_rows_fp8."""
+    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype in (torch.bfloat16, torch.float32)
+    N, K = w.shape
+    codes = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((N,), dtype=torch.float32, device=w.device)
+    _lib.call("vy_quant_rows_fp8", w.data_ptr(), w.stride(0), codes.data_ptr(), K, scales.data_ptr(), N, K,
+              _lib.dtype_code(w.dtype), torch.cuda.current_stream(w.device).cuda_stream)
+    return codes, scales
+
+
 class GemmaDecodePlan:
     """vy_gemma_plan of a models.paligemma.PaliGemmaForConditionalGeneration and its per-layer (k, v) cache
     buffers: `step(x, pos)` runs one token through all layers, the final norm and the tied vocabulary
@@ -174,15 +196,37 @@ class GemmaDecodePlan:
 
     prescale: fold the RMSNorm weights into the projections that follow them, so the step needs no RMSNorm launch.
     None = wherever the step runs the fused matrix-vector chain (bf16, batch <= 4, widths multiples of 8); False = a plan
-    with the weights as they are (separate RMSNorm launches); True where that chain cannot run is an error."""
+    with the weights as they are (separate RMSNorm launches); True where that chain cannot run is an error.
 
-    def __init__(self, model, caches, batch: int, prescale=None):
+    weight_dtype: None = the model's weights as they are; "fp8" = every projection and a copy of the vocabulary matrix
+    quantised once to e4m3fn codes with one fp32 scale per output row (vy_quant_rows_fp8), the step then streams half
+    the bytes per token (vy_gemma_decoder_step_w8: bf16 model, batch 1, every K one of W8_K, vocab % 4 == 0; anything
+    else is a ValueError here).  With prescale the fp32 product W (1 + w_norm) is quantised, not its bf16 rounding.  The
+    model keeps its bf16 weights (prefill runs on them): the option buys time per token, not memory."""
+
+    def __init__(self, model, caches, batch: int, prescale=None, weight_dtype=None):
         from .models.paligemma import _packed
         lib = _lib.load()
         t = model.shape.text
         dt = model.embed_tokens.weight.dtype
         dev = model.embed_tokens.weight.device
         self.keep = []
+        if weight_dtype not in (None, "fp8"):
+            raise ValueError(f"weight_dtype={weight_dtype!r}: None or 'fp8'")
+        w8 = weight_dtype == "fp8"
+        if w8:
+            ks = (t.hidden_size, t.num_attention_heads * t.head_dim, t.intermediate_size)
+            why = None
+            if dt != torch.bfloat16:
+                why = f"a bf16 model (this one is {dt})"
+            elif batch != 1:
+                why = f"batch 1 (got {batch})"
+            elif any(k not in W8_K for k in ks):
+                why = f"hidden, heads * head_dim and intermediate sizes in {W8_K} (got {ks})"
+            elif t.vocab_size % 4 or t.head_dim % 4 or t.head_dim & (t.head_dim - 1):
+                why = f"vocab % 4 == 0 and a power-of-two head_dim (got {t.vocab_size}, {t.head_dim})"
+            if why:
+                raise ValueError("weight_dtype='fp8' needs " + why)
 
         def ptr(x):
             if x is None:
@@ -192,8 +236,22 @@ class GemmaDecodePlan:
             self.keep.append(x)
             return x.data_ptr()
 
+        self.weight_bytes = {}     # name -> bytes of the matrix (and its scales) that one step reads
+        self._w8 = {}              # name -> (codes, scales)
+
+        def weight(name, w):
+            """-> the pointer the plan holds for matrix `name`, and for fp8 the pointer of its scales"""
+            if not w8:
+                self.weight_bytes[name] = w.numel() * w.element_size()
+                return ptr(w), None
+            codes, scales = quant_rows_fp8(w.detach().contiguous())
+            self._w8[name] = (codes, scales)
+            self.weight_bytes[name] = codes.numel() + 4 * scales.numel()
+            return codes.data_ptr(), scales.data_ptr()
+
         layers = list(model.layers)
         arr = (VyGemmaLayer * len(layers))()
+        sarr = (VyGemmaW8Layer * len(layers))()
         # single-sequence bf16 decode: RMSNorm folded into the weights -- only where the step will run the chain that
         # skips the RMSNorm launches (the same predicate as vy_gemma_decoder_step's `fused`; the C side refuses a
         # pre-scaled plan on any other chain)
@@ -209,18 +267,24 @@ class GemmaDecodePlan:
             wgu, _ = _packed([m.gate_proj, m.up_proj], m, "_gu")
             if prescale:
                 # the norms' (1 + w) folded into the K axis of the weights that follow them (done once; the step then
-                # needs no RMSNorm launch: each product scales itself by the row's rsqrt(mean x^2 + eps))
+                # needs no RMSNorm launch: each product scales itself by the row's rsqrt(mean x^2 + eps)); fp8 codes
+                # quantise the fp32 product itself
                 with torch.no_grad():
-                    wqkv = (wqkv.float() * (1.0 + layer.input_layernorm.weight.detach().float())[None, :]).to(dt).contiguous()
-                    wgu = (wgu.float() * (1.0 + layer.post_attention_layernorm.weight.detach().float())[None, :]).to(dt).contiguous()
+                    wqkv = wqkv.float() * (1.0 + layer.input_layernorm.weight.detach().float())[None, :]
+                    wgu = wgu.float() * (1.0 + layer.post_attention_layernorm.weight.detach().float())[None, :]
+                    if not w8:
+                        wqkv, wgu = wqkv.to(dt).contiguous(), wgu.to(dt).contiguous()
             kc, vc = caches[i]
             if kc.dtype != dt or kc.shape[0] < batch or kc.stride(3) != 1 or kc.stride() != vc.stride():
                 raise ValueError(f"cache buffers {tuple(kc.shape)} do not fit (B={batch})")
-            L = arr[i]
-            L.wqkv, L.bqkv = ptr(wqkv), ptr(bqkv)
-            L.wo, L.bo = ptr(a.o_proj.weight), ptr(a.o_proj.bias)
+            L, S = arr[i], sarr[i]
+            L.wqkv, S.s_qkv = weight(f"layers.{i}.wqkv", wqkv)
+            L.bqkv = ptr(bqkv)
+            L.wo, S.s_o = weight(f"layers.{i}.wo", a.o_proj.weight)
+            L.bo = ptr(a.o_proj.bias)
             L.ln_in, L.ln_post = ptr(layer.input_layernorm.weight), ptr(layer.post_attention_layernorm.weight)
-            L.wgu, L.wdown = ptr(wgu), ptr(m.down_proj.weight)
+            L.wgu, S.s_gu = weight(f"layers.{i}.wgu", wgu)
+            L.wdown, S.s_down = weight(f"layers.{i}.wdown", m.down_proj.weight)
             L.kcache, L.vcache = kc.data_ptr(), vc.data_ptr()
             L.c_sb, L.c_sh, L.c_sl = kc.stride(0), kc.stride(1), kc.stride(2)
             self.keep += [kc, vc]
@@ -237,7 +301,18 @@ class GemmaDecodePlan:
         assert cos.is_contiguous() and sin.is_contiguous() and cos.dim() >= 2
         p.cos_tab, p.sin_tab = cos.data_ptr() + off, sin.data_ptr() + off
         p.layers = C.cast(arr, C.POINTER(VyGemmaLayer))
-        p.norm_w, p.head_w = ptr(model.norm.weight), ptr(model.embed_tokens.weight)
+        p.norm_w = ptr(model.norm.weight)
+        # the head: the (tied) embedding table; fp8 plans hold a quantised copy, the embedding lookup stays bf16
+        head, head_scale = weight("head", model.embed_tokens.weight)
+        self.w8 = None
+        if w8:
+            self.w8_layers = sarr
+            self.w8 = VyGemmaW8()
+            self.w8.layers = C.cast(sarr, C.POINTER(VyGemmaW8Layer))
+            self.w8.head_codes, self.w8.head_scale = head, head_scale
+            p.head_w = None        # nothing on this plan may be read as bf16 weights
+        else:
+            p.head_w = head
         lib.vy_gemma_ws_bytes.restype = C.c_int64
         lib.vy_gemma_ws_bytes.argtypes = [C.c_int32] * 6
         nbytes = lib.vy_gemma_ws_bytes(batch, p.d, p.h, p.dh, p.ffn, p.dtype)
@@ -255,6 +330,17 @@ class GemmaDecodePlan:
         if not 0 <= pos < self.capacity:   # the kernels write K/V at `pos` unchecked
             raise ValueError(f"position {pos} exceeds the cache size {self.capacity} (max_cache_len)")
         logits = torch.empty((self.batch, self.ldv), dtype=self.dtype, device=self.device)
-        _lib.call("vy_gemma_decoder_step", C.byref(self.plan), x.data_ptr(), int(pos), logits.data_ptr(), self.ldv,
-                  torch.cuda.current_stream().cuda_stream)
+        st = torch.cuda.current_stream().cuda_stream
+        if self.w8 is not None:
+            _lib.call("vy_gemma_decoder_step_w8", C.byref(self.plan), C.byref(self.w8), x.data_ptr(), int(pos), logits.data_ptr(),
+                      self.ldv, st)
+        else:
+            _lib.call("vy_gemma_decoder_step", C.byref(self.plan), x.data_ptr(), int(pos), logits.data_ptr(), self.ldv, st)
         return logits[:, : self.vocab]
+
+    def dequantized(self):
+        """name -> the fp32 matrix codes * scale an fp8 plan computes with ("layers.<i>.wqkv" / "wo" / "wgu" / "wdown", "head";
+        wqkv and wgu carry the norms' (1 + w) when the plan is pre-scaled)."""
+        if self.w8 is None:
+            raise ValueError("dequantized() is for weight_dtype='fp8' plans")
+        return {k: c.view(torch.float8_e4m3fn).float() * s[:, None] for k, (c, s) in self._w8.items()}

@@ -302,7 +302,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     def _weights_key(self):
         return tuple(p._version for p in self.parameters()) + (self.embed_tokens.weight.data_ptr(),)
 
-    def _generation_state(self, pixel_values, input_ids, max_cache_len: int):
+    def _generation_state(self, pixel_values, input_ids, max_cache_len: int, weight_dtype=None):
         """Everything of generate() that does not depend on the VALUES of the inputs, built once per (batch, prompt length,
         cache length) and kept while the weights are untouched: the K/V buffers (slots past the prefix are written before
         they are read, so they need no clearing between calls), the decode plan over them (its RMSNorm-folded weight copies
@@ -312,7 +312,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         t = self.shape.text
         dev, dt = pixel_values.device, self.embed_tokens.weight.dtype
         B, T = input_ids.shape
-        key = (B, T, tuple(pixel_values.shape), max_cache_len, dt, dev)
+        key = (B, T, tuple(pixel_values.shape), max_cache_len, dt, dev, weight_dtype)
         st = getattr(self, "_gen_state", None)
         wkey = self._weights_key()
         if st is not None and st["key"] == key and st["wkey"] == wkey:
@@ -348,7 +348,9 @@ class PaliGemmaForConditionalGeneration(nn.Module):
 
     @torch.no_grad()
     def generate(self, pixel_values: torch.Tensor, input_ids: torch.Tensor, max_new_tokens: int = 64,
-                 max_cache_len: int = 384) -> torch.Tensor:
+                 max_cache_len: int = 384, weight_dtype=None) -> torch.Tensor:
+        """weight_dtype="fp8": the decode steps stream e4m3fn weight codes with per-row scales (GemmaDecodePlan; batch 1,
+        bf16).  The prefill is unchanged: bf16 weights, the captured graph."""
         t = self.shape.text
         dev = pixel_values.device
         B = input_ids.shape[0]
@@ -356,7 +358,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         pos = n_img + input_ids.shape[1]
         if pos + max_new_tokens - 1 > max_cache_len:
             raise ValueError(f"{pos} prefix tokens + {max_new_tokens} new tokens exceed max_cache_len={max_cache_len}")
-        st = self._generation_state(pixel_values, input_ids, max_cache_len)
+        st = self._generation_state(pixel_values, input_ids, max_cache_len, weight_dtype)
         first = self._run_prefill(st, pixel_values, input_ids)
         # greedy loop: the first token comes from the prefill; every later one is ONE native call through the
         # stack (vy_gemma_decoder_step) plus one for the pick (vy_greedy_step) -- no per-layer Python
@@ -367,7 +369,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
         if max_new_tokens > 1:
             if st["plan"] is None:
                 from ..decode_plan import GemmaDecodePlan
-                st["plan"] = GemmaDecodePlan(self, st["caches"], B)
+                st["plan"] = GemmaDecodePlan(self, st["caches"], B, weight_dtype=weight_dtype)
             plan = st["plan"]
             scale = self._embed_scale(self.embed_tokens.weight)
             for i in range(1, max_new_tokens):
