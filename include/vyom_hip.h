@@ -269,14 +269,15 @@ int vy_layernorm_fwd(const void* x, int64_t ldx, const void* gamma, const void* 
                      int dtype, void* stream);
 
 /* vy_rmsnorm_fwd: y = x * rsqrt(mean(x^2) + eps) * (w_offset + w); Gemma uses w_offset = 1
- * (Examples/paligemma.ipynb cell 11, GemmaRMSNorm).  Statistics in fp32. */
+ * (Examples/paligemma.ipynb cell 11, GemmaRMSNorm).  Statistics in fp32.
+ * N, ldx, ldy: multiples of 8 (bf16) / 4 (f32); N <= 8192.  A row stride below N (rows would overlap) is VY_ERR_ARG. */
 int vy_rmsnorm_fwd(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int64_t M,
                    int64_t N, float eps, float w_offset, int dtype, void* stream);
 
 /* vy_gated_act_fwd: out[m, i] = act(gate_up[m, i]) * gate_up[m, I + i] -- the GeGLU of GemmaMLP
  * (Examples/paligemma.ipynb cell 11: gelu_tanh(gate_proj(x)) * up_proj(x)) and the SwiGLU of the custom
  * transformer's MLP (VyomAI/models/custom_transformer.py:88) after one packed [gate; up] projection.  Any vy_act
- * but VY_ACT_NONE. */
+ * but VY_ACT_NONE.  ldg < 2 I or ldo < I (rows would overlap) is VY_ERR_ARG, as in vy_gated_act_bwd. */
 int vy_gated_act_fwd(const void* gate_up, int64_t ldg, void* out, int64_t ldo, int64_t M, int64_t I,
                      int act, int dtype, void* stream);
 

@@ -57,25 +57,31 @@ LN_FWD_WIDTHS = {BF: (8, 64, 512, 520, 1024, 1032, 2048, 2056, 4096, 4104, 8192)
                  F32: (4, 256, 260, 512, 516, 1024, 1028, 2048, 2052, 4096)}
 LN_FWD_ROWS = (5, 7)                       # a workgroup holds four rows (one per wave): a ragged last workgroup both times
 LN_FWD_TOO_WIDE = {BF: 8200, F32: 4100}
-LN_FWD_STRIDED = {BF: 1032, F32: 516}      # the width that also runs with ldx = ldy = N + VEC
+LN_FWD_STRIDED = {BF: 1032, F32: 516}      # the width that also runs with ldx = N + VEC, ldy = N + 2 VEC
+LN_FWD_PADS = (1, 2)                       # a different pad per operand: a stride read from the wrong one shows
 LN_FWD_NO_STATS = {BF: 520, F32: 260}      # the width that also runs without mean / rstd pointers
-# offset regime: N = 768 and the widest row of every CH
+# the offset, small and constant regimes: N = 768 and the widest row of every CH
 LN_FWD_OFFSET_WIDTHS = {BF: (768, 512, 1024, 2048, 4096, 8192), F32: (768, 256, 512, 1024, 2048, 4096)}
-REGIMES = ("plain", "offset")
+REGIMES = ("plain", "offset", "small", "constant")
 
 
 def ln_fwd_cases(dtype):
     """(regime, M, N) of every forward case of a type."""
     out = [("plain", M, N) for N in LN_FWD_WIDTHS[dtype] for M in LN_FWD_ROWS]
-    return out + [("offset", M, N) for N in LN_FWD_OFFSET_WIDTHS[dtype] for M in LN_FWD_ROWS]
+    return out + [(regime, M, N) for regime in REGIMES[1:] for N in LN_FWD_OFFSET_WIDTHS[dtype] for M in LN_FWD_ROWS]
 
 
 def ln_fwd_inputs(dtype, regime, M, N):
     """x (M, N), gamma, beta (N), cast to dtype.  plain: the data of test_layernorm (mean 0.5, sigma 2).  offset: rows of
     64 + 2 randn -- E[x^2] is a thousand times the variance, so a variance taken in one pass (E[x^2] - mean^2) loses three
-    digits in fp32 and a two-pass one loses none."""
+    digits in fp32 and a two-pass one loses none.  small: 2^-9 randn, a variance of 3.8e-6 beside eps = 1e-5, so a
+    dropped eps nearly doubles rstd (on plain and offset data it moves rstd by 1.25e-6).  constant: each row one
+    bf16-exact value: the variance is 0, rstd = eps^-1/2, y = beta, and without eps 0 * inf."""
     base = rnd(M, N, seed=1)
-    x = (base * 2 + 0.5) if regime == "plain" else (64.0 + 2.0 * base)
+    if regime == "constant":
+        x = (4.0 * rnd(M, seed=7)).to(BF).float()[:, None].expand(M, N).clone()
+    else:
+        x = {"plain": base * 2 + 0.5, "offset": 64.0 + 2.0 * base, "small": base * 2.0 ** -9}[regime]
     return x.to(dtype), (1 + 0.1 * rnd(N, seed=2)).to(dtype), (0.1 * rnd(N, seed=3)).to(dtype)
 
 
@@ -106,7 +112,8 @@ LN_BWD_TOO_WIDE = {BF: 2056, F32: 1028}
 # vy_ln_colsum_slices).  257: 65 slab rows, sixteen slices of 5, three of them empty.  2049: the slab is capped at 512 rows
 # = 2048 waves, wave 0 takes a second row through the pipeline.  4100: waves 0..3 take three rows, the others two.
 LN_BWD_ROWS = (1, 3, 5, 252, 253, 257, 2049, 4100)
-LN_BWD_STRIDED = (257, 768)                # (M, N) that also runs with lddy = ldx = lddx = N + VEC, per type
+LN_BWD_STRIDED = (257, 768)                # (M, N) that also runs with a different pad per operand, per type
+LN_BWD_PADS = (1, 2, 3)                    # lddy, ldx, lddx = N + 1, 2, 3 VEC
 LN_BWD_COLSUM_ROWS = (3, 253, 257, 2049)   # partial + ColSum against vy_layernorm_bwd, at N = 768
 
 

@@ -13,7 +13,7 @@ import torch
 from tests.golden import cases_causal_lm as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VY_ERR_ARG = -1
+VY_ERR_ARG, VY_ERR_UNSUPPORTED = -1, -2
 
 
 def small():
@@ -160,6 +160,42 @@ def test_argument_errors_of_the_new_kernels_without_a_gpu():
         a = list(ok)
         a[8] = act
         assert lib.vy_gated_act_bwd(*a) == VY_ERR_ARG and b"unsupported act" in lib.vy_last_error()
+    del buf
+
+
+def test_forward_launchers_refuse_a_row_stride_below_the_row_width():
+    """vy_rmsnorm_fwd and vy_gated_act_fwd refuse what their backward launchers refuse: rows that would overlap.
+    Validation comes before any launch: nothing below reaches the device."""
+    from vyomai_amd import _lib
+    lib = _lib.load()
+    buf, p = _aligned_buffer()
+    for dtype, vec in ((_lib.VY_BF16, 8), (_lib.VY_F32, 4)):
+        # vy_rmsnorm_fwd(x, ldx, w, y, ldy, M, N, eps, w_offset, dtype, stream)
+        for ldx, ldy in ((64 - vec, 64), (64, 64 - vec), (0, 64)):
+            assert lib.vy_rmsnorm_fwd(p, ldx, p, p, ldy, 4, 64, 1e-6, 1.0, dtype, None) == VY_ERR_ARG, (ldx, ldy)
+            assert b"vy_rmsnorm_fwd: row stride below" in lib.vy_last_error(), lib.vy_last_error()
+        # vy_gated_act_fwd(gate_up, ldg, out, ldo, M, I, act, dtype, stream)
+        for ldg, ldo in ((128 - vec, 64), (64, 64), (128, 64 - vec), (128, 0)):
+            assert lib.vy_gated_act_fwd(p, ldg, p, ldo, 4, 64, _lib.ACT_SILU, dtype, None) == VY_ERR_ARG, (ldg, ldo)
+            assert b"vy_gated_act_fwd: row stride below" in lib.vy_last_error(), lib.vy_last_error()
+    del buf
+
+
+def test_rmsnorm_launchers_refuse_one_chunk_past_the_widest_row():
+    """8200 (bf16) / 8196 (fp32) forward, 8200 / 4100 backward: "too wide", on the host."""
+    from tests import prenorm_cases as P
+    from vyomai_amd import _lib
+    lib = _lib.load()
+    buf, p = _aligned_buffer()
+    for dtype in P.DTYPES:
+        code = _lib.dtype_code(dtype)
+        N = P.RMS_FWD_TOO_WIDE[dtype]
+        assert lib.vy_rmsnorm_fwd(p, N, p, p, N, 4, N, 1e-6, 1.0, code, None) == VY_ERR_UNSUPPORTED, N
+        assert b"too wide" in lib.vy_last_error()
+        N = P.RMS_BWD_TOO_WIDE[dtype]
+        # vy_rmsnorm_bwd(dy, lddy, x, ldx, w, add_to, ldadd, dx, lddx, dw, beta, ws, M, N, eps, w_offset, dtype, stream)
+        assert lib.vy_rmsnorm_bwd(p, N, p, N, p, None, 0, p, N, p, 0.0, p, 4, N, 1e-6, 1.0, code, None) == VY_ERR_UNSUPPORTED, N
+        assert b"too wide" in lib.vy_last_error()
     del buf
 
 

@@ -6,8 +6,10 @@ lanes, the variance about the mean) and a one-pass variant (E[x^2] - mean^2).  B
 (wave w takes rows w, w + W, ...), the four-wave sum of a workgroup, the slab and the sliced column sums of
 vy_colsum, with two faults: the last row of a walk of more than one row is skipped; row r uses the statistics of row
 r + W.  Asserted: the faithful restatements sit at no more than half of every bar on every case of the tables, the
-one-pass variant breaks the rstd bar on every offset case and none on the plain ones, each backward fault breaks the exact
-twin wherever a wave walks more than one row, and the twin's expected values are the same in fp64 and fp32."""
+one-pass variant breaks the rstd bar on every offset case and none on the others, a dropped eps breaks the small and the
+constant regime and passes on plain and offset data, each backward fault breaks the exact twin wherever a wave walks more
+than one row, x read with dy's row stride shows only when every operand has a different pad, and the twin's expected values
+are the same in fp64 and fp32."""
 import pytest
 import torch
 
@@ -41,7 +43,7 @@ def wave_sum(s):
     return s[:, 0]
 
 
-def ln_fwd_restated(x, gamma, beta, dtype, one_pass=False):
+def ln_fwd_restated(x, gamma, beta, dtype, one_pass=False, no_eps=False):
     v, N = x.float(), x.shape[1]
     mean = wave_sum(lane_sums(v, dtype)) / N
     if one_pass:
@@ -49,12 +51,20 @@ def ln_fwd_restated(x, gamma, beta, dtype, one_pass=False):
     else:
         d = v - mean[:, None]
         var = wave_sum(lane_sums(d * d, dtype)) / N
-    rstd = 1.0 / torch.sqrt(var + S.EPS)
+    rstd = 1.0 / torch.sqrt(var if no_eps else var + S.EPS)
     y = ((v - mean[:, None]) * rstd[:, None] * gamma.float() + beta.float()).to(dtype)
     return y, mean, rstd
 
 
 BWD_FAULTS = ("skip_last", "stats_ahead")
+
+
+def read_with_stride(t, ld, read_ld):
+    """t (M, N) laid out with a row stride of ld in a sentinel-filled buffer, read back with a row stride of read_ld."""
+    M, N = t.shape
+    buf = torch.full((M, ld), S.SENTINEL, dtype=t.dtype)
+    buf[:, :N] = t
+    return torch.as_strided(buf.reshape(-1), (M, N), (read_ld, 1))
 
 
 def colsum_restated(slab, out, acc):
@@ -82,9 +92,13 @@ def colsum_restated(slab, out, acc):
     return base + a
 
 
-def ln_bwd_restated(dy, x, gamma, mean, rstd, dtype, fault=None, dgamma=None, dbeta=None):
-    """-> dx (cast to dtype), dgamma, dbeta; dgamma / dbeta given: accumulated onto."""
+def ln_bwd_restated(dy, x, gamma, mean, rstd, dtype, fault=None, dgamma=None, dbeta=None, pads=None):
+    """-> dx (cast to dtype), dgamma, dbeta; dgamma / dbeta given: accumulated onto.  pads (of dy, of x, of dx, in chunks):
+    the operands sit in buffers with those row strides; the fault swapped_stride reads x with dy's."""
     M, N = x.shape
+    if pads is not None:
+        lddy, ldx = N + pads[0] * S.VEC[dtype], N + pads[1] * S.VEC[dtype]
+        dy, x = read_with_stride(dy, lddy, lddy), read_with_stride(x, ldx, lddy if fault == "swapped_stride" else ldx)
     WB = S.ln_bwd_ws_rows(M)
     W = 4 * WB
     xv, dv, g = x.float(), dy.float(), gamma.float()
@@ -136,6 +150,9 @@ def test_tables_cover_every_instantiation(dtype):
     assert all((M, N) in cases for N in Ns for M in (5, 257))
     assert all((M, N) in cases for M in S.LN_BWD_ROWS for N in (768, min(Ns), max(Ns)))
     assert S.LN_BWD_STRIDED in cases
+    assert len(set(S.LN_BWD_PADS)) == 3 and len(set(S.LN_FWD_PADS)) == 2 and 0 not in S.LN_BWD_PADS + S.LN_FWD_PADS
+    assert {S.dispatch_chunks(N, dtype, 16) for N in S.LN_FWD_OFFSET_WIDTHS[dtype]} == {1, 2, 4, 8, 16}      # every regime
+    assert all((g, M, N) in S.ln_fwd_cases(dtype) for g in S.REGIMES[1:] for N in S.LN_FWD_OFFSET_WIDTHS[dtype] for M in S.LN_FWD_ROWS)
 
 
 def test_row_counts_cover_the_wave_walk_and_the_column_sum_slices():
@@ -160,10 +177,12 @@ def test_adamw_sizes_reach_the_vector_path_and_the_tail():
 
 
 # ---- LayerNorm forward ------------------------------------------------------------------------------------------------
-def fwd_ratios(dtype, regime, M, N, one_pass):
+def fwd_ratios(dtype, regime, M, N, one_pass, no_eps=False):
     x, g, b = S.ln_fwd_inputs(dtype, regime, M, N)
     y, mean, rstd = S.ln_fwd_reference(x, g, b)
-    gy, gm, gr = ln_fwd_restated(x, g, b, dtype, one_pass)
+    gy, gm, gr = ln_fwd_restated(x, g, b, dtype, one_pass, no_eps)
+    if not (torch.isfinite(gy.float()).all() and torch.isfinite(gr).all()):
+        return (float("inf"),) * 3
     return (S.worst_ratio(gy, y, S.ln_fwd_y_bar(dtype, regime, g, y, mean, rstd)),
             S.worst_ratio(gm, mean, S.linear_bar(mean, *S.STAT_BAR)),
             S.worst_ratio(gr, rstd, S.linear_bar(rstd, *S.STAT_BAR)))
@@ -186,6 +205,30 @@ def test_one_pass_variance_breaks_the_offset_regime_only(dtype):
             assert rr > 1.0, (M, N, rr)
         else:
             assert max(ry, rm, rr) <= 1.0, (M, N, ry, rm, rr)
+
+
+@pytest.mark.parametrize("dtype", S.DTYPES, ids=IDS)
+def test_dropped_eps_breaks_the_small_and_constant_regimes_only(dtype):
+    """Without eps rstd nearly doubles on small data and is 1 / 0 on a constant row (y = 0 * inf); on plain and offset
+    data, a variance of 4 beside eps = 1e-5, it passes every bar at every width of 256 and more: why the two regimes are
+    there."""
+    for regime, M, N in S.ln_fwd_cases(dtype):
+        ry, rm, rr = fwd_ratios(dtype, regime, M, N, one_pass=False, no_eps=True)
+        if regime == "small":
+            assert ry > 1.0 and rr > 1.0, (M, N, ry, rr)
+        elif regime == "constant":
+            assert ry == float("inf"), (M, N, ry)
+        elif N >= 256:      # (a row of 4 or 8 elements can have a variance small enough on its own for eps to show)
+            assert max(ry, rm, rr) <= 1.0, (regime, M, N, ry, rm, rr)
+
+
+def test_a_constant_row_gives_beta():
+    for dtype in S.DTYPES:
+        x, g, b = S.ln_fwd_inputs(dtype, "constant", 5, 768)
+        assert bool((x == x[:, :1]).all()) and torch.equal(x.float(), x.to(BF).float()) and len(set(x[:, 0].tolist())) == 5
+        y, mean, rstd = S.ln_fwd_reference(x, g, b)
+        assert torch.equal(y, b.double().expand(5, 768)) and torch.equal(mean, x[:, 0].double())
+        assert torch.equal(ln_fwd_restated(x, g, b, dtype)[0], b.expand(5, 768))
 
 
 # ---- LayerNorm backward -----------------------------------------------------------------------------------------------
@@ -226,6 +269,22 @@ def test_exact_twin_is_exact_and_catches_both_faults(dtype):
             if fault == "stats_ahead" and walks_on:
                 assert not torch.equal(dg.double(), want[0])          # wrong statistics show in dgamma (dbeta has none)
     assert reachable >= 6                                             # 2049 and 4100 rows at three widths
+
+
+@pytest.mark.parametrize("dtype", S.DTYPES, ids=IDS)
+def test_swapped_stride_shows_only_with_a_different_pad_per_operand(dtype):
+    """x read with dy's row stride: invisible without pads and with the same pad on every operand (what the strided case
+    first ran with), a broken dx bar with LN_BWD_PADS."""
+    M, N = S.LN_BWD_STRIDED
+    case = S.ln_bwd_inputs(dtype, M, N)
+    dx, dg, db = S.ln_bwd_reference(*case)
+    for pads, caught in ((None, False), ((1, 1, 1), False), (S.LN_BWD_PADS, True)):
+        for fault in (None, "swapped_stride"):
+            gx, gg, gb = ln_bwd_restated(*case, dtype, fault=fault, pads=pads)
+            rx = S.worst_ratio(gx, dx, S.linear_bar(dx, *S.elementwise_bars(dtype)))
+            rg = S.worst_ratio(gg, dg, S.linear_bar(dg, *S.colsum_bars(dtype, M)))
+            assert (rx > 1.0) == (caught and fault is not None), (pads, fault, rx)
+            assert fault is not None or rg <= 0.5, (pads, rg)
 
 
 # ---- the cast's halfway values ----------------------------------------------------------------------------------------

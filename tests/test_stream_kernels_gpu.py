@@ -69,15 +69,16 @@ def bits16(t):
 
 
 # ---- 1. LayerNorm forward ---------------------------------------------------------------------------------------------
-def ln_fwd_launch(x, gamma, beta, pad, stats=True):
-    """vy_layernorm_fwd on padded buffers -> y (M, N), mean, rstd (M) (None without stats); the sentinels are checked."""
+def ln_fwd_launch(x, gamma, beta, pads=(0, 0), stats=True):
+    """vy_layernorm_fwd on buffers padded by pads = (of x, of y) elements -> y (M, N), mean, rstd (M) (None without
+    stats); the sentinels are checked."""
     L = _lib()
     M, N = x.shape
-    xv, yb = in_pad(x, pad), out_pad(M, N, pad, x.dtype)
+    xv, yb = in_pad(x, pads[0]), out_pad(M, N, pads[1], x.dtype)
     g, b = gamma.to(DEV), beta.to(DEV)
     mean = torch.full((M + 1,), S.SENTINEL, device=DEV)
     rstd = torch.full((M + 1,), S.SENTINEL, device=DEV)
-    L.call("vy_layernorm_fwd", xv.data_ptr(), N + pad, g.data_ptr(), b.data_ptr(), yb.data_ptr(), N + pad,
+    L.call("vy_layernorm_fwd", xv.data_ptr(), N + pads[0], g.data_ptr(), b.data_ptr(), yb.data_ptr(), N + pads[1],
            mean.data_ptr() if stats else None, rstd.data_ptr() if stats else None, M, N, S.EPS, L.dtype_code(x.dtype), _st())
     torch.cuda.synchronize()
     sentinel_intact(yb, M, N, "y")
@@ -98,20 +99,21 @@ def ln_fwd_params():
 @pytest.mark.parametrize("dtype,regime,N", ln_fwd_params())
 def test_layernorm_fwd(dtype, regime, N):
     """layernorm_fwd_kernel<T, CH> at both sides of every CH boundary, 5 and 7 rows; y, mean and rstd against fp64.  The
-    strided width also runs with ldx = ldy = N + VEC, another one without the statistics pointers."""
+    strided width also runs with ldx = N + VEC and ldy = N + 2 VEC, another one without the statistics pointers.  The
+    small and constant regimes are the ones a dropped eps shows in; a constant row gives y = beta."""
     print(f"{S.tname(dtype)} {regime} N={N}: layernorm_fwd_kernel<{S.tname(dtype)}, {S.dispatch_chunks(N, dtype, 16)}>")
     for M in S.LN_FWD_ROWS:
         x, g, b = S.ln_fwd_inputs(dtype, regime, M, N)
         want_y, want_mean, want_rstd = S.ln_fwd_reference(x, g, b)
         y_bar = S.ln_fwd_y_bar(dtype, regime, g, want_y, want_mean, want_rstd)
-        runs = [(0, True)]
+        runs = [((0, 0), True)]
         if regime == "plain" and N == S.LN_FWD_STRIDED[dtype]:
-            runs.append((S.VEC[dtype], True))
+            runs.append((tuple(p * S.VEC[dtype] for p in S.LN_FWD_PADS), True))
         if regime == "plain" and N == S.LN_FWD_NO_STATS[dtype]:
-            runs.append((0, False))
-        for pad, stats in runs:
-            y, mean, rstd = ln_fwd_launch(x, g, b, pad, stats)
-            what = f"M={M} pad={pad}"
+            runs.append(((0, 0), False))
+        for pads, stats in runs:
+            y, mean, rstd = ln_fwd_launch(x, g, b, pads, stats)
+            what = f"M={M} pads={pads}"
             held_to(y, want_y, y_bar, "y " + what)
             if stats:
                 held(mean, want_mean, *S.STAT_BAR, "mean " + what)
@@ -135,21 +137,23 @@ def test_layernorm_fwd_refusals(dtype):
 
 
 # ---- 2. LayerNorm backward --------------------------------------------------------------------------------------------
-def ln_bwd_launch(case, dgamma, dbeta, accumulate, pad=0):
-    """vy_layernorm_bwd on padded buffers -> dx (M, N); dgamma / dbeta are written in place; the sentinels are checked."""
+def ln_bwd_launch(case, dgamma, dbeta, accumulate, pads=(0, 0, 0)):
+    """vy_layernorm_bwd on buffers padded by pads = (of dy, of x, of dx) elements -> dx (M, N); dgamma / dbeta are written
+    in place; the sentinels are checked and the inputs must keep their bits."""
     L = _lib()
     dy, x, gamma, mean, rstd = case
     M, N = x.shape
     WB = L.load().vy_layernorm_bwd_ws_rows(M)
     assert WB == S.ln_bwd_ws_rows(M)
-    dv, xv, dxb = in_pad(dy, pad), in_pad(x, pad), out_pad(M, N, pad, x.dtype)
+    dv, xv, dxb = in_pad(dy, pads[0]), in_pad(x, pads[1]), out_pad(M, N, pads[2], x.dtype)
     g, mu, rs = gamma.to(DEV), mean.to(DEV), rstd.to(DEV)
     ws = torch.empty(2 * WB * N, dtype=F32, device=DEV)
-    L.call("vy_layernorm_bwd", dv.data_ptr(), N + pad, xv.data_ptr(), N + pad, g.data_ptr(), mu.data_ptr(), rs.data_ptr(),
-           dxb.data_ptr(), N + pad, dgamma.data_ptr(), dbeta.data_ptr(), 1.0 if accumulate else 0.0, ws.data_ptr(), M, N,
+    L.call("vy_layernorm_bwd", dv.data_ptr(), N + pads[0], xv.data_ptr(), N + pads[1], g.data_ptr(), mu.data_ptr(), rs.data_ptr(),
+           dxb.data_ptr(), N + pads[2], dgamma.data_ptr(), dbeta.data_ptr(), 1.0 if accumulate else 0.0, ws.data_ptr(), M, N,
            L.dtype_code(x.dtype), _st())
     torch.cuda.synchronize()
     sentinel_intact(dxb, M, N, "dx")
+    assert torch.equal(dv.cpu(), dy) and torch.equal(xv.cpu(), x), "an input was written"
     return dxb[:M, :N]
 
 
@@ -158,7 +162,9 @@ def ln_bwd_params():
 
 
 def bwd_pads(dtype, M, N):
-    return (0, S.VEC[dtype]) if (M, N) == S.LN_BWD_STRIDED else (0,)
+    """The pads (of dy, of x, of dx) a case runs with: none, and on the strided case a different one per operand."""
+    strided = (tuple(p * S.VEC[dtype] for p in S.LN_BWD_PADS),) if (M, N) == S.LN_BWD_STRIDED else ()
+    return ((0, 0, 0),) + strided
 
 
 @pytest.mark.parametrize("dtype,M,N", ln_bwd_params())

@@ -904,6 +904,7 @@ extern "C" int vy_rmsnorm_fwd(const void* x, int64_t ldx, const void* w, void* y
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == VY_BF16 ? 8 : 4;
   if (N % vec || ldx % vec || ldy % vec) VY_FAIL(VY_ERR_ARG, "vy_rmsnorm_fwd: N/ld must be multiples of %d", vec);
+  if (ldx < N || ldy < N) VY_FAIL(VY_ERR_ARG, "vy_rmsnorm_fwd: row stride below N");
   const int nch = (int)(N / vec);
   const dim3 grid((unsigned)vy_cdiv(M, 4)), block(256);
 #define RMS_GO(T, CH) hipLaunchKernelGGL((rmsnorm_fwd_kernel<T, CH>), grid, block, 0, st, (const T*)x, ldx, (const T*)w, (T*)y, ldy, M, (int)N, eps, w_offset)
@@ -934,6 +935,7 @@ extern "C" int vy_gated_act_fwd(const void* gate_up, int64_t ldg, void* out, int
   hipStream_t st = (hipStream_t)stream;
   const int vec = dtype == VY_BF16 ? 8 : 4;
   if (I % vec || ldg % vec || ldo % vec) VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: I/ld must be multiples of %d", vec);
+  if (ldg < 2 * I || ldo < I) VY_FAIL(VY_ERR_ARG, "vy_gated_act_fwd: row stride below the row width");
   const int64_t want = vy_cdiv(M * (I / vec), 256);
   const dim3 grid((unsigned)(want < 8192 ? want : 8192)), block(256);
 #define GA_GO(T, A) hipLaunchKernelGGL((gated_act_kernel<T, A>), grid, block, 0, st, (const T*)gate_up, ldg, (T*)out, ldo, M, (int)I, act)
