@@ -421,6 +421,34 @@ int vy_linear_wgrad_grouped_opt(const vy_wgrad_desc* descs, int32_t n, const vy_
                                 vy_adamw_ride_desc* opt, int32_t nopt, const vy_adamw_hyper* hyper, int dtype,
                                 void* stream);
 
+/* vy_linear_wgrad with data movement riding in it.  Only the 256 x 256 bf16 launch (N >= 8192, M >= 4096: the vocabulary
+ * projection) carries anything: its workgroups are dispatched in rounds of 256, and the workgroups appended behind them
+ * land on the 256 - items % 256 CUs that the last round leaves idle.  Two tables, both optional:
+ *   zero       up to 8 fp32 ranges {p, n} (p 16-byte aligned) to clear, e.g. the gradient arena before the kernels that
+ *              accumulate into it.  A range that meets dw, db, dy or x of this launch is refused (VY_ERR_ARG).
+ *   transposes the device table of vy_transpose_batched (below): tr_n descriptors, tr_total_tiles tiles, tr_dtype.  The
+ *              table lives on the device, so that no destination meets dw, db, dy or x is the CALLER's to guarantee.
+ * Nothing a rider writes may be read or written by anything else before the launch has ended (the riders' only ordering
+ * is the stream's kernel boundary).  How much rides is the launcher's decision: idle CUs x a measured per-CU rate x the
+ * estimated duration of one tile workgroup, none when the last round is full or leaves fewer than 8 CUs idle.  With
+ * both tables present each may use half of that, the zero ranges also what the transposes leave of their half.  The
+ * leading *tr_taken (out, nullable) tiles of the table ride: all, or a multiple of 8; the caller runs the rest with
+ * vy_transpose_batched_range(first = *tr_taken).  The zero ranges are taken in order: zero[i].taken (out) leading
+ * elements of each were cleared -- n, 0, or whole 65536-element chunks of the last range that fit; the caller clears
+ * the rest.  fp32, a bf16 launch of the 128 x 128 tiles and an fp32
+ * table carry nothing and report 0.  dw / db are what vy_linear_wgrad computes, bit for bit where that is itself
+ * order-fixed: the tiles keep their block-to-tile mapping. */
+typedef struct vy_zero_ride_desc {
+  float* p;
+  int64_t n;
+  int64_t taken;
+} vy_zero_ride_desc;
+struct vy_transpose_desc;
+int vy_linear_wgrad_riders(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw,
+                           float* db, float beta, const float* alpha_dev, int64_t M, int64_t N, int64_t K, int dtype,
+                           vy_zero_ride_desc* zero, int32_t nzero, const struct vy_transpose_desc* tr_descs_dev,
+                           int32_t tr_n, int32_t tr_total_tiles, int tr_dtype, int32_t* tr_taken, void* stream);
+
 /* LayerNorm backward: dx = rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma;
  * dgamma/dbeta fp32 [N] accumulated (beta) from per-block partials in `ws`
  * (ws: fp32, at least 2 * ws_rows * N elements; ws_rows = vy_layernorm_bwd_ws_rows(M)). */
@@ -630,6 +658,9 @@ typedef struct vy_transpose_desc {
 } vy_transpose_desc;              /* 48 bytes */
 int vy_transpose_batched(const vy_transpose_desc* descs_dev, int32_t n, int32_t total_tiles, int dtype,
                          void* stream);
+/* Tiles first .. first + count - 1 of the same table (what vy_linear_wgrad_riders did not take). */
+int vy_transpose_batched_range(const vy_transpose_desc* descs_dev, int32_t n, int32_t first, int32_t count, int dtype,
+                               void* stream);
 
 /* Sampling front end of the generate loops.
  * vy_greedy_step replaces reference models/decoder.py:478-507 (topk(k=1), the where() that forces prompt

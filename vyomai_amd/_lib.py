@@ -59,6 +59,7 @@ PROTOTYPES = {
     "vy_rope_fwd": [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i, _i64, _i, _i, _i, _p],
     "vy_linear_dgrad": [_p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _p],
     "vy_linear_wgrad": [_p, _i64, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _i64, _i, _p],
+    "vy_linear_wgrad_riders": [_p, _i64, _p, _i64, _p, _i64, _p, _f, _p, _i64, _i64, _i64, _i, _p, _i, _p, _i, _i, _i, _p, _p],
     "vy_linear_wgrad_grouped": [_p, _i, _i, _p],
     "vy_linear_wgrad_grouped_cs": [_p, _i, _p, _i, _i, _p],
     "vy_linear_wgrad_grouped_opt": [_p, _i, _p, _i, _p, _i, _p, _i, _p],
@@ -87,6 +88,7 @@ PROTOTYPES = {
     "vy_logprob_bwd": [_p, _i64, _p, _p, _p, _i64, _i64, _i, _p],
     "vy_logprob_fused": [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _i, _p],
     "vy_transpose_batched": [_p, _i, _i, _i, _p],
+    "vy_transpose_batched_range": [_p, _i, _i, _i, _i, _p],
     "vy_embedding_fwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _i, _p],
     "vy_embedding_bwd": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "vy_transpose": [_p, _i64, _p, _i64, _i64, _i64, _i, _p],
@@ -136,6 +138,11 @@ class VyColsumDesc(C.Structure):
 class VyAdamwRideDesc(C.Structure):
     """vy_adamw_ride_desc of include/vyom_hip.h (taken: written by the launcher)."""
     _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("p_bf16", _p), ("n", _i64), ("taken", _i64)]
+
+
+class VyZeroRideDesc(C.Structure):
+    """vy_zero_ride_desc of include/vyom_hip.h (taken: written by the launcher)."""
+    _fields_ = [("p", _p), ("n", _i64), ("taken", _i64)]
 
 
 class VyAdamwHyper(C.Structure):

@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, lazy_zero, ops
 from ._lib import ACT_GELU_ERF, ACT_NONE, VyomHipError
 from .autograd import gated_mlp
 from .layers.attention import _shadow
@@ -49,16 +49,19 @@ class _WtRegistry:
         self.entries.append(e)
         return e
 
-    def refresh(self) -> None:
-        """Re-transpose the recently used matrices for the current WEIGHT_EPOCH (once per epoch)."""
+    def refresh(self, hand_off=None):
+        """Re-transpose the recently used matrices for the current WEIGHT_EPOCH (once per epoch).
+        hand_off: a dtype whose batch is built and accounted for as usual but RETURNED instead of run -- the caller runs
+        it before anything reads a W^T (the vocabulary weight gradient carries it as rider workgroups)."""
         ep = WEIGHT_EPOCH[0]
         if self.epoch_done == ep:
-            return
+            return None
+        handed = None
         self.epoch_done = ep
         self.entries = [e for e in self.entries if e[0]() is not None]
         live = [e for e in self.entries if e[4] >= ep - 1 and getattr(e[0](), "_vy_wt_key", None) != e[1](e[0]())]
         if not live:
-            return
+            return None
         pairs = [(e[2](e[0]()), e[3]) for e in live]
         # one launch per dtype (a bf16 model and an fp32 one trained in the same process share this registry)
         for dt in sorted({s_.dtype for s_, _ in pairs}, key=str):
@@ -67,9 +70,13 @@ class _WtRegistry:
             batch = self.batches.get(dt)
             if batch is None or batch.keys != keys:
                 batch = self.batches[dt] = ops.TransposeBatch(sub)
-            batch.run()
+            if dt == hand_off:
+                handed = batch
+            else:
+                batch.run()
         for e in live:
             e[0]()._vy_wt_key = e[1](e[0]())
+        return handed
 
 
 _WT = _WtRegistry()
@@ -242,13 +249,71 @@ _GROUP_LN_COLSUMS = os.environ.get("VY_LN_COLSUM_GROUP", "1") != "0"          # 
 _wgrad_group = _WgradGroup()
 
 
-def _wgrad(dy, x, w: torch.Tensor, b: Optional[torch.Tensor], alpha: Optional[torch.Tensor] = None):
-    """-> (dw, db) to return to autograd (None when accumulated in place)."""
+class _WgradRiders:
+    """The vocabulary weight gradient (N >= 8192, M >= 4096: the one 256 x 256 launch that is not grouped) runs 2.3 rounds
+    of tiles on the benchmark model and leaves 177 CUs idle for a tile time.  When it is the first launch of backward it
+    carries, as rider workgroups (ops.linear_wgrad_riders), the two passes over memory that depend on nothing backward
+    produces: the W^T refresh of the weight epoch and the zeroing of the gradient arena (lazy_zero).  What the launcher's
+    budget does not take follows in plain launches right behind it.
+    on: VY_WGRAD_RIDERS (default on), overridden per backward by FlatTrainer(wgrad_riders=); stats: the running
+    trainer's per-step counters."""
+
+    def __init__(self):
+        self.on = os.environ.get("VY_WGRAD_RIDERS", "1") != "0"
+        self.stats = None
+
+    def carries(self, dy, w, b) -> bool:
+        """Will _wgrad(dy, ., w, b) be the direct 256 x 256 bf16 launch?"""
+        return (self.on and dy.dtype == BF16 and dy.is_cuda and _direct(w) and (b is None or _direct(b))
+                and w.shape[0] >= 8192 and dy.numel() // dy.shape[-1] >= 4096 and w.shape[1] % 8 == 0)
+
+    def launch(self, dy, x, w, b, alpha, claim) -> None:
+        """The accumulating weight gradient of (w, b) with whatever may ride.  The transposes read the weights' shadows
+        and write the W^T copies, the zero ranges are arena gradients of OTHER parameters: none of them is dy, x, w.grad
+        or b.grad (the launcher checks the zero ranges itself)."""
+        zero = lazy_zero.take(claim) or []
+        batch = _WT.refresh(hand_off=dy.dtype)
+        dw, db = w.grad, None if b is None else b.grad
+        if not zero and batch is None:
+            ops.linear_wgrad(dy, x, dw, db, accumulate=True, alpha=alpha)
+            return
+        try:
+            took, tiles = ops.linear_wgrad_riders(dy, x, dw, db, True, alpha, zero=zero[:8], transposes=batch)
+        except BaseException:   # the refresh is already accounted for and the claim is spent: do both before giving up
+            if batch is not None:
+                batch.run()
+            for z in zero:
+                z.zero_()
+            raise
+        took += [0] * (len(zero) - len(took))
+        if batch is not None:
+            batch.run(first=tiles)
+        for z, n in zip(zero, took):
+            if n < z.numel():
+                z[n:].zero_()
+        st = self.stats if claim is None or claim.stats is None else claim.stats
+        if st is not None:
+            st["zero_rode_bytes"] += 4 * sum(took)
+            st["zero_plain_bytes"] += 4 * sum(z.numel() - n for z, n in zip(zero, took))
+            if batch is not None:
+                st["wt_rode_tiles"] += tiles
+                st["wt_plain_tiles"] += batch.total - tiles
+
+
+_wgrad_riders = _WgradRiders()
+
+
+def _wgrad(dy, x, w: torch.Tensor, b: Optional[torch.Tensor], alpha: Optional[torch.Tensor] = None, zero_claim=None):
+    """-> (dw, db) to return to autograd (None when accumulated in place).  zero_claim: LMHeadLossFn's claim on the
+    arena's pending zeroing (only the launch that _wgrad_riders.carries was true for is given one)."""
     if _direct(w) and (b is None or _direct(b)):
         if _wgrad_group.wants(dy, w, alpha):
             _wgrad_group.add(dy, x, w, b)
             return None, None
-        ops.linear_wgrad(dy, x, w.grad, None if b is None else b.grad, accumulate=True, alpha=alpha)
+        if _wgrad_riders.carries(dy, w, b):
+            _wgrad_riders.launch(dy, x, w, b, alpha, zero_claim)
+        else:
+            ops.linear_wgrad(dy, x, w.grad, None if b is None else b.grad, accumulate=True, alpha=alpha)
         _notify(w, b)
         return None, None
     dw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
@@ -839,6 +904,14 @@ class LMHeadLossFn(torch.autograd.Function):
         ctx.params = (wd, bd, ln_w, ln_b, wv, bias)
         ctx.ignore = ignore_index
         ctx.fused = fused
+        # the arena's pending zeroing rides in this node's first backward launch, if the trainer finds this node at the
+        # root of the loss (lazy_zero); wv / bias are marked so that train_step() clears THEIR gradients at once
+        ctx.zero_claim = None
+        if _wgrad_riders.carries(logits, wv, bias):
+            wv._vy_carrier = True
+            if bias is not None:
+                bias._vy_carrier = True
+            ctx.zero_claim = lazy_zero.PENDING.claim_for(wv.grad, None if bias is None else bias.grad)
         if sampled is None:
             return loss
         sampled = sampled.view(labels.shape)
@@ -852,11 +925,18 @@ class LMHeadLossFn(torch.autograd.Function):
         dt = hidden.dtype
         logits = buf[:, :wv.shape[0]]
         alpha = _xent_backward(logits, shifted, ctx.ignore, lse, acc, ctx.fused, gout)
+        # the weight gradient FIRST when it carries riders (_WgradRiders): both GEMMs only read buf and n, that launch does
+        # the W^T refresh the dgrad reads, and its parameters' bucket is final one launch earlier.  Any other launch keeps
+        # its place behind the dgrad
+        first = _wgrad_riders.carries(logits, wv, bias)
+        if first:
+            dwv, dbias = _wgrad(logits, n.view(buf.shape[0], -1), wv, bias, alpha=alpha, zero_claim=ctx.zero_claim)
         # contract over the padded vocabulary width (pad columns of both operands are zero)
         dn = ops.linear_dgrad(buf, _wt_padded(wv, dt, buf.shape[1]))
         if alpha is not None:
             dn = dn * alpha.to(dt)
-        dwv, dbias = _wgrad(logits, n.view(buf.shape[0], -1), wv, bias, alpha=alpha)
+        if not first:
+            dwv, dbias = _wgrad(logits, n.view(buf.shape[0], -1), wv, bias, alpha=alpha)
         dh, dwd, dbd, dgam, dbet = _head_transform_backward(dn.view(g.shape), hidden, pre, g, mean, rstd, wd, bd, ln_w, ln_b)
         return dh, None, None, dwd, dbd, dgam, dbet, dwv, dbias, None, None, None, None
 

@@ -18,6 +18,7 @@
 // (dS = P o (dP - rowsum(dO o O))).
 #include "vy_attn_tile.h"
 #include "vy_colsum.h"
+#include "vy_transpose_tile.h"
 #include <float.h>
 #include <string.h>
 
@@ -334,6 +335,14 @@ struct WgradMma16 {
   }
 };
 
+// The stage memory of a weight-gradient workgroup: one LDS array per size, so that a workgroup which never runs the tile
+// body (a transposing rider, below) can use the same bytes
+template <int BYTES>
+__device__ __forceinline__ char* wgrad_smem() {
+  __shared__ __attribute__((aligned(16))) char smem[BYTES];
+  return smem;
+}
+
 // The ring: NS stages of LDS, the loads of the next NS-1 stages in flight while a stage is multiplied; a stage is
 // waited for with a COUNTED vmcnt (its 2 PP LDS-DMA instructions are the wave's oldest) and one raw s_barrier.
 template <int BN, int BKW, int MS, int NS>
@@ -350,7 +359,7 @@ __device__ __forceinline__ void wgrad_tn_bf16_body(
   typedef WgradTile<BN, MS, MF16> Tile;
   typedef std::conditional_t<MF16, WgradMma16<Tile>, WgradMma32<Tile>> Mma;
   constexpr int STAGE = Tile::STAGE, PS = 2 * Tile::PP;   // LDS-DMA instructions per wave and stage
-  __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
+  char* const smem = wgrad_smem<NS * STAGE>();
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave >> 1, wk = wave & 1;
@@ -382,13 +391,68 @@ __device__ __forceinline__ void wgrad_tn_bf16_body(
   mma.epilogue(dW, lddw, db, do_db, alpha, n0 + wn * 64, k0 + wk * Tile::WKT, N, K);
 }
 
+// Riders of the single-launch 256 x 256 weight gradient (vy_linear_wgrad_riders): the vocabulary projection's 591 tiles
+// are 2.31 rounds on 256 CUs, so for about one tile time 177 CUs have nothing to do.  The workgroups behind the
+// `items` tile workgroups are dispatched last and move data that no kernel before the launch's end reads or writes:
+//   transposing riders  WGRAD_RIDE_TR_TILES consecutive 64 x 64 tiles of a vy_transpose_batched table each (the W^T
+//                       refresh), through the stage memory
+//   zero riders         one WGRAD_RIDE_ZERO_CHUNK of one fp32 range each (the gradient arena), 16-byte stores
+struct ZeroRange { float* p; int64_t n; int blk0; };   // blk0: first chunk of this range
+struct WgradRiders {
+  ZeroRange z[8]; int nz;
+  const vy_transpose_desc* tr; int tr_n, tr_tiles, tr_blocks;   // tr_tiles: the leading tiles that ride; tr_blocks: their workgroups
+  int items;                                                    // tile workgroups of the launch (= the grid without riders)
+};
+constexpr int WGRAD_RIDE_TR_TILES = 8;          // 8 x 8.25 KiB of the 128-KiB stage memory; 64 KiB read + 64 KiB written per rider
+constexpr int WGRAD_RIDE_ZERO_CHUNK = 1 << 16;  // floats per zero rider (256 KiB)
+
+template <int NT>
+__device__ __forceinline__ void zero_ride_chunk(const ZeroRange& r, int chunk) {
+  const int64_t c0 = (int64_t)chunk * WGRAD_RIDE_ZERO_CHUNK;
+  const int64_t c1 = c0 + WGRAD_RIDE_ZERO_CHUNK < r.n ? c0 + WGRAD_RIDE_ZERO_CHUNK : r.n;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t i = c0 + (int64_t)threadIdx.x * 4; i < c1; i += NT * 4) {
+    if (i + 3 < c1) {
+      *reinterpret_cast<f32x4*>(r.p + i) = z4;
+    } else {   // the element-wise tail of a range
+      for (int e = 0; e < 4; ++e)
+        if (i + e < c1) r.p[i + e] = 0.f;
+    }
+  }
+}
+
 template <int BN, int BKW, int MS, int NS>
 __global__ __launch_bounds__(BN * 2, BN == 128 ? 2 : 1) void wgrad_tn_bf16_kernel(
     const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X, int64_t ldx,
     float* __restrict__ dW, int64_t lddw, float* __restrict__ db, const float* __restrict__ alpha_dev,
-    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk) {
+    int M, int N, int K, int tiles_k, int tiles_nk, int m_chunk, WgradRiders rd) {
+  if constexpr (BN == 256) {
+    if ((int)blockIdx.x >= rd.items) {   // (workgroup-uniform) the riders: dispatched behind the tiles, onto the idle CUs
+      const int rb = (int)blockIdx.x - rd.items;
+      if (rb < rd.tr_blocks) {
+        static_assert(WGRAD_RIDE_TR_TILES * VyTransposeTile<bf16>::ELEMS * 2 <= NS * WgradTile<BN, MS, true>::STAGE,
+                      "the riders' LDS tiles alias the stage memory");
+        const int first = rb * WGRAD_RIDE_TR_TILES;
+        vy_transpose_tiles<bf16, WGRAD_RIDE_TR_TILES, BN * 2>(rd.tr, rd.tr_n, first, min(WGRAD_RIDE_TR_TILES, rd.tr_tiles - first),
+                                                             reinterpret_cast<bf16*>(wgrad_smem<NS * WgradTile<BN, MS, true>::STAGE>()));
+        return;
+      }
+      const int blk = rb - rd.tr_blocks;
+      int d = 0;
+#pragma unroll
+      for (int i = 1; i < 8; ++i)
+        if (i < rd.nz && blk >= rd.z[i].blk0) d = i;
+      ZeroRange r = rd.z[0];
+#pragma unroll
+      for (int i = 1; i < 8; ++i)
+        if (d == i) r = rd.z[i];
+      zero_ride_chunk<BN * 2>(r, blk - r.blk0);
+      return;
+    }
+  }
+  // the tiles keep the block-to-tile mapping of a grid without riders
   wgrad_tn_bf16_body<BN, BKW, MS, NS>(dY, lddy, X, ldx, dW, lddw, db, alpha_dev, M, N, K, tiles_k, tiles_nk, m_chunk,
-                                      xcd_remap(blockIdx.x, gridDim.x));
+                                      xcd_remap(blockIdx.x, rd.items));
 }
 
 // Several weight gradients in ONE launch (vy_linear_wgrad_grouped): the four GEMMs of a transformer layer
@@ -968,10 +1032,57 @@ WgradSplit wgrad_split(int64_t M, int64_t want) {
 
 }  // namespace
 
-extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
-                               int64_t lddw, float* db, float beta, const float* alpha_dev, int64_t M,
-                               int64_t N, int64_t K, int dtype, void* stream) {
-  const char* who = "vy_linear_wgrad";
+// ---- how much AdamW rides in a grouped launch (the one statement of the rule) --------------------------------
+// budget = idle CUs x what one CU streams x how long the longest weight-gradient workgroup runs.
+// ADAMW_RIDE_CU_BYTES_PER_US: one rider workgroup per CU, 40 workgroups on an otherwise idle chip stream 18.6 GB/s each
+// (tools/bench_adamw_ride.py, DESIGN section 3 "AdamW in the grouped launch"); beside the tiles they share L2 and HBM with
+// the tiles' loads, and the grouped kernel already grows at 16, so 16 it is.  ADAMW_RIDE_ITEM_US: wgrad_tn_bf16_grouped_kernel<256,256,32,4> at the
+// benchmark layer (108 tiles x 2 M-splits, 8192 rows per workgroup) takes 276 us (profiles/r04_train_step_kernel_stats.csv);
+// every workgroup is a 256 x 256 tile, so its time scales with its rows.
+constexpr double ADAMW_RIDE_CU_BYTES_PER_US = 16000.0;
+constexpr double ADAMW_RIDE_ITEM_US = 276.0;
+constexpr int64_t ADAMW_RIDE_ITEM_ROWS = 8192;
+constexpr int ADAMW_RIDE_MIN_IDLE_CUS = 8;
+constexpr int VY_CUS = 256;
+
+// bytes a launch of `items` weight-gradient workgroups of at most `rows` rows may carry (items = 0: no limit, nothing to slow down)
+static int64_t adamw_ride_budget(int64_t items, int64_t rows) {
+  if (items == 0) return INT64_MAX;
+  const int64_t idle = VY_CUS - items;
+  if (idle < ADAMW_RIDE_MIN_IDLE_CUS) return 0;
+  return (int64_t)((double)idle * ADAMW_RIDE_CU_BYTES_PER_US * ADAMW_RIDE_ITEM_US * (double)rows / (double)ADAMW_RIDE_ITEM_ROWS);
+}
+
+static bool ranges_meet(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+  if (!a || !b || abytes <= 0 || bbytes <= 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+// ---- how much rides behind the single-launch 256 x 256 weight gradient (vy_linear_wgrad_riders) ------------------
+// The riders are dispatched behind ALL tile workgroups, so what they find idle is the last round's remainder:
+// 256 - items % 256 CUs for one tile time (none when the last round is full).  The tile time is ADAMW_RIDE_ITEM_US
+// scaled by the workgroup's rows, as above.  WGRAD_RIDE_CU_BYTES_PER_US: see DESIGN section 3 "Riders in the
+// vocabulary weight gradient" (tools/bench_wgrad_riders.py).
+constexpr double WGRAD_RIDE_CU_BYTES_PER_US = 12000.0;
+
+static int64_t wgrad_ride_budget(int64_t items, int64_t rows) {
+  const int64_t last = items % VY_CUS;
+  if (last == 0) return 0;
+  const int64_t idle = VY_CUS - last;
+  if (idle < ADAMW_RIDE_MIN_IDLE_CUS) return 0;
+  return (int64_t)((double)idle * WGRAD_RIDE_CU_BYTES_PER_US * ADAMW_RIDE_ITEM_US * (double)rows / (double)ADAMW_RIDE_ITEM_ROWS);
+}
+
+// vy_linear_wgrad and vy_linear_wgrad_riders.  The riders (zero / ntr / tr_taken all optional) are carried by the `big`
+// bf16 branch only, as far as wgrad_ride_budget goes: the leading transposing tiles of the table, then the zero ranges in
+// order, a range that does not fit whole gives its leading chunks.  Every other path carries nothing and reports 0.
+static int linear_wgrad_impl(const char* who, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
+                             int64_t lddw, float* db, float beta, const float* alpha_dev, int64_t M, int64_t N, int64_t K,
+                             int dtype, vy_zero_ride_desc* zero, int32_t nzero, const vy_transpose_desc* tr_dev,
+                             int32_t tr_n, int32_t tr_total, int32_t* tr_taken, void* stream) {
+  for (int i = 0; i < nzero; ++i) zero[i].taken = 0;
+  if (tr_taken) *tr_taken = 0;
   if (dtype != VY_BF16 && dtype != VY_F32) VY_FAIL(VY_ERR_ARG, "%s: bad dtype %d", who, dtype);
   if (!dy || !x || !dw || M <= 0 || N <= 0 || K <= 0) VY_FAIL(VY_ERR_ARG, "%s: bad arguments", who);
   if (dtype == VY_F32) {
@@ -1001,39 +1112,82 @@ extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int6
   const int tiles_k = (int)vy_cdiv(K, BT), tiles = (int)vy_cdiv(N, BT) * tiles_k;
   // 128 x 128: ~1.5 workgroups per CU; 256 x 256: at most one round of 256 workgroups
   const WgradSplit sp = wgrad_split(M, big ? 256 / tiles : vy_cdiv(384, tiles));
+  const int64_t items = tiles * sp.splits;
+  WgradRiders rd;
+  memset(&rd, 0, sizeof(rd));
+  rd.items = (int)items;
+  int64_t riders = 0;
+  if (big) {
+    int64_t left = wgrad_ride_budget(items, sp.m_chunk);
+    if (tr_dev && tr_n > 0 && tr_total > 0) {
+      const int64_t tile_bytes = 2 * 64 * 64 * 2;   // read + written, bf16
+      // with both tables present each may use half of the budget, and the zero ranges what the transposes leave of theirs
+      const int64_t mine = nzero > 0 ? left / 2 : left;
+      int64_t take = tr_total;
+      if (mine / tile_bytes < take) take = mine / tile_bytes / WGRAD_RIDE_TR_TILES * WGRAD_RIDE_TR_TILES;
+      if (take > 0) {
+        rd.tr = tr_dev; rd.tr_n = tr_n; rd.tr_tiles = (int)take; rd.tr_blocks = (int)vy_cdiv(take, WGRAD_RIDE_TR_TILES);
+        riders += rd.tr_blocks;
+        left -= take * tile_bytes;
+        if (tr_taken) *tr_taken = (int32_t)take;
+      }
+    }
+    int64_t chunks = 0;
+    for (int i = 0; i < nzero; ++i) {
+      int64_t take = zero[i].n;
+      if (left / 4 < take) take = left / 4 / WGRAD_RIDE_ZERO_CHUNK * WGRAD_RIDE_ZERO_CHUNK;
+      if (take <= 0) break;
+      ZeroRange& r = rd.z[rd.nz++];
+      r.p = zero[i].p; r.n = take; r.blk0 = (int)chunks;
+      chunks += vy_cdiv(take, WGRAD_RIDE_ZERO_CHUNK);
+      zero[i].taken = take;
+      left -= take * 4;
+      if (take < zero[i].n) break;
+    }
+    for (int i = rd.nz; i < 8; ++i) rd.z[i] = rd.z[0];
+    riders += chunks;
+  }
+  if (items + riders > INT32_MAX) VY_FAIL(VY_ERR_ARG, "%s: too many workgroups", who);
   auto kernel = big ? wgrad_tn_bf16_kernel<256, 256, 32, 4> : wgrad_tn_bf16_kernel<128, 128, 64, 2>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * sp.splits)), dim3(BT * 2), 0, st, (const bf16*)dy, lddy, (const bf16*)x,
-                     ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, (int)K, tiles_k, tiles, (int)sp.m_chunk);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(items + riders)), dim3(BT * 2), 0, st, (const bf16*)dy, lddy, (const bf16*)x,
+                     ldx, dw, lddw, db, alpha_dev, (int)M, (int)N, (int)K, tiles_k, tiles, (int)sp.m_chunk, rd);
   VY_CHECK_LAUNCH(who);
   return VY_OK;
 }
 
-// ---- how much AdamW rides in a grouped launch (the one statement of the rule) --------------------------------
-// budget = idle CUs x what one CU streams x how long the longest weight-gradient workgroup runs.
-// ADAMW_RIDE_CU_BYTES_PER_US: one rider workgroup per CU, 40 workgroups on an otherwise idle chip stream 18.6 GB/s each
-// (tools/bench_adamw_ride.py, DESIGN section 3 "AdamW in the grouped launch"); beside the tiles they share L2 and HBM with
-// the tiles' loads, and the grouped kernel already grows at 16, so 16 it is.  ADAMW_RIDE_ITEM_US: wgrad_tn_bf16_grouped_kernel<256,256,32,4> at the
-// benchmark layer (108 tiles x 2 M-splits, 8192 rows per workgroup) takes 276 us (profiles/r04_train_step_kernel_stats.csv);
-// every workgroup is a 256 x 256 tile, so its time scales with its rows.
-constexpr double ADAMW_RIDE_CU_BYTES_PER_US = 16000.0;
-constexpr double ADAMW_RIDE_ITEM_US = 276.0;
-constexpr int64_t ADAMW_RIDE_ITEM_ROWS = 8192;
-constexpr int ADAMW_RIDE_MIN_IDLE_CUS = 8;
-constexpr int VY_CUS = 256;
-
-// bytes a launch of `items` weight-gradient workgroups of at most `rows` rows may carry (items = 0: no limit, nothing to slow down)
-static int64_t adamw_ride_budget(int64_t items, int64_t rows) {
-  if (items == 0) return INT64_MAX;
-  const int64_t idle = VY_CUS - items;
-  if (idle < ADAMW_RIDE_MIN_IDLE_CUS) return 0;
-  return (int64_t)((double)idle * ADAMW_RIDE_CU_BYTES_PER_US * ADAMW_RIDE_ITEM_US * (double)rows / (double)ADAMW_RIDE_ITEM_ROWS);
+extern "C" int vy_linear_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
+                               int64_t lddw, float* db, float beta, const float* alpha_dev, int64_t M,
+                               int64_t N, int64_t K, int dtype, void* stream) {
+  return linear_wgrad_impl("vy_linear_wgrad", dy, lddy, x, ldx, dw, lddw, db, beta, alpha_dev, M, N, K, dtype, nullptr, 0,
+                           nullptr, 0, 0, nullptr, stream);
 }
 
-static bool ranges_meet(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-  if (!a || !b || abytes <= 0 || bbytes <= 0) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+extern "C" int vy_linear_wgrad_riders(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw,
+                                      float* db, float beta, const float* alpha_dev, int64_t M, int64_t N, int64_t K,
+                                      int dtype, vy_zero_ride_desc* zero, int32_t nzero,
+                                      const vy_transpose_desc* tr_descs_dev, int32_t tr_n, int32_t tr_total_tiles,
+                                      int tr_dtype, int32_t* tr_taken, void* stream) {
+  const char* who = "vy_linear_wgrad_riders";
+  if (nzero < 0 || nzero > 8 || (nzero > 0 && !zero)) VY_FAIL(VY_ERR_ARG, "%s: 0..8 zero ranges", who);
+  if (tr_n < 0 || tr_total_tiles < 0 || (tr_n > 0 && (!tr_descs_dev || tr_total_tiles <= 0)))
+    VY_FAIL(VY_ERR_ARG, "%s: bad transpose table", who);
+  if (!dy || !x || !dw || M <= 0 || N <= 0 || K <= 0) VY_FAIL(VY_ERR_ARG, "%s: bad arguments", who);
+  const int64_t esz = dtype == VY_F32 ? 4 : 2;
+  for (int i = 0; i < nzero; ++i) {
+    const vy_zero_ride_desc& z = zero[i];
+    if (!z.p || z.n <= 0) VY_FAIL(VY_ERR_ARG, "%s: zero range %d: bad arguments", who, i);
+    if ((uintptr_t)z.p % 16) VY_FAIL(VY_ERR_ARG, "%s: zero range %d must be 16-byte aligned", who, i);
+    // no data dependence on this launch: a rider writes nothing the tiles read or accumulate into
+    if (ranges_meet(z.p, z.n * 4, dw, ((N - 1) * lddw + K) * 4) || ranges_meet(z.p, z.n * 4, db, N * 4) ||
+        ranges_meet(z.p, z.n * 4, dy, ((M - 1) * lddy + N) * esz) || ranges_meet(z.p, z.n * 4, x, ((M - 1) * ldx + K) * esz))
+      VY_FAIL(VY_ERR_ARG, "%s: zero range %d intersects an operand or a gradient of the same launch", who, i);
+  }
+  // (the transposes' destinations live in a device table: that they meet none of dw, db, dy, x is the caller's to guarantee)
+  if (tr_n > 0 && tr_dtype != VY_BF16) { tr_descs_dev = nullptr; tr_n = 0; }   // the riders transpose bf16 only: nothing rides
+  return linear_wgrad_impl(who, dy, lddy, x, ldx, dw, lddw, db, beta, alpha_dev, M, N, K, dtype, zero, nzero, tr_descs_dev,
+                           tr_n, tr_total_tiles, tr_taken, stream);
 }
+
 
 static int wgrad_grouped(const char* who, const vy_wgrad_desc* descs, int32_t n, const vy_colsum_desc* cs, int32_t ncs,
                         vy_adamw_ride_desc* opt, int32_t nopt, const vy_adamw_hyper* hy, int dtype, void* stream) {

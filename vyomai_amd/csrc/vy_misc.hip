@@ -3,6 +3,7 @@
 // accesses per lane; LayerNorm keeps the whole row in registers (one wave per row).
 #include "vy_common.h"
 #include "vy_colsum.h"
+#include "vy_transpose_tile.h"
 #include <stdarg.h>
 #include <string.h>
 
@@ -393,58 +394,10 @@ __global__ void transpose_kernel(const T* __restrict__ in, int64_t ldin, T* __re
 // all the W^T copies of a model in ONE launch (the per-matrix launches are latency-bound: ~8 us for
 // a 1-5 MB matrix, 50 of them per training step): block -> matrix by bisection of the tile prefix
 template <typename T>
-__global__ __launch_bounds__(256) void transpose_batched_kernel(const vy_transpose_desc* __restrict__ descs, int n) {
-  // 64 x 64 tile (tile0 / tiles_c count 64-wide tiles): 16-byte loads along the input rows, 16-byte
-  // stores along the output rows, the transposition through LDS (row pitch 66 elements: the eight
-  // column reads of a store hit different banks)
-  constexpr int VEC = 16 / (int)sizeof(T);   // 8 (bf16) or 4 (fp32)
-  constexpr int CPRW = 64 / VEC;              // 16-byte chunks per 64-element row
-  __shared__ T tile[64][66];
-  int lo = 0, hi = n - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (descs[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-  }
-  const vy_transpose_desc d = descs[lo];
-  const int t = b - d.tile0;
-  const int c0 = (t % d.tiles_c) * 64, r0 = (t / d.tiles_c) * 64;
-  const T* in = (const T*)d.in;
-  T* out = (T*)d.out;
-  const bool vec_in = (d.ldin % VEC) == 0 && ((uintptr_t)in % 16) == 0;
-  const bool vec_out = (d.ldout % VEC) == 0 && ((uintptr_t)out % 16) == 0;
-  for (int c = threadIdx.x; c < 64 * CPRW; c += 256) {
-    const int r = c / CPRW, cc = (c % CPRW) * VEC;
-    const int gr = r0 + r, gc = c0 + cc;
-    if (gr >= d.R) continue;
-    if (vec_in && gc + VEC <= d.C) {
-      typedef typename Chunk<T>::Raw Raw;
-      const Raw raw = *reinterpret_cast<const Raw*>(in + (int64_t)gr * d.ldin + gc);
-      const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) tile[r][cc + k] = e[k];
-    } else {
-      for (int k = 0; k < VEC; ++k)
-        if (gc + k < d.C) tile[r][cc + k] = in[(int64_t)gr * d.ldin + gc + k];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < 64 * CPRW; c += 256) {
-    const int oc = c / CPRW, rr = (c % CPRW) * VEC;   // output row = input column c0 + oc
-    const int gc = c0 + oc, gr = r0 + rr;
-    if (gc >= d.C) continue;
-    if (vec_out && gr + VEC <= d.R) {
-      typedef typename Chunk<T>::Raw Raw;
-      Raw raw;
-      T* e = reinterpret_cast<T*>(&raw);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) e[k] = tile[rr + k][oc];
-      *reinterpret_cast<Raw*>(out + (int64_t)gc * d.ldout + gr) = raw;
-    } else {
-      for (int k = 0; k < VEC; ++k)
-        if (gr + k < d.R) out[(int64_t)gc * d.ldout + gr + k] = tile[rr + k][oc];
-    }
-  }
+__global__ __launch_bounds__(256) void transpose_batched_kernel(const vy_transpose_desc* __restrict__ descs, int n, int first) {
+  // one 64 x 64 tile (tile0 / tiles_c count 64-wide tiles) per workgroup: vy_transpose_tile.h
+  __shared__ T tile[VyTransposeTile<T>::ELEMS];
+  vy_transpose_tiles<T, 1, 256>(descs, n, first + (int)blockIdx.x, 1, tile);
 }
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -1200,17 +1153,23 @@ extern "C" int vy_transpose(const void* in, int64_t ldin, void* out, int64_t ldo
   return VY_OK;
 }
 
-extern "C" int vy_transpose_batched(const vy_transpose_desc* descs_dev, int32_t n, int32_t total_tiles, int dtype,
-                                    void* stream) {
-  if (!descs_dev || n <= 0 || total_tiles <= 0) VY_FAIL(VY_ERR_ARG, "vy_transpose_batched: bad arguments");
+// tiles first .. first + count - 1 of the table (the whole table: 0, total_tiles)
+extern "C" int vy_transpose_batched_range(const vy_transpose_desc* descs_dev, int32_t n, int32_t first, int32_t count,
+                                          int dtype, void* stream) {
+  if (!descs_dev || n <= 0 || first < 0 || count <= 0) VY_FAIL(VY_ERR_ARG, "vy_transpose_batched: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VY_BF16)
-    hipLaunchKernelGGL(transpose_batched_kernel<bf16>, dim3((unsigned)total_tiles), dim3(256), 0, st, descs_dev, (int)n);
+    hipLaunchKernelGGL(transpose_batched_kernel<bf16>, dim3((unsigned)count), dim3(256), 0, st, descs_dev, (int)n, (int)first);
   else if (dtype == VY_F32)
-    hipLaunchKernelGGL(transpose_batched_kernel<float>, dim3((unsigned)total_tiles), dim3(256), 0, st, descs_dev, (int)n);
+    hipLaunchKernelGGL(transpose_batched_kernel<float>, dim3((unsigned)count), dim3(256), 0, st, descs_dev, (int)n, (int)first);
   else VY_FAIL(VY_ERR_ARG, "vy_transpose_batched: bad dtype %d", dtype);
   VY_CHECK_LAUNCH("vy_transpose_batched");
   return VY_OK;
+}
+
+extern "C" int vy_transpose_batched(const vy_transpose_desc* descs_dev, int32_t n, int32_t total_tiles, int dtype,
+                                    void* stream) {
+  return vy_transpose_batched_range(descs_dev, n, 0, total_tiles, dtype, stream);
 }
 
 extern "C" int vy_adamw_step_gated(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,

@@ -367,6 +367,32 @@ def linear_wgrad(dy: Tensor, x: Tensor, dw: Tensor, db: Optional[Tensor], accumu
          dw.stride(0), _ptr(db), 1.0 if accumulate else 0.0, _ptr(alpha), M, N, K, dtype_code(dy.dtype), _stream())
 
 
+def linear_wgrad_riders(dy: Tensor, x: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool,
+                        alpha: Optional[Tensor] = None, zero=(), transposes: Optional["TransposeBatch"] = None):
+    """linear_wgrad with data movement riding on the CUs its last round of tiles leaves idle (vy_linear_wgrad_riders).
+    zero: up to 8 contiguous fp32 tensors to clear; transposes: a TransposeBatch none of whose destinations is dy, x,
+    dw or db.  -> ([elements of each zero range that were cleared], tiles of the batch that were transposed): the
+    launcher takes what its budget allows (nothing outside the 256 x 256 bf16 launch), the rest is the caller's."""
+    _need_gpu(dy, x, dw, db, alpha, *zero)
+    assert alpha is None or (alpha.dtype == torch.float32 and alpha.numel() == 1)
+    d2, x2 = _rows(dy), _rows(x)
+    M, N = d2.shape
+    K = x2.shape[1]
+    assert dw.dtype == torch.float32 and dw.shape == (N, K) and dw.stride(1) == 1
+    assert len(zero) <= 8 and all(z.dtype == torch.float32 and z.is_contiguous() for z in zero)
+    import ctypes as C
+    zd = (_lib.VyZeroRideDesc * max(1, len(zero)))()
+    for i, z in enumerate(zero):
+        zd[i] = _lib.VyZeroRideDesc(z.data_ptr(), z.numel(), 0)
+    took = C.c_int32(0)
+    tb = transposes
+    call("vy_linear_wgrad_riders", d2.data_ptr(), d2.stride(0), x2.data_ptr(), x2.stride(0), dw.data_ptr(),
+         dw.stride(0), _ptr(db), 1.0 if accumulate else 0.0, _ptr(alpha), M, N, K, dtype_code(dy.dtype),
+         C.cast(zd, C.c_void_p) if zero else None, len(zero), tb.table.data_ptr() if tb else None, tb.n if tb else 0,
+         tb.total if tb else 0, dtype_code(tb.dtype) if tb else 0, C.byref(took), _stream())
+    return [int(zd[i].taken) for i in range(len(zero))], int(took.value)
+
+
 class ColSum(NamedTuple):
     """An entry of linear_wgrad_grouped's list that is no weight gradient: the column sums of the slab `ws` that
     layernorm_bwd_partial returned, written (accumulate: added) to the fp32 [N] tensors dgamma / dbeta.  dtype: the
@@ -595,8 +621,13 @@ class TransposeBatch:
         host = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy())
         self.table = host.to(pairs[0][0].device)
 
-    def run(self) -> None:
-        call("vy_transpose_batched", self.table.data_ptr(), self.n, self.total, dtype_code(self.dtype), _stream())
+    def run(self, first: int = 0) -> None:
+        """first: the leading tiles that are already done (by riders of ops.linear_wgrad_riders)."""
+        if first == 0:
+            call("vy_transpose_batched", self.table.data_ptr(), self.n, self.total, dtype_code(self.dtype), _stream())
+        elif first < self.total:
+            call("vy_transpose_batched_range", self.table.data_ptr(), self.n, first, self.total - first,
+                 dtype_code(self.dtype), _stream())
 
 
 def cast(src: Tensor, dst: Tensor) -> Tensor:

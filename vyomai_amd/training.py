@@ -409,7 +409,7 @@ class FlatTrainer:
                  process_group=None, bucket_bytes: int = 64 << 20, overlap_optimizer: bool = True,
                  accumulate_steps: int = 1, max_grad_norm: Optional[float] = None,
                  grad_comm_dtype: Optional[torch.dtype] = None, native_rccl: Optional[bool] = None,
-                 adamw_ride: bool = True):
+                 adamw_ride: bool = True, wgrad_riders: bool = True):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         for m in model.modules():
@@ -458,6 +458,16 @@ class FlatTrainer:
         # per step (reset by zero_grad): AdamW ranges / bytes of optimizer traffic that rode in grouped launches, and that
         # found no seat and were stepped with launches of their own (_drain_rides)
         self.ride_stats = {"rode_ranges": 0, "rode_bytes": 0, "drained_ranges": 0, "drained_bytes": 0}
+        # The vocabulary weight gradient is the first launch of backward and leaves most CUs idle in its last round of
+        # tiles: it carries the W^T refresh and the zeroing of the gradient arena as rider workgroups
+        # (autograd_train._WgradRiders, lazy_zero).  Any world size, with or without accumulation; bf16 compute only.
+        if os.environ.get("VY_WGRAD_RIDERS") == "0":   # A/B knob
+            wgrad_riders = False
+        self._wgrad_riders = bool(wgrad_riders and self.arena.master.is_cuda and self.arena.shadow is not None)
+        self._carrier_ranges: Optional[List[Tuple[int, int]]] = None
+        # per step (reset by zero_grad): bytes of the arena cleared by riders / by plain fills, 64 x 64 tiles of the W^T
+        # refresh transposed by riders / by plain launches
+        self.rider_stats = {"zero_rode_bytes": 0, "zero_plain_bytes": 0, "wt_rode_tiles": 0, "wt_plain_tiles": 0}
 
     def rode(self, ranges: int, nbytes: int) -> None:
         self.ride_stats["rode_ranges"] += ranges
@@ -483,14 +493,37 @@ class FlatTrainer:
             i += 1
         return out
 
-    def zero_grad(self) -> None:
+    def _carriers(self) -> List[Tuple[int, int]]:
+        """Arena ranges of the parameters whose weight gradient carries the riders (marked by LMHeadLossFn.forward the
+        first time it runs: until then there is nobody to defer to)."""
+        if not self._carrier_ranges:
+            a = self.arena
+            ends = a.offsets[1:] + [a.numel]   # (up to the next parameter: the pad stays with it, every range starts aligned)
+            self._carrier_ranges = [(o, e) for p, o, e in zip(a.params, a.offsets, ends) if getattr(p, "_vy_carrier", False)]
+        return self._carrier_ranges
+
+    def zero_grad(self, defer: bool = False) -> None:
+        """defer (train_step() only): clear at once only what the carrier launch itself accumulates into and post the rest
+        of the arena as pending (lazy_zero); backward() sees to it that it is cleared before anything accumulates."""
+        from .lazy_zero import PENDING, complement
+        PENDING.drop(self)   # (a list an aborted step left: everything is filled below)
         if 0 < self._micro < self.accumulate_steps:   # in the middle of an accumulation window: keep adding
             return
         self._micro = 0            # (a finished window that was never stepped is dropped here: its gradients are cleared)
         from .autograd_train import _wgrad_group, reset_embedding_uses
         _wgrad_group.discard()   # (only an aborted backward can have left deferred weight gradients behind)
         reset_embedding_uses()   # (likewise embedding forwards whose backward never ran)
-        self.arena.zero_grad()
+        self.rider_stats = dict.fromkeys(self.rider_stats, 0)
+        carriers = self._carriers() if (defer and self._wgrad_riders) else []
+        if carriers:
+            g = self.arena.grad
+            for lo, hi in carriers:
+                g[lo:hi].zero_()
+                self.rider_stats["zero_plain_bytes"] += (hi - lo) * 4
+            PENDING.post(self, [g[lo:hi] for lo, hi in complement(self.arena.numel, carriers)], self.rider_stats)
+        else:
+            self.arena.zero_grad()
+            self.rider_stats["zero_plain_bytes"] += self.arena.numel * 4
         self.reducer.reset()
         self._stepped = set()
         self._needs_zero = False
@@ -518,7 +551,23 @@ class FlatTrainer:
         if last:
             self.reducer._seen = set()
         self._micro += 1
-        (loss / k if k > 1 else loss).backward()
+        # the arena's pending zeroing: the head's weight-gradient launch clears it if that node is the root of the loss
+        # (then nothing runs before it); else it is filled here, before autograd starts
+        from .autograd_train import _wgrad_riders
+        from .lazy_zero import PENDING
+        claim = PENDING.settle(self, loss.grad_fn if k == 1 else None)
+        was = (_wgrad_riders.on, _wgrad_riders.stats)
+        _wgrad_riders.on, _wgrad_riders.stats = self._wgrad_riders, self.rider_stats
+        try:
+            (loss / k if k > 1 else loss).backward()
+        finally:
+            _wgrad_riders.on, _wgrad_riders.stats = was
+            left = None
+            if claim is not None:
+                left, claim.ranges = claim.ranges, None   # whatever happened, the claim is spent
+        if left is not None:   # (the claiming node never ran: cannot happen for the root of a loss that was reached)
+            for r in left:
+                r.zero_()
         self.reducer.enabled = True
         # what found no seat in a grouped launch: the last buckets, anything over the launches' budget.  Stepped here and
         # not in optimizer_step(), so that a backward pass leaves the buckets it has finished stepped whichever way they
@@ -625,9 +674,14 @@ class FlatTrainer:
     def train_step(self, loss_fn: Callable[[], torch.Tensor]) -> torch.Tensor:
         """zero_grad -> loss_fn() -> backward (overlapped all-reduce) -> fused AdamW.  With
         accumulate_steps = k this is ONE micro-step; the update happens on every k-th call."""
-        self.zero_grad()
-        loss = loss_fn()
-        self.backward(loss)
+        self.zero_grad(defer=True)
+        try:
+            loss = loss_fn()
+            self.backward(loss)
+        except BaseException:
+            from .lazy_zero import PENDING
+            PENDING.drop(self)   # nothing stays pending: the next zero_grad() fills the whole arena
+            raise
         self.optimizer_step()
         return loss.detach()
 
